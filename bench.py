@@ -11,7 +11,7 @@ region starts; outputs stay in HBM.  One process per GPU; ranks work on independ
 (weak scaling, no data-path collective; RCCL only for the barriers / max-reduction of the
 timing).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--storage f64|f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--storage f64|f32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process touches no GPU; it starts
@@ -19,10 +19,16 @@ timing).
 as a CHILD process, relays the child's JSON line and exits with its code (reference `-p N`,
 parallel.py:18-32 / step_03_apply_to_era.py:630-638).  Every rank asserts WORLD_SIZE == --gpus.
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus `roofline` (dominant
-kernel, HIP-event timed inside this run, beside the figure recomputed from the committed rocprofv3
-summary), `cpu_baseline` (the numpy oracle on the host cores, rank 0, N = 1 only: one process and
-file-parallel processes, on bounded latitude bands of the same file) and, at N = 1, `extras`
+A plain run sets up, warms up, times the K steps (no per-launch events), writes the outputs of the last timed file
+with `--dump-outputs DIR` and prints ONE JSON line (rank 0) with the contract keys (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  Inputs are seeded: the same arguments give the same inputs, hence the
+same outputs, in every run.
+
+`--full` adds the side measurements: the CPU baseline runs before the GPU is touched, the per-launch HIP events and the
+card telemetry cover warm-up and the timed steps, everything else runs after them.  The line then also carries `kernels`,
+`roofline` (dominant kernel, HIP-event timed inside this run, beside the figure recomputed from the committed rocprofv3
+summary), `device_state`, `signature_kernels`, `overlap`, `cpu_baseline` (the numpy oracle on the host cores, rank 0,
+N = 1 only: one process and file-parallel processes, on bounded latitude bands of the same file) and, at N = 1, `extras`
 (PCIe-inclusive rate, end-to-end rate through the command line incl. NetCDF I/O, step_02 regridding of
 BASELINE.json configs[3], float32-storage rates) - reported, never `value`; at N > 1 also `latency_mode`: ONE file over
 all ranks in latitude bands, the loop's stopping test made global by an all-reduce MAX (RCCL) of the per-pass maxima.
@@ -40,6 +46,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X spec (MI355X_MICROARCH.md: 8.0 TB/s; 6.29 TB/s measured copy)
+DUMP_BUDGET = 30 << 20         # bytes of values --dump-outputs writes at most (masks add at most as much again); larger
+                               # outputs are cut to a fixed sample of columns
+DUMP_SEED = 20061
+DUMP_NAMES = ('PS', 'T', 'QV', 'U', 'V', 'T_SKIN', 'T_SO', 'FR_SEA_ICE')     # process_file_device's outputs
 
 
 def parse(argv=None):
@@ -70,7 +80,18 @@ def parse(argv=None):
     p.add_argument('--dry-run', action='store_true',
                    help='no GPU work: ranks rendezvous, count each other and print the line with value null '
                         '(CPU rehearsal of the multi-rank launch path; use with PGW_BENCH_BACKEND=gloo)')
-    return p.parse_args(argv)
+    p.add_argument('--full', action='store_true',
+                   help='everything beside the headline figure as well: per-launch HIP-event kernel table and roofline, card '
+                        'telemetry, CPU baseline, bare-pattern probe, signature kernels, overlap region, extras (N = 1), '
+                        'latency mode and all-ranks legs (N > 1).  The --no-* / --overlap-streams / --e2e-* flags act within it')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help="write what the timed path returned for its last file as DIR/<name>.npy (rank 0; a fixed, seeded "
+                        "sample of columns when the arrays exceed %d MB; non-finite entries as 0 with DIR/<name>_finite.npy "
+                        "marking them)" % (DUMP_BUDGET >> 20))
+    a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error('--steps must be at least 1 and --warmup at least 0')
+    return a
 
 
 def spawn_ranks(a, argv):
@@ -354,6 +375,49 @@ def dom_streams_ok(era, out):
     return all(k in era for k in ('T', 'QV', 'U', 'V')) and all(k in out for k in ('T', 'QV', 'U', 'V'))
 
 
+def dump_columns(ncol, col_bytes):
+    """The columns --dump-outputs writes: all of them when `ncol` columns of `col_bytes` fit in DUMP_BUDGET, else a fixed
+    (seeded, sorted) sample of as many as fit - the same for every run of one grid."""
+    import numpy as np
+    k = int(DUMP_BUDGET // max(col_bytes, 1))
+    if k >= ncol:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(ncol, k, replace=False))
+
+
+def dump_outputs(out, info, path):
+    """--dump-outputs: what process_file_device returned to its caller for the last timed file, as `path`/<name>.npy - its
+    output arrays in the dtype it computed them in (float32 / float64; shape (..., nlat, nlon), or (..., k) over the
+    columns of dump_columns), and info's n_iter and per-pass max_err as float64.  Every file holds finite numbers only: an
+    array with NaN entries (FR_SEA_ICE over land: NaN in ERA5 files, passed through as the reference does) is written
+    with 0 there, beside <name>_finite.npy, float32 1 where the value is finite and 0 where it is not."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = [k for k in DUMP_NAMES if k in out]
+    nlat, nlon = out['PS'].shape[-2:]
+    ncol = nlat * nlon
+    cols = dump_columns(ncol, sum(out[k].nbytes for k in names) / ncol)
+    written = []
+
+    def save(name, v):
+        ok = np.isfinite(v)
+        if not ok.all():
+            np.save(os.path.join(path, name + '_finite.npy'), ok.astype(np.float32))
+            written.append(name + '_finite')
+            v = np.where(ok, v, v.dtype.type(0))
+        np.save(os.path.join(path, name + '.npy'), v)
+        written.append(name)
+    for k in names:
+        v = out[k].numpy()
+        if cols is not None:
+            v = np.ascontiguousarray(v.reshape(v.shape[:-2] + (ncol,))[..., cols])
+        save(k, v)
+    save('n_iter', np.array([info['n_iter']], dtype=np.float64))
+    save('max_err', np.asarray(info['max_err'], dtype=np.float64))
+    return {'dir': path, 'arrays': written, 'columns': ncol if cols is None else len(cols),
+            'of_columns': ncol, 'sample_seed': None if cols is None else DUMP_SEED}
+
+
 def kernel_table(prof, N, S, ncol, s, kinfo):
     """per-kernel launches / average ms / algorithmic GB / GB/s from the context's HIP-event profile"""
     kern = {}
@@ -452,9 +516,10 @@ def main(argv=None):
     t0 = time.time()
     case = synthetic.make_case(nlat=a.nlat, nlon=a.nlon, nlev=a.nlev, seed=1 + rank, dtype=dtype)
     t_gen = time.time() - t0
+    full = a.full
     # CPU baseline first: this process has not touched the GPU yet, so the file-parallel leg can fork its workers
     cpu = None
-    if not a.no_cpu_baseline and world == 1 and rank == 0:
+    if full and not a.no_cpu_baseline and world == 1 and rank == 0:
         try:
             cpu = cpu_baseline(case, a, np)
         except Exception as e:                      # noqa: BLE001 - reported in the line, the GPU measurement goes on
@@ -468,6 +533,7 @@ def main(argv=None):
     N, S = a.nlev, len(case['plev'])
     # level arrays over the card's memory regions (settings.placement = 'spread'; PGW_PLACEMENT=plain for the A/B): inputs,
     # outputs and the vapour-pressure workspace of the file path, 9 arrays of one float64 field (+ 8 for the float32 leg's file, + 2 for the signature kernels' pa_hl and pa)
+    # - the same draw with and without --full, so that the timed arrays lie alike in both
     nt_, N_, nlat_, nlon_ = case['era']['T'].shape
     placement = ctx.enable_placement(nt_ * (N_ + 1) * nlat_ * nlon_ * 8,            # the half-level field pa_hl is the largest
                                      (9 if a.no_extras else 17) + (2 if (rank == 0 and world == 1) else 0))
@@ -488,7 +554,7 @@ def main(argv=None):
 
     infos = []
     smi = None
-    if rank == 0 and not os.environ.get('PGW_BENCH_NOSMI'):
+    if full and rank == 0 and not os.environ.get('PGW_BENCH_NOSMI'):
         # the card's own telemetry over the run (gfx clock, socket power against its cap, temperatures): the file path drives
         # an MI355X to its power cap, and the clock the firmware then allows is what differs between boxes
         try:
@@ -497,7 +563,7 @@ def main(argv=None):
             smi = Sampler(device=local).start()
         except Exception:                           # noqa: BLE001 - telemetry is optional
             smi = None
-    if not os.environ.get('PGW_BENCH_NOPROF'):      # A/B knob: cost of the per-launch HIP events
+    if full and not os.environ.get('PGW_BENCH_NOPROF'):     # A/B knob: cost of the per-launch HIP events
         ctx.profile(True)                           # on during warm-up too, so the event pool is populated
     for i in range(a.warmup):
         _, info = s3.process_file_device(ctx, era, coeffs, deltas, stamps[i], True, out=out, ref_dtype=ref)
@@ -511,10 +577,13 @@ def main(argv=None):
     barrier()
     elapsed = time.perf_counter() - t0
     tm1 = time.monotonic()
-    prof = {k: ctx.profile_get(k) for k in FILE_KERNELS}
+    dumped = None
+    if a.dump_outputs and rank == 0:                # before any later leg overwrites the outputs of the last file
+        dumped = dump_outputs(out, infos[-1], a.dump_outputs)
+    prof = {k: ctx.profile_get(k) for k in FILE_KERNELS} if full else None
     solo = (rank == 0 and world == 1)
     bare = None
-    if rank == 0 and dom_streams_ok(era, out):
+    if full and rank == 0 and dom_streams_ok(era, out):
         # the quad kernel's access pattern with no arithmetic (4 read + 4 write streams, Context.placement_probe) on the very
         # arrays of this run: what this box gives the pattern WHERE these arrays lie (5.0-6.2 TB/s between allocations, DESIGN.md
         # section 4).  Overwrites the outputs of the last file; every later leg writes them anew.
@@ -530,7 +599,7 @@ def main(argv=None):
             ctx.profile(not os.environ.get('PGW_BENCH_NOPROF'))
         except Exception as e:                      # noqa: BLE001 - a side measurement
             bare = {'error': '%s: %s' % (type(e).__name__, e)}
-    micro = microbench(ctx, era, coeffs, a, np) if solo else {}       # N = 1 only: keeps multi-rank runs short
+    micro = microbench(ctx, era, coeffs, a, np) if (full and solo) else {}     # N = 1 only: keeps multi-rank runs short
     for k, v in micro.items():
         # beside the HIP-event figure of this run: the fraction from the committed rocprofv3 trace of the same command.
         # They differ most for `pressure`, a pure-write kernel whose event time depends on what the kernel before it left
@@ -540,12 +609,12 @@ def main(argv=None):
             v['frac_rocprof'] = rp['frac_rocprof']
             v['rocprof_timed_avg_launch_ms'] = rp['rocprof_timed_avg_launch_ms']
             v['rocprof_source'] = rp['rocprof_source']
-    overlap = overlap_region(local, era, coeffs, deltas, stamps[a.warmup:], a, ref) if (solo and a.overlap_streams > 1) else None
+    overlap = overlap_region(local, era, coeffs, deltas, stamps[a.warmup:], a, ref) if (full and solo and a.overlap_streams > 1) else None
     ctx.profile(False)
     latency = None
     bk_host = case['era']['bk']
     pcie_rank, cli_all = None, None
-    if dist is not None:                            # N > 1 (and the one-rank RCCL rehearsal, PGW_BENCH_FORCE_DIST=1)
+    if full and dist is not None:                   # N > 1 (and the one-rank RCCL rehearsal, PGW_BENCH_FORCE_DIST=1)
         if world > 1:
             if not a.no_extras:
                 try:                                # every rank at once: PCIe and host memory bandwidth are shared
@@ -558,7 +627,7 @@ def main(argv=None):
             latency = latency_mode(ctx, a, rank, world, dist, backend, dtype, ref)
         except Exception as e:                      # noqa: BLE001 - a side measurement, never costs the headline line
             latency = {'error': '%s: %s' % (type(e).__name__, e)}
-    if dist is not None and world > 1 and not a.no_extras and a.e2e_files > 0:
+    if full and dist is not None and world > 1 and not a.no_extras and a.e2e_files > 0:
         try:
             cli_all = cli_leg_all_ranks(a, rank, world, dist, barrier)
         except Exception as e:                      # noqa: BLE001
@@ -574,26 +643,6 @@ def main(argv=None):
         n_iter = [i['n_iter'] for i in infos]
         passes = sum(n_iter)
         lv_per_launch = sum(i['levels_touched'] for i in infos) / max(passes, 1)
-        bk = bk_host
-        n_pure = 0
-        while n_pure < N and (0.5 * (bk[n_pure + 1] - bk[n_pure]) + bk[n_pure]) == 0.0:
-            n_pure += 1
-        # pure-pressure levels: their final QV is written by k_delta_quad (stop-above-p_ref passes)
-        quad = not a.full_column and ctx.get_option('quad') != 0
-        launches_multi = prof['ps_loop_multi'][0]
-        kinfo = dict(levels_per_launch=lv_per_launch, qv_done_levels=n_pure if quad else 0, so=so,
-                     passes_per_launch=(sum(i.get('passes_launched', 0) for i in infos) / launches_multi) if launches_multi else 1.0)
-        kern = kernel_table(prof, N, S, ncol, s, kinfo)
-        cand = [k for k in kern if kern[k]['GBps']]
-        if not cand:                       # PGW_BENCH_NOPROF: no per-kernel timings
-            print(json.dumps({'ms_per_step': round(elapsed / a.steps * 1e3, 3), 'note': 'launch profiling disabled'}), flush=True)
-            return 0
-        dom = max(cand, key=lambda k: kern[k]['total_ms'])
-        roof = roofline_object(dom, kern, a)
-        if bare is not None:
-            roof['bare_pattern_same_arrays'] = bare
-            if bare.get('GBps') and kern[dom]['GBps']:
-                roof['frac_of_bare_pattern'] = round(kern[dom]['GBps'] / bare['GBps'], 4)
         files = a.steps * world
         res = {
             'metric': 'ERA5 files/hour (0.25deg L137), step_03 hot path, inputs resident in HBM',
@@ -610,28 +659,46 @@ def main(argv=None):
                        'iterations_per_file_over_ranks': [iters_min, iters_max],
                        'pass_kernel': 'full_column' if a.full_column else 'stops_above_p_ref',
                        'passes_launched_per_file': round(sum(i.get('passes_launched', 0) for i in infos) / len(infos), 2),
-                       'loop_launches_per_file': round((prof['ps_loop_multi'][0] + prof['adjust_ps_step'][0]) / len(infos), 2),
                        'mean_levels_read_per_column_per_pass': round(lv_per_launch / ncol, 2)},
             'collective': {'backend': ('rccl (torch nccl)' if backend == 'nccl' else backend) if dist is not None else None,
                            'ranks_counted_by_all_reduce': ranks_seen,
                            'use': 'barrier + MAX of the elapsed time; files are independent'},
-            'roofline': roof,
-            'kernels': kern,
-            'signature_kernels': micro,
-            'extras': None,
-            'overlap': overlap,
-            'latency_mode': latency,
             'device': ctx.device_name(),
             'placement': placement if placement is not None else {'mode': 'plain'},
             'setup_s': round(t_gen, 1),
         }
-        if solo and not a.no_extras:
+        if dumped is not None:
+            res['dump_outputs'] = dumped
+        if full:
+            bk = bk_host
+            n_pure = 0
+            while n_pure < N and (0.5 * (bk[n_pure + 1] - bk[n_pure]) + bk[n_pure]) == 0.0:
+                n_pure += 1
+            # pure-pressure levels: their final QV is written by k_delta_quad (stop-above-p_ref passes)
+            quad = not a.full_column and ctx.get_option('quad') != 0
+            launches_multi = prof['ps_loop_multi'][0]
+            kinfo = dict(levels_per_launch=lv_per_launch, qv_done_levels=n_pure if quad else 0, so=so,
+                         passes_per_launch=(sum(i.get('passes_launched', 0) for i in infos) / launches_multi) if launches_multi else 1.0)
+            kern = kernel_table(prof, N, S, ncol, s, kinfo)
+            cand = [k for k in kern if kern[k]['GBps']]
+            if not cand:                       # PGW_BENCH_NOPROF: no per-kernel timings
+                print(json.dumps({'ms_per_step': round(elapsed / a.steps * 1e3, 3), 'note': 'launch profiling disabled'}), flush=True)
+                return 0
+            dom = max(cand, key=lambda k: kern[k]['total_ms'])
+            roof = roofline_object(dom, kern, a)
+            if bare is not None:
+                roof['bare_pattern_same_arrays'] = bare
+                if bare.get('GBps') and kern[dom]['GBps']:
+                    roof['frac_of_bare_pattern'] = round(kern[dom]['GBps'] / bare['GBps'], 4)
+            res['config']['loop_launches_per_file'] = round((prof['ps_loop_multi'][0] + prof['adjust_ps_step'][0]) / len(infos), 2)
+            res.update(roofline=roof, kernels=kern, signature_kernels=micro, extras=None, overlap=overlap, latency_mode=latency)
+        if full and solo and not a.no_extras:
             try:
                 res['extras'] = extras(ctx, case, era, coeffs, deltas, a, np)
             except Exception as e:          # noqa: BLE001 - side measurements never cost the headline line
                 res['extras'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        f32s = (res['extras'] or {}).get('f32_storage') or {}
-        if world == 1 and res['extras']:            # the same legs, measured by `extras` at N = 1
+        f32s = (res.get('extras') or {}).get('f32_storage') or {}
+        if world == 1 and res.get('extras'):        # the same legs, measured by `extras` at N = 1
             ex = res['extras']
             pcie_all = [{'float64_out': f32s.get('pcie_inclusive_reference'), 'float32_out': f32s.get('pcie_inclusive_reference_f32_out')}]
             cli_all = {'files': a.e2e_files, 'ranks': 1, 'float64_out': ex.get('end_to_end_cli'), 'float32_out': ex.get('end_to_end_cli_f32_out')}

@@ -301,7 +301,7 @@ def test_bench_rank_under_torch_distributed_run_with_rccl(tmp_path):
         env.pop(k, None)
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                         '--master-port', '29531', os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-                        '--nlat', '45', '--nlon', '64', '--nlev', '40', '--no-cpu-baseline', '--no-extras', '--overlap-streams', '0'],
+                        '--nlat', '45', '--nlon', '64', '--nlev', '40', '--full', '--no-cpu-baseline', '--no-extras', '--overlap-streams', '0'],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -311,6 +311,35 @@ def test_bench_rank_under_torch_distributed_run_with_rccl(tmp_path):
     lm = line['latency_mode']
     assert 'error' not in lm, lm
     assert lm['bands'] == 1 and lm['ms_per_file'] > 0 and lm['exchange'].endswith('rccl')
+
+
+def test_bench_plain_run_dumps_the_outputs_of_its_last_file(tmp_path):
+    """`bench.py` without --full: the contract keys and none of the side measurements; --dump-outputs writes what the timed
+    path returned for its last file (stamp warm-up + steps - 1 hours after the case's), which is the oracle's for that file."""
+    import json
+    from pgw4era5_amd import synthetic
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--nlat', '45', '--nlon', '64', '--nlev', '40', '--dump-outputs', str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert line['unit'] == 'files/hour' and line['higher_is_better'] is True and line['dtype'] == 'f64'
+    assert not set(line) & {'roofline', 'kernels', 'signature_kernels', 'extras', 'cpu_baseline', 'device_state'}
+    case = synthetic.make_case(nlat=45, nlon=64, nlev=40, seed=1)
+    want = O.pgw_for_era5_arrays(case['era'], case['deltas'], case['delta_times'], case['plev'],
+                                 case['target_dt'] + dt.timedelta(hours=3), ignore_top_pressure_error=True)
+    assert all(np.isfinite(np.load(str(f))).all() for f in out.glob('*.npy'))
+    assert np.load(str(out / 'n_iter.npy')).tolist() == [want['n_iter']]
+    assert (out / 'FR_SEA_ICE_finite.npy').exists()          # NaN over land, as in ERA5 files and the reference
+    for k in ['PS', 'T', 'QV', 'U', 'V', 'T_SKIN', 'T_SO', 'FR_SEA_ICE']:
+        got = np.load(str(out / (k + '.npy')))
+        assert got.dtype == np.float64
+        mask = out / (k + '_finite.npy')
+        if mask.exists():
+            got = np.where(np.load(str(mask)) == 1, got, np.nan)
+        np.testing.assert_allclose(got, want[k], rtol=1e-9, atol=1e-12, equal_nan=True, err_msg=k)
 
 
 def test_step03_24_hourly_files_two_ranks(tmp_path):

@@ -555,6 +555,55 @@ def test_rank_cpu_sets_follow_the_gpus_numa_nodes_and_are_disjoint():
         os.sched_setaffinity(0, before)
 
 
+def test_bench_options_and_dump_sample():
+    """bench.py's side measurements are off unless --full; --steps sets the timed steps (at least one); --dump-outputs keeps
+    every column of a grid that fits its budget and otherwise one fixed sample of columns, the same in every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(['--steps', '7', '--warmup', '0'])
+    assert a.steps == 7 and a.warmup == 0 and a.full is False and a.dump_outputs is None
+    a = bench.parse(['--full', '--dump-outputs', 'd'])
+    assert a.full is True and a.dump_outputs == 'd'
+    with pytest.raises(SystemExit):
+        bench.parse(['--steps', '0'])
+    assert bench.dump_columns(45 * 64, 4 * 40 * 8 + 64) is None
+    ncol, col_bytes = 721 * 1440, 4 * 137 * 8 + 7 * 8
+    c = bench.dump_columns(ncol, col_bytes)
+    assert np.array_equal(c, bench.dump_columns(ncol, col_bytes))
+    assert len(c) * col_bytes <= bench.DUMP_BUDGET and len(c) > 1000
+    assert np.all(np.diff(c) > 0) and c[0] >= 0 and c[-1] < ncol
+
+
+def test_bench_dump_outputs_files_are_finite(tmp_path):
+    """--dump-outputs writes finite numbers only: NaN entries (FR_SEA_ICE over land) become 0 beside a <name>_finite mask, from
+    which the array comes back exactly; arrays without NaN get no mask."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Host:                                       # stands in for a DeviceArray: shape, nbytes, numpy()
+        def __init__(self, v):
+            self.v, self.shape, self.nbytes = v, v.shape, v.nbytes
+
+        def numpy(self):
+            return self.v.copy()
+    rng = np.random.default_rng(0)
+    ps = rng.uniform(5e4, 1e5, (1, 6, 8))
+    sic = np.where(rng.uniform(size=(1, 6, 8)) > 0.5, np.nan, 0.3)
+    t = rng.uniform(200, 300, (1, 5, 6, 8))
+    res = bench.dump_outputs({'PS': Host(ps), 'FR_SEA_ICE': Host(sic), 'T': Host(t), '_ws': Host(t)},
+                             {'n_iter': 4, 'max_err': [3.0, float('nan')]}, str(tmp_path))
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == sorted(['PS.npy', 'T.npy', 'FR_SEA_ICE.npy', 'FR_SEA_ICE_finite.npy', 'n_iter.npy', 'max_err.npy',
+                            'max_err_finite.npy'])
+    assert sorted(res['arrays']) == sorted(f[:-4] for f in files) and res['columns'] == 48
+    assert all(np.isfinite(np.load(str(tmp_path / f))).all() for f in files)
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'PS.npy')), ps)
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'T.npy')), t)
+    m = np.load(str(tmp_path / 'FR_SEA_ICE_finite.npy'))
+    assert m.dtype == np.float32 and set(np.unique(m)) == {0.0, 1.0}
+    np.testing.assert_array_equal(np.where(m == 1, np.load(str(tmp_path / 'FR_SEA_ICE.npy')), np.nan), sic)
+
+
 def test_bench_cpu_baseline_legs():
     """The two legs of bench.py's cpu_baseline (one process, file-parallel processes) on a toy file."""
     import argparse

@@ -7,4 +7,4 @@ sys.path.insert(0, ROOT)
 from pgw4era5_amd import settings as S
 S.thresh_phi_ref_max_error = 1e300
 import bench
-sys.exit(bench.main(['--no-cpu-baseline', '--no-extras', '--overlap-streams', '0', '--steps', '10', '--warmup', '2'] + sys.argv[1:]))
+sys.exit(bench.main(['--full', '--no-cpu-baseline', '--no-extras', '--overlap-streams', '0', '--steps', '10', '--warmup', '2'] + sys.argv[1:]))

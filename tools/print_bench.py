@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The figures of a bench.py line one looks at first.  Usage: python tools/print_bench.py gpurun_out/bench.json"""
+"""The figures of a `bench.py --full` line one looks at first.  Usage: python tools/print_bench.py bench.json"""
 import json
 import sys
 

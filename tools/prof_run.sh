@@ -5,8 +5,8 @@ tag=$1; shift
 export TMPDIR=/tmp
 out=gpurun_out/prof_$tag
 mkdir -p $out
-B="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --overlap-streams 0 --no-extras $@"
-P="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --overlap-streams 0 --e2e-files 0 $@"
+B="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --overlap-streams 0 --no-extras $@"
+P="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --overlap-streams 0 --e2e-files 0 $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $B > $out/bench_trace.json 2> $out/trace.err || echo "trace failed"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -- $P > $out/bench_fetch.json 2> $out/fetch.err || echo "fetch failed"
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -- $P > $out/bench_write.json 2> $out/write.err || echo "write failed"
