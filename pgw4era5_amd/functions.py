@@ -103,6 +103,22 @@ def _aligned(x, like):
     return x
 
 
+def _fit(x, shape, name):
+    """Operand `x` for a kernel that indexes it as `shape` (the leading operand's): a host array is broadcast to it like the
+    reference's numpy arithmetic would (ValueError when it cannot be), a DeviceArray must have exactly that shape.  Called
+    before anything is uploaded or launched: a shorter operand would otherwise be read past its end."""
+    shape = tuple(int(n) for n in shape)
+    r = _raw(x)
+    if isinstance(r, DeviceArray):
+        if r.shape != shape:
+            raise ValueError('%s: device array of shape %s, expected %s' % (name, r.shape, shape))
+        return r
+    try:
+        return np.broadcast_to(r, shape)
+    except ValueError:
+        raise ValueError('%s: shape %s does not broadcast to %s' % (name, r.shape, shape)) from None
+
+
 def _shape4(x):
     s = _raw(x).shape
     if len(s) != 4:
@@ -117,7 +133,8 @@ def specific_to_relative_humidity(hus, pa, ta):
     pa, ta = _aligned(pa, hus), _aligned(ta, hus)
     dt = _common_dtype(hus, pa, ta)
     shp = _raw(hus).shape
-    dh, dp_, dt_ = _dev(ctx, hus, dt), _dev(ctx, np.broadcast_to(_raw(pa), shp) if not isinstance(_raw(pa), DeviceArray) else pa, dt), _dev(ctx, ta, dt)
+    pa_, ta_ = _fit(pa, shp, 'pa'), _fit(ta, shp, 'ta')
+    dh, dp_, dt_ = _dev(ctx, hus, dt), _dev(ctx, pa_, dt), _dev(ctx, ta_, dt)
     out = ctx.empty(shp, dt)
     ctx._check(ctx.lib.pgw_specific_to_relative_humidity(ctx.handle, dtype_tag(dt), out.size, dh.ptr, dp_.ptr, dt_.ptr, out.ptr))
     return _out(ctx, out, hus)
@@ -129,7 +146,8 @@ def relative_to_specific_humidity(hur, pa, ta):
     pa, ta = _aligned(pa, hur), _aligned(ta, hur)
     dt = _common_dtype(hur, pa, ta)
     shp = _raw(hur).shape
-    dh, dp_, dt_ = _dev(ctx, hur, dt), _dev(ctx, np.broadcast_to(_raw(pa), shp) if not isinstance(_raw(pa), DeviceArray) else pa, dt), _dev(ctx, ta, dt)
+    pa_, ta_ = _fit(pa, shp, 'pa'), _fit(ta, shp, 'ta')
+    dh, dp_, dt_ = _dev(ctx, hur, dt), _dev(ctx, pa_, dt), _dev(ctx, ta_, dt)
     out = ctx.empty(shp, dt)
     ctx._check(ctx.lib.pgw_relative_to_specific_humidity(ctx.handle, dtype_tag(dt), out.size, dh.ptr, dp_.ptr, dt_.ptr, out.ptr))
     return _out(ctx, out, hur)
@@ -139,11 +157,9 @@ def _humidity_leaf(which, a, b, like):
     ctx = default_context()
     dt = _common_dtype(a) if b is None else _common_dtype(a, b)
     shp = _raw(a).shape
+    b_ = None if b is None else _fit(_aligned(b, a), shp, 'pa')
     da = _dev(ctx, a, dt)
-    db = None
-    if b is not None:
-        b = _aligned(b, a)
-        db = _dev(ctx, np.broadcast_to(_raw(b), shp) if not isinstance(_raw(b), DeviceArray) else b, dt)
+    db = None if b_ is None else _dev(ctx, b_, dt)
     out = ctx.empty(shp, dt)
     ctx._check(ctx.lib.pgw_humidity_leaf(ctx.handle, dtype_tag(dt), which, out.size, da.ptr, db.ptr if db is not None else None, out.ptr))
     return _out(ctx, out, like)
@@ -211,7 +227,8 @@ def integ_geopot(pa_hl, zgs, ta, hus, level1, p_ref, full_column=True):
         raise ValueError('level dimensions are inconsistent')
     dt = _common_dtype(pa_hl, zgs, ta, hus)
     nt, n, ncol = s[0], st[1], s[2] * s[3]
-    d_p, d_z, d_t, d_q = _dev(ctx, pa_hl, dt), _dev(ctx, zgs, dt, (nt, s[2], s[3])), _dev(ctx, ta, dt), _dev(ctx, hus, dt)
+    ta_, hus_ = _fit(ta, (nt, n, s[2], s[3]), 'ta'), _fit(hus, (nt, n, s[2], s[3]), 'hus')
+    d_p, d_z, d_t, d_q = _dev(ctx, pa_hl, dt), _dev(ctx, zgs, dt, (nt, s[2], s[3])), _dev(ctx, ta_, dt), _dev(ctx, hus_, dt)
     pref_field = None
     pref_scalar = 0.0
     pr = _raw(p_ref) if not np.isscalar(p_ref) else None
@@ -290,7 +307,8 @@ def time_lerp(v_before, v_after, x_hi, x_new):
     `.interp(time=...)` (reference functions.py:288-292; scipy interp1d linear)."""
     ctx = default_context()
     dt = _common_dtype(v_before, v_after)
-    d_b, d_a = _dev(ctx, v_before, dt), _dev(ctx, v_after, dt)
+    v_after_ = _fit(v_after, _raw(v_before).shape, 'v_after')
+    d_b, d_a = _dev(ctx, v_before, dt), _dev(ctx, v_after_, dt)
     out = ctx.empty(d_b.shape, dt)
     ctx._check(ctx.lib.pgw_time_lerp(ctx.handle, dtype_tag(dt), out.size, d_b.ptr, d_a.ptr, float(x_hi), float(x_new), out.ptr))
     return _out(ctx, out, v_before)
@@ -334,10 +352,11 @@ def vert_interp_delta(delta, target_P, delta_sfc=None, ps_hist=None, ignore_top_
         raise ValueError('delta_sfc and ps_hist must be given together')
     dt = _common_dtype(delta, target_P, delta_sfc, ps_hist, add_to)
     nt, S, ncol, N = sd[0], sd[1], sd[2] * sd[3], st[1]
+    add_ = _fit(add_to, st, 'add_to') if add_to is not None else None
     d_d, d_t = _dev(ctx, delta, dt), _dev(ctx, target_P, dt)
     d_s = _dev(ctx, delta_sfc, dt, (nt, sd[2], sd[3])) if delta_sfc is not None else None
     d_p = _dev(ctx, ps_hist, dt, (nt, sd[2], sd[3])) if ps_hist is not None else None
-    d_add = _dev(ctx, add_to, dt) if add_to is not None else None
+    d_add = _dev(ctx, add_, dt) if add_ is not None else None
     out = ctx.empty(st, dt)
     ctx._check(ctx.lib.pgw_vert_interp_delta(
         ctx.handle, dtype_tag(dt), nt, S, N, ncol, pl.ctypes.data_as(_dp),

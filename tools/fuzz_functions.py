@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Randomised parity sweep of the function-level entries (the `functions.py` mirror) against the oracles:
 interp_logp_4d in all four modes (against the serial C column loops, oracle/pgw_oracle_c.c: pinned by the reference's own
-vectors), vert_interp_delta with and without the surface insertion, integ_geopot with a scalar and a per-column p_ref,
-the humidity pair, regrid_field on random source / target grids (periodic or not, pole rows or not, target longitudes in
+vectors), vert_interp_delta with and without the surface insertion, integ_geopot with a scalar and a per-column p_ref and
+the humidity pair (both over 1..3 time steps, float32 storage on ~30 % of the cases: the fp64 oracle on the stored values,
+rounded once), regrid_field on random source / target grids (periodic or not, pole rows or not, target longitudes in
 -180..180 or 0..360), smooth_annual_cycle on random record counts.  Errors must agree as well.
 Test infrastructure (imports oracle/).  usage: python tools/fuzz_functions.py [--cases 400] [--seed 0]"""
 import argparse
@@ -104,40 +105,60 @@ def case_vert(rng):
     return 'vert_interp_delta', 'ok' if close(got, want, *((2e-6, 2e-6) if f32 else (1e-9, 1e-9))) else 'FAIL values'
 
 
+def _storage(rng):
+    """(ntime, storage dtype) of a function-level case: 1..3 time steps, float32 on ~30 % of the cases."""
+    return int(rng.integers(1, 4)), (np.float32 if rng.random() < 0.3 else np.float64)
+
+
 def case_geopot(rng):
-    c = synthetic.make_case(nlat=int(rng.integers(1, 7)), nlon=int(rng.integers(1, 9)), nlev=int(rng.integers(6, 40)),
-                            seed=int(rng.integers(0, 1 << 30)))
-    era = c['era']
-    pa_hl, _ = O.hybrid_pressure(era['ak'], era['bk'], era['PS'])
-    level1 = np.arange(1, len(era['ak']) + 1)
+    nt, dt = _storage(rng)
+    nlat, nlon, nlev, seed = int(rng.integers(1, 7)), int(rng.integers(1, 9)), int(rng.integers(6, 40)), int(rng.integers(0, 1 << 30))
+    # time steps: synthetic cases of consecutive seeds on one grid (ak / bk depend on nlev only)
+    cs = [synthetic.make_case(nlat=nlat, nlon=nlon, nlev=nlev, seed=seed + k, dtype=dt)['era'] for k in range(nt)]
+    era = {k: np.concatenate([c[k] for c in cs]) for k in ('PS', 'FIS', 'T', 'QV')}
+    ak, bk = cs[0]['ak'], cs[0]['bk']
+    pa_hl = O.hybrid_pressure(ak, bk, era['PS'].astype(np.float64))[0].astype(dt)
+    level1 = np.arange(1, len(ak) + 1)
     r = rng.random()
     if r < 0.5:
         p_ref = float(rng.choice([30000.0, 50000.0, 70000.0, 20000.0]))
     elif r < 0.9:
-        p_ref = rng.uniform(1.0e4, 0.9 * era['PS'].min(), era['PS'].shape)
+        p_ref = rng.uniform(1.0e4, 0.9 * era['PS'].min(), era['PS'].shape).astype(dt)
     else:
         p_ref = 2.0e5                                                        # below the surface -> ValueError
+    f64 = {k: v.astype(np.float64) for k, v in era.items()}                # the oracle: fp64 on the stored values
     got, want, note = both(lambda: F.integ_geopot(pa_hl, era['FIS'], era['T'], era['QV'], level1, p_ref),
-                           lambda: O.integ_geopot(pa_hl, era['FIS'], era['T'], era['QV'], level1, p_ref))
+                           lambda: O.integ_geopot(pa_hl.astype(np.float64), f64['FIS'], f64['T'], f64['QV'], level1,
+                                                  np.asarray(p_ref, dtype=np.float64)))
     if note:
         return 'integ_geopot', note
-    return 'integ_geopot', 'ok' if close(got, want, 1e-11, 1e-6) else 'FAIL values'
+    if got.dtype != dt:
+        return 'integ_geopot', 'FAIL dtype %s' % got.dtype
+    # float32: the fp64 result rounded once (plus the fp64 differences, ~1e-13)
+    return 'integ_geopot', 'ok' if close(got, want, *((2.0 ** -23, 0) if dt == np.float32 else (1e-11, 1e-6))) else 'FAIL values'
 
 
 def case_humidity(rng):
-    shp = (1, int(rng.integers(1, 12)), int(rng.integers(1, 6)), int(rng.integers(1, 9)))
+    nt, dt = _storage(rng)
+    shp = (nt, int(rng.integers(1, 12)), int(rng.integers(1, 6)), int(rng.integers(1, 9)))
     ta = rng.uniform(185.0, 320.0, shp)
     ta.reshape(-1)[: min(3, ta.size)] = [273.16, 250.16, 260.0][: min(3, ta.size)]
     pa = rng.uniform(1.0, 1.05e5, shp)
     hus = 10.0 ** rng.uniform(-7, -1.7, shp)
-    got, want, note = both(lambda: F.specific_to_relative_humidity(hus, pa, ta), lambda: O.specific_to_relative_humidity(hus, pa, ta))
-    if note or not close(got, want, 1e-12, 0):
-        return 'humidity', note or 'FAIL q->rh'
     hur = rng.uniform(-5.0, 120.0, shp)
-    got, want, note = both(lambda: F.relative_to_specific_humidity(hur, pa, ta), lambda: O.relative_to_specific_humidity(hur, pa, ta))
+    ta, pa, hus, hur = (x.astype(dt).astype(np.float64) for x in (ta, pa, hus, hur))      # the stored values, in fp64
+    tol = (2.0 ** -23, 0) if dt == np.float32 else (1e-12, 0)
+    got, want, note = both(lambda: F.specific_to_relative_humidity(hus.astype(dt), pa.astype(dt), ta.astype(dt)),
+                           lambda: O.specific_to_relative_humidity(hus, pa, ta))
+    if note or got.dtype != dt or not close(got, want, *tol):
+        return 'humidity', note or 'FAIL q->rh (%s)' % got.dtype
+    got, want, note = both(lambda: F.relative_to_specific_humidity(hur.astype(dt), pa.astype(dt), ta.astype(dt)),
+                           lambda: O.relative_to_specific_humidity(hur, pa, ta))
     if note:
         return 'humidity', note
-    return 'humidity', 'ok' if close(got, want, 1e-12, 1e-300) else 'FAIL rh->q'
+    if got.dtype != dt:
+        return 'humidity', 'FAIL rh->q dtype %s' % got.dtype
+    return 'humidity', 'ok' if close(got, want, tol[0], 1e-300 if dt == np.float64 else 0) else 'FAIL rh->q'
 
 
 def case_regrid(rng):
