@@ -82,7 +82,12 @@ enum pgw_option {
     PGW_OPT_TEST_FAIL = 6,    /* test knob, default 0: pgw_step03_file fails on purpose - 1: the loop's workspace (ws_get), 2: before the
                                  first loop launch, 3: before a continuation launch - so that the latitude-band protocol can be
                                  tested where one band stops on its own                                                           */
-    PGW_OPT_COUNT = 7
+    PGW_OPT_FUSED_FIRST = 7,  /* 1 (default): in pgw_step03_file the delta kernel, which walks every column from the surface up, also
+                                 runs the loop's first two scans (phi_ref of the ERA state, pass 1) on the levels it holds in
+                                 registers; 0: the first loop launch does.  Same bits either way (see pgw_step03_file).  Takes
+                                 effect with PGW_OPT_QUAD = 1, PGW_OPT_MULTIPASS = 1, PGW_OPT_FULL_COLUMN = 0, a fixed p_ref
+                                 and i_reinterp = 0                                                              [PGW_FUSED_FIRST] */
+    PGW_OPT_COUNT = 8
 };
 
 /* ---------------------------------------------------------------- context ------------ */
@@ -355,8 +360,10 @@ typedef struct pgw_file_args {
     void *T_SKIN_out, *T_SO_out, *FR_SEA_ICE_out;
     /* results */
     int n_iter;
-    int passes_launched;  /* passes the loop kernels executed, including passes speculated beyond convergence (multi-pass launches) */
-    unsigned long long levels_touched;
+    int passes_launched;  /* passes executed, including passes speculated beyond convergence (multi-pass launches); with
+                             PGW_OPT_FUSED_FIRST the first pass, which the delta kernel runs, counts as launched */
+    unsigned long long levels_touched;   /* full levels read by the LOOP kernels' passes, summed over columns and passes up to the
+                             converged one: with PGW_OPT_FUSED_FIRST pass 1 adds only the columns the delta kernel left to them */
     double max_err_hist[32];
     /* The reference loads every delta file on its own (load_delta, functions.py:195-303): files may have different time
      * axes - monthly tos / siconc beside daily 3-D deltas - so a variable's bracketing records and abscissae are its own.
@@ -373,6 +380,14 @@ typedef struct pgw_file_args {
     double zg_x_hi, zg_x_new, siconc_x_hi, siconc_x_new, ts_x_hi, ts_x_new, tos_x_hi, tos_x_new;
 } pgw_file_args;
 
+/* Who produces the loop's state (fixed p_ref, multi-pass loop).  With PGW_OPT_FUSED_FIRST = 1 the delta kernel, walking each
+ * column from the surface up, integrates phi_ref of the ERA state and of the PGW state of pass 1 (delta_ps = 0: the same
+ * half-level pressures) while the levels below p_ref are in its registers, and leaves phi_ref_era, dphi_clim, delta_ps = 0,
+ * adj_ps, the first row of the delta_ps history and max |err| of pass 1 (status block of pass 1) - for every group of 64
+ * columns whose half-level pressures all ascend (ps >= the smallest such ps of the level table; not NaN).  The other groups
+ * are flagged; the first loop launch runs its own ERA-state scan and pass 1 for them alone and a continuation launch
+ * passes 2 .. loop_guess for all columns.  With 0 the first loop launch does all of it, as pgw_adjust_ps_loop always does.
+ * The two give the same bits, pass counts, histories and error reports. */
 int pgw_step03_file(pgw_ctx *ctx, pgw_file_args *args);
 
 /* ---------------------------------------------------------------- step_02 regridding - */

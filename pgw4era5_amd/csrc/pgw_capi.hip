@@ -58,6 +58,8 @@ struct pgw_ctx {
 };
 
 static const size_t SMALL_BYTES = 64 * 1024;
+// room behind the status blocks (device and pinned host) for the FusedFirst argument block of k_delta_quad
+static const int FUSED_BLOCKS = (int)((sizeof(FusedFirst<double>) + sizeof(DevStatus) - 1) / sizeof(DevStatus));
 
 static int fail(pgw_ctx *ctx, int code, const char *fmt, ...) {
     char buf[512];
@@ -255,9 +257,10 @@ extern "C" int pgw_ctx_create(int device, pgw_ctx **out) {
     c->opt[PGW_OPT_LOOP_GUESS] = 6;
     c->opt[PGW_OPT_FORCE_OFF64] = 0;
     c->opt[PGW_OPT_TEST_FAIL] = 0;
+    c->opt[PGW_OPT_FUSED_FIRST] = env_flag("PGW_FUSED_FIRST", 1);
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->d_status, (2 + MULTI_MAX_PASS) * sizeof(DevStatus)) != hipSuccess ||
-        hipHostMalloc(&c->h_status, (2 + 2 * MULTI_MAX_PASS) * sizeof(DevStatus)) != hipSuccess ||
+        hipMalloc(&c->d_status, (2 + MULTI_MAX_PASS + FUSED_BLOCKS) * sizeof(DevStatus)) != hipSuccess ||
+        hipHostMalloc(&c->h_status, (2 + 2 * MULTI_MAX_PASS + FUSED_BLOCKS) * sizeof(DevStatus)) != hipSuccess ||
         hipMalloc(&c->d_small, SMALL_BYTES) != hipSuccess ||
         hipEventCreate(&c->t0) != hipSuccess || hipEventCreate(&c->t1) != hipSuccess) {
         pgw_ctx_destroy(c);            // releases whatever was created before the failure
@@ -1108,6 +1111,21 @@ extern "C" int pgw_set_reduce_hook(pgw_ctx *ctx, pgw_reduce_max_fn fn, void *use
     return PGW_OK;
 }
 
+// State of the loop in workspace slot 1, six arrays of n2 doubles: phi_ref_era | dphi_clim | delta_ps | adj_ps | p_ref per
+// column (local p_ref) | its level index (n2 ints) and, in the other half of the sixth array, the flags of
+// k_delta_quad's FusedFirst (one byte per 64 columns).
+struct LoopState { double *phi_era, *dphi, *delta_ps, *adj_ps, *pref_f; int *pref_idx; unsigned char *era_flags; };
+static int loop_state(pgw_ctx *ctx, long long n2, LoopState *ls) {
+    void *state = nullptr;
+    int rc;
+    if ((rc = ws_get(ctx, 1, (size_t)n2 * 6 * sizeof(double), &state))) return rc;
+    ls->phi_era = (double *)state; ls->dphi = ls->phi_era + n2; ls->delta_ps = ls->dphi + n2; ls->adj_ps = ls->delta_ps + n2;
+    ls->pref_f = ls->adj_ps + n2;
+    ls->pref_idx = (int *)(ls->pref_f + n2);
+    ls->era_flags = (unsigned char *)(ls->pref_idx + n2);          // n2 / 64 + 1 <= 4 * n2 bytes
+    return PGW_OK;
+}
+
 // The loop of step_03_apply_to_era.py:182-319 given the iterate-independent vapour pressure
 // `evap` = hur_pgw/100 * e_sat(ta_pgw) (functions.py:123).  Shared by pgw_adjust_ps_loop and
 // pgw_step03_file.  The host reads max|err| after every pass (status copy + stream synchronisation) before it
@@ -1120,15 +1138,18 @@ static int run_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const
                        const void *dzg_b, const void *dzg_a, double x_hi, double x_new, double p_ref,
                        double adj_factor, double thresh, int max_n_iter, void *ps_pgw, void *hus_pgw, int *n_iter,
                        double *max_err_hist, int hist_len, int local_nplev = 0, const double *plev_file = nullptr,
-                       bool status_armed = false, int qv_done_levels = 0, bool ref = false) {
+                       bool status_armed = false, int qv_done_levels = 0, bool ref = false, bool fused_first = false) {
+    // fused_first (pgw_step03_file, PGW_OPT_FUSED_FIRST): k_delta_quad has run the ERA-state scan and pass 1 for the groups
+    // of columns it did not flag - the loop state in workspace slot 1, dps_hist[0] and the status block of pass 1 hold
+    // their results.  The first launch is then two: pass 1 for the flagged groups alone (k_ps_loop_multi<.., FLAGGED>),
+    // and passes 2 .. np for all columns as a continuation launch.
     const long long n2 = (long long)ntime * ncol;
-    void *state = nullptr;
     int rc;
     if (ctx->opt[PGW_OPT_TEST_FAIL] == 1) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 1: forced workspace failure (ws_get)");
-    if ((rc = ws_get(ctx, 1, (size_t)n2 * 6 * sizeof(double), &state))) return rc;
-    double *phi_era = (double *)state, *dphi = phi_era + n2, *delta_ps = dphi + n2, *adj_ps = delta_ps + n2;
-    double *pref_f = adj_ps + n2;
-    int *pref_idx = (int *)(pref_f + n2);
+    LoopState ls;
+    if ((rc = loop_state(ctx, n2, &ls))) return rc;
+    double *phi_era = ls.phi_era, *dphi = ls.dphi, *delta_ps = ls.delta_ps, *adj_ps = ls.adj_ps, *pref_f = ls.pref_f;
+    int *pref_idx = ls.pref_idx;
     const int full_column = ctx->opt[PGW_OPT_FULL_COLUMN];
     const bool local = local_nplev > 0;
     // several passes per launch: fixed p_ref, wave-level early exit (the full-column option is a per-pass traffic probe)
@@ -1190,7 +1211,9 @@ static int run_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const
             ctx->band_next_np = np;
             if (first && ctx->opt[PGW_OPT_TEST_FAIL] == 2) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 2: forced failure before the first loop launch");
             if (!first && ctx->opt[PGW_OPT_TEST_FAIL] == 3) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 3: forced failure before a continuation launch");
-            HIPCHK(ctx, hipMemcpyAsync(mst, hzero, sizeof(DevStatus) * np, hipMemcpyHostToDevice, ctx->stream));
+            const bool fused_launch = first && fused_first;                // (block of pass 1: armed before the delta kernel)
+            if (!fused_launch) HIPCHK(ctx, hipMemcpyAsync(mst, hzero, sizeof(DevStatus) * np, hipMemcpyHostToDevice, ctx->stream));
+            else if (np > 1) HIPCHK(ctx, hipMemcpyAsync(mst + 1, hzero + 1, sizeof(DevStatus) * (np - 1), hipMemcpyHostToDevice, ctx->stream));
             {
                 // one column per lane (two columns: 168 VGPRs + scratch; measured 1.36 vs 1.39 ms before the log table)
                 constexpr int MULTI_MAXV = 1;
@@ -1200,16 +1223,26 @@ static int run_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const
                 const LocalPRef loc{ptf, ctx->h_akN, ctx->h_bkN, pref_f, pref_idx};
                 DISPATCH_TLV(dtype, ref, vec, {
                     DeltaSrc<T> z{(const T *)dzg_b, (x_hi == 0.0) ? nullptr : (const T *)dzg_a, x_hi, x_new};
-                    if (!local)
+                    if (fused_launch) {
+                        hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, REF, false, true>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
+                                           ctx->stream, lv, ntime, ncol, (const T *)era_T, (const T *)era_QV, (const TL *)ta_pgw,
+                                           (const TL *)evap, (const T *)PS, (const T *)FIS, z, phi_era, dphi, delta_ps, adj_ps, dps_hist,
+                                           p_ref, adj_factor, 1, 1, ctx->d_status, mst, loc, ls.era_flags, ctx->d_status + 1);
+                        if (np > 1)
+                            hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, REF, false>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
+                                               ctx->stream, lv, ntime, ncol, (const T *)era_T, (const T *)era_QV, (const TL *)ta_pgw,
+                                               (const TL *)evap, (const T *)PS, (const T *)FIS, z, phi_era, dphi, delta_ps, adj_ps,
+                                               dps_hist + n2, p_ref, adj_factor, 0, np - 1, ctx->d_status, mst + 1, loc, nullptr, nullptr);
+                    } else if (!local)
                         hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, REF, false>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
                                            ctx->stream, lv, ntime, ncol, (const T *)era_T, (const T *)era_QV, (const TL *)ta_pgw,
                                            (const TL *)evap, (const T *)PS, (const T *)FIS, z, phi_era, dphi, delta_ps, adj_ps, dps_hist,
-                                           p_ref, adj_factor, first ? 1 : 0, np, ctx->d_status, mst, loc);
+                                           p_ref, adj_factor, first ? 1 : 0, np, ctx->d_status, mst, loc, nullptr, nullptr);
                     else if constexpr (V == 1)                                 // MULTI_MAXV = 1: always this branch
                         hipLaunchKernelGGL((k_ps_loop_multi<T, TL, 1, STEP_U, REF, true>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0,
                                            ctx->stream, lv, ntime, ncol, (const T *)era_T, (const T *)era_QV, (const TL *)ta_pgw,
                                            (const TL *)evap, (const T *)PS, (const T *)FIS, z, phi_era, dphi, delta_ps, adj_ps, dps_hist,
-                                           0.0, adj_factor, first ? 1 : 0, np, ctx->d_status, mst, loc);
+                                           0.0, adj_factor, first ? 1 : 0, np, ctx->d_status, mst, loc, nullptr, nullptr);
                 });
             }
             HIPCHK(ctx, hipGetLastError());
@@ -1555,6 +1588,10 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     const int N = a->nlev;
     int rc;
     int qv_done = 0;          // leading levels whose final QV the quad kernel has already written
+    // PGW_OPT_FUSED_FIRST: the quad kernel runs the first two scans of the multi-pass loop with a fixed p_ref.  float64
+    // storage only: the float32 instantiations of the quad kernel lose more than the loop kernel gains
+    const bool fused_first = dtype == PGW_F64 && ctx->opt[PGW_OPT_FUSED_FIRST] && ctx->opt[PGW_OPT_QUAD] && ctx->opt[PGW_OPT_MULTIPASS] &&
+                           !ctx->opt[PGW_OPT_FULL_COLUMN] && !a->local_p_ref && !a->i_reinterp;
     if ((rc = plev_table(ctx, a->nplev, a->plev))) return rc;
     void *evap = nullptr;
     if ((rc = ws_get(ctx, 0, (size_t)ntime * N * ncol * es, &evap))) return rc;
@@ -1614,17 +1651,48 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
         if ((rc = status_reset(ctx))) return rc;
         if (ctx->opt[PGW_OPT_QUAD]) {
             // ---- all four variables in one kernel (production)
-            const size_t qlds = (size_t)3 * N * sizeof(double);
+            const size_t qlds = (size_t)(5 * N + 2) * sizeof(double);
             qv_done = ctx->opt[PGW_OPT_FULL_COLUMN] ? 0 : ctx->n_pure;     // full-column passes read e at every level
+            LoopState ls;
+            memset(&ls, 0, sizeof(ls));
+            void *dps_hist = nullptr;
+            if (fused_first) {
+                // the delta kernel writes into the loop's state: the workspace and the armed status block come first
+                if ((rc = loop_state(ctx, (long long)ntime * ncol, &ls))) return rc;
+                if ((rc = ws_get(ctx, 6, (size_t)ntime * ncol * MULTI_MAX_PASS * sizeof(double), &dps_hist))) return rc;
+                // blocks 1 (errors of the kernel's ERA-state scan) and 2 (pass 1) of the device status
+                DevStatus *blank = ctx->h_status + 2 + MULTI_MAX_PASS;     // (run_ps_loop's zero blocks: same content)
+                for (int k = 0; k < 2; ++k) {
+                    memset(&blank[k], 0, sizeof(DevStatus));
+                    blank[k].col = ~0ull; blank[k].min_targ_bits = ~0ull; blank[k].min_src_bits = ~0ull;
+                }
+                HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + 1, blank, 2 * sizeof(DevStatus), hipMemcpyHostToDevice, ctx->stream));
+            }
             {
                 Prof pr(ctx, PGW_K_QUAD_DELTA);
-#define LAUNCH_QUAD(OT, LERP_)                                                                                        \
-                    hipLaunchKernelGGL((k_delta_quad<T, TL, QUAD_U, QUAD_TPB, OT, LERP_, REF>), dim3(nblocks((long long)ntime * ncol, QUAD_TPB)), \
+#define LAUNCH_QUAD(OT, LERP_)   do { if (fuse) LAUNCH_QUAD_(OT, LERP_, (sizeof(T) == 8)); else LAUNCH_QUAD_(OT, LERP_, false); } while (0)
+#define LAUNCH_QUAD_(OT, LERP_, FUSE_)                                                                                \
+                    hipLaunchKernelGGL((k_delta_quad<T, TL, QUAD_U, QUAD_TPB, OT, LERP_, REF, FUSE_>), dim3(nblocks((long long)ntime * ncol, QUAD_TPB)), \
                                        dim3(QUAD_TPB), qlds, ctx->stream, ctx->plev_tab, lv, ntime, ncol, (const T *)a->T,     \
                                        (const T *)a->QV, (const T *)a->U, (const T *)a->V, (const T *)a->PS, dth, ds, ph, \
                                        dwd, check_top, (TL *)a->T_out, (TL *)evap, (TL *)a->hur_pgw_out, (TL *)a->U_out,      \
-                                       (TL *)a->V_out, (TL *)a->QV_out, qv_done, ctx->n_pure, ctx->d_status)
+                                       (TL *)a->V_out, (TL *)a->QV_out, qv_done, ctx->n_pure, ctx->d_status, a->p_ref, d_ff)
                 DISPATCH_TLV(dtype, ref, 1, {
+                    const double zx = a->per_var_time ? a->zg_x_hi : a->x_hi, zn = a->per_var_time ? a->zg_x_new : a->x_new;
+                    const bool fuse = fused_first;
+                    const FusedFirst<T> ff{a->adj_factor, (const T *)a->FIS,
+                                           {(const T *)a->zg_b, zx == 0.0 ? nullptr : (const T *)a->zg_a, zx, zn},
+                                           ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, (double *)dps_hist, ls.era_flags,
+                                           ctx->d_status + 1, ctx->d_status + 2};
+                    // the kernel reads the block from device memory (the host copy is free again after this file's read-back)
+                    static_assert(sizeof(FusedFirst<T>) <= FUSED_BLOCKS * sizeof(DevStatus), "FusedFirst block");
+                    FusedFirst<T> *h_ff = (FusedFirst<T> *)(ctx->h_status + 2 + 2 * MULTI_MAX_PASS);
+                    const FusedFirst<T> *d_ff = (const FusedFirst<T> *)(ctx->d_status + 2 + MULTI_MAX_PASS);
+                    if (fuse) {
+                        *h_ff = ff;
+                        if (hipMemcpyAsync((void *)d_ff, h_ff, sizeof(ff), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+                            return fail(ctx, PGW_ERR_HIP, "hipMemcpyAsync (FusedFirst block)");
+                    }
                     PairSrc<T> dth{{(const T *)a->ta_b, exact ? nullptr : (const T *)a->ta_a, a->x_hi, a->x_new},
                                    {(const T *)a->hur_b, exact ? nullptr : (const T *)a->hur_a, a->x_hi, a->x_new}};
                     PairSrc<T> ds{{(const T *)a->tas_b, exact ? nullptr : (const T *)a->tas_a, a->x_hi, a->x_new},
@@ -1641,6 +1709,7 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
                     (void)V;
                 });
 #undef LAUNCH_QUAD
+#undef LAUNCH_QUAD_
             }
             HIPCHK(ctx, hipGetLastError());
         } else {
@@ -1690,7 +1759,7 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
                      a->local_p_ref ? a->zg3_b : a->zg_b, a->local_p_ref ? a->zg3_a : a->zg_a,
                      a->per_var_time ? a->zg_x_hi : a->x_hi, a->per_var_time ? a->zg_x_new : a->x_new, a->p_ref, a->adj_factor, a->thresh, a->max_n_iter, a->PS_out, a->QV_out, &a->n_iter,
                      a->max_err_hist, 32, a->local_p_ref ? a->nplev : 0, a->plev,
-                     !check_top && !a->local_p_ref, qv_done, ref);
+                     !check_top && !a->local_p_ref, qv_done, ref, fused_first);
     a->levels_touched = ctx->last_levels_touched;
     a->passes_launched = ctx->last_passes_launched;
     return rc;

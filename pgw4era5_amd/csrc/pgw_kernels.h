@@ -242,6 +242,52 @@ __device__ __forceinline__ double geo_finish(GeoAcc &a, double p_ref, DevStatus 
     return a.phi_s - a.rtv_s * (pgw_log(p_ref) - a.lnp_s);    // :174-179
 }
 
+// The same scan for columns whose half-level pressures are known to ascend (ps >= Levels::ps_mono_min), in fewer live
+// registers (k_delta_quad carries it beside its own state), for NS states that share their half-level pressures (the ERA
+// state and the PGW state of the loop's first pass, where delta_ps = 0): one fix_p, one logarithm and one k* test per
+// level serve all of them.  In such a column d = p_lo - p_ref only falls on the way up, so every half level with d >= 0
+// replaces the candidate before it (`d <= dmin` always holds) and k* is the last of them: instead of capturing
+// (phi_s, rtv_s, lnp_s) the candidate's phi_ref is formed at once, with geo_finish's expression on the operands
+// geo_layer would have captured, and dmin is not needed.  Same operations on the same values: same bits.
+template <int NS>
+struct GeoMono {
+    double phi[NS];        // phi at the lower half level of the current layer
+    double cand[NS];       // phi_ref if the current candidate is k*
+    double p_lo, lnp_lo;   // pressure / ln p at that half level
+    bool have;             // a candidate exists (geo_layer's kstar >= 0)
+};
+template <int NS>
+__device__ __forceinline__ void geo_mono_init(GeoMono<NS> &a, double zgs, double p_bottom, const double *logtab) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) { a.phi[i] = zgs; a.cand[i] = 0.0; }
+    a.p_lo = fix_p(p_bottom);
+    a.lnp_lo = pgw_log_tab(a.p_lo, logtab);
+    a.have = false;
+}
+// lnp_ref = pgw_log(p_ref), geo_finish's logarithm
+template <bool REF, int NS>
+__device__ __forceinline__ void geo_mono_layer(GeoMono<NS> &a, const double (&rtv)[NS], double p_top, double p_ref, double lnp_ref,
+                                               const double *logtab) {
+    double d = a.p_lo - p_ref;
+    if (d >= 0) {
+        a.have = true;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) a.cand[i] = a.phi[i] - rtv[i] * (lnp_ref - a.lnp_lo);
+    }
+    double p_hi = fix_p(p_top);
+    double lnp_hi = pgw_log_tab(p_hi, logtab);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) a.phi[i] = phi_store<REF>(a.phi[i] + rtv[i] * (a.lnp_lo - lnp_hi));
+    a.p_lo = p_hi; a.lnp_lo = lnp_hi;
+}
+template <int NS>
+__device__ __forceinline__ double geo_mono_finish(const GeoMono<NS> &a, int i, double p_ref, DevStatus *st, long long col) {
+    double d = a.p_lo - p_ref;                        // candidate k = 0: the model top is not above p_ref
+    if (d >= 0) { report(st, 14 /*PGW_ERR_PREF_AT_TOP*/, col); return __builtin_nan(""); }
+    if (!a.have) { report(st, 13 /*PGW_ERR_PREF_BELOW_SURFACE*/, col); return __builtin_nan(""); }
+    return a.cand[i];
+}
+
 // TO = type of the phi_ref output (T for the signature-faithful call, double for the loop state)
 template <typename T, int V, int U, typename TO>
 __global__ __launch_bounds__(BLOCK) void k_integ_geopot(int nlev, int ntime, long long ncol,
@@ -1542,7 +1588,30 @@ __global__ __launch_bounds__(TPB, THERMO ? 4 : 1) void k_delta_pair(PlevTable pt
 #define QLD ld_off_nt
 #define QST st_off_nt
 #define QST2 st_off
-template <typename T, typename TO, int U, int TPB, typename O, bool LERP, bool REF>
+// What the kernel does for the loop when it takes the loop's first two scans along (FUSE; fixed p_ref, multi-pass loop).
+// A template parameter, not an argument: the float32 instantiations (4 waves of 128 VGPRs, issue-bound) lose more in
+// the level loop than the loop kernel gains - even with the scans switched off at run time - so they are built without.
+// While a column is below p_ref its T, QV and then T_pgw, e are in registers, and in the loop's first pass delta_ps = 0:
+// both states stand on the same half-level pressures.  So on the way up the kernel accumulates phi_ref of the ERA state
+// (step_03:280-287) and of the PGW state (:196-199, 289), with scan_columns' expressions on the values the loop kernel
+// would read back (T_pgw and e rounded to their storage type), and at the end does what pass 1 of k_ps_loop_multi does:
+// err, adj_ps (:298-304), max |err| into the status block of pass 1, dps_hist[0] = delta_ps = 0; phi_ref_era and g * dzg
+// (:292-295) are stored for the passes that follow.  Only waves whose 64 columns all have ascending half-level
+// pressures (ps >= ps_mono_min; false for NaN) do this.  Any other wave sets its entry of `flags` (one byte per 64 columns)
+// and leaves the loop state alone: k_ps_loop_multi<.., FLAGGED = true> then runs the loop kernel's own first scan and pass for the waves
+// that hold a flagged column (both ways give the same bits).  Errors 13 / 14 of the ERA state go to `st_era`, which that
+// launch folds into the status block of the file - after every error of this kernel, as when the loop kernel found them.
+template <typename T>
+struct FusedFirst {
+    double adj_factor;
+    const T *FIS;
+    DeltaSrc<T> zg;
+    double *phi_ref_era, *dphi_clim, *delta_ps, *adj_ps, *dps_hist;
+    unsigned char *flags;
+    DevStatus *st_era, *st_pass;
+};
+
+template <typename T, typename TO, int U, int TPB, typename O, bool LERP, bool REF, bool FUSE>
 __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) void k_delta_quad(PlevTable pt, Levels lv, int ntime, long long ncol,
                                                        const T *__restrict__ fT, const T *__restrict__ fQ,
                                                        const T *__restrict__ fU, const T *__restrict__ fV,
@@ -1550,28 +1619,39 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
                                                        PairSrc<T> dth, PairSrc<T> dsfc, DeltaSrc<T> psh, PairSrc<T> dw,
                                                        int check_top, TO *__restrict__ oT, TO *__restrict__ oE,
                                                        TO *__restrict__ oHur, TO *__restrict__ oU, TO *__restrict__ oV,
-                                                       TO *__restrict__ oQ, int n_pure, int n_pure_lv, DevStatus *st) {
+                                                       TO *__restrict__ oQ, int n_pure, int n_pure_lv, DevStatus *st,
+                                                       double p_ref, const FusedFirst<T> *__restrict__ ffp) {
+    // FusedFirst is read from device memory where it is used (start and end of the walk): as a by-value argument its
+    // 30 scalar registers were loaded at the top and lived through the level loop in spilled form (v_readlane reloads)
     // n_pure > 0: the first n_pure full levels are pure-pressure levels (bkm == 0): their pressure does not depend
     // on the surface pressure, so the final QV = e_to_q(e, akm) (step_03:262-266,370) is written here already
     // (instead of e, which only the levels below p_ref and k_finalize_ps_hus need) and the finalize kernel skips them.
     // n_pure_lv: number of leading pure-pressure levels (n_pure is 0 when the QV shortcut is off); their pressure akm[l]
     // is the same in every column, so ln(akm[l]) is taken once per block instead of once per column and level
-    extern __shared__ double lds_quad[];            // akm[N] | bkm[N] | ln(akm)[N] (first n_pure_lv entries)
+    extern __shared__ double lds_quad[];            // akm[N] | bkm[N] | ln(akm)[N] (first n_pure_lv entries) | ak[N+1] | bk[N+1]
+    __shared__ double s_lnpref;                     // pgw_log(p_ref)
     __shared__ double s_mint[TPB / 64], s_mins[TPB / 64];
     __shared__ int s_nan[TPB / 64];
     __shared__ double s_lnp[MAX_PLEV];
     __shared__ double s_logt[2 * LOG_TABLE_N];      // table of pgw_log_tab: every logarithm of the delta kernels (see k_vert_interp_delta)
     const int S = pt.n;
     double *s_akm = lds_quad, *s_bkm = lds_quad + lv.nlev, *s_lnpa = lds_quad + 2 * lv.nlev;
+    double *s_ak = lds_quad + 3 * lv.nlev, *s_bk = s_ak + lv.nlev + 1;
     stage_log_table(s_logt, TPB);
     for (int i = threadIdx.x; i < MAX_PLEV; i += TPB) s_lnp[i] = pt.lnp[i];
     for (int i = threadIdx.x; i < lv.nlev; i += TPB) { s_akm[i] = lv.akm[i]; s_bkm[i] = lv.bkm[i]; }
+    if (FUSE) {
+        for (int i = threadIdx.x; i <= lv.nlev; i += TPB) { s_ak[i] = lv.ak[i]; s_bk[i] = lv.bk[i]; }
+        if (threadIdx.x == 0) s_lnpref = pgw_log(p_ref);
+    }
     __syncthreads();
     for (int i = threadIdx.x; i < n_pure_lv; i += TPB) s_lnpa[i] = pgw_log_tab(s_akm[i], s_logt);
     __syncthreads();
     long long flat = (long long)blockIdx.x * TPB + threadIdx.x;
     double min_t = __builtin_inf(), min_s = __builtin_inf();
     int nanflag = 0;
+    bool fuse_wave = false;
+    double abs_err = -1.0;                          // |err| of pass 1 in this column (FusedFirst); -1: none
     // every delta record of a file is interpolated to the same instant: ONE (x_hi, x_new) pair and one reciprocal
     // instead of the seven copies in the argument structs (28 SGPRs; the kernel was spilling scalars to VGPR lanes)
     const double x_hi = dth.a.x_hi, x_new = dth.a.x_new;
@@ -1633,18 +1713,18 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
             if (ci1 == i1) return;
             const int ih = (i1 + 1 < S) ? i1 + 1 : i1;
             const O oh = off_of(ih);
-            const bool seq = (ci1 + 1 == i1);
-            T hb0 = ld_off(sTa.b, oh), hb1 = ld_off(sHur.b, oh), ha0 = 0, ha1 = 0, lb0 = 0, lb1 = 0, la0 = 0, la1 = 0;
-            if (LERP) { ha0 = ld_off(sTa.a, oh); ha1 = ld_off(sHur.a, oh); }
+            const bool seq = (ci1 - 1 == i1);
+            const O o = off_of(i1);
+            T lb0 = ld_off(sTa.b, o), lb1 = ld_off(sHur.b, o), la0 = 0, la1 = 0, hb0 = 0, hb1 = 0, ha0 = 0, ha1 = 0;
+            if (LERP) { la0 = ld_off(sTa.a, o); la1 = ld_off(sHur.a, o); }
             if (!seq) {
-                const O o = off_of(i1);
-                lb0 = ld_off(sTa.b, o); lb1 = ld_off(sHur.b, o);
-                if (LERP) { la0 = ld_off(sTa.a, o); la1 = ld_off(sHur.a, o); }
+                hb0 = ld_off(sTa.b, oh); hb1 = ld_off(sHur.b, oh);
+                if (LERP) { ha0 = ld_off(sTa.a, oh); ha1 = ld_off(sHur.a, oh); }
             }
-            if (seq) { a_lo = a_hi; b_lo = b_hi; }
-            else { a_lo = is_sfc(i1) ? sfa : tl(sTa, lb0, la0); b_lo = is_sfc(i1) ? sfb : tl(sHur, lb1, la1); }
-            a_hi = is_sfc(ih) ? sfa : tl(sTa, hb0, ha0);
-            b_hi = is_sfc(ih) ? sfb : tl(sHur, hb1, ha1);
+            if (seq) { a_hi = a_lo; b_hi = b_lo; }
+            else { a_hi = is_sfc(ih) ? sfa : tl(sTa, hb0, ha0); b_hi = is_sfc(ih) ? sfb : tl(sHur, hb1, ha1); }
+            a_lo = is_sfc(i1) ? sfa : tl(sTa, lb0, la0);
+            b_lo = is_sfc(i1) ? sfb : tl(sHur, lb1, la1);
             ci1 = i1;
         };
         // plain-axis bracket (ci2, ci2 + 1): its lower abscissa and the reciprocal of its ln-pressure interval, taken when the
@@ -1659,74 +1739,81 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
             if (ci2 == i1) return;
             const int ih = (i1 + 1 < S) ? i1 + 1 : i1;
             const O oh = off_of(ih);
-            const bool seq = (ci2 + 1 == i1);
+            const bool seq = (ci2 - 1 == i1);
             plain_bracket(i1, ih);
-            T hb0 = ld_off(sUa.b, oh), hb1 = ld_off(sVa.b, oh), ha0 = 0, ha1 = 0, lb0 = 0, lb1 = 0, la0 = 0, la1 = 0;
-            if (LERP) { ha0 = ld_off(sUa.a, oh); ha1 = ld_off(sVa.a, oh); }
+            const O o = off_of(i1);
+            T lb0 = ld_off(sUa.b, o), lb1 = ld_off(sVa.b, o), la0 = 0, la1 = 0, hb0 = 0, hb1 = 0, ha0 = 0, ha1 = 0;
+            if (LERP) { la0 = ld_off(sUa.a, o); la1 = ld_off(sVa.a, o); }
             if (!seq) {
-                const O o = off_of(i1);
-                lb0 = ld_off(sUa.b, o); lb1 = ld_off(sVa.b, o);
-                if (LERP) { la0 = ld_off(sUa.a, o); la1 = ld_off(sVa.a, o); }
+                hb0 = ld_off(sUa.b, oh); hb1 = ld_off(sVa.b, oh);
+                if (LERP) { ha0 = ld_off(sUa.a, oh); ha1 = ld_off(sVa.a, oh); }
             }
-            if (seq) { c_lo = c_hi; d_lo = d_hi; }
-            else { c_lo = tl(sUa, lb0, la0); d_lo = tl(sVa, lb1, la1); }
-            c_hi = tl(sUa, hb0, ha0);
-            d_hi = tl(sVa, hb1, ha1);
+            if (seq) { c_hi = c_lo; d_hi = d_lo; }
+            else { c_hi = tl(sUa, hb0, ha0); d_hi = tl(sVa, hb1, ha1); }
+            c_lo = tl(sUa, lb0, la0);
+            d_lo = tl(sVa, lb1, la1);
             ci2 = i1;
         };
-        // both axes step to the same bracket (they coincide above the surface insertion): the records of all four
+        // both axes step down to the same bracket (they coincide above the surface insertion): the records of all four
         // variables in one batch
         auto fetch12 = [&](int i1) {
-            if (!(ci1 + 1 == i1 && ci2 + 1 == i1)) { fetch2(i1); fetch1(i1); return; }
-            const int ih = (i1 + 1 < S) ? i1 + 1 : i1;
-            const O oh = off_of(ih);
-            T b0 = ld_off(sTa.b, oh), b1 = ld_off(sHur.b, oh), b2 = ld_off(sUa.b, oh), b3 = ld_off(sVa.b, oh);
+            if (!(ci1 - 1 == i1 && ci2 - 1 == i1)) { fetch2(i1); fetch1(i1); return; }
+            const O o = off_of(i1);
+            T b0 = ld_off(sTa.b, o), b1 = ld_off(sHur.b, o), b2 = ld_off(sUa.b, o), b3 = ld_off(sVa.b, o);
             T a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-            if (LERP) { a0 = ld_off(sTa.a, oh); a1 = ld_off(sHur.a, oh); a2 = ld_off(sUa.a, oh); a3 = ld_off(sVa.a, oh); }
-            plain_bracket(i1, ih);
-            a_lo = a_hi; b_lo = b_hi; c_lo = c_hi; d_lo = d_hi;
-            a_hi = is_sfc(ih) ? sfa : tl(sTa, b0, a0);
-            b_hi = is_sfc(ih) ? sfb : tl(sHur, b1, a1);
-            c_hi = tl(sUa, b2, a2);
-            d_hi = tl(sVa, b3, a3);
+            if (LERP) { a0 = ld_off(sTa.a, o); a1 = ld_off(sHur.a, o); a2 = ld_off(sUa.a, o); a3 = ld_off(sVa.a, o); }
+            plain_bracket(i1, i1 + 1);
+            a_hi = a_lo; b_hi = b_lo; c_hi = c_lo; d_hi = d_lo;
+            a_lo = is_sfc(i1) ? sfa : tl(sTa, b0, a0);
+            b_lo = is_sfc(i1) ? sfb : tl(sHur, b1, a1);
+            c_lo = tl(sUa, b2, a2);
+            d_lo = tl(sVa, b3, a3);
             ci1 = ci2 = i1;
         };
         // y_hi - y_lo of the column interpolation (functions.py:575-578): numba takes it in the delta's dtype - float64
         // after a time interpolation, the file's float32 when the instant is a record (REF && !LERP)
         auto ydiff = [](double hi, double lo) -> double {
             return (REF && !LERP) ? (double)((float)hi - (float)lo) : hi - lo; };
-        int j1 = 0, j2 = 0;
-        double xprev = -__builtin_inf();
-        // ---- level loop, chunks of U levels with the next chunk's 4*U rows in flight
+        // the column is walked from the surface up: targets descend, both scans start above the last source level and
+        // step down while the level below them still satisfies the reference's rule (`src == x or src > x`)
+        int j1 = S, j2 = S;
+        double xprev = __builtin_inf();
+        // ---- the loop's first two scans (FusedFirst): wave-uniform switches, the accumulators of this lane's column
+        fuse_wave = FUSE && __all(ps >= lv.ps_mono_min);
+        if (FUSE && (threadIdx.x & 63) == 0) ffp->flags[flat >> 6] = fuse_wave ? 0 : 1;
+        bool below_pref = fuse_wave;                  // some column of the wave has not passed p_ref yet
+        GeoMono<2> geo{{0.0, 0.0}, {0.0, 0.0}, 0.0, 0.0, false};          // [0] ERA state, [1] PGW state of pass 1
+        if (FUSE && fuse_wave) geo_mono_init(geo, (double)ffp->FIS[flat], s_ak[N] + ps * s_bk[N], s_logt);          // step_03:198
+        // ---- level loop from the surface up, chunks of U levels with the next chunk's 4*U rows in flight
         T nT[U], nQ[U], nU[U], nV[U];                 // prefetched rows stay in the storage type until they are used
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            O o = base + (O)(u < N ? u : N - 1) * row;
+            O o = base + (O)((N - 1 - u) > 0 ? (N - 1 - u) : 0) * row;
             nT[u] = QLD(fT, o); nQ[u] = QLD(fQ, o); nU[u] = QLD(fU, o); nV[u] = QLD(fV, o);
         }
-        for (int l0 = 0; l0 < N; l0 += U) {
+        for (int l0 = N - 1; l0 >= 0; l0 -= U) {
             T cT[U], cQ[U], cU[U], cV[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) { cT[u] = nT[u]; cQ[u] = nQ[u]; cU[u] = nU[u]; cV[u] = nV[u]; }
-            if (l0 + U < N) {
+            if (l0 - U >= 0) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    O o = base + (O)((l0 + U + u) < N ? (l0 + U + u) : N - 1) * row;
+                    O o = base + (O)((l0 - U - u) > 0 ? (l0 - U - u) : 0) * row;
                     nT[u] = QLD(fT, o); nQ[u] = QLD(fQ, o); nU[u] = QLD(fU, o); nV[u] = QLD(fV, o);
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int l = l0 + u;
-                if (l < N) {
+                const int l = l0 - u;
+                if (l >= 0) {
                     double pa = s_akm[l] + ps * s_bkm[l];                          // step_03:87-88
                     if (check_top) { if (pa != pa) nanflag |= 1; else min_t = fmin(min_t, pa); }
                     double x;                                                      // functions.py:471
                     if (l < n_pure_lv) x = ps_finite ? s_lnpa[l] : pa;             // pa == akm[l]; NaN for a non-finite ps
                     else x = pgw_log_tab(pa, s_logt);
-                    if (!(x >= xprev)) { j1 = 0; j2 = 0; }
-                    while (j2 < S) { double xs = s_lnp[j2]; if (xs == x || xs > x) break; ++j2; }
-                    xprev = x;           // a NaN target leaves NaN here: the next level's `!(x >= xprev)` restarts the scans, as +inf did
+                    if (!(x <= xprev)) { j1 = S; j2 = S; }
+                    while (j2 > 0) { double xs = s_lnp[j2 - 1]; if (!(xs == x || xs > x)) break; --j2; }
+                    xprev = x;           // a NaN target leaves NaN here: the next level's `!(x <= xprev)` restarts the scans, as -inf did
                     // ua, va on the plain plev axis
                     double dc, dd;
                     int p1, p2;                                                    // its bracket
@@ -1762,8 +1849,8 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
                             db = b_lo + by_Dp.divide(dxp * ydiff(b_hi, b_lo));
                         }
                     } else {
-                        // j1 may lag behind (it only moves here); targets ascend, so resuming from it finds the same index
-                        while (j1 < S) { double xs = sx1(j1); if (xs == x || xs > x) break; ++j1; }
+                        // j1 only moves here: at and below the surface insertion, where the walk starts
+                        while (j1 > 0) { double xs = sx1(j1 - 1); if (!(xs == x || xs > x)) break; --j1; }
                         int i1, i2;
                         if (j1 >= S) { i1 = i2 = S - 1; }
                         else {
@@ -1795,9 +1882,41 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
                     if (l < n_pure) QST(oQ, o, (TO)e_to_q_ns(e_pgw, pa));          // pa == akm[l] for every finite ps
                     else QST2(oE, o, (TO)e_pgw);
                     if (oHur) st_off(oHur, o, (TO)hur_pgw);
+                    if (FUSE && below_pref) {                                      // layer l of both scans, as in scan_columns
+                        double rtv[2];
+                        if (REF) rtv[0] = rd_tv_f32((double)cT[u], (double)cQ[u]);
+                        else rtv[0] = CON_RD * ((double)cT[u] * (1 + 0.61 * (double)cQ[u]));   // functions.py:144
+                        const double tp = (double)(TO)ta_pgw, ep = (double)(TO)e_pgw;          // what the loop kernel reads back
+                        const double q = SharedDivisor(pa - (1 - CON_MW_MD) * ep).divide(CON_MW_MD * ep);   // e_to_q, ps_of(ps, 0) == ps
+                        rtv[1] = CON_RD * (tp * (1 + 0.61 * q));
+                        geo_mono_layer<REF>(geo, rtv, s_ak[l] + ps * s_bk[l], p_ref, s_lnpref, s_logt);
+                        below_pref = !__all(geo.p_lo < p_ref && geo.have);      // scan_columns' stop, level by level
+                    }
                 }
             }
         }
+        if (FUSE && fuse_wave) {                                                   // pass k = 0 of k_ps_loop_multi
+            const FusedFirst<T> ff = *ffp;
+            const double phi_era = geo_mono_finish(geo, 0, p_ref, ff.st_era, flat);
+            const double phi_pgw = geo_mono_finish(geo, 1, p_ref, ff.st_pass, flat);
+            double dphi;
+            if (REF && !ff.zg.a) dphi = (double)((float)ff.zg.b[flat] * (float)CON_G);                    // see k_dphi_clim
+            else dphi = ff.zg.template get<REF>(flat) * CON_G;                                            // step_03:292-295
+            const double tlow = (double)ld_off(oT, obase + (O)(N - 1) * orow);     // T_pgw of the lowest level as stored above, :303
+            const double err = (phi_pgw - phi_era) - dphi;                         // :289,298
+            const double fps = REF ? (double)((float)(-ff.adj_factor) * (float)ps) : -ff.adj_factor * ps;
+            const double ae = fabs(err);
+            if (ae == ae) abs_err = ae;                                            // :308 skipna
+            ff.phi_ref_era[flat] = phi_era;
+            ff.dphi_clim[flat] = dphi;
+            ff.dps_hist[flat] = 0.0;                                               // next_delta_ps(0, 0), :182-184,192
+            ff.delta_ps[flat] = 0.0;
+            ff.adj_ps[flat] = fps / (CON_RD * tlow) * err;                         // :301-304
+        }
+    }
+    if (FUSE) {                                        // all lanes of the wave meet here (wave_max shuffles)
+        const double wm = wave_max(abs_err);
+        if ((threadIdx.x & 63) == 0 && wm >= 0.0) { DevStatus *sp = ffp->st_pass; atomicMax(&sp->max_bits, dbits(wm)); atomicAdd(&sp->valid, 1ull); }
     }
     if (check_top) {
         double wt = wave_min(min_t), ws = wave_min(min_s);
@@ -2202,6 +2321,11 @@ __global__ __launch_bounds__(BLOCK) void k_dphi_clim(long long n, DeltaSrc<T> z,
 // 0.03-0.045 ms of a 0.22 ms pass) and one host round trip per pass.  Each pass re-reads its rows (L2 / Infinity Cache / HBM).
 // `first` != 0 (first launch of a file): phi_ref of the ERA state (step_03:280-287) and g * dzg (:292-295) are computed
 // here and stored for continuation launches; delta_ps = adj_ps = 0 (:182-184).
+// FLAGGED (with first != 0, npass = 1): the launch that follows a k_delta_quad<.., FUSE = true>.  That kernel has done the
+// ERA-state scan and pass 1 for every group of 64 columns whose byte in `flags` is 0; here only the waves that hold a
+// flagged column run (scan, zeroed state, pass 1, for all of their columns: the same bits), the others leave at once, and
+// thread 0 folds the errors of the delta kernel's ERA-state scan (`st_era`) into `st0`.  The passes after the first then
+// run as a continuation launch (first = 0) of the unchanged FLAGGED = false instantiation.
 // -------------------------------------------------------------------------------------
 constexpr int MULTI_MAX_PASS = 8;
 #ifndef MULTI_MINW
@@ -2215,7 +2339,7 @@ constexpr int MULTI_MAX_PASS = 8;
 // continuation launch resumes from.  One column per lane (V = 1).
 struct LocalPRef { PlevTable pt; double akN, bkN; double *p_ref_col; int *p_idx_col; };
 
-template <typename T, typename TL, int V, int U, bool REF, bool LOCAL>
+template <typename T, typename TL, int V, int U, bool REF, bool LOCAL, bool FLAGGED = false>
 __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, int ntime, long long ncol,
                                                          const T *__restrict__ Tera, const T *__restrict__ QVera,
                                                          const TL *__restrict__ ta, const TL *__restrict__ evap,
@@ -2226,8 +2350,11 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
                                                          double *__restrict__ dps_hist /* [npass][ntime*ncol] */,
                                                          double p_ref_s, double adj_factor, int first, int npass,
                                                          DevStatus *st0 /* errors of the ERA-state scan */,
-                                                         DevStatus *st /* [npass] */, LocalPRef loc) {
+                                                         DevStatus *st /* [npass] */, LocalPRef loc,
+                                                         const unsigned char *__restrict__ flags = nullptr,
+                                                         const DevStatus *st_era = nullptr) {
     static_assert(!LOCAL || V == 1, "local p_ref: one column per lane");
+    static_assert(!FLAGGED || !LOCAL, "the fused first pass needs a fixed p_ref");
     __shared__ unsigned long long s_max[MULTI_MAX_PASS];          // per pass: max |err| as ordered bits, #valid, levels read
     __shared__ unsigned int s_valid[MULTI_MAX_PASS];
     __shared__ unsigned long long s_touched[MULTI_MAX_PASS];
@@ -2243,7 +2370,16 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
     // there made an all-NaN partial wave "valid" with |err| = 0).
     const bool live = g < ngroups;
     if (!live) g = ngroups - 1;
-    {
+    bool run = true;
+    if (FLAGGED) {
+        const long long c2 = g * V;
+        bool flagged = false;
+#pragma unroll
+        for (int v = 0; v < V; ++v) flagged = flagged || flags[(c2 + v) >> 6] != 0;
+        run = __any(flagged);
+        if (blockIdx.x == 0 && threadIdx.x == 0 && st_era->code != 0) report(st0, st_era->code, (long long)st_era->col);
+    }
+    if (run) {
         ColIdx ix = col_index(g, V, ncol);
         const int N = lv.nlev;
         long long c2 = ix.t * ncol + ix.c;
