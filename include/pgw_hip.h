@@ -63,7 +63,8 @@ enum pgw_kernel_id {
     PGW_K_ADJUST_PS_STEP = 7, PGW_K_REGRID = 8, PGW_K_SURFACE = 9, PGW_K_FINALIZE = 10,
     PGW_K_THERMO_DELTA = 11, PGW_K_WIND_DELTA = 12, PGW_K_PHI_REF_HYBRID = 13, PGW_K_QUAD_DELTA = 14,
     PGW_K_BYTESWAP = 15, PGW_K_HARMONIC = 16, PGW_K_GAUSS_INTERP = 17, PGW_K_PS_LOOP_MULTI = 18,
-    PGW_K_COUNT = 19
+    PGW_K_HYBRID_TO_PLEV = 19, PGW_K_MAGNUS_RH = 20, PGW_K_HUR_MERGE = 21,
+    PGW_K_COUNT = 22
 };
 
 /* per-context options (pgw_set_option).  Defaults come from the environment variables named below, which are read
@@ -503,6 +504,47 @@ int pgw_test_shared_div(pgw_ctx *ctx, long long n, const double *num, const doub
 /* integrate_tos(tos_field, ts_field, land_frac, ice_frac)  functions.py:1145-1186, flat over n */
 int pgw_integrate_tos(pgw_ctx *ctx, int dtype, long long n, const void *tos, const void *ts,
                       const void *land, const void *ice, void *out);
+
+/* ---------------------------------------------------------------- step_01 ------------ */
+/* s1 model levels -> fixed pressure levels, fused       step_01_extract_deltas/CFday_interp_to_plev.py:89-134
+ * = interp_logp_4d(var, ap + b * ps, targ_plev broadcast to every column, extrapolate) for one block of time steps,
+ * without either 4-D pressure field: the source pressure ap[k] + b[k] * ps (:91) is formed per column in registers,
+ * the logarithms of the one target list are taken once per thread block.
+ *  var (ntime, nsrc, ncol), ps (ntime, ncol): device arrays of dtype_in; out (ntime, ntarg, ncol): device, dtype_out.
+ *  ap, b (nsrc), targ_plev (ntarg): HOST arrays; nsrc in [2, 256], ntarg in [1, 256].
+ *  src_reversed != 0: var, ap, b are stored with pressure DESCENDING along the level axis (surface first) and are read in
+ *    reverse, which is the reference's reindex of :89; the kernel requires ascending source pressure like
+ *    functions.py:500-501 (PGW_ERR_SRC_NOT_ASCENDING).  targ_plev is given ascending (np.sort, :114;
+ *    PGW_ERR_TARG_NOT_ASCENDING when its last logarithm is below its first, functions.py:502-503); a list that is not
+ *    monotone in between is served like interp_extrap_1d serves it.
+ *  out_reversed != 0: row l of out holds target ntarg - 1 - l (pressure descending, :133-134).
+ *  extrapolate: enum pgw_extrap; 'off' reports PGW_ERR_EXTRAP_OFF with the smallest offending column (pgw_error_column).
+ *  dtype pairs: F32 -> F64 is the reference's dtype flow on float32 files (source pressure float64, src_y[i2] - src_y[i1]
+ *    taken in float32 as numba does at functions.py:575-578, everything else and the result float64); F64 -> F64 is
+ *    plain float64; F32 -> F32 is float64 arithmetic narrowed on the store (half the output; NOT the reference's bits).
+ *    F64 -> F32 is not offered. */
+int pgw_interp_hybrid_to_plev(pgw_ctx *ctx, int dtype_in, int dtype_out, int ntime, int nsrc, int ntarg, long long ncol,
+                              const void *var, const void *ps, const double *ap, const double *b,
+                              const double *targ_plev, int extrapolate, int src_reversed, int out_reversed, void *out);
+
+/* s2 specific_to_relative_humidity(QV, P, T) of step_01_extract_deltas/Emon_convert_hus_to_hur.py:16-21 (a Magnus
+ * formula; NOT the IFS formulas of functions.py:107-116):
+ *   RH = 0.263 * P * QV * (exp(17.67 * (T - 273.15) / (T - 29.65)))**(-1)
+ * qv, ta (ntime, nplev, ncol) device arrays of `dtype`; plev (nplev) HOST array, the pressure of each level (:53-55 make a
+ * 4-D array of it; none exists here); rh (ntime, nplev, ncol) device, ALWAYS float64: on float32 files numpy evaluates
+ * the exponent, exp and the reciprocal in float32 and the three-factor product in float64 (P is float64). */
+int pgw_magnus_rh(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const void *qv, const double *plev,
+                  const void *ta, double *rh);
+
+/* s3 the coarse Amon hur carried onto the finer Emon levels     Emon_convert_hus_to_hur.py:82-122
+ * hur (ntime, nplev, ncol) float64: the computed Emon field; amon (ntime, namon, ncol) of dtype_amon; out like hur.
+ * Level table (HOST int arrays of length nplev, made by the caller from the two plev coordinates): copy_from[l] >= 0:
+ * out level l = amon level copy_from[l] as it is (:122); otherwise (:85-118)
+ *   a = |hur[l] - hur[e_above[l]]|, b = |hur[l] - hur[e_below[l]]|, w_above = 1 - a / (a + b), w_below = 1 - b / (a + b),
+ *   out = amon[a_above[l]] * w_above + amon[a_below[l]] * w_below        (float64, this order; 0 / 0 = NaN is kept). */
+int pgw_hur_merge_levels(pgw_ctx *ctx, int dtype_amon, int ntime, int nplev, int namon, long long ncol, const double *hur,
+                         const void *amon, const int *copy_from, const int *e_above, const int *e_below,
+                         const int *a_above, const int *a_below, double *out);
 
 #ifdef __cplusplus
 }

@@ -645,6 +645,124 @@ extern "C" int pgw_interp_logp_4d(pgw_ctx *ctx, int dtype, int ntime, int nsrc, 
     return status_check(ctx);
 }
 
+// ------------------------------------------------------------------ step_01: model levels -> pressure levels
+#ifndef PGW_H2P_MAX_V
+#define PGW_H2P_MAX_V 1
+#endif
+constexpr int H2P_MAX_V = PGW_H2P_MAX_V;      // 1 or 2 columns per thread of k_hybrid_to_plev (see pgw_interp_hybrid_to_plev)
+static_assert(H2P_MAX_V == 1 || H2P_MAX_V == 2, "PGW_H2P_MAX_V");
+template <typename TI, typename TO, int V, typename O>
+static void launch_hybrid_to_plev(pgw_ctx *ctx, int mode, int ntime, int S, int N, long long ncol, const void *var,
+                                  const void *ps, const double *d_ap, const double *d_b, const double *d_plev,
+                                  int src_rev, int out_rev, void *out) {
+    const dim3 grid(nblocks((long long)ntime * ncol / V, BLOCK));
+#define H2P(M) hipLaunchKernelGGL((k_hybrid_to_plev<TI, TO, V, M, O>), grid, dim3(BLOCK), 0, ctx->stream, ntime, S, N, ncol, \
+                                  (const TI *)var, (const TI *)ps, d_ap, d_b, d_plev, src_rev, out_rev, (TO *)out, ctx->d_status)
+    switch (mode) {
+        case 0: H2P(0); break;
+        case 1: H2P(1); break;
+        case 2: H2P(2); break;
+        default: H2P(3); break;
+    }
+#undef H2P
+}
+
+extern "C" int pgw_interp_hybrid_to_plev(pgw_ctx *ctx, int dtype_in, int dtype_out, int ntime, int nsrc, int ntarg,
+                                         long long ncol, const void *var, const void *ps, const double *ap,
+                                         const double *b, const double *targ_plev, int extrapolate, int src_reversed,
+                                         int out_reversed, void *out) {
+    CHECK_COMMON(ctx, dtype_in, ntime, ncol);
+    NEED(ctx, dtype_out == PGW_F64 || (dtype_out == PGW_F32 && dtype_in == PGW_F32), "dtype pair must be F32->F64, F64->F64 or F32->F32");
+    NEED(ctx, nsrc >= 2 && nsrc <= MAX_NLEV, "nsrc must be in [2, 256]");
+    NEED(ctx, ntarg >= 1 && ntarg <= MAX_TARG_PLEV, "ntarg must be in [1, 256]");
+    NEED(ctx, var && ps && ap && b && targ_plev && out, "null pointer");
+    if (extrapolate < 0 || extrapolate > 3) return fail(ctx, PGW_ERR_ARG, "Invalid input value for \"extrapolate\"");
+    int rc = status_reset(ctx);
+    if (rc) return rc;
+    // ap | b | targ_plev -> the context's small device scratch (pageable source: the copy has left the caller's arrays on return)
+    double *d_ap = ctx->d_small, *d_b = d_ap + MAX_NLEV, *d_plev = d_b + MAX_NLEV;
+    HIPCHK(ctx, hipMemcpyAsync(d_ap, ap, sizeof(double) * nsrc, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_b, b, sizeof(double) * nsrc, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_plev, targ_plev, sizeof(double) * ntarg, hipMemcpyHostToDevice, ctx->stream));
+    const size_t s_in = dtype_in == PGW_F64 ? 8 : 4, s_out = dtype_out == PGW_F64 ? 8 : 4;
+    // columns per thread: the kernel is bound by instruction issue (about 95 logarithms and 99 interpolations per column),
+    // not by its streams, and the second column's registers cost a wave per SIMD (122 -> 4 waves against 88 -> 5): same
+    // box, S = 95, N = 99, 2 GB in, V = 2 / 1: 2.57 / 2.35 ms (float32 in), 1.40 / 1.30 ms (float64 in).  PGW_H2P_MAX_V = 2
+    // compiles the two-column form in (16-B stores per lane); pick_vec then chooses it by shape and alignment.
+    const int vec = pick_vec(ctx, dtype_in, ncol, {var, ps, out}, H2P_MAX_V);
+    const unsigned long long big_in = (unsigned long long)ntime * nsrc * ncol * s_in, big_out = (unsigned long long)ntime * ntarg * ncol * s_out;
+    const bool o32 = big_in < (1ull << 32) && big_out < (1ull << 32) && !ctx->opt[PGW_OPT_FORCE_OFF64];
+    const int sr = src_reversed != 0, orv = out_reversed != 0;
+    {
+        Prof pr(ctx, PGW_K_HYBRID_TO_PLEV);
+#define H2P_V(TI_, TO_, O_)                                                                                                       \
+    do {                                                                                                                          \
+        if constexpr (H2P_MAX_V >= 2) {                                                                                           \
+            if (vec == 2) { launch_hybrid_to_plev<TI_, TO_, H2P_MAX_V, O_>(ctx, extrapolate, ntime, nsrc, ntarg, ncol, var, ps, d_ap, d_b, d_plev, sr, orv, out); break; } \
+        }                                                                                                                         \
+        launch_hybrid_to_plev<TI_, TO_, 1, O_>(ctx, extrapolate, ntime, nsrc, ntarg, ncol, var, ps, d_ap, d_b, d_plev, sr, orv, out);             \
+    } while (0)
+#define H2P_O(TI_, TO_) do { if (o32) H2P_V(TI_, TO_, boff32); else H2P_V(TI_, TO_, boff64); } while (0)
+        if (dtype_in == PGW_F64) H2P_O(double, double);
+        else if (dtype_out == PGW_F64) H2P_O(float, double);
+        else H2P_O(float, float);
+#undef H2P_O
+#undef H2P_V
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return status_check(ctx);
+}
+
+// ------------------------------------------------------------------ step_01: Emon hus -> hur
+extern "C" int pgw_magnus_rh(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const void *qv,
+                             const double *plev, const void *ta, double *rh) {
+    CHECK_COMMON(ctx, dtype, ntime, ncol);
+    NEED(ctx, nplev >= 1 && nplev <= MAX_TARG_PLEV, "nplev must be in [1, 256]");
+    NEED(ctx, qv && plev && ta && rh, "null pointer");
+    double *d_plev = ctx->d_small;
+    HIPCHK(ctx, hipMemcpyAsync(d_plev, plev, sizeof(double) * nplev, hipMemcpyHostToDevice, ctx->stream));
+    const long long n = (long long)ntime * nplev * ncol;
+    unsigned int nb = nblocks(n, BLOCK);
+    if (nb > 256 * 16) nb = 256 * 16;
+    {
+        Prof pr(ctx, PGW_K_MAGNUS_RH);
+        DISPATCH_T(dtype, hipLaunchKernelGGL((k_magnus_rh<T>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, nplev, ncol,
+                                             (const T *)qv, d_plev, (const T *)ta, rh));
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_hur_merge_levels(pgw_ctx *ctx, int dtype_amon, int ntime, int nplev, int namon, long long ncol,
+                                    const double *hur, const void *amon, const int *copy_from, const int *e_above,
+                                    const int *e_below, const int *a_above, const int *a_below, double *out) {
+    CHECK_COMMON(ctx, dtype_amon, ntime, ncol);
+    NEED(ctx, nplev >= 1 && nplev <= MAX_TARG_PLEV && namon >= 1, "nplev must be in [1, 256], namon positive");
+    NEED(ctx, hur && amon && copy_from && e_above && e_below && a_above && a_below && out, "null pointer");
+    NEED(ctx, hur != out, "out must not alias hur");
+    std::vector<MergeLevel> tab(nplev);
+    for (int l = 0; l < nplev; ++l) {
+        MergeLevel m = {copy_from[l], e_above[l], e_below[l], a_above[l], a_below[l]};
+        if (m.copy >= 0) NEED(ctx, m.copy < namon, "copy_from out of range");
+        else NEED(ctx, m.e_above >= 0 && m.e_above < nplev && m.e_below >= 0 && m.e_below < nplev && m.a_above >= 0 &&
+                       m.a_above < namon && m.a_below >= 0 && m.a_below < namon, "level table out of range");
+        tab[l] = m;
+    }
+    MergeLevel *d_tab = (MergeLevel *)ctx->d_small;
+    HIPCHK(ctx, hipMemcpyAsync(d_tab, tab.data(), sizeof(MergeLevel) * nplev, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // `tab` goes out of scope
+    const long long n = (long long)ntime * nplev * ncol;
+    unsigned int nb = nblocks(n, BLOCK);
+    if (nb > 256 * 16) nb = 256 * 16;
+    {
+        Prof pr(ctx, PGW_K_HUR_MERGE);
+        DISPATCH_T(dtype_amon, hipLaunchKernelGGL((k_hur_merge_levels<T>), dim3(nb), dim3(BLOCK), 0, ctx->stream, ntime, nplev,
+                                                  namon, ncol, hur, (const T *)amon, d_tab, out));
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
 // ------------------------------------------------------------------ time lerp
 extern "C" int pgw_time_lerp(pgw_ctx *ctx, int dtype, long long n, const void *v_before, const void *v_after,
                              double x_hi, double x_new, void *out) {

@@ -712,8 +712,216 @@ __global__ __launch_bounds__(BLOCK, PGW_INTERP_MINB) void k_interp_logp_stream(i
 }
 
 #undef PGW_LOGT
+
 // =====================================================================================
-// a7  time lerp of load_delta                                   functions.py:288-292
+// s1  hybrid model levels -> fixed pressure levels, fused      step_01_extract_deltas/CFday_interp_to_plev.py:89-134
+// The source pressure of a column is ap[k] + b[k] * ps (:91; product, then sum: two roundings), formed in registers
+// from ap / b staged in LDS and the column's one ps; the targets are ONE ascending list (:114) whose logarithms are
+// taken once per block into LDS with the logarithm the source pressures go through (pgw_log_tab), so that the
+// exact-hit rule (functions.py:540) sees equal logarithms for equal pressures.  No pressure field exists in memory:
+// per column S * sizeof(TI) + sizeof(TI) bytes in, N * sizeof(TO) out, about S logarithms.
+// Selection and arithmetic are interp_extrap_1d's (functions.py:511-580) as in k_interp_logp_stream above: the same
+// register window (levels j-2 .. j+1 of the scan position j, the load of level j+2 in flight), the same restart for
+// a target below its predecessor or NaN (only a non-monotone list takes it; the list is uniform, so a whole wave does).
+// One thread owns V adjacent columns: the target loop is uniform over the wave, so each target level is one
+// V-wide streaming store per lane (one coalesced segment per wave); every column keeps its own scan position, its
+// source loads are per column (neighbouring lanes -> neighbouring addresses while their surface pressures are close).
+// The C-ABI dispatches V = 1: the kernel is issue-bound and the second column's registers cost occupancy (pgw_capi.hip).
+// src_rev / out_rev: the file's level order is surface-first (:89) / the result is wanted with pressure descending
+// (:133-134) - index arithmetic on var, ap, b and on the output row, nothing is copied.
+// TI = float, TO = double is the reference's dtype flow on CFday files: src_y[i2] - src_y[i1] in float32 (numba,
+// functions.py:575-578), everything else float64.  TI = TO: float64 arithmetic, narrowed on the store.
+// =====================================================================================
+constexpr int MAX_TARG_PLEV = 256;
+template <typename TI, typename TO, int V, int MODE, typename O>
+__global__ __launch_bounds__(BLOCK) void k_hybrid_to_plev(int ntime, int S, int N, long long ncol,
+                                                          const TI *__restrict__ var, const TI *__restrict__ ps,
+                                                          const double *__restrict__ ap, const double *__restrict__ b,
+                                                          const double *__restrict__ plev, int src_rev, int out_rev,
+                                                          TO *__restrict__ out, DevStatus *st) {
+    __shared__ double s_logt[2 * LOG_TABLE_N];
+    __shared__ double s_ap[MAX_NLEV], s_b[MAX_NLEV];       // pressure ascending with the index
+    __shared__ double s_lx[MAX_TARG_PLEV];                 // ln(target), :471
+    // the leading levels with b = 0 (the model's pure-pressure levels, about a third of a CMIP6 model's) have the same
+    // pressure ap + 0 * ps = ap in every column with a finite ps: their logarithms are taken once per block
+    __shared__ double s_lap[MAX_NLEV];
+    __shared__ int s_npure;
+    stage_log_table(s_logt, BLOCK);
+    if (threadIdx.x == 0) s_npure = S;
+    for (int i = threadIdx.x; i < S; i += BLOCK) {
+        const int k = src_rev ? S - 1 - i : i;
+        s_ap[i] = ap[k]; s_b[i] = b[k];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < N; i += BLOCK) s_lx[i] = pgw_log_tab(plev[i], s_logt);
+    for (int i = threadIdx.x; i < S; i += BLOCK) {
+        s_lap[i] = pgw_log_tab(s_ap[i], s_logt);
+        if (!(s_b[i] == 0.0)) atomicMin(&s_npure, i);
+    }
+    __syncthreads();
+    const int n_pure = s_npure;
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= (long long)ntime * ncol / V) return;
+    const long long flat = g * V;                          // V | ncol: a group lies within one time step
+    const long long t = flat / ncol, c = flat - t * ncol;
+    if (g == 0 && s_lx[N - 1] < s_lx[0]) report(st, 11, 0);               // functions.py:502-503 (the same list in every column)
+    double psv[V];
+    loadv<TI, V>(ps + flat, psv);
+    const O rowb_in = (O)((unsigned long long)ncol * sizeof(TI)), rowb_out = (O)((unsigned long long)ncol * sizeof(TO));
+    const O ov = (O)((unsigned long long)(t * S * ncol + c) * sizeof(TI));
+    const O oo = (O)((unsigned long long)(t * N * ncol + c) * sizeof(TO));
+    bool ps_finite[V];                                                     // 0 * ps = 0: not for NaN / inf
+#pragma unroll
+    for (int v = 0; v < V; ++v) ps_finite[v] = (psv[v] - psv[v] == 0.0);
+    auto srcx = [&](int k, int v) {                                        // ln(ap + b * ps), :91 and functions.py:470
+        const int kk = k < S ? k : S - 1;
+        if (kk < n_pure && ps_finite[v]) return s_lap[kk];
+        return pgw_log_tab(no_speculate(s_ap[kk] + s_b[kk] * psv[v]), s_logt);
+    };
+    auto ldy = [&](int k, int v) {
+        const int kk = k < S ? k : S - 1;
+        const int fk = src_rev ? S - 1 - kk : kk;
+        return ld_off_nt<TI, O>(var, ov + (O)fk * rowb_in + (O)(v * sizeof(TI)));
+    };
+    int j[V];
+    double xmm[V], ymm[V], xm[V], ym[V], xj[V], yj[V], xn[V], yn[V], x_first[V];
+    // source levels j+2 .. j+1+H2P_DEPTH of every column: loads in flight ahead of the window.  Same box, S = 95, N = 99,
+    // 2 GB in, V = 2: depth 1 / 4 / 8 = 2.83 / 2.60 / 3.11 ms for float32 in (one register per level) and 1.45 / 1.69 /
+    // 2.31 ms for float64 in (two registers per level: the occupancy they cost outweighs the loads)
+    constexpr int H2P_DEPTH = sizeof(TI) == 4 ? 4 : 1;
+    TI ry[V][H2P_DEPTH];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        x_first[v] = srcx(0, v);
+        if (srcx(S - 1, v) < x_first[v]) report(st, 10, flat + v);        // functions.py:500-501
+    }
+    auto reset = [&]() {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            j[v] = 0;
+            xmm[v] = ymm[v] = xm[v] = ym[v] = 0;
+            xj[v] = x_first[v]; yj[v] = (double)ldy(0, v);
+            xn[v] = srcx(1, v); yn[v] = (double)ldy(1, v);                 // S >= 2
+#pragma unroll
+            for (int d = 0; d < H2P_DEPTH; ++d) ry[v][d] = ldy(2 + d, v);
+        }
+    };
+    reset();
+    double xprev = -__builtin_inf();
+    for (int l = 0; l < N; ++l) {
+        double x = s_lx[l];
+        if (__builtin_expect(!(x >= xprev), 0)) {                          // restart (descending or NaN target)
+            x = no_speculate(x);
+            reset();
+        }
+        double y[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            while (j[v] < S && !(xj[v] == x || xj[v] > x)) {               // first s with src[s] == x or src[s] > x
+                xmm[v] = xm[v]; ymm[v] = ym[v]; xm[v] = xj[v]; ym[v] = yj[v]; xj[v] = xn[v]; yj[v] = yn[v];
+                yn[v] = (double)ry[v][0];
+#pragma unroll
+                for (int d = 0; d + 1 < H2P_DEPTH; ++d) ry[v][d] = ry[v][d + 1];
+                ++j[v];
+                xn[v] = srcx(j[v] + 1, v);
+                ry[v][H2P_DEPTH - 1] = ldy(j[v] + 1 + H2P_DEPTH, v);
+            }
+            auto diff = [](double y2, double y1) {                         // src_y[i2] - src_y[i1], :577
+                if constexpr (sizeof(TI) == 4 && sizeof(TO) == 8) return (double)((float)y2 - (float)y1);       // numba: float32 - float32
+                else return y2 - y1;
+            };
+            // the scan stopped at the first level with src == x or src > x; 0 < j < S and src > x is the bracket (:545-548),
+            // which is nearly every target: the other three cases sit behind one real branch
+            if (__builtin_expect(j[v] > 0 && j[v] < S && !(xj[v] == x), 1)) {
+                y[v] = ym[v] + (x - xm[v]) * diff(yj[v], ym[v]) / (xj[v] - xm[v]);                           // :575-578
+            } else {
+                const double xs = no_speculate(x);
+                bool extrap = true, same = (MODE != 1);                    // same: i1 == i2, take y1
+                double x1, y1, x2, y2;
+                if (j[v] >= S) {                                           // above range            :554-561
+                    x1 = (MODE == 1) ? xmm[v] : xm[v]; y1 = (MODE == 1) ? ymm[v] : ym[v]; x2 = xm[v]; y2 = ym[v];
+                } else if (xj[v] == xs) {                                  // exact                  :540-543
+                    extrap = false; same = true; x1 = x2 = xj[v]; y1 = y2 = yj[v];
+                } else {                                                   // j == 0: below range    :530-538
+                    x1 = xj[v]; y1 = yj[v]; x2 = xn[v]; y2 = yn[v];
+                }
+                if (extrap && MODE == 3) y[v] = __builtin_nan("");         // :569-570
+                else if (same) y[v] = y1;                                  // :572-573
+                else y[v] = y1 + (xs - x1) * diff(y2, y1) / (x2 - x1);     // :575-578
+                if (MODE == 0 && extrap) report(st, 12, flat + v);         // :564-566
+            }
+        }
+        const O orow = oo + (O)(out_rev ? N - 1 - l : l) * rowb_out;
+        storev_nt<TO, V>(reinterpret_cast<TO *>(reinterpret_cast<char *>(out) + orow), y);
+        xprev = (x == x) ? x : __builtin_inf();                            // after a NaN target: restart
+    }
+}
+
+// =====================================================================================
+// s2  Magnus relative humidity of the Emon conversion          step_01_extract_deltas/Emon_convert_hus_to_hur.py:16-21
+// RH = 0.263 * P * QV * (exp(17.67 * (T - 273.15) / (T - 29.65)))**(-1) on (time, plev, column) arrays, P the 1-D plev
+// coordinate (float64).  numpy's dtype flow on float32 files: 0.263 * P is float64, so both products are float64;
+// the exponent, exp and the reciprocal (x**(-1) = 1 / x) are float32.  float64 files: float64 throughout.
+// =====================================================================================
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_magnus_rh(long long n, int nplev, long long ncol, const T *__restrict__ qv,
+                                                     const double *__restrict__ plev, const T *__restrict__ ta,
+                                                     double *__restrict__ rh) {
+    const long long stride = (long long)gridDim.x * BLOCK;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        const double p = plev[(i / ncol) % nplev];
+        const T tk = SIG_LD(ta + i);
+        const double q = (double)SIG_LD(qv + i);
+        double r;
+        if constexpr (sizeof(T) == 4) {
+            const float a = 17.67f * (tk - 273.15f) / (tk - 29.65f);
+            // pgw_expf_core is expf without its range selects: |a| < 87 covers every temperature above 36 K
+            const float e = (a > -87.0f && a < 87.0f) ? pgw_expf_core(a) : expf(a);
+            r = (double)(1.0f / e);
+        } else {
+            const double a = 17.67 * (tk - 273.15) / (tk - 29.65);
+            const double e = (a > -700.0 && a < 700.0) ? pgw_exp_finite(a) : pgw_exp(a);
+            r = 1.0 / e;
+        }
+        SIG_ST(0.263 * p * q * r, rh + i);
+    }
+}
+
+// =====================================================================================
+// s3  coarse Amon hur carried onto the finer Emon levels       step_01_extract_deltas/Emon_convert_hus_to_hur.py:82-122
+// Per Emon level l the host table holds either (copy = Amon index, :122) or the three Emon indices (l, the nearest
+// Amon level above = lower pressure, below = higher pressure: :85-96) and the two Amon indices (:113-114).
+// a = |hur_l - hur_above|, b = |hur_l - hur_below|, w_above = 1 - a / (a + b), w_below = 1 - b / (a + b),
+// out = amon_above * w_above + amon_below * w_below in this order; 0 / 0 = NaN is kept.  float64 arithmetic only.
+// =====================================================================================
+struct MergeLevel { int copy, e_above, e_below, a_above, a_below; };       // copy >= 0: take Amon level `copy`
+template <typename TA>
+__global__ __launch_bounds__(BLOCK) void k_hur_merge_levels(int ntime, int nplev, int namon, long long ncol,
+                                                            const double *__restrict__ hur, const TA *__restrict__ amon,
+                                                            const MergeLevel *__restrict__ tab, double *__restrict__ out) {
+    const long long n = (long long)ntime * nplev * ncol;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        const long long row = i / ncol, c = i - row * ncol;
+        const long long t = row / nplev;
+        const int l = (int)(row - t * nplev);
+        const MergeLevel m = tab[l];
+        const double *h = hur + t * nplev * ncol + c;
+        const TA *a = amon + t * namon * ncol + c;
+        double r;
+        if (m.copy >= 0) r = (double)a[(long long)m.copy * ncol];
+        else {
+            const double hl = h[(long long)l * ncol], ha = h[(long long)m.e_above * ncol], hb = h[(long long)m.e_below * ncol];
+            const double da = fabs(hl - ha), db = fabs(hl - hb);
+            const double wa = 1 - da / (da + db), wb = 1 - db / (da + db);
+            r = (double)a[(long long)m.a_above * ncol] * wa + (double)a[(long long)m.a_below * ncol] * wb;
+        }
+        out[i] = r;
+    }
+}
+
+// =====================================================================================
+// a7  time lerp of load_delta                                  functions.py:288-292
 // =====================================================================================
 template <typename T, int V>
 __global__ __launch_bounds__(BLOCK) void k_time_lerp(long long n, const T *__restrict__ vb, const T *__restrict__ va,
