@@ -88,7 +88,10 @@ enum pgw_option {
                                  registers; 0: the first loop launch does.  Same bits either way (see pgw_step03_file).  Takes
                                  effect with PGW_OPT_QUAD = 1, PGW_OPT_MULTIPASS = 1, PGW_OPT_FULL_COLUMN = 0, a fixed p_ref
                                  and i_reinterp = 0                                                              [PGW_FUSED_FIRST] */
-    PGW_OPT_COUNT = 8
+    PGW_OPT_MIXED_VEC = 8,    /* columns / elements per thread of the `_mixed` entries (operands of different element size), cap:
+                                 4 (default): a float32 row is one 16-byte access per lane, a float64 row beside it two; 2: 8 and
+                                 16 bytes; 1: scalar.  A/B knob of tools/function_flow_time.py                                       */
+    PGW_OPT_COUNT = 9
 };
 
 /* ---------------------------------------------------------------- context ------------ */
@@ -504,6 +507,63 @@ int pgw_test_shared_div(pgw_ctx *ctx, long long n, const double *num, const doub
 /* integrate_tos(tos_field, ts_field, land_frac, ice_frac)  functions.py:1145-1186, flat over n */
 int pgw_integrate_tos(pgw_ctx *ctx, int dtype, long long n, const void *tos, const void *ts,
                       const void *land, const void *ice, void *out);
+
+/* ---------------------------------------------------------------- reference dtype flow, function level ---- */
+/* settings.function_dtype_flow = 'reference' of pgw4era5_amd/functions.py.  The entries above take ONE `dtype` for all
+ * operands and compute in fp64.  These take one dtype tag (PGW_F32 / PGW_F64) PER OPERAND, read every operand in its own
+ * storage type and reproduce numpy's promotion through the cited reference lines: a python-float constant takes the type of
+ * the array it meets, float32 (op) float32 is ONE IEEE float32 operation (-ffp-contract=off), float32 (op) float64 is
+ * float64.  Only expf and the fp64 logarithm are not numpy's last bit.  Results have the dtype the reference returns.
+ * A float32 pressure operand (pa_hl, a p_ref field, source / target pressures: the reference would take a float32
+ * logarithm) and any other combination that is not instantiated: PGW_ERR_ARG with a message.  Data errors and their
+ * codes as in the uniform entries. */
+
+/* integ_geopot, functions.py:128-189: phi_hl rounded to the dtype of zgs at every level (:141, :149-152),
+ * tav = ta*(1+0.61*hus) and CON_RD*tav in the promoted type of (ta, hus) (:144, :150), logarithms and the final expression
+ * (:174-179) float64.  pa_hl and p_ref_field (may be NULL) float64 (dt_pa_hl = PGW_F64), phi_ref float64. */
+int pgw_integ_geopot_mixed(pgw_ctx *ctx, int dt_pa_hl, int dt_zgs, int dt_ta, int dt_hus, int ntime, int nlev,
+                           long long ncol, const void *pa_hl, const void *zgs, const void *ta, const void *hus,
+                           double p_ref, const void *p_ref_field, double *phi_ref, int full_column);
+
+/* The humidity functions, functions.py:58-125, the expression in numpy's promoted type at every node, e_sat and alpha wholly
+ * in the type of ta.  which: 0 q -> e (a = hus, b = pa; :58-64), 1 e -> q (a = vapp, b = pa; :66-72), 2 / 3 e_sat over
+ * water / ice (a = ta; :74-89), 4 mixed-phase e_sat (a = ta; :91-105), 5 q -> RH (a = hus, b = pa, c = ta; :107-116),
+ * 6 RH -> q (a = hur, b = pa, c = ta; :118-125).  Operands a function does not take: NULL, tag ignored.  `out` has the
+ * promoted type of the operands the function takes. */
+int pgw_humidity_mixed(pgw_ctx *ctx, int which, int dt_a, int dt_b, int dt_c, long long n, const void *a,
+                       const void *b, const void *c, void *out);
+
+/* interp_logp_4d / interp_1d_for_timelatlon / interp_extrap_1d, functions.py:434-580: `src_y[i2] - src_y[i1]` in the
+ * dtype of var (:575-578), everything else float64; all four `extrapolate` modes.  Pressures float64 (dt_p = PGW_F64),
+ * out float64.  Other arguments as pgw_interp_logp_4d. */
+int pgw_interp_logp_4d_mixed(pgw_ctx *ctx, int dt_var, int dt_p, int ntime, int nsrc, int ntarg, long long ncol,
+                             const void *var, const void *source_P, const void *targ_P, int extrapolate,
+                             int logp_in, double *out);
+
+/* vert_interp_delta, functions.py:369-431 (+ :343-366): delta_sfc stored in the delta's dtype, ps_hist inserted into the
+ * float64 source pressures, then as interp_logp_4d with 'constant'; `add_to` (may be NULL) is added in float64.
+ * delta (ntime, nplev, ncol) in file order; delta_sfc, ps_hist (ntime, ncol), both or neither; targ_P (ntime, nlev_t, ncol)
+ * float64 (dt_targ = PGW_F64); out float64.  No time interpolation and no hybrid-level targets in this entry. */
+int pgw_vert_interp_delta_mixed(pgw_ctx *ctx, int dt_delta, int dt_sfc, int dt_pshist, int dt_targ, int dt_add,
+                                int ntime, int nplev, int nlev_t, long long ncol, const double *plev,
+                                const void *delta, const void *delta_sfc, const void *ps_hist, const void *targ_P,
+                                int ignore_top, const void *add_to, double *out);
+
+/* replace_delta_sfc, functions.py:343-366: out_P float64, out_delta in the delta's dtype (np.vectorize allocates its
+ * outputs from the first call's dtypes).  Other arguments as pgw_replace_delta_sfc. */
+int pgw_replace_delta_sfc_mixed(pgw_ctx *ctx, int dt_delta, int dt_sfc, int dt_pshist, int ntime, int nplev,
+                                long long ncol, const double *plev_asc, const void *delta, const void *delta_sfc,
+                                const void *ps_hist, double *out_P, void *out_delta);
+
+/* time interpolation of load_delta, functions.py:288-292 (scipy interp1d._call_linear): v_after - v_before in the promoted
+ * type of the two records, slope and result float64. */
+int pgw_time_lerp_mixed(pgw_ctx *ctx, int dt_before, int dt_after, long long n, const void *v_before,
+                        const void *v_after, double x_hi, double x_new, double *out);
+
+/* integrate_tos, functions.py:1145-1186: the blend (:1183-1184) in the operands' promoted type at every node, written into
+ * the float64 array of :1180. */
+int pgw_integrate_tos_mixed(pgw_ctx *ctx, int dt_tos, int dt_ts, int dt_land, int dt_ice, long long n,
+                            const void *tos, const void *ts, const void *land, const void *ice, double *out);
 
 /* ---------------------------------------------------------------- step_01 ------------ */
 /* s1 model levels -> fixed pressure levels, fused       step_01_extract_deltas/CFday_interp_to_plev.py:89-134

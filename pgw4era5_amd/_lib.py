@@ -27,7 +27,7 @@ KERNEL_IDS = dict(pressure=0, q_to_rh=1, rh_to_q=2, integ_geopot=3, interp_logp=
                   hybrid_to_plev=19, magnus_rh=20, hur_merge=21)
 
 # enum pgw_option (include/pgw_hip.h)
-OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7)
+OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7, mixed_vec=8)
 
 PGW_OK = 0
 PGW_ERR_HIP = 1
@@ -140,6 +140,14 @@ SIGNATURES['pgw_gauss_interp'] = (_i, [_vp, _ll, _vp, _vp, _i, _i, _d, _d, _d, _
 SIGNATURES['pgw_planar_metres'] = (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp])
 SIGNATURES['pgw_interp_hybrid_to_plev'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _vp, _vp, _dp, _dp, _dp, _i, _i, _i, _vp])
 SIGNATURES['pgw_magnus_rh'] = (_i, [_vp, _i, _i, _i, _ll, _vp, _dp, _vp, _vp])
+# settings.function_dtype_flow = 'reference': one dtype tag per operand
+SIGNATURES['pgw_integ_geopot_mixed'] = (_i, [_vp, _i, _i, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i])
+SIGNATURES['pgw_humidity_mixed'] = (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _vp])
+SIGNATURES['pgw_interp_logp_4d_mixed'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _i, _i, _vp])
+SIGNATURES['pgw_vert_interp_delta_mixed'] = (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _dp, _vp, _vp, _vp, _vp, _i, _vp, _vp])
+SIGNATURES['pgw_replace_delta_sfc_mixed'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _dp, _vp, _vp, _vp, _vp, _vp])
+SIGNATURES['pgw_time_lerp_mixed'] = (_i, [_vp, _i, _i, _ll, _vp, _vp, _d, _d, _vp])
+SIGNATURES['pgw_integrate_tos_mixed'] = (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp])
 SIGNATURES['pgw_hur_merge_levels'] = (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _vp, _ip, _ip, _ip, _ip, _ip, _vp])
 
 _lib = None

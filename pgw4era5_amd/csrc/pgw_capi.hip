@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace pgw;
@@ -258,6 +259,7 @@ extern "C" int pgw_ctx_create(int device, pgw_ctx **out) {
     c->opt[PGW_OPT_FORCE_OFF64] = 0;
     c->opt[PGW_OPT_TEST_FAIL] = 0;
     c->opt[PGW_OPT_FUSED_FIRST] = env_flag("PGW_FUSED_FIRST", 1);
+    c->opt[PGW_OPT_MIXED_VEC] = 4;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc(&c->d_status, (2 + MULTI_MAX_PASS + FUSED_BLOCKS) * sizeof(DevStatus)) != hipSuccess ||
         hipHostMalloc(&c->h_status, (2 + 2 * MULTI_MAX_PASS + FUSED_BLOCKS) * sizeof(DevStatus)) != hipSuccess ||
@@ -617,7 +619,7 @@ static int launch_interp_mode(pgw_ctx *ctx, int ntime, int S, int N, long long n
                               const T *tp, T *out, int logp_in) {
     long long total = (long long)ntime * ncol;
     Prof pr(ctx, PGW_K_INTERP_LOGP);
-    hipLaunchKernelGGL((k_interp_logp_stream<T, MODE>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
+    hipLaunchKernelGGL((k_interp_logp_stream<T, T, T, MODE>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
                        ntime, S, N, ncol, var, sp, tp, out, logp_in, ctx->d_status);
     return PGW_OK;
 }
@@ -806,6 +808,21 @@ static int plev_table(pgw_ctx *ctx, int nplev, const double *plev) {
     return PGW_OK;
 }
 
+// functions.py:417-425 on the minima a delta kernel left in the status block (already fetched by status_check):
+// np.min(target_P) < np.min(source_P); NaN in either -> comparison False
+static int top_pressure_check(pgw_ctx *ctx, int ignore_top) {
+    if (!ignore_top) {
+        DevStatus *h = ctx->h_status;
+        if (!h->nan_seen && h->min_targ_bits != ~0ull && h->min_src_bits != ~0ull) {
+            double mt, ms;
+            memcpy(&mt, &h->min_targ_bits, 8);
+            memcpy(&ms, &h->min_src_bits, 8);
+            if (mt < ms) { ctx->err = status_text(PGW_ERR_TOP_PRESSURE); ctx->err_col = -1; return PGW_ERR_TOP_PRESSURE; }
+        }
+    }
+    return PGW_OK;
+}
+
 extern "C" int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int nplev, int nlev_t, long long ncol,
                                      const double *plev, const void *delta_b, const void *delta_a, double x_hi,
                                      double x_new, const void *dsfc_b, const void *dsfc_a, const void *pshist_b,
@@ -836,11 +853,11 @@ extern "C" int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int npl
             DeltaSrc<T> s{(const T *)dsfc_b, (const T *)dsfc_a, x_hi, x_new};
             DeltaSrc<T> p{(const T *)pshist_b, (const T *)pshist_a, x_hi, x_new};
             if (dsfc_b)
-                hipLaunchKernelGGL((k_vert_interp_delta<T, true>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
+                hipLaunchKernelGGL((k_vert_interp_delta<T, T, T, true>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
                                    ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const T *)targ_P, (const T *)ps,
                                    ignore_top ? 0 : 1, (const T *)add_to, (T *)out, ctx->d_status);
             else
-                hipLaunchKernelGGL((k_vert_interp_delta<T, false>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
+                hipLaunchKernelGGL((k_vert_interp_delta<T, T, T, false>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
                                    ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const T *)targ_P, (const T *)ps,
                                    ignore_top ? 0 : 1, (const T *)add_to, (T *)out, ctx->d_status);
         });
@@ -848,17 +865,7 @@ extern "C" int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int npl
     HIPCHK(ctx, hipGetLastError());
     rc = status_check(ctx);
     if (rc) return rc;
-    if (!ignore_top) {
-        // functions.py:417-425: np.min(target_P) < np.min(source_P); NaN in either -> comparison False
-        DevStatus *h = ctx->h_status;
-        if (!h->nan_seen && h->min_targ_bits != ~0ull && h->min_src_bits != ~0ull) {
-            double mt, ms;
-            memcpy(&mt, &h->min_targ_bits, 8);
-            memcpy(&ms, &h->min_src_bits, 8);
-            if (mt < ms) { ctx->err = status_text(PGW_ERR_TOP_PRESSURE); ctx->err_col = -1; return PGW_ERR_TOP_PRESSURE; }
-        }
-    }
-    return PGW_OK;
+    return top_pressure_check(ctx, ignore_top);
 }
 
 extern "C" int pgw_reinterp_field(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const double *plev,
@@ -2162,6 +2169,254 @@ extern "C" int pgw_surface_update(pgw_ctx *ctx, int dtype, int ntime, long long 
                                               st, (const T *)sic, (const T *)dsic, (const T *)dtos, (const T *)dts, (const T *)land,
                                               (const T *)ts_clim, (const T *)tskin, (const T *)tso, (T *)sic_out, (T *)dts_comb_out,
                                               (T *)tskin_out, (T *)tso_out));
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// ================================================================== the reference's dtype flow, function level
+// settings.function_dtype_flow = 'reference': one dtype tag per operand, nothing is cast up front; the kernels reproduce
+// numpy's promotion through the cited reference lines (include/pgw_hip.h).  A tag combination that is not instantiated is
+// PGW_ERR_ARG with a message, never another instantiation.
+#define TAG_OK(t) ((t) == PGW_F32 || (t) == PGW_F64)
+template <typename F> static inline void with_type(int tag, F &&f) { if (tag == PGW_F64) f(double()); else f(float()); }
+template <typename F> static inline void with_vec(int vec, F &&f) {
+    if (vec == 4) f(std::integral_constant<int, 4>());
+    else if (vec == 2) f(std::integral_constant<int, 2>());
+    else f(std::integral_constant<int, 1>());
+}
+// Elements per thread of a kernel whose rows differ in element size: the narrowest row loads as one 16-byte (V = 4 float32)
+// or 8-byte (V = 2) access per lane, a float64 row beside it as V / 2 16-byte accesses; all rows float64: V = 2 as in
+// pick_vec.  PGW_OPT_MIXED_VEC caps V (A/B knob of tools/function_flow_time.py).
+static int pick_vec_mixed(pgw_ctx *ctx, bool any_f32, long long ncol, std::initializer_list<const void *> ptrs) {
+    int v = any_f32 ? 4 : 2;
+    if (v > ctx->opt[PGW_OPT_MIXED_VEC]) v = ctx->opt[PGW_OPT_MIXED_VEC] < 1 ? 1 : ctx->opt[PGW_OPT_MIXED_VEC];
+    if (v == 3) v = 2;
+    if (ctx->opt[PGW_OPT_FORCE_VEC1]) return 1;
+    for (const void *p : ptrs) if (!aligned16(p)) return 1;
+    while (v > 1 && ncol % v != 0) v >>= 1;
+    return v;
+}
+
+extern "C" int pgw_integ_geopot_mixed(pgw_ctx *ctx, int dt_pa_hl, int dt_zgs, int dt_ta, int dt_hus, int ntime, int nlev,
+                                      long long ncol, const void *pa_hl, const void *zgs, const void *ta, const void *hus,
+                                      double p_ref, const void *p_ref_field, double *phi_ref, int full_column) {
+    NEED(ctx, TAG_OK(dt_pa_hl) && TAG_OK(dt_zgs) && TAG_OK(dt_ta) && TAG_OK(dt_hus), "dtype tags must be PGW_F32 or PGW_F64");
+    NEED(ctx, dt_pa_hl == PGW_F64, "pgw_integ_geopot_mixed: float32 pa_hl / p_ref field (a float32 logarithm) is not instantiated");
+    NEED(ctx, ntime >= 1 && ncol >= 1 && nlev >= 1, "ntime, nlev and ncol must be positive");
+    NEED(ctx, pa_hl && zgs && ta && hus && phi_ref, "null pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = status_reset(ctx);
+    if (rc) return rc;
+    const bool any32 = dt_ta == PGW_F32 || dt_hus == PGW_F32;
+    const int vec = pick_vec_mixed(ctx, any32, ncol, {pa_hl, zgs, ta, hus, p_ref_field, phi_ref});
+    {
+        Prof pr(ctx, PGW_K_INTEG_GEOPOT);
+        with_type(dt_zgs, [&](auto z_) { with_type(dt_ta, [&](auto t_) { with_type(dt_hus, [&](auto q_) { with_vec(vec, [&](auto v_) {
+            using TZ = decltype(z_); using TT = decltype(t_); using TQ = decltype(q_);
+            constexpr int V = decltype(v_)::value;
+            if constexpr (V <= 2 || sizeof(TT) == 4 || sizeof(TQ) == 4)
+                hipLaunchKernelGGL((k_integ_geopot<double, V, 4, double, TZ, TT, TQ, true>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
+                                   dim3(BLOCK), 0, ctx->stream, nlev, ntime, ncol, (const double *)pa_hl, (const TZ *)zgs,
+                                   (const TT *)ta, (const TQ *)hus, p_ref, (const double *)p_ref_field, phi_ref, full_column,
+                                   ctx->d_status);
+        }); }); }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return status_check(ctx);
+}
+
+template <int WHICH>
+static void launch_humidity_mixed(pgw_ctx *ctx, int dt_a, int dt_b, int dt_c, long long n, const void *a, const void *b,
+                                  const void *c, void *out) {
+    const int vec = pick_vec_mixed(ctx, true, n, {a, b, c, out}) == 4 ? 4 : 1;
+    unsigned int nb = nblocks(n / vec, BLOCK);
+    if (nb > 256 * 16) nb = 256 * 16;
+    with_type(dt_a, [&](auto a_) { with_type(dt_b, [&](auto b_) { with_type(dt_c, [&](auto c_) { with_vec(vec, [&](auto v_) {
+        using TA = decltype(a_); using TB = decltype(b_); using TC = decltype(c_);
+        constexpr int V = decltype(v_)::value;
+        if constexpr (V != 2) {
+            using TO = humidity_out_t<WHICH, TA, TB, TC>;
+            hipLaunchKernelGGL((k_humidity_mixed<WHICH, TA, TB, TC, V>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, (const TA *)a,
+                               (const TB *)b, (const TC *)c, (TO *)out);
+        }
+    }); }); }); });
+}
+
+extern "C" int pgw_humidity_mixed(pgw_ctx *ctx, int which, int dt_a, int dt_b, int dt_c, long long n, const void *a,
+                                  const void *b, const void *c, void *out) {
+    NEED(ctx, which >= 0 && which <= 6, "which must be 0..6");
+    NEED(ctx, TAG_OK(dt_a) && TAG_OK(dt_b) && TAG_OK(dt_c), "dtype tags must be PGW_F32 or PGW_F64");
+    NEED(ctx, n >= 1 && a && out && ((which >= 2 && which <= 4) || b) && (which < 5 || c), "bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // operands a function does not take carry the tag of `a`: one instantiation per combination that exists
+    if (which >= 2 && which <= 4) dt_b = dt_a;
+    if (which < 5) dt_c = dt_a;
+    {
+        Prof pr(ctx, which == 6 ? PGW_K_RH_TO_Q : PGW_K_Q_TO_RH);
+        switch (which) {
+            case 0: launch_humidity_mixed<0>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
+            case 1: launch_humidity_mixed<1>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
+            case 2: launch_humidity_mixed<2>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
+            case 3: launch_humidity_mixed<3>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
+            case 4: launch_humidity_mixed<4>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
+            case 5: launch_humidity_mixed<5>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
+            default: launch_humidity_mixed<6>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
+        }
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_interp_logp_4d_mixed(pgw_ctx *ctx, int dt_var, int dt_p, int ntime, int nsrc, int ntarg, long long ncol,
+                                        const void *var, const void *source_P, const void *targ_P, int extrapolate,
+                                        int logp_in, double *out) {
+    NEED(ctx, TAG_OK(dt_var) && TAG_OK(dt_p), "dtype tags must be PGW_F32 or PGW_F64");
+    NEED(ctx, dt_p == PGW_F64, "pgw_interp_logp_4d_mixed: float32 pressures (a float32 logarithm) are not instantiated");
+    NEED(ctx, ntime >= 1 && ncol >= 1, "ntime and ncol must be positive");
+    NEED(ctx, nsrc >= 2 && ntarg >= 1, "need at least 2 source levels and 1 target level");
+    NEED(ctx, var && source_P && targ_P && out, "null pointer");
+    if (extrapolate < 0 || extrapolate > 3) return fail(ctx, PGW_ERR_ARG, "Invalid input value for \"extrapolate\"");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = status_reset(ctx);
+    if (rc) return rc;
+    const long long total = (long long)ntime * ncol;
+    {
+        Prof pr(ctx, PGW_K_INTERP_LOGP);
+        with_type(dt_var, [&](auto v_) {
+            using TV = decltype(v_);
+#define INTERP_M(M) hipLaunchKernelGGL((k_interp_logp_stream<TV, double, double, M>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0,  \
+                                       ctx->stream, ntime, nsrc, ntarg, ncol, (const TV *)var, (const double *)source_P,           \
+                                       (const double *)targ_P, out, logp_in, ctx->d_status)
+            switch (extrapolate) {
+                case 0: INTERP_M(0); break;
+                case 1: INTERP_M(1); break;
+                case 2: INTERP_M(2); break;
+                default: INTERP_M(3); break;
+            }
+#undef INTERP_M
+        });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return status_check(ctx);
+}
+
+extern "C" int pgw_vert_interp_delta_mixed(pgw_ctx *ctx, int dt_delta, int dt_sfc, int dt_pshist, int dt_targ, int dt_add,
+                                           int ntime, int nplev, int nlev_t, long long ncol, const double *plev,
+                                           const void *delta, const void *delta_sfc, const void *ps_hist, const void *targ_P,
+                                           int ignore_top, const void *add_to, double *out) {
+    NEED(ctx, TAG_OK(dt_delta) && TAG_OK(dt_sfc) && TAG_OK(dt_pshist) && TAG_OK(dt_targ) && TAG_OK(dt_add),
+         "dtype tags must be PGW_F32 or PGW_F64");
+    NEED(ctx, dt_targ == PGW_F64, "pgw_vert_interp_delta_mixed: float32 target pressures (a float32 logarithm) are not instantiated");
+    NEED(ctx, ntime >= 1 && ncol >= 1 && nlev_t >= 1, "ntime, nlev_t and ncol must be positive");
+    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, plev && delta && targ_P && out, "null pointer");
+    NEED(ctx, (delta_sfc == nullptr) == (ps_hist == nullptr), "delta_sfc and ps_hist must be given together");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = plev_table(ctx, nplev, plev);
+    if (rc) return rc;
+    rc = status_reset(ctx);
+    if (rc) return rc;
+    Levels lv = levels_of(ctx);
+    lv.akm = lv.bkm = nullptr;
+    const long long total = (long long)ntime * ncol;
+    if (!add_to) dt_add = PGW_F64;
+    if (!delta_sfc) { dt_sfc = dt_delta; dt_pshist = PGW_F64; }
+    {
+        Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
+        with_type(dt_delta, [&](auto d_) { with_type(dt_add, [&](auto a_) {
+            using TD = decltype(d_); using TA = decltype(a_);
+            DeltaSrc<TD> d{(const TD *)delta, nullptr, 0.0, 0.0};
+            if (!delta_sfc) {
+                DeltaSrc<TD> s{nullptr, nullptr, 0.0, 0.0};
+                DeltaSrc<double> p{nullptr, nullptr, 0.0, 0.0};
+                hipLaunchKernelGGL((k_vert_interp_delta<TD, double, double, false, TA, TD, double>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
+                                   0, ctx->stream, ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const double *)targ_P,
+                                   (const double *)nullptr, ignore_top ? 0 : 1, (const TA *)add_to, out, ctx->d_status);
+            } else {
+                with_type(dt_sfc, [&](auto s_) { with_type(dt_pshist, [&](auto h_) {
+                    using TS = decltype(s_); using TH = decltype(h_);
+                    DeltaSrc<TS> s{(const TS *)delta_sfc, nullptr, 0.0, 0.0};
+                    DeltaSrc<TH> p{(const TH *)ps_hist, nullptr, 0.0, 0.0};
+                    hipLaunchKernelGGL((k_vert_interp_delta<TD, double, double, true, TA, TS, TH>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
+                                       0, ctx->stream, ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const double *)targ_P,
+                                       (const double *)nullptr, ignore_top ? 0 : 1, (const TA *)add_to, out, ctx->d_status);
+                }); });
+            }
+        }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    rc = status_check(ctx);
+    if (rc) return rc;
+    return top_pressure_check(ctx, ignore_top);
+}
+
+extern "C" int pgw_replace_delta_sfc_mixed(pgw_ctx *ctx, int dt_delta, int dt_sfc, int dt_pshist, int ntime, int nplev,
+                                           long long ncol, const double *plev_asc, const void *delta, const void *delta_sfc,
+                                           const void *ps_hist, double *out_P, void *out_delta) {
+    NEED(ctx, TAG_OK(dt_delta) && TAG_OK(dt_sfc) && TAG_OK(dt_pshist), "dtype tags must be PGW_F32 or PGW_F64");
+    NEED(ctx, ntime >= 1 && ncol >= 1, "ntime and ncol must be positive");
+    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV, "nplev must be in [1, 64]");
+    NEED(ctx, plev_asc && delta && delta_sfc && ps_hist && out_P && out_delta, "null pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlevTable t;
+    memset(&t, 0, sizeof(t));
+    t.n = nplev; t.pmax = -INFINITY; t.pmin = INFINITY;
+    for (int i = 0; i < nplev; ++i) {
+        t.p[i] = plev_asc[i];
+        if (t.p[i] > t.pmax) t.pmax = t.p[i];
+        if (t.p[i] < t.pmin) t.pmin = t.p[i];
+    }
+    int rc = status_reset(ctx);
+    if (rc) return rc;
+    const long long total = (long long)ntime * ncol;
+    {
+        Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
+        with_type(dt_delta, [&](auto d_) { with_type(dt_sfc, [&](auto s_) { with_type(dt_pshist, [&](auto h_) {
+            using TD = decltype(d_); using TS = decltype(s_); using TH = decltype(h_);
+            hipLaunchKernelGGL((k_replace_delta_sfc<TD, TS, TH, double>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, t,
+                               ntime, ncol, (const TD *)delta, (const TS *)delta_sfc, (const TH *)ps_hist, out_P, (TD *)out_delta,
+                               ctx->d_status);
+        }); }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return status_check(ctx);
+}
+
+extern "C" int pgw_time_lerp_mixed(pgw_ctx *ctx, int dt_before, int dt_after, long long n, const void *v_before,
+                                   const void *v_after, double x_hi, double x_new, double *out) {
+    NEED(ctx, TAG_OK(dt_before) && TAG_OK(dt_after), "dtype tags must be PGW_F32 or PGW_F64");
+    NEED(ctx, n >= 1 && v_before && v_after && out, "bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int vec = pick_vec_mixed(ctx, dt_before == PGW_F32 || dt_after == PGW_F32, n, {v_before, v_after, out}) >= 2 ? 2 : 1;
+    unsigned int nb = nblocks(n / vec, BLOCK);
+    if (nb > 256 * 16) nb = 256 * 16;
+    {
+        Prof pr(ctx, PGW_K_TIME_LERP);
+        with_type(dt_before, [&](auto b_) { with_type(dt_after, [&](auto a_) { with_vec(vec, [&](auto v_) {
+            using TB = decltype(b_); using TA = decltype(a_);
+            constexpr int V = decltype(v_)::value;
+            if constexpr (V <= 2)
+                hipLaunchKernelGGL((k_time_lerp<TB, V, TA, double, true>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, (const TB *)v_before,
+                                   (const TA *)v_after, x_hi, x_new, out);
+        }); }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_integrate_tos_mixed(pgw_ctx *ctx, int dt_tos, int dt_ts, int dt_land, int dt_ice, long long n,
+                                       const void *tos, const void *ts, const void *land, const void *ice, double *out) {
+    NEED(ctx, TAG_OK(dt_tos) && TAG_OK(dt_ts) && TAG_OK(dt_land) && TAG_OK(dt_ice), "dtype tags must be PGW_F32 or PGW_F64");
+    NEED(ctx, n >= 1 && tos && ts && land && ice && out, "bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    {
+        Prof pr(ctx, PGW_K_SURFACE);
+        with_type(dt_tos, [&](auto o_) { with_type(dt_ts, [&](auto s_) { with_type(dt_land, [&](auto l_) { with_type(dt_ice, [&](auto i_) {
+            using TO_ = decltype(o_); using TS = decltype(s_); using TL = decltype(l_); using TI = decltype(i_);
+            hipLaunchKernelGGL((k_integrate_tos_mixed<TO_, TS, TL, TI>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n,
+                               (const TO_ *)tos, (const TS *)ts, (const TL *)land, (const TI *)ice, out);
+        }); }); }); });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "pgw_log_table.h"
 
 namespace pgw {
@@ -50,7 +51,15 @@ template <typename T, int V> struct VecOf { typedef T type __attribute__((ext_ve
 template <typename T, int V>
 __device__ __forceinline__ void loadv_nt(const T *__restrict__ p, double (&out)[V]) {
     if constexpr (V == 1) out[0] = (double)__builtin_nontemporal_load(p);
-    else {
+    else if constexpr (sizeof(T) * V > 16) {          // a row wider than one access (double beside float32 rows): 16-byte pieces
+        constexpr int H = 16 / sizeof(T);
+#pragma unroll
+        for (int h = 0; h < V; h += H) {
+            typename VecOf<T, H>::type t = __builtin_nontemporal_load(reinterpret_cast<const typename VecOf<T, H>::type *>(p + h));
+#pragma unroll
+            for (int i = 0; i < H; ++i) out[h + i] = (double)t[i];
+        }
+    } else {
         typename VecOf<T, V>::type t = __builtin_nontemporal_load(reinterpret_cast<const typename VecOf<T, V>::type *>(p));
 #pragma unroll
         for (int i = 0; i < V; ++i) out[i] = (double)t[i];
@@ -64,6 +73,36 @@ __device__ __forceinline__ void storev_nt(T *__restrict__ p, const double (&in)[
 #pragma unroll
         for (int i = 0; i < V; ++i) t[i] = (T)in[i];
         __builtin_nontemporal_store(t, reinterpret_cast<typename VecOf<T, V>::type *>(p));
+    }
+}
+
+// loadv / storev for kernels whose operands differ in element size: at most 16 bytes per access (V float64 elements are
+// V / 2 accesses), the single access of loadv / storev otherwise
+template <typename T, int V>
+__device__ __forceinline__ void loadv16(const T *__restrict__ p, double (&out)[V]) {
+    if constexpr (sizeof(T) * V <= 16) loadv<T, V>(p, out);
+    else {
+        constexpr int H = 16 / sizeof(T);
+#pragma unroll
+        for (int h = 0; h < V; h += H) {
+            Pack<T, H> t = *reinterpret_cast<const Pack<T, H> *>(p + h);
+#pragma unroll
+            for (int i = 0; i < H; ++i) out[h + i] = (double)t.v[i];
+        }
+    }
+}
+template <typename T, int V>
+__device__ __forceinline__ void storev16(T *__restrict__ p, const double (&in)[V]) {
+    if constexpr (sizeof(T) * V <= 16) storev<T, V>(p, in);
+    else {
+        constexpr int H = 16 / sizeof(T);
+#pragma unroll
+        for (int h = 0; h < V; h += H) {
+            Pack<T, H> t;
+#pragma unroll
+            for (int i = 0; i < H; ++i) t.v[i] = (T)in[h + i];
+            *reinterpret_cast<Pack<T, H> *>(p + h) = t;
+        }
     }
 }
 
@@ -208,6 +247,50 @@ __device__ __forceinline__ double pgw_log_impl(double x) {
 }
 __device__ __forceinline__ double pgw_log(double x) { return pgw_log_impl<false>(x); }
 __device__ __forceinline__ double pgw_log_f3(double x) { return pgw_log_impl<true>(x); }    // same bits
+
+// The fdlibm kernel again, with the quotient s = f / (2 + f) and the final sum k ln2 + f - f^2/2 + s (f^2/2 + R) carried as
+// double-double pairs (error-free two-sums, FMA residuals): the result is the correctly rounded logarithm for all but ~3 in
+// 10^4 arguments (checked against a long-double logarithm), where pgw_log is up to one ulp off for 1-2 % of them.  About twice the
+// instructions: for the few logarithms whose last bit reaches a float64 RESULT - the final expression of integ_geopot
+// (functions.py:174-179) in the reference's dtype flow, which is compared with numpy's bit for bit - not for level loops.
+__device__ __forceinline__ void two_sum(double a, double b, double &s, double &e) {
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+__device__ __forceinline__ double pgw_log_dd(double x) {
+    if (__builtin_expect(!(x >= 2.2250738585072014e-308 && x <= 1.7976931348623157e308), 0)) return log(no_speculate(x));
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+    const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
+                 Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+                 Lg7 = 1.479819860511658591e-01;
+    int k = __builtin_amdgcn_frexp_exp(x);
+    double m = __builtin_amdgcn_frexp_mant(x);
+    if (m < 0.70710678118654752440) { m = m * 2.0; k -= 1; }
+    const double f = m - 1.0;                              // exact
+    const double d_hi = 2.0 + f, d_lo = f - (d_hi - 2.0);  // 2 + f as a pair (|f| < 2: fast two-sum)
+    double r = __builtin_amdgcn_rcp(d_hi);
+    r = __builtin_fma(__builtin_fma(-d_hi, r, 1.0), r, r);
+    r = __builtin_fma(__builtin_fma(-d_hi, r, 1.0), r, r);
+    double s = f * r;
+    s = __builtin_fma(__builtin_fma(-d_hi, s, f) - d_lo * s, r, s);
+    const double s_lo = (__builtin_fma(-d_hi, s, f) - d_lo * s) * r;
+    const double dk = (double)k, z = s * s, w = z * z;
+    const double t1 = w * __builtin_fma(w, __builtin_fma(w, Lg6, Lg4), Lg2);
+    const double t2 = z * __builtin_fma(w, __builtin_fma(w, __builtin_fma(w, Lg7, Lg5), Lg3), Lg1);
+    const double R = t2 + t1 + 2.0 * s * s_lo * Lg1;       // first-order effect of s_lo on z = s^2
+    const double hf = 0.5 * f, h_hi = hf * f, h_lo = __builtin_fma(hf, f, -h_hi);
+    double u_hi, u_lo;
+    two_sum(h_hi, R, u_hi, u_lo);
+    u_lo += h_lo;
+    const double T_hi = s * u_hi, T_lo = __builtin_fma(s, u_hi, -T_hi) + s * u_lo + s_lo * u_hi;
+    double a_hi, a_lo, e;
+    two_sum(dk * ln2_hi, f, a_hi, a_lo);                   // k ln2_hi is exact (21 trailing zero bits)
+    two_sum(a_hi, -h_hi, a_hi, e); a_lo += e;
+    two_sum(a_hi, T_hi, a_hi, e); a_lo += e;
+    a_lo += (T_lo - h_lo) + dk * ln2_lo;
+    return a_hi + a_lo;
+}
 
 // ---- table-driven natural logarithm for the level loops ------------------------------------
 // The level loops of the surface-pressure iteration are bound by fp64 issue (94 % of the SIMD cycles), and the
@@ -425,6 +508,74 @@ __device__ __forceinline__ double rh_to_e(double hur, double ta) {         // :1
 }
 __device__ __forceinline__ double rh_to_q(double hur, double pa, double ta) {   // :118-125
     return e_to_q(rh_to_e(hur, ta), pa);
+}
+
+// ---- settings.function_dtype_flow = 'reference': functions.py:58-125 in numpy's promoted type at every node ----
+// float (op) float -> float, float (op) double -> double: C++'s usual arithmetic conversions are numpy's lattice for
+// float32 / float64 arrays, and a python-float constant takes the type of the array it meets (written T(c) below).
+// Every float32 node is one IEEE operation (-ffp-contract=off, correctly rounded float32 division); e_sat runs wholly in
+// the type of `ta` (esat_mixed_f32 / esat_mixed above, which both evaluate :91-105 as written).
+template <typename A, typename B> using promo_t = decltype(A() + B());
+// result type of humidity_expr<WHICH> below
+template <int WHICH, typename TA, typename TB, typename TC>
+using humidity_out_t = std::conditional_t<(WHICH >= 2 && WHICH <= 4), TA,
+                                          std::conditional_t<(WHICH <= 1), promo_t<TA, TB>, promo_t<promo_t<TA, TB>, TC>>>;
+__device__ __forceinline__ float esat_x_t(float ta, bool water) {
+    return water ? esat_x_f32(ta, 17.502f, 32.19f) : esat_x_f32(ta, 22.587f, -0.7f);
+}
+__device__ __forceinline__ double esat_x_t(double ta, bool water) {               // the literal form of k_humidity_leaf
+    return water ? 611.21 * pgw_exp(17.502 * (ta - 273.16) / (ta - 32.19)) : 611.21 * pgw_exp(22.587 * (ta - 273.16) / (ta - (-0.7)));
+}
+__device__ __forceinline__ float esat_mixed_t(float ta) { return esat_mixed_f32(ta); }
+__device__ __forceinline__ double esat_mixed_t(double ta) { return esat_mixed(ta); }
+// WHICH 0: q -> e (:58-64; a = hus, b = pa)   1: e -> q (:66-72; a = vapp, b = pa)   2 / 3: e_sat over water / ice (:74-89; a = ta)
+// 4: mixed-phase e_sat (:91-105; a = ta)      5: q -> RH (:107-116; hus, pa, ta)    6: RH -> q (:118-125; hur, pa, ta)
+template <int WHICH, typename TA, typename TB, typename TC>
+__device__ __forceinline__ auto humidity_expr(TA a, TB b, TC c) {
+    if constexpr (WHICH == 0) return a * b / (TA(CON_MW_MD) + TA(0.378) * a);
+    else if constexpr (WHICH == 1) return TA(CON_MW_MD) * a / (b - TA(1 - CON_MW_MD) * a);
+    else if constexpr (WHICH == 2) return esat_x_t(a, true);
+    else if constexpr (WHICH == 3) return esat_x_t(a, false);
+    else if constexpr (WHICH == 4) return esat_mixed_t(a);
+    else if constexpr (WHICH == 5) {
+        // the mix a float32 file produces (float32 QV and T, float64 pressure) and the uniform float64 one through the
+        // helpers the file kernels use: the same expression with the scale-free quotients (div_ns: same bits)
+        if constexpr (sizeof(TA) == 4 && sizeof(TB) == 8 && sizeof(TC) == 4) return q_to_rh_f32(a, b, c);
+        else if constexpr (sizeof(TA) == 8 && sizeof(TB) == 8 && sizeof(TC) == 8) return q_to_rh(a, b, c);
+        else {
+            const auto r = humidity_expr<0>(a, b, c) / esat_mixed_t(c);
+            return r * decltype(r)(100);
+        }
+    } else {
+        if constexpr (sizeof(TA) == 8 && sizeof(TB) == 8 && sizeof(TC) == 8) return rh_to_q(a, b, c);
+        else {
+            const auto vapp = a / TA(100) * esat_mixed_t(c);
+            return humidity_expr<1>(vapp, b, c);
+        }
+    }
+}
+
+// V elements of T as themselves (no widening), at most 16 bytes per access
+template <typename T, int V>
+__device__ __forceinline__ void loadv_typed(const T *__restrict__ p, T (&out)[V]) {
+    constexpr int H = (sizeof(T) * V <= 16) ? V : (int)(16 / sizeof(T));
+#pragma unroll
+    for (int h = 0; h < V; h += H) {
+        Pack<T, H> t = *reinterpret_cast<const Pack<T, H> *>(p + h);
+#pragma unroll
+        for (int i = 0; i < H; ++i) out[h + i] = t.v[i];
+    }
+}
+template <typename T, int V>
+__device__ __forceinline__ void storev_typed(T *__restrict__ p, const T (&in)[V]) {
+    constexpr int H = (sizeof(T) * V <= 16) ? V : (int)(16 / sizeof(T));
+#pragma unroll
+    for (int h = 0; h < V; h += H) {
+        Pack<T, H> t;
+#pragma unroll
+        for (int i = 0; i < H; ++i) t.v[i] = in[h + i];
+        *reinterpret_cast<Pack<T, H> *>(p + h) = t;
+    }
 }
 
 // functions.py:135  pa_hl.where(pa_hl > 0, 0.0001): NaN > 0 is False -> 1e-4

@@ -136,6 +136,31 @@ __global__ __launch_bounds__(BLOCK) void k_humidity_leaf(long long n, const T *_
     }
 }
 
+// The humidity functions in the reference's dtype flow (settings.function_dtype_flow = 'reference'): every operand in its
+// own storage type, the expression in numpy's promoted type at every node (humidity_expr, pgw_device.h), the result in
+// the promoted type of the whole expression.  b / c are not read by the functions that do not take them.
+template <int WHICH, typename TA, typename TB, typename TC, int V>
+__global__ __launch_bounds__(BLOCK) void k_humidity_mixed(long long n, const TA *__restrict__ a, const TB *__restrict__ b,
+                                                          const TC *__restrict__ c,
+                                                          humidity_out_t<WHICH, TA, TB, TC> *__restrict__ out) {
+    using TO = humidity_out_t<WHICH, TA, TB, TC>;
+    static_assert(std::is_same<TO, decltype(humidity_expr<WHICH>(TA(), TB(), TC()))>::value, "humidity_out_t");
+    long long stride = (long long)gridDim.x * BLOCK;
+    for (long long g = (long long)blockIdx.x * BLOCK + threadIdx.x; g * V < n; g += stride) {
+        TA x[V]; TB y[V]; TC z[V]; TO r[V];
+        loadv_typed<TA, V>(a + g * V, x);
+        if constexpr (WHICH <= 1 || WHICH >= 5) loadv_typed<TB, V>(b + g * V, y);
+        if constexpr (WHICH >= 5) loadv_typed<TC, V>(c + g * V, z);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            if constexpr (WHICH >= 5) r[v] = humidity_expr<WHICH>(x[v], y[v], z[v]);
+            else if constexpr (WHICH <= 1) r[v] = humidity_expr<WHICH>(x[v], y[v], TC());
+            else r[v] = humidity_expr<WHICH>(x[v], TB(), TC());
+        }
+        storev_typed<TO, V>(out + g * V, r);
+    }
+}
+
 // RELHUM of a float32 ERA state in reference-dtype mode (step_03:91-94 on a float32 file): float32 QV, T, PS in, the float64
 // field numpy's promotion produces out (q_to_rh_f32: float64 pressure, float32 e_sat chain)
 __global__ __launch_bounds__(BLOCK) void k_relhum_ref(Levels lv, int ntime, long long ncol, const float *__restrict__ hus,
@@ -197,6 +222,7 @@ struct GeoAcc {            // per-column running state of the upward scan
     double p_lo, lnp_lo;   // pressure / ln p at that half level
     double dmin;           // smallest non-negative p_hl - p_ref so far
     double phi_s, rtv_s, lnp_s;   // phi, CON_RD*tv and ln p captured at the candidate k*
+    double p_s;            // the pressure itself there (geo_layer<.., .., CAP = true> only, for geo_finish_exact)
     int kstar;             // -1 = none yet
 };
 
@@ -220,13 +246,15 @@ __device__ __forceinline__ void geo_init(GeoAcc &a, double zgs, double p_bottom,
     a.dmin = __builtin_inf();
     a.kstar = -1;
     a.phi_s = a.rtv_s = a.lnp_s = 0.0;
+    a.p_s = 1.0;
 }
 // process layer l (between half levels l and l+1); rtv = CON_RD * tv of the layer; p_top = pa_hl[l] raw
-template <bool REF = false, bool TAB = false>
+template <bool REF = false, bool TAB = false, bool CAP = false>
 __device__ __forceinline__ void geo_layer(GeoAcc &a, int l, double rtv, double p_top, double p_ref, const double *logtab = nullptr) {
     double d = a.p_lo - p_ref;                        // candidate k = l+1         :160-161
     if (d >= 0 && d <= a.dmin) {
         a.dmin = d; a.kstar = l + 1; a.phi_s = a.phi; a.rtv_s = rtv; a.lnp_s = a.lnp_lo;
+        if (CAP) a.p_s = a.p_lo;
     }
     double p_hi = fix_p(p_top);                       // :135
     double lnp_hi = TAB ? pgw_log_tab(p_hi, logtab) : pgw_log_f3(p_hi);      // the log of the level loops
@@ -240,6 +268,17 @@ __device__ __forceinline__ double geo_finish(GeoAcc &a, double p_ref, DevStatus 
     if (a.kstar < 0) { report(st, 13 /*PGW_ERR_PREF_BELOW_SURFACE*/, col); return __builtin_nan(""); }
     if (a.kstar == 0) { report(st, 14 /*PGW_ERR_PREF_AT_TOP*/, col); return __builtin_nan(""); }
     return a.phi_s - a.rtv_s * (pgw_log(p_ref) - a.lnp_s);    // :174-179
+}
+
+// geo_finish for the reference's dtype flow of the function-level API: the final expression (:174-179) is float64 and no
+// float32 rounding follows it, so the last bit of its two logarithms is the last bit of the result - they are taken with
+// pgw_log_dd (numpy's bits for all but a few in 10^4 arguments) from the pressures themselves (CAP)
+__device__ __forceinline__ double geo_finish_exact(GeoAcc &a, double p_ref, DevStatus *st, long long col) {
+    double d = a.p_lo - p_ref;
+    if (d >= 0 && d <= a.dmin) a.kstar = 0;
+    if (a.kstar < 0) { report(st, 13 /*PGW_ERR_PREF_BELOW_SURFACE*/, col); return __builtin_nan(""); }
+    if (a.kstar == 0) { report(st, 14 /*PGW_ERR_PREF_AT_TOP*/, col); return __builtin_nan(""); }
+    return a.phi_s - a.rtv_s * (pgw_log_dd(p_ref) - pgw_log_dd(a.p_s));
 }
 
 // The same scan for columns whose half-level pressures are known to ascend (ps >= Levels::ps_mono_min), in fewer live
@@ -288,27 +327,42 @@ __device__ __forceinline__ double geo_mono_finish(const GeoMono<NS> &a, int i, d
     return a.cand[i];
 }
 
-// TO = type of the phi_ref output (T for the signature-faithful call, double for the loop state)
-template <typename T, int V, int U, typename TO>
+// Numpy's promotion of `CON_RD * (ta * (1 + 0.61 * hus))` (functions.py:144, :150) for storage types TT / TQ: a python float
+// takes the dtype of the array it meets, so 1 + 0.61*hus is evaluated in TQ, the product with ta in the promoted type of
+// (TT, TQ) - C++'s usual arithmetic conversions on float / double operands - and CON_RD in that type.  Both float: rd_tv_f32.
+template <typename TT, typename TQ>
+__device__ __forceinline__ double rd_tv_promoted(double t, double q) {
+    if constexpr (sizeof(TT) == 4 && sizeof(TQ) == 4) return rd_tv_f32(t, q);
+    else if constexpr (sizeof(TQ) == 4) return CON_RD * (t * (double)(1.0f + 0.61f * (float)q));     // float64 ta, float32 hus
+    else return CON_RD * (t * (1 + 0.61 * q));
+}
+
+// Per-operand storage types: TP half-level pressures and a p_ref field, TZ zgs, TT / TQ the state, TO the phi_ref output
+// (TP for the signature-faithful call, double for the loop state).  REF = false: float64 arithmetic on the stored values
+// whatever the types (settings.function_dtype_flow = 'common': one type for all operands).  REF = true: the reference's
+// dtype flow - phi_hl rounded to TZ at every level (phi_store), CON_RD * tav in the promoted type of (TT, TQ), logarithms
+// and the final expression float64.  A thread owns V columns: a row of 8-byte elements is then V / 2 16-byte accesses.
+template <typename TP, int V, int U, typename TO, typename TZ = TP, typename TT = TP, typename TQ = TT, bool REF = false>
 __global__ __launch_bounds__(BLOCK) void k_integ_geopot(int nlev, int ntime, long long ncol,
-                                                        const T *__restrict__ pa_hl, const T *__restrict__ zgs,
-                                                        const T *__restrict__ ta, const T *__restrict__ hus,
-                                                        double p_ref_s, const T *__restrict__ p_ref_f,
+                                                        const TP *__restrict__ pa_hl, const TZ *__restrict__ zgs,
+                                                        const TT *__restrict__ ta, const TQ *__restrict__ hus,
+                                                        double p_ref_s, const TP *__restrict__ p_ref_f,
                                                         TO *__restrict__ phi_ref, int full_column,
                                                         DevStatus *st) {
+    constexpr bool PHI32 = REF && sizeof(TZ) == 4;
     long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
     long long ngroups = (long long)ntime * ncol / V;
     if (g >= ngroups) return;
     ColIdx ix = col_index(g, V, ncol);
     const int N = nlev;
-    const T *ph = pa_hl + ix.t * (N + 1) * ncol + ix.c;
-    const T *pt = ta + ix.t * N * ncol + ix.c;
-    const T *pq = hus + ix.t * N * ncol + ix.c;
+    const TP *ph = pa_hl + ix.t * (N + 1) * ncol + ix.c;
+    const TT *pt = ta + ix.t * N * ncol + ix.c;
+    const TQ *pq = hus + ix.t * N * ncol + ix.c;
     long long c2 = ix.t * ncol + ix.c;
     double z[V], pb[V], pref[V];
-    loadv<T, V>(zgs + c2, z);
-    loadv<T, V>(ph + (long long)N * ncol, pb);
-    if (p_ref_f) loadv<T, V>(p_ref_f + c2, pref);
+    loadv16<TZ, V>(zgs + c2, z);
+    loadv16<TP, V>(ph + (long long)N * ncol, pb);
+    if (p_ref_f) loadv16<TP, V>(p_ref_f + c2, pref);
     else {
 #pragma unroll
         for (int v = 0; v < V; ++v) pref[v] = p_ref_s;
@@ -322,17 +376,19 @@ __global__ __launch_bounds__(BLOCK) void k_integ_geopot(int nlev, int ntime, lon
         double p[U][V], t[U][V], q[U][V];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            SIG_LOADV<T, V>(ph + (long long)(l - u) * ncol, p[u]);
-            SIG_LOADV<T, V>(pt + (long long)(l - u) * ncol, t[u]);
-            SIG_LOADV<T, V>(pq + (long long)(l - u) * ncol, q[u]);
+            SIG_LOADV<TP, V>(ph + (long long)(l - u) * ncol, p[u]);
+            SIG_LOADV<TT, V>(pt + (long long)(l - u) * ncol, t[u]);
+            SIG_LOADV<TQ, V>(pq + (long long)(l - u) * ncol, q[u]);
         }
         bool above = true;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
 #pragma unroll
             for (int v = 0; v < V; ++v) {
-                double tv = t[u][v] * (1 + 0.61 * q[u][v]);          // :144
-                geo_layer(acc[v], l - u, CON_RD * tv, p[u][v], pref[v]);
+                double rtv;
+                if constexpr (REF) rtv = rd_tv_promoted<TT, TQ>(t[u][v], q[u][v]);
+                else rtv = CON_RD * (t[u][v] * (1 + 0.61 * q[u][v]));          // :144
+                geo_layer<PHI32, false, REF>(acc[v], l - u, rtv, p[u][v], pref[v]);
             }
         }
         if (!full_column) {
@@ -345,17 +401,22 @@ __global__ __launch_bounds__(BLOCK) void k_integ_geopot(int nlev, int ntime, lon
     }
     for (; l >= 0; --l) {
         double p[V], t[V], q[V];
-        SIG_LOADV<T, V>(ph + (long long)l * ncol, p);
-        SIG_LOADV<T, V>(pt + (long long)l * ncol, t);
-        SIG_LOADV<T, V>(pq + (long long)l * ncol, q);
+        SIG_LOADV<TP, V>(ph + (long long)l * ncol, p);
+        SIG_LOADV<TT, V>(pt + (long long)l * ncol, t);
+        SIG_LOADV<TQ, V>(pq + (long long)l * ncol, q);
 #pragma unroll
-        for (int v = 0; v < V; ++v) geo_layer(acc[v], l, CON_RD * (t[v] * (1 + 0.61 * q[v])), p[v], pref[v]);
+        for (int v = 0; v < V; ++v) {
+            double rtv;
+            if constexpr (REF) rtv = rd_tv_promoted<TT, TQ>(t[v], q[v]);
+            else rtv = CON_RD * (t[v] * (1 + 0.61 * q[v]));
+            geo_layer<PHI32, false, REF>(acc[v], l, rtv, p[v], pref[v]);
+        }
     }
 done:
     double r[V];
 #pragma unroll
-    for (int v = 0; v < V; ++v) r[v] = geo_finish(acc[v], pref[v], st, c2 + v);
-    storev<TO, V>(phi_ref + c2, r);
+    for (int v = 0; v < V; ++v) r[v] = REF ? geo_finish_exact(acc[v], pref[v], st, c2 + v) : geo_finish(acc[v], pref[v], st, c2 + v);
+    storev16<TO, V>(phi_ref + c2, r);
 }
 
 // =====================================================================================
@@ -614,11 +675,15 @@ __global__ __launch_bounds__(BLOCK) void k_finalize_ps_hus(Levels lv, int ntime,
 #define PGW_INTERP_MINB 1
 #endif
 #define PGW_LOGT(x) pgw_log_tab((x), s_logt)
-template <typename T, int MODE>
+// TV / TP / TO: storage types of var, of the two pressure fields and of the result.  One type for all three: float64
+// arithmetic on the stored values.  TV = float with TO = double is the reference's dtype flow (numba, functions.py:575-578,
+// as in k_hybrid_to_plev below): `src_y[i2] - src_y[i1]` is a float32 subtraction, everything else float64.
+template <typename TV, typename TP, typename TO, int MODE>
 __global__ __launch_bounds__(BLOCK, PGW_INTERP_MINB) void k_interp_logp_stream(int ntime, int S, int N, long long ncol,
-                                                              const T *__restrict__ var, const T *__restrict__ srcP,
-                                                              const T *__restrict__ trgP, T *__restrict__ out,
+                                                              const TV *__restrict__ var, const TP *__restrict__ srcP,
+                                                              const TP *__restrict__ trgP, TO *__restrict__ out,
                                                               int logp_in, DevStatus *st) {
+    constexpr bool DY32 = sizeof(TV) == 4 && sizeof(TO) == 8;
     // np.log of both pressure fields (:470-471) through the table-driven logarithm of the level loops (pgw_log_tab: ~27
     // instead of ~40 instructions, same <= 1 ulp; S + N = 156 logarithms per column made this kernel issue-bound: 0.86 busy).
     // Source and target logarithms come from the one implementation, so the exact-hit rule (:540) is unaffected.
@@ -628,10 +693,10 @@ __global__ __launch_bounds__(BLOCK, PGW_INTERP_MINB) void k_interp_logp_stream(i
     long long flat = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (flat >= (long long)ntime * ncol) return;
     long long t = flat / ncol, c = flat - t * ncol;
-    const T *pv = var + t * S * ncol + c;
-    const T *pp = srcP + t * S * ncol + c;
-    const T *pt = trgP + t * N * ncol + c;
-    T *po = out + t * N * ncol + c;
+    const TV *pv = var + t * S * ncol + c;
+    const TP *pp = srcP + t * S * ncol + c;
+    const TP *pt = trgP + t * N * ncol + c;
+    TO *po = out + t * N * ncol + c;
     const double s_first = logp_in ? (double)pp[0] : PGW_LOGT((double)pp[0]);                         // :470
     {
         double s_last = (double)pp[(long long)(S - 1) * ncol];
@@ -702,9 +767,10 @@ __global__ __launch_bounds__(BLOCK, PGW_INTERP_MINB) void k_interp_logp_stream(i
                 double y;
                 if (extrap && MODE == 3) y = __builtin_nan("");          // :569-570
                 else if (same) y = y1;                                   // :572-573
+                else if constexpr (DY32) y = y1 + (x - x1) * (double)((float)y2 - (float)y1) / (x2 - x1);
                 else y = y1 + (x - x1) * (y2 - y1) / (x2 - x1);          // :575-578
                 if (MODE == 0 && extrap) report(st, 12, flat);           // :564-566
-                SIG_ST((T)y, po + (long long)l * ncol);
+                SIG_ST((TO)y, po + (long long)l * ncol);
                 xprev = (x == x) ? x : __builtin_inf();                  // after a NaN target restart
             }
         }
@@ -923,17 +989,23 @@ __global__ __launch_bounds__(BLOCK) void k_hur_merge_levels(int ntime, int nplev
 // =====================================================================================
 // a7  time lerp of load_delta                                  functions.py:288-292
 // =====================================================================================
-template <typename T, int V>
-__global__ __launch_bounds__(BLOCK) void k_time_lerp(long long n, const T *__restrict__ vb, const T *__restrict__ va,
-                                                     double x_hi, double x_new, T *__restrict__ out) {
+// TB / TA / TO: storage types of the two records and of the result.  REF (settings.function_dtype_flow = 'reference'):
+// scipy's interp1d._call_linear takes `y_hi - y_lo` in the promoted type of the data - one float32 subtraction for float32
+// records - slope and result in float64.
+template <typename TB, int V, typename TA = TB, typename TO = TB, bool REF = false>
+__global__ __launch_bounds__(BLOCK) void k_time_lerp(long long n, const TB *__restrict__ vb, const TA *__restrict__ va,
+                                                     double x_hi, double x_new, TO *__restrict__ out) {
     long long stride = (long long)gridDim.x * BLOCK;
     for (long long g = (long long)blockIdx.x * BLOCK + threadIdx.x; g * V < n; g += stride) {
         double b[V], a[V], r[V];
-        loadv<T, V>(vb + g * V, b);
-        loadv<T, V>(va + g * V, a);
+        loadv16<TB, V>(vb + g * V, b);
+        loadv16<TA, V>(va + g * V, a);
 #pragma unroll
-        for (int v = 0; v < V; ++v) r[v] = (a[v] - b[v]) / x_hi * x_new + b[v];
-        storev<T, V>(out + g * V, r);
+        for (int v = 0; v < V; ++v) {
+            const double diff = (REF && sizeof(TB) == 4 && sizeof(TA) == 4) ? (double)((float)a[v] - (float)b[v]) : a[v] - b[v];
+            r[v] = diff / x_hi * x_new + b[v];
+        }
+        storev16<TO, V>(out + g * V, r);
     }
 }
 
@@ -988,12 +1060,18 @@ struct DeltaSrc {
     }
 };
 
-template <typename T, bool HAS_SFC>
+// Storage types: TD the delta records, TP the target pressures (or `ps`), TO the result, TA the addend, TS / TH the surface
+// delta and the HIST surface pressure.  One type for all: float64 arithmetic on the stored values.  TD = float with
+// TO = double is the reference's dtype flow: the surface delta is stored in the delta's dtype (np.vectorize keeps it,
+// functions.py:343-366), ps_hist enters the float64 source pressures, `src_y[i2] - src_y[i1]` is a float32 subtraction
+// (numba, :575-578) and everything else float64.
+template <typename TD, typename TP, typename TO, bool HAS_SFC, typename TA = TO, typename TS = TD, typename TH = TP>
 __global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PlevTable pt, Levels lv, int ntime, int N, long long ncol,
-                                                             DeltaSrc<T> dsrc, DeltaSrc<T> sfc, DeltaSrc<T> psh,
-                                                             const T *__restrict__ trgP, const T *__restrict__ ps,
-                                                             int check_top, const T *__restrict__ add_to,
-                                                             T *__restrict__ out, DevStatus *st) {
+                                                             DeltaSrc<TD> dsrc, DeltaSrc<TS> sfc, DeltaSrc<TH> psh,
+                                                             const TP *__restrict__ trgP, const TP *__restrict__ ps,
+                                                             int check_top, const TA *__restrict__ add_to,
+                                                             TO *__restrict__ out, DevStatus *st) {
+    constexpr bool DY32 = sizeof(TD) == 4 && sizeof(TO) == 8;
     __shared__ double s_mint[BLOCK / 64], s_mins[BLOCK / 64];
     __shared__ int s_nan[BLOCK / 64];
     // plev / ln(plev) staged in LDS: lanes index them with their own (divergent) scan position
@@ -1026,6 +1104,7 @@ __global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PlevTable pt, Level
         if (HAS_SFC) {
             pshv = psh.get(c2);
             d_sfc = sfc.get(c2);
+            if constexpr (sizeof(TS) > sizeof(TD)) d_sfc = (double)(TD)d_sfc;     // stored in the delta's dtype
             if (pshv > pt.pmax) {                                  // :356-359
                 ksfc = S - 1;
             } else if (pshv < pt.pmin) {                           // :360-361
@@ -1051,7 +1130,7 @@ __global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PlevTable pt, Level
             }
         }
         double psv = 0.0;
-        const T *ptg = nullptr;
+        const TP *ptg = nullptr;
         if (trgP) ptg = trgP + t * N * ncol + c; else psv = (double)ps[c2];
         long long obase = t * N * ncol + c;
         int j = 0;
@@ -1103,11 +1182,12 @@ __global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PlevTable pt, Level
                 else {
                     if (ci != j - 1) { y_lo = srcy(j - 1); y_hi = srcy(j); ci = j - 1; }
                     double x1 = srcx(j - 1);
-                    y = y_lo + (x - x1) * (y_hi - y_lo) / (xs - x1);    // :575-578
+                    if constexpr (DY32) y = y_lo + (x - x1) * (double)((float)y_hi - (float)y_lo) / (xs - x1);
+                    else y = y_lo + (x - x1) * (y_hi - y_lo) / (xs - x1);    // :575-578
                 }
             }
             if (add_to) y = ca_[u] + y;                                        // step_03:170-173
-            SIG_ST((T)y, out + obase + (long long)l * ncol);
+            SIG_ST((TO)y, out + obase + (long long)l * ncol);
             xprev = (x == x) ? x : __builtin_inf();
         }
         }
@@ -2409,10 +2489,13 @@ __global__ __launch_bounds__(BLOCK) void k_surface_update(int ntime, long long n
 
 // replace_delta_sfc (functions.py:343-366) on many ascending-pressure columns: source_P is the
 // broadcast 1-D table, delta (ntime, S, ncol) ascending order; outputs the modified columns.
-template <typename T>
+// T: the delta (and its output column); TS / TH: delta_sfc and ps_hist; TP: the pressure output.  The surface delta is
+// stored in the delta's dtype and ps_hist in the pressures' (np.vectorize allocates its outputs from the first call's
+// dtypes: float64 pressures, the delta's own type).
+template <typename T, typename TS = T, typename TH = T, typename TP = T>
 __global__ __launch_bounds__(BLOCK) void k_replace_delta_sfc(PlevTable pt, int ntime, long long ncol,
-                                                             const T *__restrict__ delta, const T *__restrict__ dsfc,
-                                                             const T *__restrict__ pshist, T *__restrict__ outP,
+                                                             const T *__restrict__ delta, const TS *__restrict__ dsfc,
+                                                             const TH *__restrict__ pshist, TP *__restrict__ outP,
                                                              T *__restrict__ outD, DevStatus *st) {
     __shared__ double s_p[MAX_PLEV];
     const int S = pt.n;
@@ -2438,7 +2521,7 @@ __global__ __launch_bounds__(BLOCK) void k_replace_delta_sfc(PlevTable pt, int n
             if (i == k) { P = ps; D = ds; }
             else if (fill && i > k) D = ds;
         }
-        outP[base + (long long)i * ncol] = (T)P;
+        outP[base + (long long)i * ncol] = (TP)P;
         outD[base + (long long)i * ncol] = (T)D;
     }
 }
@@ -2458,6 +2541,27 @@ __global__ __launch_bounds__(BLOCK) void k_integrate_tos(long long n, const T *_
         r = fr * s + (1 - fr) * o;                                  // :1184
     }
     out[i] = (T)r;
+}
+
+// integrate_tos in the reference's dtype flow: every operand in its own storage type, the blend (:1183-1184) in numpy's
+// promoted type at every node (C++'s usual arithmetic conversions; np.clip keeps the dtype of its array), written into the
+// float64 array of :1180 (np.ones)
+template <typename TO_, typename TS, typename TL, typename TI>
+__global__ __launch_bounds__(BLOCK) void k_integrate_tos_mixed(long long n, const TO_ *__restrict__ tos, const TS *__restrict__ ts,
+                                                               const TL *__restrict__ land, const TI *__restrict__ ice,
+                                                               double *__restrict__ out) {
+    long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const TO_ o = tos[i];
+    const TS s = ts[i];
+    const TI ic = ice[i];
+    double r = (double)s;                                           // :1180-1181
+    if (ic == ic && o == o) {                                       // :1173
+        auto fr = ic + land[i];
+        fr = (fr < 0) ? decltype(fr)(0) : ((fr > 1) ? decltype(fr)(1) : fr);      // :1183: NaN stays NaN
+        r = (double)(fr * s + (decltype(fr)(1) - fr) * o);          // :1184
+    }
+    out[i] = r;
 }
 
 // p_ref_inp = None (step_03:219-253 with determine_p_ref, functions.py:583-598): per column the first

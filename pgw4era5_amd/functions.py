@@ -119,6 +119,106 @@ def _fit(x, shape, name):
         raise ValueError('%s: shape %s does not broadcast to %s' % (name, r.shape, shape)) from None
 
 
+# ------------------------------------------------------------------------------- dtype flow
+_F32, _F64 = np.dtype('float32'), np.dtype('float64')
+
+# per function of settings.function_dtype_flow = 'reference': (operands that go to the device in their own dtype, operands
+# that must be float64, result).  The result is 'promote' (numpy's promoted type of all operands), the name of the operand
+# whose dtype it takes, 'float64', or a tuple of those for a function with several results.
+_FLOW_RULES = {
+    'specific_humidity_to_vapor_pressure': (('hus', 'pa'), (), 'promote'),                       # functions.py:58-64
+    'vapor_pressure_to_specific_humidity': (('vapp', 'pa'), (), 'promote'),                      # :66-72
+    'saturation_vapor_pressure_water_or_ice': (('ta',), (), 'ta'),                               # :74-89 (pa is unused)
+    'saturation_vapor_pressure_water_and_ice': (('ta',), (), 'ta'),                              # :91-105
+    'specific_to_relative_humidity': (('hus', 'pa', 'ta'), (), 'promote'),                       # :107-116
+    'relative_to_specific_humidity': (('hur', 'pa', 'ta'), (), 'promote'),                       # :118-125
+    'integ_geopot': (('zgs', 'ta', 'hus'), ('pa_hl', 'p_ref'), 'float64'),                       # :128-189
+    'interp_logp_4d': (('var',), ('source_P', 'targ_P'), 'float64'),                             # :434-477
+    'interp_1d_for_timelatlon': (('orig_array',), ('src_p', 'targ_p'), 'float64'),               # :479-508
+    'interp_extrap_1d': (('src_y',), ('src_x', 'targ_x'), 'float64'),                            # :511-580
+    'replace_delta_sfc': (('delta', 'delta_sfc', 'ps_hist'), ('source_P',), ('float64', 'delta')),   # :343-366
+    'vert_interp_delta': (('delta', 'delta_sfc', 'ps_hist', 'add_to'), ('target_P',), 'float64'),    # :369-431
+    'time_lerp': (('v_before', 'v_after'), (), 'float64'),                                       # :288-292
+    'integrate_tos': (('tos_field', 'ts_field', 'land_frac', 'ice_frac'), (), 'float64'),        # :1145-1186
+}
+
+
+def _check_flow(value):
+    if value not in ('common', 'reference'):
+        raise ValueError("settings.function_dtype_flow must be 'common' or 'reference', got %r" % (value,))
+    return value
+
+
+def _flow():
+    """settings.function_dtype_flow, read at call time."""
+    from . import settings as S
+    return _check_flow(S.function_dtype_flow)
+
+
+def _float_dtype(dt):
+    """float32 / float64 as they are; anything else (integers, bool) as the float64 numpy's promotion with a python float
+    gives."""
+    dt = np.dtype(dt)
+    return dt if dt in (_F32, _F64) else _F64
+
+
+def reference_dtype_flow(function, **dtypes):
+    """What settings.function_dtype_flow = 'reference' does with operands of the given dtypes, without touching a GPU:
+    `(tags, result)` - `tags[operand]` is the C-ABI dtype tag (`_lib.PGW_F32` / `PGW_F64`) the operand is handed over with, in
+    its own dtype; `result` the dtype the reference returns (a tuple of dtypes for replace_delta_sfc: P, D).  Operands that
+    are None (an absent delta_sfc, a scalar p_ref) are left out.  A float32 array where the reference would then take a
+    float32 logarithm (pa_hl, a p_ref field, the pressures / abscissae of the interpolations) raises NotImplementedError:
+    that flow is not built, and it is not computed in float64 under the name 'reference'."""
+    try:
+        own, need64, result = _FLOW_RULES[function]
+    except KeyError:
+        raise ValueError('%s has no reference dtype flow' % function) from None
+    unknown = set(dtypes) - set(own) - set(need64)
+    if unknown:
+        raise TypeError('%s: unknown operand(s) %s' % (function, sorted(unknown)))
+    given = {k: _float_dtype(v) for k, v in dtypes.items() if v is not None}
+    for name in need64:
+        if name in given and given[name] != _F64:
+            raise NotImplementedError(
+                "%s: a float32 `%s` would make the reference take its logarithm in float32; that flow is not built - use "
+                "settings.function_dtype_flow = 'common' (or hand `%s` over as float64)" % (function, name, name))
+    tags = {k: dtype_tag(v) for k, v in given.items()}
+
+    def res(rule):
+        if rule == 'float64':
+            return _F64
+        if rule == 'promote':
+            have = [given[k] for k in own if k in given]
+            return np.result_type(*have) if have else None
+        return given.get(rule)
+    return tags, (tuple(res(r) for r in result) if isinstance(result, tuple) else res(result))
+
+
+def _own(x):
+    """ndarray (float32 / float64 as it is, anything else as float64) or DeviceArray behind an operand: no cast."""
+    r = _raw(x)
+    if isinstance(r, DeviceArray):
+        return r
+    return r if r.dtype in (_F32, _F64) else r.astype(_F64)
+
+
+def _dev_own(ctx, x, shape=None):
+    """Device array of `x` in ITS OWN dtype (the 'reference' flow: host arrays are uploaded as they are)."""
+    if x is None:
+        return None
+    r = _own(x)
+    if isinstance(r, DeviceArray):
+        return r if shape is None else r.view(shape)
+    a = np.ascontiguousarray(r)
+    if shape is not None:
+        a = a.reshape(shape)
+    return ctx.to_device(a, a.dtype)
+
+
+def _dt(x):
+    return None if x is None else _own(x).dtype
+
+
 def _shape4(x):
     s = _raw(x).shape
     if len(s) != 4:
@@ -131,6 +231,8 @@ def specific_to_relative_humidity(hus, pa, ta):
     """RH [%] from specific humidity (IFS 7.92/7.93).  reference functions.py:107-116."""
     ctx = default_context()
     pa, ta = _aligned(pa, hus), _aligned(ta, hus)
+    if _flow() == 'reference':
+        return _humidity_ref('specific_to_relative_humidity', 5, ('hus', 'pa', 'ta'), (hus, pa, ta), hus)
     dt = _common_dtype(hus, pa, ta)
     shp = _raw(hus).shape
     pa_, ta_ = _fit(pa, shp, 'pa'), _fit(ta, shp, 'ta')
@@ -144,6 +246,8 @@ def relative_to_specific_humidity(hur, pa, ta):
     """Specific humidity from RH [%].  reference functions.py:118-125."""
     ctx = default_context()
     pa, ta = _aligned(pa, hur), _aligned(ta, hur)
+    if _flow() == 'reference':
+        return _humidity_ref('relative_to_specific_humidity', 6, ('hur', 'pa', 'ta'), (hur, pa, ta), hur)
     dt = _common_dtype(hur, pa, ta)
     shp = _raw(hur).shape
     pa_, ta_ = _fit(pa, shp, 'pa'), _fit(ta, shp, 'ta')
@@ -153,7 +257,28 @@ def relative_to_specific_humidity(hur, pa, ta):
     return _out(ctx, out, hur)
 
 
+def _humidity_ref(function, which, names, operands, like):
+    """The humidity functions under settings.function_dtype_flow = 'reference' (`pgw_humidity_mixed`)."""
+    ctx = default_context()
+    shp = _raw(operands[0]).shape
+    fitted = [operands[0]] + [_fit(x, shp, n) for n, x in zip(names[1:], operands[1:])]
+    tags, res = reference_dtype_flow(function, **{n: _dt(x) for n, x in zip(names, fitted)})
+    d = [_dev_own(ctx, x) for x in fitted] + [None, None]
+    t = [tags[n] for n in names] + [0, 0]
+    out = ctx.empty(shp, res)
+    ctx._check(ctx.lib.pgw_humidity_mixed(ctx.handle, which, t[0], t[1], t[2], out.size, d[0].ptr, ptr(d[1]), ptr(d[2]), out.ptr))
+    return _out(ctx, out, like)
+
+
+_LEAF_NAMES = {0: ('specific_humidity_to_vapor_pressure', ('hus', 'pa')), 1: ('vapor_pressure_to_specific_humidity', ('vapp', 'pa')),
+               2: ('saturation_vapor_pressure_water_or_ice', ('ta',)), 3: ('saturation_vapor_pressure_water_or_ice', ('ta',)),
+               4: ('saturation_vapor_pressure_water_and_ice', ('ta',))}
+
+
 def _humidity_leaf(which, a, b, like):
+    if _flow() == 'reference':
+        fn, names = _LEAF_NAMES[which]
+        return _humidity_ref(fn, which, names, (a,) if b is None else (a, _aligned(b, a)), like)
     ctx = default_context()
     dt = _common_dtype(a) if b is None else _common_dtype(a, b)
     shp = _raw(a).shape
@@ -225,6 +350,8 @@ def integ_geopot(pa_hl, zgs, ta, hus, level1, p_ref, full_column=True):
     st = _shape4(ta)
     if len(level1) != s[1] or st[1] != s[1] - 1 or _shape4(hus) != st:
         raise ValueError('level dimensions are inconsistent')
+    if _flow() == 'reference':
+        return _integ_geopot_ref(ctx, pa_hl, zgs, ta, hus, p_ref, full_column, s, st)
     dt = _common_dtype(pa_hl, zgs, ta, hus)
     nt, n, ncol = s[0], st[1], s[2] * s[3]
     ta_, hus_ = _fit(ta, (nt, n, s[2], s[3]), 'ta'), _fit(hus, (nt, n, s[2], s[3]), 'hus')
@@ -239,6 +366,26 @@ def integ_geopot(pa_hl, zgs, ta, hus, level1, p_ref, full_column=True):
     out = ctx.empty((nt, s[2], s[3]), dt)
     ctx._check(ctx.lib.pgw_integ_geopot(ctx.handle, dtype_tag(dt), nt, n, ncol, d_p.ptr, d_z.ptr, d_t.ptr, d_q.ptr,
                                         pref_scalar, ptr(pref_field), out.ptr, 1 if full_column else 0))
+    return _out(ctx, out, zgs)
+
+
+def _integ_geopot_ref(ctx, pa_hl, zgs, ta, hus, p_ref, full_column, s, st):
+    """integ_geopot under settings.function_dtype_flow = 'reference' (`pgw_integ_geopot_mixed`): phi_hl in the dtype of zgs,
+    tav in the promoted dtype of (ta, hus), float64 pressures, float64 result."""
+    nt, n, ncol = s[0], st[1], s[2] * s[3]
+    ta_, hus_ = _fit(ta, (nt, n, s[2], s[3]), 'ta'), _fit(hus, (nt, n, s[2], s[3]), 'hus')
+    pr = _raw(p_ref) if not np.isscalar(p_ref) else None
+    is_field = pr is not None and (isinstance(pr, DeviceArray) or pr.ndim > 0)
+    tags, res = reference_dtype_flow('integ_geopot', pa_hl=_dt(pa_hl), zgs=_dt(zgs), ta=_dt(ta_), hus=_dt(hus_),
+                                     p_ref=_dt(p_ref) if is_field else None)
+    d_p, d_z = _dev_own(ctx, pa_hl), _dev_own(ctx, zgs, (nt, s[2], s[3]))
+    d_t, d_q = _dev_own(ctx, ta_), _dev_own(ctx, hus_)
+    pref_field = _dev_own(ctx, p_ref, (nt, s[2], s[3])) if is_field else None
+    pref_scalar = 0.0 if is_field else float(p_ref)
+    out = ctx.empty((nt, s[2], s[3]), res)
+    ctx._check(ctx.lib.pgw_integ_geopot_mixed(ctx.handle, tags['pa_hl'], tags['zgs'], tags['ta'], tags['hus'], nt, n, ncol,
+                                              d_p.ptr, d_z.ptr, d_t.ptr, d_q.ptr, pref_scalar, ptr(pref_field), out.ptr,
+                                              1 if full_column else 0))
     return _out(ctx, out, zgs)
 
 
@@ -263,6 +410,13 @@ def interp_logp_4d(var, source_P, targ_P, extrapolate='off', time_key=None, lat_
     if sv[1] != ss[1]:
         raise ValueError('Level dimension of var and source_P is inconsistent!')
     ctx = default_context()
+    if _flow() == 'reference':
+        tags, res = reference_dtype_flow('interp_logp_4d', var=_dt(var), source_P=_dt(source_P), targ_P=_dt(targ_P))
+        d_v, d_s, d_t = _dev_own(ctx, var), _dev_own(ctx, source_P), _dev_own(ctx, targ_P)
+        out = ctx.empty(st, res)
+        ctx._check(ctx.lib.pgw_interp_logp_4d_mixed(ctx.handle, tags['var'], tags['targ_P'], st[0], sv[1], st[1], st[2] * st[3],
+                                                    d_v.ptr, d_s.ptr, d_t.ptr, mode, 0, out.ptr))
+        return _out(ctx, out, targ_P)
     dt = _common_dtype(var, source_P, targ_P)
     d_v, d_s, d_t = _dev(ctx, var, dt), _dev(ctx, source_P, dt), _dev(ctx, targ_P, dt)
     out = ctx.empty(st, dt)
@@ -276,6 +430,14 @@ def interp_1d_for_timelatlon(orig_array, src_p, targ_p, interp_array, ntime, nla
     mode = _check_extrapolate(extrapolate)
     ctx = default_context()
     dt = np.dtype('float64')
+    if _flow() == 'reference':
+        tags, res = reference_dtype_flow('interp_1d_for_timelatlon', orig_array=_dt(orig_array), src_p=_dt(src_p), targ_p=_dt(targ_p))
+        d_v, d_s, d_t = _dev_own(ctx, orig_array), _dev_own(ctx, src_p), _dev_own(ctx, targ_p)
+        out = ctx.empty(d_t.shape, res)
+        ctx._check(ctx.lib.pgw_interp_logp_4d_mixed(ctx.handle, tags['orig_array'], tags['targ_p'], ntime, d_s.shape[1], d_t.shape[1],
+                                                    nlat * nlon, d_v.ptr, d_s.ptr, d_t.ptr, mode, 1, out.ptr))
+        interp_array[...] = out.numpy()
+        return
     d_v, d_s, d_t = _dev(ctx, orig_array, dt), _dev(ctx, src_p, dt), _dev(ctx, targ_p, dt)
     out = ctx.empty(d_t.shape, dt)
     ctx._check(ctx.lib.pgw_interp_logp_4d(ctx.handle, dtype_tag(dt), ntime, d_s.shape[1], d_t.shape[1], nlat * nlon,
@@ -289,6 +451,14 @@ def interp_extrap_1d(src_x, src_y, targ_x, extrapolate):
     ctx = default_context()
     dt = np.dtype('float64')
     S, N = len(src_x), len(targ_x)
+    if _flow() == 'reference':
+        tags, res = reference_dtype_flow('interp_extrap_1d', src_x=_dt(src_x), src_y=_dt(src_y), targ_x=_dt(targ_x))
+        d_s, d_v, d_t = _dev_own(ctx, src_x, (1, S, 1, 1)), _dev_own(ctx, src_y, (1, S, 1, 1)), _dev_own(ctx, targ_x, (1, N, 1, 1))
+        out = ctx.empty((1, N, 1, 1), res)
+        rc = ctx.lib.pgw_interp_logp_4d_mixed(ctx.handle, tags['src_y'], tags['targ_x'], 1, S, N, 1, d_v.ptr, d_s.ptr, d_t.ptr, mode, 1,
+                                              out.ptr)
+        ctx._check(0 if rc in (10, 11) else rc)             # no ascending pre-check in the 1-D function (see below)
+        return out.numpy().reshape(N)
     d_s = _dev(ctx, np.asarray(src_x, dtype=dt).reshape(1, S, 1, 1), dt)
     d_v = _dev(ctx, np.asarray(src_y, dtype=dt).reshape(1, S, 1, 1), dt)
     d_t = _dev(ctx, np.asarray(targ_x, dtype=dt).reshape(1, N, 1, 1), dt)
@@ -306,6 +476,14 @@ def time_lerp(v_before, v_after, x_hi, x_new):
     """(v_after - v_before)/x_hi * x_new + v_before: the arithmetic under load_delta's
     `.interp(time=...)` (reference functions.py:288-292; scipy interp1d linear)."""
     ctx = default_context()
+    if _flow() == 'reference':
+        v_after_ = _fit(v_after, _raw(v_before).shape, 'v_after')
+        tags, res = reference_dtype_flow('time_lerp', v_before=_dt(v_before), v_after=_dt(v_after_))
+        d_b, d_a = _dev_own(ctx, v_before), _dev_own(ctx, v_after_)
+        out = ctx.empty(d_b.shape, res)
+        ctx._check(ctx.lib.pgw_time_lerp_mixed(ctx.handle, tags['v_before'], tags['v_after'], out.size, d_b.ptr, d_a.ptr,
+                                               float(x_hi), float(x_new), out.ptr))
+        return _out(ctx, out, v_before)
     dt = _common_dtype(v_before, v_after)
     v_after_ = _fit(v_after, _raw(v_before).shape, 'v_after')
     d_b, d_a = _dev(ctx, v_before, dt), _dev(ctx, v_after_, dt)
@@ -318,6 +496,16 @@ def replace_delta_sfc(source_P, ps_hist, delta, delta_sfc):
     """reference functions.py:343-366 for one ascending-pressure column."""
     ctx = default_context()
     dt = np.dtype('float64')
+    if _flow() == 'reference':
+        S = len(source_P)
+        tags, (res_p, res_d) = reference_dtype_flow('replace_delta_sfc', source_P=_dt(source_P), delta=_dt(delta),
+                                                    delta_sfc=_dt(delta_sfc), ps_hist=_dt(ps_hist))
+        P = np.ascontiguousarray(_own(source_P))
+        d_d, d_s, d_p = _dev_own(ctx, delta, (1, S, 1)), _dev_own(ctx, delta_sfc, (1, 1)), _dev_own(ctx, ps_hist, (1, 1))
+        oP, oD = ctx.empty((1, S, 1), res_p), ctx.empty((1, S, 1), res_d)
+        ctx._check(ctx.lib.pgw_replace_delta_sfc_mixed(ctx.handle, tags['delta'], tags['delta_sfc'], tags['ps_hist'], 1, S, 1,
+                                                       P.ctypes.data_as(_dp), d_d.ptr, d_s.ptr, d_p.ptr, oP.ptr, oD.ptr))
+        return oP.numpy().reshape(S), oD.numpy().reshape(S)
     P = np.ascontiguousarray(source_P, dtype=dt)
     S = len(P)
     d_d = _dev(ctx, np.asarray(delta, dtype=dt).reshape(1, S, 1), dt)
@@ -350,9 +538,21 @@ def vert_interp_delta(delta, target_P, delta_sfc=None, ps_hist=None, ignore_top_
         raise ValueError()
     if (delta_sfc is None) != (ps_hist is None):
         raise ValueError('delta_sfc and ps_hist must be given together')
-    dt = _common_dtype(delta, target_P, delta_sfc, ps_hist, add_to)
     nt, S, ncol, N = sd[0], sd[1], sd[2] * sd[3], st[1]
     add_ = _fit(add_to, st, 'add_to') if add_to is not None else None
+    if _flow() == 'reference':
+        tags, res = reference_dtype_flow('vert_interp_delta', delta=_dt(delta), target_P=_dt(target_P), delta_sfc=_dt(delta_sfc),
+                                         ps_hist=_dt(ps_hist), add_to=_dt(add_))
+        d_d, d_t = _dev_own(ctx, delta), _dev_own(ctx, target_P)
+        d_s, d_p = _dev_own(ctx, delta_sfc, (nt, sd[2], sd[3])), _dev_own(ctx, ps_hist, (nt, sd[2], sd[3]))
+        d_add = _dev_own(ctx, add_)
+        out = ctx.empty(st, res)
+        ctx._check(ctx.lib.pgw_vert_interp_delta_mixed(
+            ctx.handle, tags['delta'], tags.get('delta_sfc', 0), tags.get('ps_hist', 0), tags['target_P'], tags.get('add_to', 0),
+            nt, S, N, ncol, pl.ctypes.data_as(_dp), d_d.ptr, ptr(d_s), ptr(d_p), d_t.ptr,
+            1 if ignore_top_pressure_error else 0, ptr(d_add), out.ptr))
+        return _out(ctx, out, target_P)
+    dt = _common_dtype(delta, target_P, delta_sfc, ps_hist, add_to)
     d_d, d_t = _dev(ctx, delta, dt), _dev(ctx, target_P, dt)
     d_s = _dev(ctx, delta_sfc, dt, (nt, sd[2], sd[3])) if delta_sfc is not None else None
     d_p = _dev(ctx, ps_hist, dt, (nt, sd[2], sd[3])) if ps_hist is not None else None
@@ -378,8 +578,17 @@ def integrate_tos(tos_field, ts_field, land_frac, ice_frac):
     """Blend SST and skin-temperature deltas by land + sea-ice fraction.
     reference functions.py:1145-1186."""
     ctx = default_context()
-    dt = _common_dtype(tos_field, ts_field, land_frac, ice_frac)
     shp = _raw(tos_field).shape
+    if _flow() == 'reference':
+        names = ('tos_field', 'ts_field', 'land_frac', 'ice_frac')
+        ops = (tos_field, ts_field, land_frac, ice_frac)
+        tags, res = reference_dtype_flow('integrate_tos', **{n: _dt(x) for n, x in zip(names, ops)})
+        d = [_dev_own(ctx, x) for x in ops]
+        out = ctx.empty(shp, res)
+        ctx._check(ctx.lib.pgw_integrate_tos_mixed(ctx.handle, *[tags[n] for n in names], out.size, d[0].ptr, d[1].ptr, d[2].ptr,
+                                                   d[3].ptr, out.ptr))
+        return _out(ctx, out, tos_field)
+    dt = _common_dtype(tos_field, ts_field, land_frac, ice_frac)
     d = [_dev(ctx, x, dt) for x in (tos_field, ts_field, land_frac, ice_frac)]
     out = ctx.empty(shp, dt)
     ctx._check(ctx.lib.pgw_integrate_tos(ctx.handle, dtype_tag(dt), out.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, out.ptr))

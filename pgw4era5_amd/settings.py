@@ -41,6 +41,20 @@ i_reinterp = 0
 #     the reference by a few 1e-7 relative and, when the last pass ends within ~0.03 m2/s2 of the threshold, by one pass.
 f32_file_mode = 'reference'
 
+# ---- not in the reference: dtype flow of the function-level API, pgw4era5_amd/functions.py ----------
+# 'common': one dtype for all operands of a call - float64 as soon as one of them is - every operand cast to it on the host,
+#     float64 arithmetic on the device, the result in that dtype.  What the functions have always done: existing callers keep
+#     their bits.
+# 'reference': what the reference's functions compute when operands differ in dtype, as they do on float32 ERA5 files (a
+#     float32 T beside float64 pressures).  No cast: every operand goes to the device in its own dtype (half the upload for
+#     the float32 ones; DeviceArrays of different dtypes are accepted), the kernels follow numpy's promotion operation by
+#     operation (phi_hl in the dtype of zgs, functions.py:141,149; float32 tav / e_sat chain, :144, :74-105; float32 value
+#     differences in the interpolations, :575-578) and the result has the dtype the reference returns.  This is what an
+#     import swap of the reference's own step_03_apply_to_era.py wants on float32 files (INTEGRATION.md route A).  A float32
+#     pressure field (float32 ak / bk; no published file) raises NotImplementedError.
+# Read at every call; any other value: ValueError.
+function_dtype_flow = 'common'
+
 # Output dtype of T, QV, U, V on float32 files in 'reference' mode.  'float64': what the reference writes (`era + delta`
 # promotes; the output file is twice the input).  'float32': the same float64 fields, narrowed on the GPU on the way out -
 # half the download and half the file written (file I/O is what bounds the end-to-end rate); PS and the pass count are the

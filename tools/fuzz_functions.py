@@ -5,7 +5,11 @@ vectors), vert_interp_delta with and without the surface insertion, integ_geopot
 the humidity pair (both over 1..3 time steps, float32 storage on ~30 % of the cases: the fp64 oracle on the stored values,
 rounded once), regrid_field on random source / target grids (periodic or not, pole rows or not, target longitudes in
 -180..180 or 0..360), smooth_annual_cycle on random record counts.  Errors must agree as well.
-Test infrastructure (imports oracle/).  usage: python tools/fuzz_functions.py [--cases 400] [--seed 0]"""
+--dtype-flow reference: settings.function_dtype_flow = 'reference' instead - every case draws a random float32 / float64 mix
+of its operands and is checked against oracle/pgw_oracle_refdtype.py (result dtype, values, errors): the humidity pair and
+leaves, integ_geopot, interp_logp_4d, vert_interp_delta, time_lerp and integrate_tos.  Without the option the tool draws
+exactly the cases it always drew.
+Test infrastructure (imports oracle/).  usage: python tools/fuzz_functions.py [--cases 400] [--seed 0] [--dtype-flow reference]"""
 import argparse
 import json
 import os
@@ -230,6 +234,114 @@ def case_ocean(rng):
     return 'ocean', 'ok'
 
 
+# ---- settings.function_dtype_flow = 'reference': random dtype mixes against the reference-dtype oracle --------------------
+EXP_F32 = 4 * 2.0 ** -23           # device expf against numpy's float32 exp
+
+
+def _dt(rng):
+    return np.float32 if rng.random() < 0.5 else np.float64
+
+
+def _verdict(name, got, want, rtol, atol=0.0):
+    if np.asarray(got).dtype != np.asarray(want).dtype:
+        return name, 'FAIL dtype %s, reference %s' % (np.asarray(got).dtype, np.asarray(want).dtype)
+    return name, 'ok' if close(got, want, rtol, atol) else 'FAIL values'
+
+
+def ref_humidity(rng):
+    from oracle import pgw_oracle_refdtype as R
+    shp = (int(rng.integers(1, 3)), int(rng.integers(1, 12)), int(rng.integers(1, 6)), int(rng.integers(1, 9)))
+    a, b, c = _dt(rng), _dt(rng), _dt(rng)
+    ta = rng.uniform(185.0, 320.0, shp).astype(c)
+    pa = rng.uniform(1.0e3, 1.05e5, shp).astype(b)
+    which = int(rng.integers(0, 5))
+    tol = 1e-12 if c == np.float64 else EXP_F32
+    if which == 0:
+        hus = (10.0 ** rng.uniform(-7, -1.7, shp)).astype(a)
+        got, want, note = both(lambda: F.specific_to_relative_humidity(hus, pa, ta), lambda: R.specific_to_relative_humidity(hus, pa, ta))
+    elif which == 1:
+        hur = rng.uniform(0.5, 120.0, shp).astype(a)
+        got, want, note = both(lambda: F.relative_to_specific_humidity(hur, pa, ta), lambda: R.relative_to_specific_humidity(hur, pa, ta))
+    elif which == 2:
+        hus = (10.0 ** rng.uniform(-7, -1.7, shp)).astype(a)
+        got, want, note = both(lambda: F.specific_humidity_to_vapor_pressure(hus, pa), lambda: R.specific_humidity_to_vapor_pressure(hus, pa))
+        tol = 0.0
+    elif which == 3:
+        e = rng.uniform(0.0, 900.0, shp).astype(a)
+        got, want, note = both(lambda: F.vapor_pressure_to_specific_humidity(e, pa), lambda: R.vapor_pressure_to_specific_humidity(e, pa))
+        tol = 0.0
+    else:
+        got, want, note = both(lambda: F.saturation_vapor_pressure_water_and_ice(pa, ta), lambda: R.saturation_vapor_pressure_water_and_ice(pa, ta))
+    return ('ref_humidity_%d' % which, note) if note else _verdict('ref_humidity_%d' % which, got, want, tol)
+
+
+def ref_geopot(rng):
+    from oracle import pgw_oracle_refdtype as R
+    nlat, nlon, nlev, seed = int(rng.integers(1, 7)), int(rng.integers(1, 9)), int(rng.integers(6, 40)), int(rng.integers(0, 1 << 30))
+    era = synthetic.make_case(nlat=nlat, nlon=nlon, nlev=nlev, seed=seed, dtype=np.float32)['era']
+    pa_hl = R.hybrid_pressure(era['ak'], era['bk'], era['PS'])[0]
+    z, t, q = era['FIS'].astype(_dt(rng)), era['T'].astype(_dt(rng)), era['QV'].astype(_dt(rng))
+    level1 = np.arange(1, nlev + 2)
+    r = rng.random()
+    p_ref = float(rng.choice([30000.0, 50000.0, 20000.0])) if r < 0.5 else (
+        rng.uniform(1.0e4, 0.9 * era['PS'].min(), era['PS'].shape) if r < 0.9 else 2.0e5)
+    got, want, note = both(lambda: F.integ_geopot(pa_hl, z, t, q, level1, p_ref), lambda: R.integ_geopot(pa_hl, z, t, q, level1, p_ref))
+    if note:
+        return 'ref_integ_geopot', note
+    if got.dtype != want.dtype:
+        return 'ref_integ_geopot', 'FAIL dtype %s' % got.dtype
+    ulp = np.spacing(np.abs(want).astype(np.float32 if z.dtype == np.float32 else np.float64)).astype(np.float64)
+    return 'ref_integ_geopot', 'ok' if np.all(np.abs(got - want) <= np.maximum(ulp, 1e-11 * np.abs(want))) else 'FAIL values'
+
+
+def ref_interp(rng):
+    from oracle import pgw_oracle_refdtype as R
+    nt, S, N, nlat, nlon = int(rng.integers(1, 3)), int(rng.integers(2, 24)), int(rng.integers(1, 50)), int(rng.integers(1, 6)), int(rng.integers(1, 9))
+    sp = np.sort(rng.uniform(50., 1.05e5, (nt, S, nlat, nlon)), axis=1)
+    tp = np.sort(rng.uniform(20., 1.09e5, (nt, N, nlat, nlon)), axis=1)
+    var = rng.normal(size=(nt, S, nlat, nlon)).astype(_dt(rng))
+    mode = str(rng.choice(['off', 'linear', 'constant', 'nan']))
+    if mode == 'off' and rng.random() < 0.8:
+        tp = np.clip(tp, sp[:, :1], sp[:, -1:])
+    got, want, note = both(lambda: F.interp_logp_4d(var, sp, tp, mode), lambda: R.interp_logp_4d(var, sp, tp, mode))
+    return ('ref_interp_' + mode, note) if note else _verdict('ref_interp_' + mode, got, want, 1e-9, 1e-9)
+
+
+def ref_vert(rng):
+    from oracle import pgw_oracle_refdtype as R
+    nlat, nlon, N = int(rng.integers(1, 6)), int(rng.integers(1, 9)), int(rng.integers(2, 40))
+    plev = synthetic.PLEV19
+    delta = rng.normal(size=(1, len(plev), nlat, nlon)).astype(_dt(rng))
+    tp = np.sort(rng.uniform(120., 1.06e5, (1, N, nlat, nlon)), axis=1)
+    with_sfc = rng.random() < 0.6
+    dsfc = rng.normal(size=(1, nlat, nlon)).astype(_dt(rng)) if with_sfc else None
+    psh = rng.uniform(4.0e4, 1.06e5, (1, nlat, nlon)).astype(_dt(rng)) if with_sfc else None
+    if with_sfc and rng.random() < 0.1:
+        psh[0, 0, 0] = 50.0
+    got, want, note = both(lambda: F.vert_interp_delta(delta, tp, dsfc, psh, True, plev=plev),
+                           lambda: R.vert_interp_delta(delta, plev, tp, dsfc, psh, True))
+    return ('ref_vert_interp_delta', note) if note else _verdict('ref_vert_interp_delta', got, want, 1e-9, 1e-9)
+
+
+def ref_riders(rng):
+    from oracle import pgw_oracle_refdtype as R
+    shp = (int(rng.integers(1, 9)), int(rng.integers(1, 12)))
+    if rng.random() < 0.5:
+        vb, va = rng.normal(size=shp).astype(_dt(rng)), rng.normal(size=shp).astype(_dt(rng))
+        x_hi = float(np.timedelta64(31, 'D').astype('timedelta64[ns]').astype(np.int64))
+        x_new = float(np.timedelta64(int(rng.integers(1, 31)), 'D').astype('timedelta64[ns]').astype(np.int64))
+        t1 = np.datetime64('2006-01-01') + np.timedelta64(int(x_new), 'ns')
+        got, want, note = both(lambda: F.time_lerp(vb, va, x_hi, x_new), lambda: R.time_lerp(vb, va, '2006-01-01', '2006-02-01', t1))
+        return ('ref_time_lerp', note) if note else _verdict('ref_time_lerp', got, want, 0.0)
+    tos = rng.normal(1.5, 0.5, shp); tos[rng.uniform(size=shp) < 0.3] = np.nan
+    ice = np.clip(rng.uniform(-0.5, 1.0, shp), 0, 1); ice[rng.uniform(size=shp) < 0.25] = np.nan
+    ops = [x.astype(_dt(rng)) for x in (tos, rng.normal(2.5, 0.5, shp), np.clip(rng.uniform(-0.3, 1.3, shp), 0, 1), ice)]
+    got, want, note = both(lambda: F.integrate_tos(*ops), lambda: R.integrate_tos(*ops))
+    return ('ref_integrate_tos', note) if note else _verdict('ref_integrate_tos', got, want, 0.0)
+
+
+REF_CASES = [ref_humidity, ref_humidity, ref_geopot, ref_interp, ref_interp, ref_vert, ref_vert, ref_riders]
+
 CASES = [case_interp, case_interp, case_vert, case_vert, case_geopot, case_humidity, case_regrid, case_regrid, case_smooth,
          case_ocean]
 
@@ -238,12 +350,19 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument('--cases', type=int, default=400)
     p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--dtype-flow', choices=['common', 'reference'], default='common',
+                   help="'reference': random dtype mixes under settings.function_dtype_flow = 'reference' against the reference-dtype oracle")
     a = p.parse_args()
+    cases = CASES
+    if a.dtype_flow == 'reference':
+        from pgw4era5_amd import settings
+        settings.function_dtype_flow = 'reference'
+        cases = REF_CASES
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
     counts, fails = {}, []
     for i in range(a.cases):
-        fn = CASES[int(rng.integers(0, len(CASES)))]
+        fn = cases[int(rng.integers(0, len(cases)))]
         state = rng.bit_generator.state
         name, res = fn(rng)
         key = res if res in ('ok', 'both raise') else 'FAIL'
@@ -252,7 +371,7 @@ def main():
             fails.append(dict(i=i, case=name, result=res[:300]))
             print(json.dumps(fails[-1]), flush=True)
         del state
-    print(json.dumps(dict(cases=a.cases, seed=a.seed, seconds=round(time.time() - t0, 1), counts=dict(sorted(counts.items())),
+    print(json.dumps(dict(cases=a.cases, seed=a.seed, **({'dtype_flow': 'reference'} if a.dtype_flow == 'reference' else {}), seconds=round(time.time() - t0, 1), counts=dict(sorted(counts.items())),
                          failures=fails[:20])))
     return 1 if fails else 0
 
