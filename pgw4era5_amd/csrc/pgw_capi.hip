@@ -155,22 +155,37 @@ static inline bool aligned16(const void *p) { return p == nullptr || (((uintptr_
 
 // columns per thread: 16 B per lane when shape and alignment allow, else 1
 // `max_v` caps the width for kernels whose register footprint makes the widest form slower.
-static int pick_vec(pgw_ctx *ctx, int dtype, long long ncol, std::initializer_list<const void *> ptrs, int max_v = 4) {
-    int v = (dtype == PGW_F64) ? 2 : 4;
-    if (v > max_v) v = max_v;
+// the widest form `v` the options, the alignment of every operand and the row length allow
+static int fit_vec(pgw_ctx *ctx, int v, long long ncol, std::initializer_list<const void *> ptrs) {
     if (ctx->opt[PGW_OPT_FORCE_VEC1]) return 1;          // test knob: scalar columns per thread
     for (const void *p : ptrs) if (!aligned16(p)) return 1;
     while (v > 1 && ncol % v != 0) v >>= 1;
     return v;
 }
+static int pick_vec(pgw_ctx *ctx, int dtype, long long ncol, std::initializer_list<const void *> ptrs, int max_v = 4) {
+    int v = (dtype == PGW_F64) ? 2 : 4;
+    if (v > max_v) v = max_v;
+    return fit_vec(ctx, v, ncol, ptrs);
+}
 
-static int status_reset(pgw_ctx *ctx) {
+static inline size_t elem_size(int dtype) { return dtype == PGW_F64 ? 8 : 4; }
+
+// blocks of a grid-stride kernel over n items: at most 16 for each of 256 CUs
+static inline unsigned int flat_grid(long long n) {
+    const unsigned int nb = nblocks(n, BLOCK), cap = 256 * 16;
+    return nb > cap ? cap : nb;
+}
+
+// a status block no kernel has reported into
+static DevStatus blank_status() {
     DevStatus z;
     memset(&z, 0, sizeof(z));
-    z.col = ~0ull;
-    z.min_targ_bits = ~0ull;
-    z.min_src_bits = ~0ull;
-    *ctx->h_status = z;
+    z.col = z.min_targ_bits = z.min_src_bits = ~0ull;
+    return z;
+}
+
+static int status_reset(pgw_ctx *ctx) {
+    *ctx->h_status = blank_status();
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_status, ctx->h_status, sizeof(DevStatus), hipMemcpyHostToDevice, ctx->stream));
     return PGW_OK;
 }
@@ -454,43 +469,50 @@ extern "C" int pgw_get_full_level_coeffs(pgw_ctx *ctx, double *akm_out, double *
     NEED(ctx, ntime >= 1 && ncol >= 1, "ntime and ncol must be positive");           \
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
-// dispatch on storage dtype and vector width
-#define DISPATCH_TV(dtype, vec, ...)                                        \
-    do {                                                                    \
-        if (dtype == PGW_F64) {                                             \
-            typedef double T;                                               \
-            if (vec == 2) { constexpr int V = 2; __VA_ARGS__; } else { constexpr int V = 1; __VA_ARGS__; } \
-        } else {                                                            \
-            typedef float T;                                                \
-            if (vec == 4) { constexpr int V = 4; __VA_ARGS__; }             \
-            else if (vec == 2) { constexpr int V = 2; __VA_ARGS__; }        \
-            else { constexpr int V = 1; __VA_ARGS__; }                      \
-        }                                                                   \
-    } while (0)
-
+// ------------------------------------------------------------------ dispatch
+// A run-time tag becomes the type of an argument of the generic lambda `f`: f(T()) for a storage type,
+// f(std::integral_constant<int, V>()) for a constant.  What a dispatcher does not call is not instantiated.
+template <int N> using int_c = std::integral_constant<int, N>;
+#define TAG_OK(t) ((t) == PGW_F32 || (t) == PGW_F64)
+template <typename F> static inline void with_type(int tag, F &&f) { if (tag == PGW_F64) f(double()); else f(float()); }
+template <typename F> static inline void with_vec(int vec, F &&f) {
+    if (vec == 4) f(int_c<4>());
+    else if (vec == 2) f(int_c<2>());
+    else f(int_c<1>());
+}
+// storage dtype and vector width: float64 V = 2, 1; float32 V = 4, 2, 1
+template <typename F> static inline void with_type_vec(int dtype, int vec, F &&f) {
+    if (dtype == PGW_F64) { if (vec == 2) f(double(), int_c<2>()); else f(double(), int_c<1>()); }
+    else with_vec(vec, [&](auto v_) { f(float(), v_); });
+}
 // storage type T of the ERA5 fields, TL of the PGW level arrays (ta_pgw, e, QV out), REF = reference-dtype mode
-// (float32 files only: T = float, TL = double)
-#define DISPATCH_TLV(dtype, ref, vec, ...)                                   \
-    do {                                                                     \
-        if (dtype == PGW_F64) {                                              \
-            typedef double T; typedef double TL; constexpr bool REF = false; \
-            if (vec == 2) { constexpr int V = 2; __VA_ARGS__; } else { constexpr int V = 1; __VA_ARGS__; } \
-        } else if (ref) {                                                    \
-            typedef float T; typedef double TL; constexpr bool REF = true;   \
-            if (vec >= 2) { constexpr int V = 2; __VA_ARGS__; } else { constexpr int V = 1; __VA_ARGS__; } \
-        } else {                                                             \
-            typedef float T; typedef float TL; constexpr bool REF = false;   \
-            if (vec == 4) { constexpr int V = 4; __VA_ARGS__; }              \
-            else if (vec == 2) { constexpr int V = 2; __VA_ARGS__; }         \
-            else { constexpr int V = 1; __VA_ARGS__; }                       \
-        }                                                                    \
-    } while (0)
+// (float32 files only: T = float, TL = double): f(T(), TL(), std::bool_constant<REF>())
+template <typename F> static inline void with_flow(int dtype, bool ref, F &&f) {
+    if (dtype == PGW_F64) f(double(), double(), std::false_type());
+    else if (ref) f(float(), double(), std::true_type());
+    else f(float(), float(), std::false_type());
+}
+// ... and vector width: float64 levels V = 2, 1; float32 levels V = 4, 2, 1
+template <typename F> static inline void with_flow_vec(int dtype, bool ref, int vec, F &&f) {
+    with_flow(dtype, ref, [&](auto t_, auto l_, auto ref_) {
+        if constexpr (sizeof(l_) == 8) { if (vec >= 2) f(t_, l_, ref_, int_c<2>()); else f(t_, l_, ref_, int_c<1>()); }
+        else with_vec(vec, [&](auto v_) { f(t_, l_, ref_, v_); });
+    });
+}
+// a run-time integer as f(int_c<i>()): `extrapolate`, `which`, a flag; the caller has checked that it lies in [0, N)
+template <typename F, int... I> static inline void with_int_(int i, F &&f, std::integer_sequence<int, I...>) { ((i == I ? f(int_c<I>()) : (void)0), ...); }
+template <int N, typename F> static inline void with_int(int i, F &&f) { with_int_(i, f, std::make_integer_sequence<int, N>()); }
+// 32-bit byte offsets from uniform bases when every array is smaller than 4 GiB
+template <typename F> static inline void with_offsets(bool o32, F &&f) { if (o32) f(boff32()); else f(boff64()); }
 
-#define DISPATCH_T(dtype, ...)                                   \
-    do {                                                         \
-        if (dtype == PGW_F64) { typedef double T; __VA_ARGS__; } \
-        else { typedef float T; __VA_ARGS__; }                   \
-    } while (0)
+// Record source bracketing an instant; the record after it is not read when the instant is the record before (x_hi == 0).
+template <typename T> static inline DeltaSrc<T> delta_src(const void *before, const void *after, double x_hi, double x_new) {
+    return DeltaSrc<T>{(const T *)before, x_hi == 0.0 ? nullptr : (const T *)after, x_hi, x_new};
+}
+template <typename T> static inline PairSrc<T> pair_src(const void *b0, const void *a0, const void *b1, const void *a1, double x_hi,
+                                                        double x_new) {
+    return PairSrc<T>{delta_src<T>(b0, a0, x_hi, x_new), delta_src<T>(b1, a1, x_hi, x_new)};
+}
 
 extern "C" int pgw_pressure_levels(pgw_ctx *ctx, int dtype, int ntime, long long ncol,
                                    const void *ps, void *pa_hl, void *pa) {
@@ -501,8 +523,12 @@ extern "C" int pgw_pressure_levels(pgw_ctx *ctx, int dtype, int ntime, long long
     Levels lv = levels_of(ctx);
     {
         Prof pr(ctx, PGW_K_PRESSURE);
-        DISPATCH_TV(dtype, vec, hipLaunchKernelGGL((k_pressure_levels<T, V>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
-                                                    dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)ps, (T *)pa_hl, (T *)pa));
+        with_type_vec(dtype, vec, [&](auto t_, auto v_) {
+            using T = decltype(t_);
+            constexpr int V = decltype(v_)::value;
+            hipLaunchKernelGGL((k_pressure_levels<T, V>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)), dim3(BLOCK), 0,
+                               ctx->stream, lv, ntime, ncol, (const T *)ps, (T *)pa_hl, (T *)pa);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -515,13 +541,14 @@ static int humidity_flat(pgw_ctx *ctx, int kid, int dtype, long long n, const vo
     NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
     NEED(ctx, n >= 1 && x && pa && ta && out, "bad argument");
     int vec = pick_vec(ctx, dtype, n, {x, pa, ta, out});
-    long long groups = n / vec;
-    unsigned int nb = nblocks(groups, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
+    const unsigned int nb = flat_grid(n / vec);
     {
         Prof pr(ctx, kid);
-        DISPATCH_TV(dtype, vec, hipLaunchKernelGGL((k_humidity_flat<T, V, MODE>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n,
-                                                    (const T *)x, (const T *)pa, (const T *)ta, (T *)out));
+        with_type_vec(dtype, vec, [&](auto t_, auto v_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_humidity_flat<T, decltype(v_)::value, MODE>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n,
+                               (const T *)x, (const T *)pa, (const T *)ta, (T *)out);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -540,19 +567,12 @@ extern "C" int pgw_humidity_leaf(pgw_ctx *ctx, int dtype, int which, long long n
     NEED(ctx, which >= 0 && which <= 4, "which must be 0..4");
     NEED(ctx, n >= 1 && a && out && (which >= 2 || b), "bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    unsigned int nb = nblocks(n, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
-#define LEAF(W) hipLaunchKernelGGL((k_humidity_leaf<T, W>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, (const T *)a, (const T *)b, (T *)out)
-    DISPATCH_T(dtype, {
-        switch (which) {
-            case 0: LEAF(0); break;
-            case 1: LEAF(1); break;
-            case 2: LEAF(2); break;
-            case 3: LEAF(3); break;
-            default: LEAF(4); break;
-        }
-    });
-#undef LEAF
+    const unsigned int nb = flat_grid(n);
+    with_type(dtype, [&](auto t_) { with_int<5>(which, [&](auto w_) {
+        using T = decltype(t_);
+        hipLaunchKernelGGL((k_humidity_leaf<T, decltype(w_)::value>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, (const T *)a,
+                           (const T *)b, (T *)out);
+    }); });
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
 }
@@ -567,9 +587,12 @@ static int humidity_hybrid(pgw_ctx *ctx, int kid, int dtype, int ntime, long lon
     Levels lv = levels_of(ctx);
     {
         Prof pr(ctx, kid);
-        DISPATCH_TV(dtype, vec, hipLaunchKernelGGL((k_humidity_hybrid<T, V, MODE>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
-                                                    dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)x, (const T *)ps,
-                                                    (const T *)ta, (T *)out));
+        with_type_vec(dtype, vec, [&](auto t_, auto v_) {
+            using T = decltype(t_);
+            constexpr int V = decltype(v_)::value;
+            hipLaunchKernelGGL((k_humidity_hybrid<T, V, MODE>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)), dim3(BLOCK), 0,
+                               ctx->stream, lv, ntime, ncol, (const T *)x, (const T *)ps, (const T *)ta, (T *)out);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -586,17 +609,17 @@ extern "C" int pgw_relative_to_specific_humidity_hybrid(pgw_ctx *ctx, int dtype,
 // ------------------------------------------------------------------ integ_geopot
 static int launch_integ_geopot(pgw_ctx *ctx, int dtype, int nlev, int ntime, long long ncol, const void *pa_hl,
                                const void *zgs, const void *ta, const void *hus, double p_ref,
-                               const void *p_ref_field, void *phi_ref, int full_column, bool out_f64 = false) {
+                               const void *p_ref_field, void *phi_ref, int full_column) {
     int vec = pick_vec(ctx, dtype, ncol, {pa_hl, zgs, ta, hus, p_ref_field, phi_ref});
     Prof pr(ctx, PGW_K_INTEG_GEOPOT);
-#define LAUNCH_GEO(UU, TO_)                                                                                         \
-    DISPATCH_TV(dtype, vec, hipLaunchKernelGGL((k_integ_geopot<T, V, UU, TO_>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)), \
-                                                dim3(BLOCK), 0, ctx->stream, nlev, ntime, ncol, (const T *)pa_hl,     \
-                                                (const T *)zgs, (const T *)ta, (const T *)hus, p_ref,                  \
-                                                (const T *)p_ref_field, (TO_ *)phi_ref, full_column, ctx->d_status))
-    if (out_f64) { LAUNCH_GEO(4, double); }      // levels per chunk: 2 / 4 / 8 measured the same
-    else { LAUNCH_GEO(4, T); }
-#undef LAUNCH_GEO
+    with_type_vec(dtype, vec, [&](auto t_, auto v_) {
+        using T = decltype(t_);
+        constexpr int V = decltype(v_)::value;
+        // 4 levels per chunk: 2 / 4 / 8 measured the same
+        hipLaunchKernelGGL((k_integ_geopot<T, V, 4, T>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)), dim3(BLOCK), 0,
+                           ctx->stream, nlev, ntime, ncol, (const T *)pa_hl, (const T *)zgs, (const T *)ta, (const T *)hus, p_ref,
+                           (const T *)p_ref_field, (T *)phi_ref, full_column, ctx->d_status);
+    });
     return PGW_OK;
 }
 
@@ -614,16 +637,6 @@ extern "C" int pgw_integ_geopot(pgw_ctx *ctx, int dtype, int ntime, int nlev, lo
 }
 
 // ------------------------------------------------------------------ interp_logp_4d
-template <typename T, int MODE>
-static int launch_interp_mode(pgw_ctx *ctx, int ntime, int S, int N, long long ncol, const T *var, const T *sp,
-                              const T *tp, T *out, int logp_in) {
-    long long total = (long long)ntime * ncol;
-    Prof pr(ctx, PGW_K_INTERP_LOGP);
-    hipLaunchKernelGGL((k_interp_logp_stream<T, T, T, MODE>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
-                       ntime, S, N, ncol, var, sp, tp, out, logp_in, ctx->d_status);
-    return PGW_OK;
-}
-
 extern "C" int pgw_interp_logp_4d(pgw_ctx *ctx, int dtype, int ntime, int nsrc, int ntarg, long long ncol,
                                   const void *var, const void *source_P, const void *targ_P, int extrapolate,
                                   int logp_in, void *out) {
@@ -633,16 +646,15 @@ extern "C" int pgw_interp_logp_4d(pgw_ctx *ctx, int dtype, int ntime, int nsrc, 
     if (extrapolate < 0 || extrapolate > 3) return fail(ctx, PGW_ERR_ARG, "Invalid input value for \"extrapolate\"");
     int rc = status_reset(ctx);
     if (rc) return rc;
-    DISPATCH_T(dtype, {
-        const T *v = (const T *)var; const T *sp = (const T *)source_P; const T *tp = (const T *)targ_P; T *o = (T *)out;
-        switch (extrapolate) {
-            case 0: rc = launch_interp_mode<T, 0>(ctx, ntime, nsrc, ntarg, ncol, v, sp, tp, o, logp_in); break;
-            case 1: rc = launch_interp_mode<T, 1>(ctx, ntime, nsrc, ntarg, ncol, v, sp, tp, o, logp_in); break;
-            case 2: rc = launch_interp_mode<T, 2>(ctx, ntime, nsrc, ntarg, ncol, v, sp, tp, o, logp_in); break;
-            default: rc = launch_interp_mode<T, 3>(ctx, ntime, nsrc, ntarg, ncol, v, sp, tp, o, logp_in); break;
-        }
-    });
-    if (rc) return rc;
+    {
+        Prof pr(ctx, PGW_K_INTERP_LOGP);
+        with_type(dtype, [&](auto t_) { with_int<4>(extrapolate, [&](auto m_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_interp_logp_stream<T, T, T, decltype(m_)::value>), dim3(nblocks((long long)ntime * ncol, BLOCK)),
+                               dim3(BLOCK), 0, ctx->stream, ntime, nsrc, ntarg, ncol, (const T *)var, (const T *)source_P,
+                               (const T *)targ_P, (T *)out, logp_in, ctx->d_status);
+        }); });
+    }
     HIPCHK(ctx, hipGetLastError());
     return status_check(ctx);
 }
@@ -653,21 +665,6 @@ extern "C" int pgw_interp_logp_4d(pgw_ctx *ctx, int dtype, int ntime, int nsrc, 
 #endif
 constexpr int H2P_MAX_V = PGW_H2P_MAX_V;      // 1 or 2 columns per thread of k_hybrid_to_plev (see pgw_interp_hybrid_to_plev)
 static_assert(H2P_MAX_V == 1 || H2P_MAX_V == 2, "PGW_H2P_MAX_V");
-template <typename TI, typename TO, int V, typename O>
-static void launch_hybrid_to_plev(pgw_ctx *ctx, int mode, int ntime, int S, int N, long long ncol, const void *var,
-                                  const void *ps, const double *d_ap, const double *d_b, const double *d_plev,
-                                  int src_rev, int out_rev, void *out) {
-    const dim3 grid(nblocks((long long)ntime * ncol / V, BLOCK));
-#define H2P(M) hipLaunchKernelGGL((k_hybrid_to_plev<TI, TO, V, M, O>), grid, dim3(BLOCK), 0, ctx->stream, ntime, S, N, ncol, \
-                                  (const TI *)var, (const TI *)ps, d_ap, d_b, d_plev, src_rev, out_rev, (TO *)out, ctx->d_status)
-    switch (mode) {
-        case 0: H2P(0); break;
-        case 1: H2P(1); break;
-        case 2: H2P(2); break;
-        default: H2P(3); break;
-    }
-#undef H2P
-}
 
 extern "C" int pgw_interp_hybrid_to_plev(pgw_ctx *ctx, int dtype_in, int dtype_out, int ntime, int nsrc, int ntarg,
                                          long long ncol, const void *var, const void *ps, const double *ap,
@@ -686,7 +683,7 @@ extern "C" int pgw_interp_hybrid_to_plev(pgw_ctx *ctx, int dtype_in, int dtype_o
     HIPCHK(ctx, hipMemcpyAsync(d_ap, ap, sizeof(double) * nsrc, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_b, b, sizeof(double) * nsrc, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_plev, targ_plev, sizeof(double) * ntarg, hipMemcpyHostToDevice, ctx->stream));
-    const size_t s_in = dtype_in == PGW_F64 ? 8 : 4, s_out = dtype_out == PGW_F64 ? 8 : 4;
+    const size_t s_in = elem_size(dtype_in), s_out = elem_size(dtype_out);
     // columns per thread: the kernel is bound by instruction issue (about 95 logarithms and 99 interpolations per column),
     // not by its streams, and the second column's registers cost a wave per SIMD (122 -> 4 waves against 88 -> 5): same
     // box, S = 95, N = 99, 2 GB in, V = 2 / 1: 2.57 / 2.35 ms (float32 in), 1.40 / 1.30 ms (float64 in).  PGW_H2P_MAX_V = 2
@@ -697,19 +694,21 @@ extern "C" int pgw_interp_hybrid_to_plev(pgw_ctx *ctx, int dtype_in, int dtype_o
     const int sr = src_reversed != 0, orv = out_reversed != 0;
     {
         Prof pr(ctx, PGW_K_HYBRID_TO_PLEV);
-#define H2P_V(TI_, TO_, O_)                                                                                                       \
-    do {                                                                                                                          \
-        if constexpr (H2P_MAX_V >= 2) {                                                                                           \
-            if (vec == 2) { launch_hybrid_to_plev<TI_, TO_, H2P_MAX_V, O_>(ctx, extrapolate, ntime, nsrc, ntarg, ncol, var, ps, d_ap, d_b, d_plev, sr, orv, out); break; } \
-        }                                                                                                                         \
-        launch_hybrid_to_plev<TI_, TO_, 1, O_>(ctx, extrapolate, ntime, nsrc, ntarg, ncol, var, ps, d_ap, d_b, d_plev, sr, orv, out);             \
-    } while (0)
-#define H2P_O(TI_, TO_) do { if (o32) H2P_V(TI_, TO_, boff32); else H2P_V(TI_, TO_, boff64); } while (0)
-        if (dtype_in == PGW_F64) H2P_O(double, double);
-        else if (dtype_out == PGW_F64) H2P_O(float, double);
-        else H2P_O(float, float);
-#undef H2P_O
-#undef H2P_V
+        auto launch = [&](auto ti_, auto to_) { with_offsets(o32, [&](auto o_) { with_int<4>(extrapolate, [&](auto m_) {
+            using TI = decltype(ti_); using TO = decltype(to_); using O = decltype(o_);
+            constexpr int M = decltype(m_)::value;
+            auto form = [&](auto v_) {
+                constexpr int V = decltype(v_)::value;
+                hipLaunchKernelGGL((k_hybrid_to_plev<TI, TO, V, M, O>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)), dim3(BLOCK), 0,
+                                   ctx->stream, ntime, nsrc, ntarg, ncol, (const TI *)var, (const TI *)ps, d_ap, d_b, d_plev, sr, orv,
+                                   (TO *)out, ctx->d_status);
+            };
+            if constexpr (H2P_MAX_V >= 2) { if (vec == 2) return form(int_c<H2P_MAX_V>()); }
+            form(int_c<1>());
+        }); }); };
+        if (dtype_in == PGW_F64) launch(double(), double());
+        else if (dtype_out == PGW_F64) launch(float(), double());
+        else launch(float(), float());
     }
     HIPCHK(ctx, hipGetLastError());
     return status_check(ctx);
@@ -724,12 +723,14 @@ extern "C" int pgw_magnus_rh(pgw_ctx *ctx, int dtype, int ntime, int nplev, long
     double *d_plev = ctx->d_small;
     HIPCHK(ctx, hipMemcpyAsync(d_plev, plev, sizeof(double) * nplev, hipMemcpyHostToDevice, ctx->stream));
     const long long n = (long long)ntime * nplev * ncol;
-    unsigned int nb = nblocks(n, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
+    const unsigned int nb = flat_grid(n);
     {
         Prof pr(ctx, PGW_K_MAGNUS_RH);
-        DISPATCH_T(dtype, hipLaunchKernelGGL((k_magnus_rh<T>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, nplev, ncol,
-                                             (const T *)qv, d_plev, (const T *)ta, rh));
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_magnus_rh<T>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, nplev, ncol, (const T *)qv, d_plev,
+                               (const T *)ta, rh);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -754,12 +755,14 @@ extern "C" int pgw_hur_merge_levels(pgw_ctx *ctx, int dtype_amon, int ntime, int
     HIPCHK(ctx, hipMemcpyAsync(d_tab, tab.data(), sizeof(MergeLevel) * nplev, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // `tab` goes out of scope
     const long long n = (long long)ntime * nplev * ncol;
-    unsigned int nb = nblocks(n, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
+    const unsigned int nb = flat_grid(n);
     {
         Prof pr(ctx, PGW_K_HUR_MERGE);
-        DISPATCH_T(dtype_amon, hipLaunchKernelGGL((k_hur_merge_levels<T>), dim3(nb), dim3(BLOCK), 0, ctx->stream, ntime, nplev,
-                                                  namon, ncol, hur, (const T *)amon, d_tab, out));
+        with_type(dtype_amon, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_hur_merge_levels<T>), dim3(nb), dim3(BLOCK), 0, ctx->stream, ntime, nplev, namon, ncol, hur,
+                               (const T *)amon, d_tab, out);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -771,12 +774,14 @@ extern "C" int pgw_time_lerp(pgw_ctx *ctx, int dtype, long long n, const void *v
     NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
     NEED(ctx, n >= 1 && v_before && v_after && out, "bad argument");
     int vec = pick_vec(ctx, dtype, n, {v_before, v_after, out});
-    unsigned int nb = nblocks(n / vec, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
+    const unsigned int nb = flat_grid(n / vec);
     {
         Prof pr(ctx, PGW_K_TIME_LERP);
-        DISPATCH_TV(dtype, vec, hipLaunchKernelGGL((k_time_lerp<T, V>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n,
-                                                    (const T *)v_before, (const T *)v_after, x_hi, x_new, (T *)out));
+        with_type_vec(dtype, vec, [&](auto t_, auto v_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_time_lerp<T, decltype(v_)::value>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, (const T *)v_before,
+                               (const T *)v_after, x_hi, x_new, (T *)out);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -838,7 +843,6 @@ extern "C" int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int npl
         NEED(ctx, nlev_t == ctx->nlev, "nlev_t must equal the context's nlev when targ_P is NULL");
     }
     NEED(ctx, nlev_t >= 1, "nlev_t must be positive");
-    if (x_hi == 0.0) { delta_a = nullptr; dsfc_a = nullptr; pshist_a = nullptr; }
     int rc = plev_table(ctx, nplev, plev);
     if (rc) return rc;
     rc = status_reset(ctx);
@@ -848,19 +852,13 @@ extern "C" int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int npl
     long long total = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        DISPATCH_T(dtype, {
-            DeltaSrc<T> d{(const T *)delta_b, (const T *)delta_a, x_hi, x_new};
-            DeltaSrc<T> s{(const T *)dsfc_b, (const T *)dsfc_a, x_hi, x_new};
-            DeltaSrc<T> p{(const T *)pshist_b, (const T *)pshist_a, x_hi, x_new};
-            if (dsfc_b)
-                hipLaunchKernelGGL((k_vert_interp_delta<T, T, T, true>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
-                                   ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const T *)targ_P, (const T *)ps,
-                                   ignore_top ? 0 : 1, (const T *)add_to, (T *)out, ctx->d_status);
-            else
-                hipLaunchKernelGGL((k_vert_interp_delta<T, T, T, false>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream,
-                                   ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const T *)targ_P, (const T *)ps,
-                                   ignore_top ? 0 : 1, (const T *)add_to, (T *)out, ctx->d_status);
-        });
+        with_type(dtype, [&](auto t_) { with_int<2>(dsfc_b != nullptr, [&](auto sfc_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_vert_interp_delta<T, T, T, decltype(sfc_)::value != 0>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0,
+                               ctx->stream, ctx->plev_tab, lv, ntime, nlev_t, ncol, delta_src<T>(delta_b, delta_a, x_hi, x_new),
+                               delta_src<T>(dsfc_b, dsfc_a, x_hi, x_new), delta_src<T>(pshist_b, pshist_a, x_hi, x_new),
+                               (const T *)targ_P, (const T *)ps, ignore_top ? 0 : 1, (const T *)add_to, (T *)out, ctx->d_status);
+        }); });
     }
     HIPCHK(ctx, hipGetLastError());
     rc = status_check(ctx);
@@ -877,7 +875,6 @@ extern "C" int pgw_reinterp_field(pgw_ctx *ctx, int dtype, int ntime, int nplev,
     NEED(ctx, plev && delta_b && era_field && ps_era && ps_pgw && out, "null pointer");
     NEED(ctx, (dsfc_b == nullptr) == (pshist_b == nullptr), "delta_sfc and ps_hist must be given together");
     NEED(ctx, ctx->nlev > 0, "pgw_set_levels has not been called");
-    if (x_hi == 0.0) { delta_a = nullptr; dsfc_a = nullptr; pshist_a = nullptr; }
     int rc = plev_table(ctx, nplev, plev);
     if (rc) return rc;
     if ((rc = status_reset(ctx))) return rc;
@@ -885,63 +882,38 @@ extern "C" int pgw_reinterp_field(pgw_ctx *ctx, int dtype, int ntime, int nplev,
     const long long total = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        DISPATCH_T(dtype, {
-            DeltaSrc<T> d{(const T *)delta_b, (const T *)delta_a, x_hi, x_new};
-            DeltaSrc<T> s{(const T *)dsfc_b, (const T *)dsfc_a, x_hi, x_new};
-            DeltaSrc<T> p{(const T *)pshist_b, (const T *)pshist_a, x_hi, x_new};
-            if (dsfc_b)
-                hipLaunchKernelGGL((k_reinterp_field<T, true>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, ctx->plev_tab,
-                                   lv, ntime, ncol, d, s, p, (const T *)era_field, (const T *)ps_era, (const T *)ps_pgw,
-                                   ignore_top ? 0 : 1, (T *)out, ctx->d_status);
-            else
-                hipLaunchKernelGGL((k_reinterp_field<T, false>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, ctx->plev_tab,
-                                   lv, ntime, ncol, d, s, p, (const T *)era_field, (const T *)ps_era, (const T *)ps_pgw,
-                                   ignore_top ? 0 : 1, (T *)out, ctx->d_status);
-        });
+        with_type(dtype, [&](auto t_) { with_int<2>(dsfc_b != nullptr, [&](auto sfc_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_reinterp_field<T, decltype(sfc_)::value != 0>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0,
+                               ctx->stream, ctx->plev_tab, lv, ntime, ncol, delta_src<T>(delta_b, delta_a, x_hi, x_new),
+                               delta_src<T>(dsfc_b, dsfc_a, x_hi, x_new), delta_src<T>(pshist_b, pshist_a, x_hi, x_new),
+                               (const T *)era_field, (const T *)ps_era, (const T *)ps_pgw, ignore_top ? 0 : 1, (T *)out,
+                               ctx->d_status);
+        }); });
     }
     HIPCHK(ctx, hipGetLastError());
     if ((rc = status_check(ctx))) return rc;
-    if (!ignore_top) {                                     // functions.py:417-425
-        DevStatus *h = ctx->h_status;
-        if (!h->nan_seen && h->min_targ_bits != ~0ull && h->min_src_bits != ~0ull) {
-            double mt, ms;
-            memcpy(&mt, &h->min_targ_bits, 8);
-            memcpy(&ms, &h->min_src_bits, 8);
-            if (mt < ms) { ctx->err = status_text(PGW_ERR_TOP_PRESSURE); ctx->err_col = -1; return PGW_ERR_TOP_PRESSURE; }
-        }
-    }
-    return PGW_OK;
+    return top_pressure_check(ctx, ignore_top);
 }
 
-template <typename T, bool SFC, typename O, bool EVAP, typename TE0, typename TE1, typename TO, bool REF>
-static void launch_reinterp_pair_o(pgw_ctx *ctx, const Levels &lv, int ntime, long long ncol, const ReinterpPair<T, TE0, TE1, TO> &rv,
-                                   const DeltaSrc<T> &p, const T *ps_era, const T *ps_pgw, int check_top) {
-    hipLaunchKernelGGL((k_reinterp_pair<T, SFC, O, EVAP, TE0, TE1, TO, REF>), dim3(nblocks((long long)ntime * ncol, BLOCK)), dim3(BLOCK),
-                       2 * lv.nlev * sizeof(double), ctx->stream, ctx->plev_tab, lv, ntime, ncol, rv, p, ps_era, ps_pgw,
-                       check_top, ctx->d_status);
-}
+// SFC: with the surface insertion; EVAP: the loop's ta + hur pair, which also leaves e (always with the surface insertion).
+// Reference-dtype mode without EVAP is the ua + va pair after the loop: no surface form of it is instantiated.
 template <typename T, typename TE0 = T, typename TE1 = T, typename TO = T, bool REF = false>
 static void launch_reinterp_pair(pgw_ctx *ctx, const Levels &lv, int ntime, int nplev, long long ncol,
                                  const ReinterpPair<T, TE0, TE1, TO> &rv,
                                  const DeltaSrc<T> &p, const T *ps_era, const T *ps_pgw, bool sfc, int check_top) {
     // 32-bit byte offsets when every array (fields: nlev levels, delta records: nplev levels) is smaller than 4 GiB
     const unsigned long long big = (unsigned long long)ntime * (lv.nlev > nplev ? lv.nlev : nplev) * ncol * sizeof(TO);
-    const bool o32 = big < (1ull << 32) && !ctx->opt[PGW_OPT_FORCE_OFF64];
-    if (rv.evap) {                                       // the loop's ta + hur pair (always with the surface insertion)
-        if (o32) launch_reinterp_pair_o<T, true, boff32, true, TE0, TE1, TO, REF>(ctx, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top);
-        else launch_reinterp_pair_o<T, true, boff64, true, TE0, TE1, TO, REF>(ctx, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top);
-    } else if constexpr (!REF) {
-        if (o32) {
-            if (sfc) launch_reinterp_pair_o<T, true, boff32, false, TE0, TE1, TO, REF>(ctx, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top);
-            else launch_reinterp_pair_o<T, false, boff32, false, TE0, TE1, TO, REF>(ctx, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top);
-        } else {
-            if (sfc) launch_reinterp_pair_o<T, true, boff64, false, TE0, TE1, TO, REF>(ctx, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top);
-            else launch_reinterp_pair_o<T, false, boff64, false, TE0, TE1, TO, REF>(ctx, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top);
-        }
-    } else {                                             // reference-dtype mode without EVAP: the ua + va pair after the loop
-        if (o32) launch_reinterp_pair_o<T, false, boff32, false, TE0, TE1, TO, REF>(ctx, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top);
-        else launch_reinterp_pair_o<T, false, boff64, false, TE0, TE1, TO, REF>(ctx, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top);
-    }
+    with_offsets(big < (1ull << 32) && !ctx->opt[PGW_OPT_FORCE_OFF64], [&](auto o_) {
+        auto launch = [&](auto sfc_, auto evap_) {
+            hipLaunchKernelGGL((k_reinterp_pair<T, decltype(sfc_)::value, decltype(o_), decltype(evap_)::value, TE0, TE1, TO, REF>),
+                               dim3(nblocks((long long)ntime * ncol, BLOCK)), dim3(BLOCK), 2 * lv.nlev * sizeof(double), ctx->stream,
+                               ctx->plev_tab, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top, ctx->d_status);
+        };
+        if (rv.evap) return launch(std::true_type(), std::true_type());
+        if constexpr (!REF) { if (sfc) return launch(std::true_type(), std::false_type()); }
+        launch(std::false_type(), std::false_type());
+    });
 }
 
 extern "C" int pgw_reinterp_pair(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const double *plev,
@@ -965,40 +937,27 @@ extern "C" int pgw_reinterp_pair(pgw_ctx *ctx, int dtype, int ntime, int nplev, 
     Levels lv = levels_of(ctx);
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        DISPATCH_T(dtype, {
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
             ReinterpPair<T> rv;
             for (int v = 0; v < 2; ++v) {
-                rv.d[v] = DeltaSrc<T>{(const T *)delta_b[v], lerp ? (const T *)delta_a[v] : nullptr, x_hi, x_new};
-                rv.sfc[v] = DeltaSrc<T>{dsfc_b ? (const T *)dsfc_b[v] : nullptr, (dsfc_b && lerp) ? (const T *)dsfc_a[v] : nullptr, x_hi, x_new};
+                rv.d[v] = delta_src<T>(delta_b[v], lerp ? delta_a[v] : nullptr, x_hi, x_new);
+                rv.sfc[v] = delta_src<T>(dsfc_b ? dsfc_b[v] : nullptr, (dsfc_b && lerp) ? dsfc_a[v] : nullptr, x_hi, x_new);
                 rv.out[v] = (T *)out[v];
             }
             rv.era0 = (const T *)era_field[0]; rv.era1 = (const T *)era_field[1];
             rv.evap = nullptr;
-            DeltaSrc<T> p{(const T *)pshist_b, lerp ? (const T *)pshist_a : nullptr, x_hi, x_new};
-            launch_reinterp_pair<T>(ctx, lv, ntime, nplev, ncol, rv, p, (const T *)ps_era, (const T *)ps_pgw, dsfc_b != nullptr,
-                                    ignore_top ? 0 : 1);
+            launch_reinterp_pair<T>(ctx, lv, ntime, nplev, ncol, rv, delta_src<T>(pshist_b, pshist_a, x_hi, x_new), (const T *)ps_era,
+                                    (const T *)ps_pgw, dsfc_b != nullptr, ignore_top ? 0 : 1);
         });
     }
     HIPCHK(ctx, hipGetLastError());
     if ((rc = status_check(ctx))) return rc;
-    if (!ignore_top) {                                     // functions.py:417-425
-        DevStatus *h = ctx->h_status;
-        if (!h->nan_seen && h->min_targ_bits != ~0ull && h->min_src_bits != ~0ull) {
-            double mt, ms;
-            memcpy(&mt, &h->min_targ_bits, 8);
-            memcpy(&ms, &h->min_src_bits, 8);
-            if (mt < ms) { ctx->err = status_text(PGW_ERR_TOP_PRESSURE); ctx->err_col = -1; return PGW_ERR_TOP_PRESSURE; }
-        }
-    }
-    return PGW_OK;
+    return top_pressure_check(ctx, ignore_top);
 }
 
-extern "C" int pgw_replace_delta_sfc(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol,
-                                     const double *plev_asc, const void *delta, const void *delta_sfc,
-                                     const void *ps_hist, void *out_P, void *out_delta) {
-    CHECK_COMMON(ctx, dtype, ntime, ncol);
-    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV, "nplev must be in [1, 64]");
-    NEED(ctx, plev_asc && delta && delta_sfc && ps_hist && out_P && out_delta, "null pointer");
+// pressure levels that are ascending as given (no reversal, no logarithms): p, n and the extrema
+static PlevTable ascending_plev_table(int nplev, const double *plev_asc) {
     PlevTable t;
     memset(&t, 0, sizeof(t));
     t.n = nplev; t.pmax = -INFINITY; t.pmin = INFINITY;
@@ -1007,14 +966,26 @@ extern "C" int pgw_replace_delta_sfc(pgw_ctx *ctx, int dtype, int ntime, int npl
         if (t.p[i] > t.pmax) t.pmax = t.p[i];
         if (t.p[i] < t.pmin) t.pmin = t.p[i];
     }
+    return t;
+}
+
+extern "C" int pgw_replace_delta_sfc(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol,
+                                     const double *plev_asc, const void *delta, const void *delta_sfc,
+                                     const void *ps_hist, void *out_P, void *out_delta) {
+    CHECK_COMMON(ctx, dtype, ntime, ncol);
+    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV, "nplev must be in [1, 64]");
+    NEED(ctx, plev_asc && delta && delta_sfc && ps_hist && out_P && out_delta, "null pointer");
+    const PlevTable t = ascending_plev_table(nplev, plev_asc);
     int rc = status_reset(ctx);
     if (rc) return rc;
     long long total = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        DISPATCH_T(dtype, hipLaunchKernelGGL((k_replace_delta_sfc<T>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, t,
-                                             ntime, ncol, (const T *)delta, (const T *)delta_sfc, (const T *)ps_hist,
-                                             (T *)out_P, (T *)out_delta, ctx->d_status));
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_replace_delta_sfc<T>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, t, ntime, ncol,
+                               (const T *)delta, (const T *)delta_sfc, (const T *)ps_hist, (T *)out_P, (T *)out_delta, ctx->d_status);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return status_check(ctx);
@@ -1038,10 +1009,14 @@ static int launch_step(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const
     // fp64 state arrays are read with V doubles per lane: 16*V/2 B alignment follows from ncol % V == 0
     Levels lv = levels_of(ctx);
     Prof pr(ctx, PGW_K_ADJUST_PS_STEP);
-    DISPATCH_TLV(dtype, ref, vec, hipLaunchKernelGGL((k_adjust_ps_step<T, TL, V, STEP_U, REF>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
-                                                     dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const TL *)ta, (const TL *)evap,
-                                                     (const T *)PS, (const T *)FIS, phi_ref_era, dphi_clim, delta_ps, adj_ps,
-                                                     p_ref, p_ref_field, adj_factor, full_column, apply_adj, st, clear));
+    with_flow_vec(dtype, ref, vec, [&](auto t_, auto l_, auto ref_, auto v_) {
+        using T = decltype(t_); using TL = decltype(l_);
+        constexpr int V = decltype(v_)::value;
+        hipLaunchKernelGGL((k_adjust_ps_step<T, TL, V, STEP_U, decltype(ref_)::value>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
+                           dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const TL *)ta, (const TL *)evap, (const T *)PS,
+                           (const T *)FIS, phi_ref_era, dphi_clim, delta_ps, adj_ps, p_ref, p_ref_field, adj_factor, full_column,
+                           apply_adj, st, clear);
+    });
     return PGW_OK;
 }
 
@@ -1051,10 +1026,13 @@ static int launch_phi_ref_hybrid(pgw_ctx *ctx, int dtype, int ntime, long long n
     int vec = pick_vec(ctx, dtype, ncol, {ta, hus, PS, FIS, phi_out}, 2);
     Levels lv = levels_of(ctx);
     Prof pr(ctx, PGW_K_PHI_REF_HYBRID);
-    DISPATCH_TLV(dtype, ref, vec, hipLaunchKernelGGL((k_phi_ref_hybrid<T, V, STEP_U, REF>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
-                                                     dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)ta, (const T *)hus,
-                                                     (const T *)PS, (const T *)FIS, p_ref, p_ref_field, phi_out,
-                                                     full_column, ctx->d_status));
+    with_flow_vec(dtype, ref, vec, [&](auto t_, auto, auto ref_, auto v_) {
+        using T = decltype(t_);
+        constexpr int V = decltype(v_)::value;
+        hipLaunchKernelGGL((k_phi_ref_hybrid<T, V, STEP_U, decltype(ref_)::value>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
+                           dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)ta, (const T *)hus, (const T *)PS, (const T *)FIS,
+                           p_ref, p_ref_field, phi_out, full_column, ctx->d_status);
+    });
     return PGW_OK;
 }
 
@@ -1078,9 +1056,8 @@ extern "C" int pgw_adjust_ps_step(pgw_ctx *ctx, int dtype, int ntime, long long 
     CHECK_COMMON(ctx, dtype, ntime, ncol);
     NEED(ctx, ctx->nlev > 0, "pgw_set_levels has not been called");
     NEED(ctx, ta_pgw && hur_pgw && PS && FIS && phi_ref_era && dphi_clim && delta_ps && adj_ps, "null pointer");
-    size_t es = dtype == PGW_F64 ? 8 : 4;
     void *evap = nullptr;
-    int rc = ws_get(ctx, 0, (size_t)ntime * ctx->nlev * ncol * es, &evap);
+    int rc = ws_get(ctx, 0, (size_t)ntime * ctx->nlev * ncol * elem_size(dtype), &evap);
     if (rc) return rc;
     rc = humidity_hybrid<2>(ctx, PGW_K_RH_TO_Q, dtype, ntime, ncol, hur_pgw, PS, ta_pgw, evap);
     if (rc) return rc;
@@ -1092,6 +1069,15 @@ extern "C" int pgw_adjust_ps_step(pgw_ctx *ctx, int dtype, int ntime, long long 
     rc = status_check(ctx);
     if (max_abs_err) *max_abs_err = max_err_of(ctx);
     return rc;
+}
+
+static void launch_update_ps(pgw_ctx *ctx, int dtype, long long n, const void *PS, double *delta_ps, const double *adj_ps,
+                             void *ps_pgw) {
+    with_type(dtype, [&](auto t_) {
+        using T = decltype(t_);
+        hipLaunchKernelGGL((k_update_ps<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, (const T *)PS, delta_ps, adj_ps,
+                           (T *)ps_pgw);
+    });
 }
 
 extern "C" int pgw_reinterp_pass(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const double *plev,
@@ -1110,31 +1096,28 @@ extern "C" int pgw_reinterp_pass(pgw_ctx *ctx, int dtype, int ntime, int nplev, 
     const bool lerp = (x_hi != 0.0);
     NEED(ctx, !lerp || (delta_a && delta_a[0] && delta_a[1] && dsfc_a && dsfc_a[0] && dsfc_a[1] && pshist_a),
          "the record after the instant is missing");
-    const size_t es = dtype == PGW_F64 ? 8 : 4;
     void *evap = nullptr;
-    int rc = ws_get(ctx, 0, (size_t)ntime * ctx->nlev * ncol * es, &evap);
+    int rc = ws_get(ctx, 0, (size_t)ntime * ctx->nlev * ncol * elem_size(dtype), &evap);
     if (rc) return rc;
     if ((rc = plev_table(ctx, nplev, plev))) return rc;
     if ((rc = status_reset(ctx))) return rc;
     Levels lv = levels_of(ctx);
     const long long n2 = (long long)ntime * ncol;
-    {   // step_03:192-193
-        DISPATCH_T(dtype, hipLaunchKernelGGL((k_update_ps<T>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, n2,
-                                             (const T *)PS, delta_ps, adj_ps, (T *)ps_pgw));
-    }
+    launch_update_ps(ctx, dtype, n2, PS, delta_ps, adj_ps, ps_pgw);      // step_03:192-193
     {   // :202-216 for ta and hur, + e of functions.py:123
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        DISPATCH_T(dtype, {
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
             ReinterpPair<T> rv;
             for (int v = 0; v < 2; ++v) {
-                rv.d[v] = DeltaSrc<T>{(const T *)delta_b[v], lerp ? (const T *)delta_a[v] : nullptr, x_hi, x_new};
-                rv.sfc[v] = DeltaSrc<T>{(const T *)dsfc_b[v], lerp ? (const T *)dsfc_a[v] : nullptr, x_hi, x_new};
+                rv.d[v] = delta_src<T>(delta_b[v], lerp ? delta_a[v] : nullptr, x_hi, x_new);
+                rv.sfc[v] = delta_src<T>(dsfc_b[v], lerp ? dsfc_a[v] : nullptr, x_hi, x_new);
             }
             rv.era0 = (const T *)T_era; rv.era1 = (const T *)RELHUM_era;
             rv.out[0] = (T *)ta_pgw; rv.out[1] = (T *)hur_pgw;
             rv.evap = (T *)evap;
-            DeltaSrc<T> p{(const T *)pshist_b, lerp ? (const T *)pshist_a : nullptr, x_hi, x_new};
-            launch_reinterp_pair<T>(ctx, lv, ntime, nplev, ncol, rv, p, (const T *)PS, (const T *)ps_pgw, true, ignore_top ? 0 : 1);
+            launch_reinterp_pair<T>(ctx, lv, ntime, nplev, ncol, rv, delta_src<T>(pshist_b, pshist_a, x_hi, x_new), (const T *)PS,
+                                    (const T *)ps_pgw, true, ignore_top ? 0 : 1);
         });
     }
     // :262-308: the pass on the re-interpolated fields (delta_ps already carries this pass's increment)
@@ -1144,16 +1127,7 @@ extern "C" int pgw_reinterp_pass(pgw_ctx *ctx, int dtype, int ntime, int nplev, 
     rc = status_check(ctx);
     if (max_abs_err) *max_abs_err = max_err_of(ctx);
     if (rc) return rc;
-    if (!ignore_top) {                                     // functions.py:417-425
-        DevStatus *h = ctx->h_status;
-        if (!h->nan_seen && h->min_targ_bits != ~0ull && h->min_src_bits != ~0ull) {
-            double mt, ms;
-            memcpy(&mt, &h->min_targ_bits, 8);
-            memcpy(&ms, &h->min_src_bits, 8);
-            if (mt < ms) { ctx->err = status_text(PGW_ERR_TOP_PRESSURE); ctx->err_col = -1; return PGW_ERR_TOP_PRESSURE; }
-        }
-    }
-    return PGW_OK;
+    return top_pressure_check(ctx, ignore_top);
 }
 
 extern "C" int pgw_update_ps(pgw_ctx *ctx, int dtype, long long n, const void *PS, double *delta_ps,
@@ -1161,8 +1135,7 @@ extern "C" int pgw_update_ps(pgw_ctx *ctx, int dtype, long long n, const void *P
     NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
     NEED(ctx, n >= 1 && PS && delta_ps && adj_ps && ps_pgw, "bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    DISPATCH_T(dtype, hipLaunchKernelGGL((k_update_ps<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n,
-                                         (const T *)PS, delta_ps, adj_ps, (T *)ps_pgw));
+    launch_update_ps(ctx, dtype, n, PS, delta_ps, adj_ps, ps_pgw);
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
 }
@@ -1251,62 +1224,118 @@ static int loop_state(pgw_ctx *ctx, long long n2, LoopState *ls) {
     return PGW_OK;
 }
 
+// plev coordinate in file order for the local reference level (p_ref_inp = None); nplev = 0: fixed p_ref, an empty table
+static PlevTable file_order_table(int nplev, const double *plev_file) {
+    PlevTable t;
+    memset(&t, 0, sizeof(t));
+    t.n = nplev;
+    for (int i = 0; i < nplev; ++i) t.p[i] = plev_file[i];
+    return t;
+}
+
+// n blank blocks in the pinned host area behind the read-back blocks: what a copy arms per-pass device blocks with
+static DevStatus *blank_blocks(pgw_ctx *ctx, int n) {
+    DevStatus *blank = ctx->h_status + 2 + MULTI_MAX_PASS;
+    for (int k = 0; k < n; ++k) blank[k] = blank_status();
+    return blank;
+}
+
+// g * (time-interpolated zg delta at p_ref)   step_03:292-295;   + delta_ps = adj_ps = 0   :182-184
+static void launch_dphi_clim(pgw_ctx *ctx, int dtype, bool ref, long long n2, const void *zg_b, const void *zg_a, double x_hi,
+                             double x_new, const LoopState &ls) {
+    with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
+        using T = decltype(t_);
+        hipLaunchKernelGGL((k_dphi_clim<T, decltype(ref_)::value>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, n2,
+                           delta_src<T>(zg_b, zg_a, x_hi, x_new), CON_G, ls.dphi, ls.delta_ps, ls.adj_ps);
+    });
+}
+
+// delta_ps += adj_ps; the column's reference level (never lower than the last pass's); g * zg there   :192, 219-253, 292-295
+static void launch_local_p_ref(pgw_ctx *ctx, int dtype, bool ref, const PlevTable &ptf, long long n2, long long ncol, const void *PS,
+                               const void *zg3_b, const void *zg3_a, double x_hi, double x_new, int first_pass, const LoopState &ls) {
+    with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
+        using T = decltype(t_);
+        hipLaunchKernelGGL((k_local_p_ref<T, decltype(ref_)::value>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, ptf,
+                           ctx->h_akN, ctx->h_bkN, n2, (const T *)PS, ls.delta_ps, ls.adj_ps, delta_src<T>(zg3_b, zg3_a, x_hi, x_new),
+                           ncol, first_pass, ls.pref_f, ls.pref_idx, ls.dphi, ctx->d_status);
+    });
+}
+
+// ps_pgw = PS + dps and hus_pgw from e on the final levels (:262-266, 370); the first qv_done_levels levels of hus_pgw are
+// already written
+static void launch_finalize(pgw_ctx *ctx, int dtype, bool ref, int ntime, long long ncol, const void *PS, const double *dps,
+                            const void *evap, void *ps_pgw, void *hus_pgw, int qv_done_levels) {
+    int vec = pick_vec(ctx, dtype, ncol, {PS, evap, ps_pgw, hus_pgw, dps});
+    Levels lv = levels_of(ctx);
+    Prof pr(ctx, PGW_K_FINALIZE);
+    with_flow_vec(dtype, ref, vec, [&](auto t_, auto l_, auto ref_, auto v_) {
+        using T = decltype(t_); using TL = decltype(l_);
+        constexpr int V = decltype(v_)::value;
+        hipLaunchKernelGGL((k_finalize_ps_hus<T, TL, V, decltype(ref_)::value>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
+                           dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)PS, dps, (const TL *)evap, (T *)ps_pgw,
+                           (TL *)hus_pgw, qv_done_levels);
+    });
+}
+
 // The loop of step_03_apply_to_era.py:182-319 given the iterate-independent vapour pressure
 // `evap` = hur_pgw/100 * e_sat(ta_pgw) (functions.py:123).  Shared by pgw_adjust_ps_loop and
 // pgw_step03_file.  The host reads max|err| after every pass (status copy + stream synchronisation) before it
 // launches the next - the reference's control flow literally (four device-assisted variants, with the passes
 // enqueued ahead of the host, all measured slower: DESIGN.md section 4, "tried and dropped").
-// local_nplev > 0 selects p_ref_inp = None (step_03:219-253): dzg_b/dzg_a are then the full
-// (ntime, nplev, ncol) zg records and `plev_file` the plev coordinate in file order.
-static int run_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const void *PS, const void *FIS,
-                       const void *T, const void *QV, const void *ta_pgw, const void *evap,
-                       const void *dzg_b, const void *dzg_a, double x_hi, double x_new, double p_ref,
-                       double adj_factor, double thresh, int max_n_iter, void *ps_pgw, void *hus_pgw, int *n_iter,
-                       double *max_err_hist, int hist_len, int local_nplev = 0, const double *plev_file = nullptr,
-                       bool status_armed = false, int qv_done_levels = 0, bool ref = false, bool fused_first = false) {
-    // fused_first (pgw_step03_file, PGW_OPT_FUSED_FIRST): k_delta_quad has run the ERA-state scan and pass 1 for the groups
-    // of columns it did not flag - the loop state in workspace slot 1, dps_hist[0] and the status block of pass 1 hold
-    // their results.  The first launch is then two: pass 1 for the flagged groups alone (k_ps_loop_multi<.., FLAGGED>),
-    // and passes 2 .. np for all columns as a continuation launch.
-    const long long n2 = (long long)ntime * ncol;
+struct PsLoopArgs {
+    int dtype = PGW_F64, ntime = 0;
+    long long ncol = 0;
+    const void *PS = nullptr, *FIS = nullptr, *T = nullptr, *QV = nullptr;     // ERA state
+    const void *ta_pgw = nullptr, *evap = nullptr;                             // PGW levels
+    // zg delta records bracketing the instant: at p_ref (ntime, ncol), or with local_nplev > 0 the full (ntime, nplev, ncol)
+    const void *dzg_b = nullptr, *dzg_a = nullptr;
+    double x_hi = 0.0, x_new = 0.0;
+    double p_ref = 0.0, adj_factor = 0.0, thresh = 0.0;
+    int max_n_iter = 0;
+    void *ps_pgw = nullptr, *hus_pgw = nullptr;                                // outputs (may be null)
+    int *n_iter = nullptr;
+    double *max_err_hist = nullptr;
+    int hist_len = 0;
+    // local_nplev > 0 selects p_ref_inp = None (step_03:219-253); `plev_file` is then the plev coordinate in file order
+    int local_nplev = 0;
+    const double *plev_file = nullptr;
+    // pgw_step03_file with the model-top check off: nothing is read back before the first pass; the status block keeps the
+    // first error any kernel reported, in stream order, so the first pass's check raises what an immediate check would have
+    bool status_armed = false;
+    int qv_done_levels = 0;          // leading levels of hus_pgw the caller has already written
+    bool ref = false;                // reference-dtype mode
+    // pgw_step03_file, PGW_OPT_FUSED_FIRST: k_delta_quad has run the ERA-state scan and pass 1 for the groups of columns it
+    // did not flag - the loop state in workspace slot 1, dps_hist[0] and the status block of pass 1 hold their results.  The
+    // first launch is then two: pass 1 for the flagged groups alone (k_ps_loop_multi<.., FLAGGED>), and passes 2 .. np for
+    // all columns as a continuation launch.
+    bool fused_first = false;
+};
+
+static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
+    const int dtype = a.dtype, ntime = a.ntime;
+    const long long ncol = a.ncol, n2 = (long long)ntime * ncol;
     int rc;
     if (ctx->opt[PGW_OPT_TEST_FAIL] == 1) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 1: forced workspace failure (ws_get)");
     LoopState ls;
     if ((rc = loop_state(ctx, n2, &ls))) return rc;
-    double *phi_era = ls.phi_era, *dphi = ls.dphi, *delta_ps = ls.delta_ps, *adj_ps = ls.adj_ps, *pref_f = ls.pref_f;
-    int *pref_idx = ls.pref_idx;
     const int full_column = ctx->opt[PGW_OPT_FULL_COLUMN];
-    const bool local = local_nplev > 0;
+    const bool local = a.local_nplev > 0;
     // several passes per launch: fixed p_ref, wave-level early exit (the full-column option is a per-pass traffic probe)
     const bool multipass = ctx->opt[PGW_OPT_MULTIPASS] && !full_column;
     NEED(ctx, !ctx->reduce_fn || multipass, "a reduce hook (latitude-band sharding) needs the multi-pass loop: "
                                             "PGW_OPT_MULTIPASS = 1, PGW_OPT_FULL_COLUMN = 0");
-    PlevTable ptf;
-    memset(&ptf, 0, sizeof(ptf));
-    if (local) {
-        ptf.n = local_nplev;
-        for (int i = 0; i < local_nplev; ++i) ptf.p[i] = plev_file[i];
-    }
+    const PlevTable ptf = file_order_table(a.local_nplev, a.plev_file);
     if (multipass) {
         // phi_ref of the ERA state, g * dzg and the zeroed state are produced by the first k_ps_loop_multi launch
     } else if (local) {
-        HIPCHK(ctx, hipMemsetAsync(delta_ps, 0, sizeof(double) * 2 * n2, ctx->stream));    // :182-184
+        HIPCHK(ctx, hipMemsetAsync(ls.delta_ps, 0, sizeof(double) * 2 * n2, ctx->stream));    // :182-184
     } else {
         // phi_ref_era: constant over the iterations for a fixed p_ref (step_03:280-287 recomputes it).
-        if (!status_armed && (rc = status_reset(ctx))) return rc;
-        launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, T, QV, PS, FIS, p_ref, phi_era, full_column, nullptr, ref);
+        if (!a.status_armed && (rc = status_reset(ctx))) return rc;
+        launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, a.T, a.QV, a.PS, a.FIS, a.p_ref, ls.phi_era, full_column, nullptr, a.ref);
         HIPCHK(ctx, hipGetLastError());
-        // status_armed (pgw_step03_file with the model-top check off): nothing is read back before the first pass;
-        // the status block keeps the first error any kernel reported, in stream order, so the first pass's check
-        // raises what an immediate check would have raised
-        if (!status_armed && (rc = status_check(ctx))) return rc;
-        // g * (time-interpolated zg delta at p_ref)   step_03:292-295
-        DISPATCH_TLV(dtype, ref, 1, {
-            DeltaSrc<T> z{(const T *)dzg_b, (x_hi == 0.0) ? nullptr : (const T *)dzg_a, x_hi, x_new};
-            hipLaunchKernelGGL((k_dphi_clim<T, REF>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, n2, z, CON_G, dphi,
-                               delta_ps, adj_ps);                                       // + delta_ps = adj_ps = 0  :182-184
-            (void)V;
-        });
+        if (!a.status_armed && (rc = status_check(ctx))) return rc;
+        launch_dphi_clim(ctx, dtype, a.ref, n2, a.dzg_b, a.dzg_a, a.x_hi, a.x_new, ls);
     }
 
     if (multipass) {
@@ -1316,58 +1345,52 @@ static int run_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const
         double *dps_hist = (double *)histv;
         DevStatus *mst = ctx->d_status + 2;                                // device per-pass blocks
         DevStatus *hback = ctx->h_status + 1;                              // [0] = block 0 (ERA-state scan / earlier kernels), [1..] passes
-        DevStatus *hzero = ctx->h_status + 2 + MULTI_MAX_PASS;
-        for (int k = 0; k < MULTI_MAX_PASS; ++k) {
-            memset(&hzero[k], 0, sizeof(DevStatus));
-            hzero[k].col = ~0ull; hzero[k].min_targ_bits = ~0ull; hzero[k].min_src_bits = ~0ull;
-        }
-        if (!status_armed && (rc = status_reset(ctx))) return rc;
+        DevStatus *hzero = blank_blocks(ctx, MULTI_MAX_PASS);
+        if (!a.status_armed && (rc = status_reset(ctx))) return rc;
         int it = 1;
         bool first = true;
         unsigned long long touched = 0;
         const double *conv = nullptr;
         int launched = 0;
-        const void *era_T = T, *era_QV = QV;                               // `T` names the storage type inside the dispatch macro
         while (!conv) {
-            const int allowed = max_n_iter - (it - 1);                     // passes it .. max_n_iter may still run (:313-319)
-            int np = first ? first_launch_passes(ctx, max_n_iter) : 2;    // (a caller-set guess <= 0 counts as 1)
+            const int allowed = a.max_n_iter - (it - 1);                   // passes it .. max_n_iter may still run (:313-319)
+            int np = first ? first_launch_passes(ctx, a.max_n_iter) : 2;  // (a caller-set guess <= 0 counts as 1)
             if (np > allowed) np = allowed;
             if (np < 1) np = 1;
             ctx->band_next_np = np;
             if (first && ctx->opt[PGW_OPT_TEST_FAIL] == 2) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 2: forced failure before the first loop launch");
             if (!first && ctx->opt[PGW_OPT_TEST_FAIL] == 3) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 3: forced failure before a continuation launch");
-            const bool fused_launch = first && fused_first;                // (block of pass 1: armed before the delta kernel)
+            const bool fused_launch = first && a.fused_first;              // (block of pass 1: armed before the delta kernel)
             if (!fused_launch) HIPCHK(ctx, hipMemcpyAsync(mst, hzero, sizeof(DevStatus) * np, hipMemcpyHostToDevice, ctx->stream));
             else if (np > 1) HIPCHK(ctx, hipMemcpyAsync(mst + 1, hzero + 1, sizeof(DevStatus) * (np - 1), hipMemcpyHostToDevice, ctx->stream));
             {
                 // one column per lane (two columns: 168 VGPRs + scratch; measured 1.36 vs 1.39 ms before the log table)
                 constexpr int MULTI_MAXV = 1;
-                int vec = pick_vec(ctx, dtype, ncol, {ta_pgw, evap, era_T, era_QV, PS, FIS, phi_era, dphi, delta_ps, adj_ps, dps_hist}, MULTI_MAXV);
+                int vec = pick_vec(ctx, dtype, ncol, {a.ta_pgw, a.evap, a.T, a.QV, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, dps_hist}, MULTI_MAXV);
                 Levels lv = levels_of(ctx);
                 Prof pr(ctx, PGW_K_PS_LOOP_MULTI);
-                const LocalPRef loc{ptf, ctx->h_akN, ctx->h_bkN, pref_f, pref_idx};
-                DISPATCH_TLV(dtype, ref, vec, {
-                    DeltaSrc<T> z{(const T *)dzg_b, (x_hi == 0.0) ? nullptr : (const T *)dzg_a, x_hi, x_new};
+                const LocalPRef loc{ptf, ctx->h_akN, ctx->h_bkN, ls.pref_f, ls.pref_idx};
+                with_flow_vec(dtype, a.ref, vec, [&](auto t_, auto l_, auto ref_, auto v_) {
+                    using T = decltype(t_); using TL = decltype(l_);
+                    constexpr int V = decltype(v_)::value;
+                    // `n` passes from the state as it stands (init: from the ERA state) into `blocks` and the rows of `hist`
+                    auto launch = [&](auto local_, auto flagged_, double p_ref, int init, int n, DevStatus *blocks, double *hist,
+                                      unsigned char *flags, DevStatus *st_era) {
+                        hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, decltype(ref_)::value, decltype(local_)::value, decltype(flagged_)::value>),
+                                           dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)a.T,
+                                           (const T *)a.QV, (const TL *)a.ta_pgw, (const TL *)a.evap, (const T *)a.PS, (const T *)a.FIS,
+                                           delta_src<T>(a.dzg_b, a.dzg_a, a.x_hi, a.x_new), ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps,
+                                           hist, p_ref, a.adj_factor, init, n, ctx->d_status, blocks, loc, flags, st_era);
+                    };
+                    constexpr std::true_type yes{};
+                    constexpr std::false_type no{};
                     if (fused_launch) {
-                        hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, REF, false, true>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
-                                           ctx->stream, lv, ntime, ncol, (const T *)era_T, (const T *)era_QV, (const TL *)ta_pgw,
-                                           (const TL *)evap, (const T *)PS, (const T *)FIS, z, phi_era, dphi, delta_ps, adj_ps, dps_hist,
-                                           p_ref, adj_factor, 1, 1, ctx->d_status, mst, loc, ls.era_flags, ctx->d_status + 1);
-                        if (np > 1)
-                            hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, REF, false>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
-                                               ctx->stream, lv, ntime, ncol, (const T *)era_T, (const T *)era_QV, (const TL *)ta_pgw,
-                                               (const TL *)evap, (const T *)PS, (const T *)FIS, z, phi_era, dphi, delta_ps, adj_ps,
-                                               dps_hist + n2, p_ref, adj_factor, 0, np - 1, ctx->d_status, mst + 1, loc, nullptr, nullptr);
+                        launch(no, yes, a.p_ref, 1, 1, mst, dps_hist, ls.era_flags, ctx->d_status + 1);
+                        if (np > 1) launch(no, no, a.p_ref, 0, np - 1, mst + 1, dps_hist + n2, nullptr, nullptr);
                     } else if (!local)
-                        hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, REF, false>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
-                                           ctx->stream, lv, ntime, ncol, (const T *)era_T, (const T *)era_QV, (const TL *)ta_pgw,
-                                           (const TL *)evap, (const T *)PS, (const T *)FIS, z, phi_era, dphi, delta_ps, adj_ps, dps_hist,
-                                           p_ref, adj_factor, first ? 1 : 0, np, ctx->d_status, mst, loc, nullptr, nullptr);
+                        launch(no, no, a.p_ref, first ? 1 : 0, np, mst, dps_hist, nullptr, nullptr);
                     else if constexpr (V == 1)                                 // MULTI_MAXV = 1: always this branch
-                        hipLaunchKernelGGL((k_ps_loop_multi<T, TL, 1, STEP_U, REF, true>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0,
-                                           ctx->stream, lv, ntime, ncol, (const T *)era_T, (const T *)era_QV, (const TL *)ta_pgw,
-                                           (const TL *)evap, (const T *)PS, (const T *)FIS, z, phi_era, dphi, delta_ps, adj_ps, dps_hist,
-                                           0.0, adj_factor, first ? 1 : 0, np, ctx->d_status, mst, loc, nullptr, nullptr);
+                        launch(yes, no, 0.0, first ? 1 : 0, np, mst, dps_hist, nullptr, nullptr);
                 });
             }
             HIPCHK(ctx, hipGetLastError());
@@ -1405,17 +1428,17 @@ static int run_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const
                 }
                 const double err_k = red[2 + 3 * k] != 0.0 ? red[3 + 3 * k] : NAN;   // NaN: xarray .max() of an all-NaN field
                 touched += h.levels_touched;
-                if (max_err_hist && it - 1 < hist_len) max_err_hist[it - 1] = err_k;
+                if (a.max_err_hist && it - 1 < a.hist_len) a.max_err_hist[it - 1] = err_k;
                 it += 1;                                                   // :313
-                if (it > max_n_iter) {                                     // :315-319
+                if (it > a.max_n_iter) {                                   // :315-319
                     ctx->band_agreed = true;                               // decided from reduced figures: all bands stop here
-                    if (n_iter) *n_iter = it - 1;
+                    if (a.n_iter) *a.n_iter = it - 1;
                     ctx->last_passes_launched = launched;
                     ctx->err = status_text(PGW_ERR_NOT_CONVERGED);
                     ctx->err_col = -1;
                     return PGW_ERR_NOT_CONVERGED;
                 }
-                if (!(err_k > thresh)) conv = dps_hist + (size_t)k * n2;   // :189  (NaN stops the loop too)
+                if (!(err_k > a.thresh)) conv = dps_hist + (size_t)k * n2; // :189  (NaN stops the loop too)
             }
             first = false;
         }
@@ -1423,15 +1446,9 @@ static int run_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const
         ctx->opt[PGW_OPT_LOOP_GUESS] = (it - 1) < 1 ? 1 : ((it - 1) > MULTI_MAX_PASS ? MULTI_MAX_PASS : (it - 1));
         ctx->last_levels_touched = touched;
         ctx->last_passes_launched = launched;
-        if (n_iter) *n_iter = it - 1;
-        if (ps_pgw || hus_pgw) {
-            int vec = pick_vec(ctx, dtype, ncol, {PS, evap, ps_pgw, hus_pgw, conv});
-            Levels lv = levels_of(ctx);
-            Prof pr(ctx, PGW_K_FINALIZE);
-            DISPATCH_TLV(dtype, ref, vec, hipLaunchKernelGGL((k_finalize_ps_hus<T, TL, V, REF>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
-                                                             ctx->stream, lv, ntime, ncol, (const T *)PS, conv, (const TL *)evap,
-                                                             (T *)ps_pgw, (TL *)hus_pgw, qv_done_levels));
-        }
+        if (a.n_iter) *a.n_iter = it - 1;
+        if (a.ps_pgw || a.hus_pgw)
+            launch_finalize(ctx, dtype, a.ref, ntime, ncol, a.PS, conv, a.evap, a.ps_pgw, a.hus_pgw, a.qv_done_levels);
         HIPCHK(ctx, hipGetLastError());
         return PGW_OK;
     }
@@ -1443,49 +1460,36 @@ static int run_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const
     // successor, so no reset copy is enqueued per pass (the read-back of the block being cleared was enqueued
     // before this pass was launched).
     DevStatus *blk[2] = {ctx->d_status, ctx->d_status + 1};
-    while (phi_ref_max_error > thresh) {                                   // :189
+    while (phi_ref_max_error > a.thresh) {                                 // :189
         const bool reset_here = local || it == 1;
-        if (reset_here && !(status_armed && it == 1) && (rc = status_reset(ctx))) return rc;
+        if (reset_here && !(a.status_armed && it == 1) && (rc = status_reset(ctx))) return rc;
         DevStatus *cur = local ? ctx->d_status : blk[(it - 1) & 1];
         if (local) {
-            // delta_ps += adj_ps ; per-column p_ref (never lower than last pass) ; g*zg at that level
-            DISPATCH_TLV(dtype, ref, 1, {
-                DeltaSrc<T> z{(const T *)dzg_b, (x_hi == 0.0) ? nullptr : (const T *)dzg_a, x_hi, x_new};
-                hipLaunchKernelGGL((k_local_p_ref<T, REF>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, ptf, ctx->h_akN,
-                                   ctx->h_bkN, n2, (const T *)PS, delta_ps, adj_ps, z, ncol, it == 1 ? 1 : 0, pref_f,
-                                   pref_idx, dphi, ctx->d_status);
-                (void)V;
-            });
-            launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, T, QV, PS, FIS, 0.0, phi_era, full_column, pref_f, ref);   // :280-287
-            launch_step(ctx, dtype, ntime, ncol, ta_pgw, evap, PS, FIS, phi_era, dphi, delta_ps, adj_ps, 0.0, pref_f,
-                        adj_factor, full_column, 0, nullptr, nullptr, ref);
+            launch_local_p_ref(ctx, dtype, a.ref, ptf, n2, ncol, a.PS, a.dzg_b, a.dzg_a, a.x_hi, a.x_new, it == 1 ? 1 : 0, ls);
+            launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, a.T, a.QV, a.PS, a.FIS, 0.0, ls.phi_era, full_column, ls.pref_f, a.ref);   // :280-287
+            launch_step(ctx, dtype, ntime, ncol, a.ta_pgw, a.evap, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, 0.0,
+                        ls.pref_f, a.adj_factor, full_column, 0, nullptr, nullptr, a.ref);
         } else {
-            launch_step(ctx, dtype, ntime, ncol, ta_pgw, evap, PS, FIS, phi_era, dphi, delta_ps, adj_ps, p_ref, nullptr,
-                        adj_factor, full_column, 1, cur, blk[it & 1], ref);
+            launch_step(ctx, dtype, ntime, ncol, a.ta_pgw, a.evap, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, a.p_ref,
+                        nullptr, a.adj_factor, full_column, 1, cur, blk[it & 1], a.ref);
         }
         HIPCHK(ctx, hipGetLastError());
         if ((rc = status_check(ctx, cur))) return rc;
         phi_ref_max_error = max_err_of(ctx);                               // :308
         touched += ctx->h_status->levels_touched;
-        if (max_err_hist && it - 1 < hist_len) max_err_hist[it - 1] = phi_ref_max_error;
+        if (a.max_err_hist && it - 1 < a.hist_len) a.max_err_hist[it - 1] = phi_ref_max_error;
         it += 1;                                                           // :313
-        if (it > max_n_iter) {                                             // :315-319
-            if (n_iter) *n_iter = it - 1;
+        if (it > a.max_n_iter) {                                           // :315-319
+            if (a.n_iter) *a.n_iter = it - 1;
             ctx->err = status_text(PGW_ERR_NOT_CONVERGED);
             ctx->err_col = -1;
             return PGW_ERR_NOT_CONVERGED;
         }
     }
     ctx->last_levels_touched = touched;
-    if (n_iter) *n_iter = it - 1;
-    if (ps_pgw || hus_pgw) {
-        int vec = pick_vec(ctx, dtype, ncol, {PS, evap, ps_pgw, hus_pgw, delta_ps});
-        Levels lv = levels_of(ctx);
-        Prof pr(ctx, PGW_K_FINALIZE);
-        DISPATCH_TLV(dtype, ref, vec, hipLaunchKernelGGL((k_finalize_ps_hus<T, TL, V, REF>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
-                                                         ctx->stream, lv, ntime, ncol, (const T *)PS, delta_ps, (const TL *)evap,
-                                                         (T *)ps_pgw, (TL *)hus_pgw, qv_done_levels));
-    }
+    if (a.n_iter) *a.n_iter = it - 1;
+    if (a.ps_pgw || a.hus_pgw)
+        launch_finalize(ctx, dtype, a.ref, ntime, ncol, a.PS, ls.delta_ps, a.evap, a.ps_pgw, a.hus_pgw, a.qv_done_levels);
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
 }
@@ -1498,14 +1502,20 @@ extern "C" int pgw_adjust_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long 
     CHECK_COMMON(ctx, dtype, ntime, ncol);
     NEED(ctx, ctx->nlev > 0, "pgw_set_levels has not been called");
     NEED(ctx, PS && FIS && T && QV && ta_pgw && hur_pgw && dzg_pref, "null pointer");
-    const size_t es = dtype == PGW_F64 ? 8 : 4;
     void *evap = nullptr;
     int rc;
-    if ((rc = ws_get(ctx, 0, (size_t)ntime * ctx->nlev * ncol * es, &evap))) return rc;
+    if ((rc = ws_get(ctx, 0, (size_t)ntime * ctx->nlev * ncol * elem_size(dtype), &evap))) return rc;
     // e = hur_pgw/100 * e_sat(ta_pgw): iterate-independent part of :262-266
     if ((rc = humidity_hybrid<2>(ctx, PGW_K_RH_TO_Q, dtype, ntime, ncol, hur_pgw, PS, ta_pgw, evap))) return rc;
-    return run_ps_loop(ctx, dtype, ntime, ncol, PS, FIS, T, QV, ta_pgw, evap, dzg_pref, nullptr, 0.0, 0.0, p_ref,
-                       adj_factor, thresh, max_n_iter, ps_pgw, hus_pgw, n_iter, max_err_hist, max_n_iter);
+    PsLoopArgs la;
+    la.dtype = dtype; la.ntime = ntime; la.ncol = ncol;
+    la.PS = PS; la.FIS = FIS; la.T = T; la.QV = QV;
+    la.ta_pgw = ta_pgw; la.evap = evap;
+    la.dzg_b = dzg_pref;                                  // the delta at the instant: no bracket
+    la.p_ref = p_ref; la.adj_factor = adj_factor; la.thresh = thresh; la.max_n_iter = max_n_iter;
+    la.ps_pgw = ps_pgw; la.hus_pgw = hus_pgw;
+    la.n_iter = n_iter; la.max_err_hist = max_err_hist; la.hist_len = max_n_iter;
+    return run_ps_loop(ctx, la);
 }
 
 // ------------------------------------------------------------------ whole file, settings.i_reinterp = 1
@@ -1516,29 +1526,21 @@ extern "C" int pgw_adjust_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long 
 static int run_reinterp_file(pgw_ctx *ctx, pgw_file_args *a, int check_top) {
     const int dtype = a->dtype, ntime = a->ntime, N = a->nlev, S = a->nplev;
     const long long ncol = a->ncol, n2 = (long long)ntime * ncol;
-    const bool ref = a->ref_dtype != 0, local = a->local_p_ref != 0, lerp = (a->x_hi != 0.0);
-    const size_t es = (dtype == PGW_F64 || ref) ? 8 : 4;       // element size of the level arrays the loop produces
+    const bool ref = a->ref_dtype != 0, local = a->local_p_ref != 0;
     NEED(ctx, !ctx->reduce_fn, "latitude-band sharding needs the multi-pass loop (i_reinterp = 0)");
     int rc;
-    void *evap = nullptr, *relhum = nullptr, *hur = a->hur_pgw_out, *state = nullptr;
-    const size_t field = (size_t)ntime * N * ncol * es;
+    void *evap = nullptr, *relhum = nullptr, *hur = a->hur_pgw_out;
+    const size_t field = (size_t)ntime * N * ncol * elem_size(ref ? PGW_F64 : dtype);      // a level array the loop produces
     if ((rc = ws_get(ctx, 0, field, &evap))) return rc;
     if ((rc = ws_get(ctx, 2, field, &relhum))) return rc;
     if (!hur && (rc = ws_get(ctx, 7, field, &hur))) return rc;
-    if ((rc = ws_get(ctx, 1, (size_t)n2 * 6 * sizeof(double), &state))) return rc;
-    double *phi_era = (double *)state, *dphi = phi_era + n2, *delta_ps = dphi + n2, *adj_ps = delta_ps + n2;
-    double *pref_f = adj_ps + n2;
-    int *pref_idx = (int *)(pref_f + n2);
+    LoopState ls;
+    if ((rc = loop_state(ctx, n2, &ls))) return rc;
     Levels lv = levels_of(ctx);
     const int full_column = ctx->opt[PGW_OPT_FULL_COLUMN];
     const double zx_hi = a->per_var_time ? a->zg_x_hi : a->x_hi, zx_new = a->per_var_time ? a->zg_x_new : a->x_new;
-    PlevTable ptf;
-    memset(&ptf, 0, sizeof(ptf));
-    if (local) {
-        NEED(ctx, a->zg3_b != nullptr, "local_p_ref needs the full zg records (zg3_b / zg3_a)");
-        ptf.n = S;
-        for (int i = 0; i < S; ++i) ptf.p[i] = a->plev[i];
-    }
+    if (local) NEED(ctx, a->zg3_b != nullptr, "local_p_ref needs the full zg records (zg3_b / zg3_a)");
+    const PlevTable ptf = file_order_table(local ? S : 0, a->plev);
     if ((rc = status_reset(ctx))) return rc;
     // ---- ERA state: RELHUM (step_03:87-94)
     {
@@ -1548,22 +1550,20 @@ static int run_reinterp_file(pgw_ctx *ctx, pgw_file_args *a, int check_top) {
                                (const float *)a->QV, (const float *)a->PS, (const float *)a->T, (double *)relhum);
         } else {
             int vec = pick_vec(ctx, dtype, ncol, {a->QV, a->PS, a->T, relhum});
-            DISPATCH_TV(dtype, vec, hipLaunchKernelGGL((k_humidity_hybrid<T, V, 0>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
-                                                        ctx->stream, lv, ntime, ncol, (const T *)a->QV, (const T *)a->PS,
-                                                        (const T *)a->T, (T *)relhum));
+            with_type_vec(dtype, vec, [&](auto t_, auto v_) {
+                using T = decltype(t_);
+                constexpr int V = decltype(v_)::value;
+                hipLaunchKernelGGL((k_humidity_hybrid<T, V, 0>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0, ctx->stream, lv, ntime,
+                                   ncol, (const T *)a->QV, (const T *)a->PS, (const T *)a->T, (T *)relhum);
+            });
         }
     }
     if (!local) {
         // phi_ref of the ERA state (constant for a fixed p_ref; :280-287 recomputes it) and g * dzg (:292-295); zeroed state
-        launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, a->T, a->QV, a->PS, a->FIS, a->p_ref, phi_era, full_column, nullptr, ref);
-        DISPATCH_TLV(dtype, ref, 1, {
-            DeltaSrc<T> z{(const T *)a->zg_b, (zx_hi == 0.0) ? nullptr : (const T *)a->zg_a, zx_hi, zx_new};
-            hipLaunchKernelGGL((k_dphi_clim<T, REF>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, n2, z, CON_G, dphi,
-                               delta_ps, adj_ps);
-            (void)V;
-        });
+        launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, a->T, a->QV, a->PS, a->FIS, a->p_ref, ls.phi_era, full_column, nullptr, ref);
+        launch_dphi_clim(ctx, dtype, ref, n2, a->zg_b, a->zg_a, zx_hi, zx_new, ls);
     } else {
-        HIPCHK(ctx, hipMemsetAsync(delta_ps, 0, sizeof(double) * 2 * n2, ctx->stream));    // :182-184
+        HIPCHK(ctx, hipMemsetAsync(ls.delta_ps, 0, sizeof(double) * 2 * n2, ctx->stream));    // :182-184
     }
     HIPCHK(ctx, hipGetLastError());
     if ((rc = status_check(ctx))) return rc;
@@ -1571,53 +1571,24 @@ static int run_reinterp_file(pgw_ctx *ctx, pgw_file_args *a, int check_top) {
     // one pair of variables (ERA fields + deltas) onto the levels of ps_pgw; thermo: ta + hur with e, else ua + va
     auto reinterp = [&](bool thermo) {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        const void *b0 = thermo ? a->ta_b : a->ua_b, *a0 = thermo ? a->ta_a : a->ua_a;
-        const void *b1 = thermo ? a->hur_b : a->va_b, *a1 = thermo ? a->hur_a : a->va_a;
-#define PGW_FILL_PAIR(rv)                                                                                                  \
-        rv.d[0] = DeltaSrc<T>{(const T *)b0, lerp ? (const T *)a0 : nullptr, a->x_hi, a->x_new};                           \
-        rv.d[1] = DeltaSrc<T>{(const T *)b1, lerp ? (const T *)a1 : nullptr, a->x_hi, a->x_new};                           \
-        rv.sfc[0] = DeltaSrc<T>{thermo ? (const T *)a->tas_b : nullptr, (thermo && lerp) ? (const T *)a->tas_a : nullptr, a->x_hi, a->x_new};   \
-        rv.sfc[1] = DeltaSrc<T>{thermo ? (const T *)a->hurs_b : nullptr, (thermo && lerp) ? (const T *)a->hurs_a : nullptr, a->x_hi, a->x_new}; \
-        DeltaSrc<T> p{(const T *)a->pshist_b, lerp ? (const T *)a->pshist_a : nullptr, a->x_hi, a->x_new};
-        if (ref) {
-            typedef float T;
-            if (thermo) {
-                ReinterpPair<float, float, double, double> rv;
-                PGW_FILL_PAIR(rv)
-                rv.era0 = (const float *)a->T; rv.era1 = (const double *)relhum;
-                rv.out[0] = (double *)a->T_out; rv.out[1] = (double *)hur; rv.evap = (double *)evap;
-                launch_reinterp_pair<float, float, double, double, true>(ctx, lv, ntime, S, ncol, rv, p, (const float *)a->PS,
-                                                                         (const float *)a->PS_out, true, check_top);
-            } else {
-                ReinterpPair<float, float, float, double> rv;
-                PGW_FILL_PAIR(rv)
-                rv.era0 = (const float *)a->U; rv.era1 = (const float *)a->V;
-                rv.out[0] = (double *)a->U_out; rv.out[1] = (double *)a->V_out; rv.evap = nullptr;
-                launch_reinterp_pair<float, float, float, double, true>(ctx, lv, ntime, S, ncol, rv, p, (const float *)a->PS,
-                                                                        (const float *)a->PS_out, false, check_top);
-            }
-        } else {
-            DISPATCH_T(dtype, {
-                ReinterpPair<T> rv;
-                PGW_FILL_PAIR(rv)
-                rv.era0 = (const T *)(thermo ? a->T : a->U); rv.era1 = (const T *)(thermo ? relhum : a->V);
-                rv.out[0] = (T *)(thermo ? a->T_out : a->U_out); rv.out[1] = (T *)(thermo ? hur : a->V_out);
-                rv.evap = thermo ? (T *)evap : nullptr;
-                launch_reinterp_pair<T>(ctx, lv, ntime, S, ncol, rv, p, (const T *)a->PS, (const T *)a->PS_out, thermo, check_top);
-            });
-        }
-#undef PGW_FILL_PAIR
-    };
-    auto top_check = [&]() -> int {                       // functions.py:417-425
-        if (!check_top) return PGW_OK;
-        DevStatus *h = ctx->h_status;
-        if (!h->nan_seen && h->min_targ_bits != ~0ull && h->min_src_bits != ~0ull) {
-            double mt, ms;
-            memcpy(&mt, &h->min_targ_bits, 8);
-            memcpy(&ms, &h->min_src_bits, 8);
-            if (mt < ms) { ctx->err = status_text(PGW_ERR_TOP_PRESSURE); ctx->err_col = -1; return PGW_ERR_TOP_PRESSURE; }
-        }
-        return PGW_OK;
+        // storage T of the files; TE1, TO: the second ERA field and the outputs (reference-dtype mode: float64 beside float32)
+        auto launch = [&](auto t_, auto e1_, auto o_, auto ref_) {
+            using T = decltype(t_); using TE1 = decltype(e1_); using TO = decltype(o_);
+            ReinterpPair<T, T, TE1, TO> rv;
+            rv.d[0] = delta_src<T>(thermo ? a->ta_b : a->ua_b, thermo ? a->ta_a : a->ua_a, a->x_hi, a->x_new);
+            rv.d[1] = delta_src<T>(thermo ? a->hur_b : a->va_b, thermo ? a->hur_a : a->va_a, a->x_hi, a->x_new);
+            rv.sfc[0] = delta_src<T>(thermo ? a->tas_b : nullptr, thermo ? a->tas_a : nullptr, a->x_hi, a->x_new);
+            rv.sfc[1] = delta_src<T>(thermo ? a->hurs_b : nullptr, thermo ? a->hurs_a : nullptr, a->x_hi, a->x_new);
+            rv.era0 = (const T *)(thermo ? a->T : a->U); rv.era1 = (const TE1 *)(thermo ? relhum : a->V);
+            rv.out[0] = (TO *)(thermo ? a->T_out : a->U_out); rv.out[1] = (TO *)(thermo ? hur : a->V_out);
+            rv.evap = thermo ? (TO *)evap : nullptr;
+            launch_reinterp_pair<T, T, TE1, TO, decltype(ref_)::value>(ctx, lv, ntime, S, ncol, rv,
+                                                                       delta_src<T>(a->pshist_b, a->pshist_a, a->x_hi, a->x_new),
+                                                                       (const T *)a->PS, (const T *)a->PS_out, thermo, check_top);
+        };
+        if (!ref) with_type(dtype, [&](auto t_) { launch(t_, t_, t_, std::false_type()); });
+        else if (thermo) launch(float(), double(), double(), std::true_type());      // RELHUM of the ERA state is float64
+        else launch(float(), float(), double(), std::true_type());
     };
 
     double err = INFINITY;                                                  // :186
@@ -1626,32 +1597,22 @@ static int run_reinterp_file(pgw_ctx *ctx, pgw_file_args *a, int check_top) {
     for (int i = 0; i < 32; ++i) a->max_err_hist[i] = NAN;
     while (err > a->thresh) {                                               // :189
         if ((rc = status_reset(ctx))) return rc;
-        if (local) {
-            // delta_ps += adj_ps; the column's reference level (never lower than the last pass's); g * zg there   :192, 219-253, 292-295
-            DISPATCH_TLV(dtype, ref, 1, {
-                DeltaSrc<T> z{(const T *)a->zg3_b, (zx_hi == 0.0) ? nullptr : (const T *)a->zg3_a, zx_hi, zx_new};
-                hipLaunchKernelGGL((k_local_p_ref<T, REF>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, ptf, ctx->h_akN,
-                                   ctx->h_bkN, n2, (const T *)a->PS, delta_ps, adj_ps, z, ncol, it == 1 ? 1 : 0, pref_f,
-                                   pref_idx, dphi, ctx->d_status);
-                hipLaunchKernelGGL((k_update_ps<T, REF>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, n2,
-                                   (const T *)a->PS, delta_ps, adj_ps, (T *)a->PS_out, 0);                 // :193
-                (void)V;
-            });
-            launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, a->T, a->QV, a->PS, a->FIS, 0.0, phi_era, full_column, pref_f, ref);   // :280-287
-        } else {
-            DISPATCH_TLV(dtype, ref, 1, {                                                                  // :192-193
-                hipLaunchKernelGGL((k_update_ps<T, REF>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, n2,
-                                   (const T *)a->PS, delta_ps, adj_ps, (T *)a->PS_out, 1);
-                (void)V;
-            });
-        }
+        if (local) launch_local_p_ref(ctx, dtype, ref, ptf, n2, ncol, a->PS, a->zg3_b, a->zg3_a, zx_hi, zx_new, it == 1 ? 1 : 0, ls);
+        // ps_pgw of this pass; fixed p_ref: after delta_ps += adj_ps   :192-193
+        with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_update_ps<T, decltype(ref_)::value>), dim3(nblocks(n2, BLOCK)), dim3(BLOCK), 0, ctx->stream, n2,
+                               (const T *)a->PS, ls.delta_ps, ls.adj_ps, (T *)a->PS_out, local ? 0 : 1);
+        });
+        if (local)
+            launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, a->T, a->QV, a->PS, a->FIS, 0.0, ls.phi_era, full_column, ls.pref_f, ref);   // :280-287
         reinterp(true);                                                     // :202-216 + e of functions.py:123
         // :262-308 on the re-interpolated fields (delta_ps already carries this pass's increment)
-        launch_step(ctx, dtype, ntime, ncol, a->T_out, evap, a->PS, a->FIS, phi_era, dphi, delta_ps, adj_ps, a->p_ref,
-                    local ? pref_f : nullptr, a->adj_factor, full_column, 0, nullptr, nullptr, ref);
+        launch_step(ctx, dtype, ntime, ncol, a->T_out, evap, a->PS, a->FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, a->p_ref,
+                    local ? ls.pref_f : nullptr, a->adj_factor, full_column, 0, nullptr, nullptr, ref);
         HIPCHK(ctx, hipGetLastError());
         if ((rc = status_check(ctx))) return rc;
-        if ((rc = top_check())) return rc;
+        if ((rc = top_pressure_check(ctx, !check_top))) return rc;
         err = max_err_of(ctx);                                              // :308
         if (it - 1 < 32) a->max_err_hist[it - 1] = err;
         it += 1;                                                            // :313
@@ -1667,16 +1628,11 @@ static int run_reinterp_file(pgw_ctx *ctx, pgw_file_args *a, int check_top) {
     a->levels_touched = 0;
     if ((rc = status_reset(ctx))) return rc;
     reinterp(false);                                                        // ua, va on the final levels   :330-343
-    {   // hus of the last pass (:262-266, 370) from its e; PS_out already holds ps_pgw of the last pass
-        int vec = pick_vec(ctx, dtype, ncol, {a->PS, evap, a->PS_out, a->QV_out, delta_ps});
-        Prof pr(ctx, PGW_K_FINALIZE);
-        DISPATCH_TLV(dtype, ref, vec, hipLaunchKernelGGL((k_finalize_ps_hus<T, TL, V, REF>), dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0,
-                                                         ctx->stream, lv, ntime, ncol, (const T *)a->PS, delta_ps, (const TL *)evap,
-                                                         (T *)a->PS_out, (TL *)a->QV_out, 0));
-    }
+    // hus of the last pass (:262-266, 370) from its e; PS_out already holds ps_pgw of the last pass
+    launch_finalize(ctx, dtype, ref, ntime, ncol, a->PS, ls.delta_ps, evap, a->PS_out, a->QV_out, 0);
     HIPCHK(ctx, hipGetLastError());
     if ((rc = status_check(ctx))) return rc;
-    return top_check();
+    return top_pressure_check(ctx, !check_top);
 }
 
 // ------------------------------------------------------------------ whole file
@@ -1705,11 +1661,9 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     NEED(ctx, a->max_n_iter >= 1 && a->max_n_iter <= 1000, "bad max_n_iter");
     NEED(ctx, !ctx->reduce_fn || (ctx->opt[PGW_OPT_MULTIPASS] && !ctx->opt[PGW_OPT_FULL_COLUMN]),
          "a reduce hook (latitude-band sharding) needs the multi-pass loop: PGW_OPT_MULTIPASS = 1, PGW_OPT_FULL_COLUMN = 0");
-    const bool exact = (a->x_hi == 0.0);
     const bool ref = a->ref_dtype != 0;
     NEED(ctx, !ref || dtype == PGW_F32, "ref_dtype = 1 is the float32-file mode: dtype must be PGW_F32");
     NEED(ctx, !ref || ctx->opt[PGW_OPT_QUAD], "ref_dtype = 1 needs the quad kernel (PGW_OPT_QUAD = 1)");
-    const size_t es = (dtype == PGW_F64 || ref) ? 8 : 4;      // element size of the PGW level arrays (evap, 4-D outputs)
     const int N = a->nlev;
     int rc;
     int qv_done = 0;          // leading levels whose final QV the quad kernel has already written
@@ -1718,21 +1672,12 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     const bool fused_first = dtype == PGW_F64 && ctx->opt[PGW_OPT_FUSED_FIRST] && ctx->opt[PGW_OPT_QUAD] && ctx->opt[PGW_OPT_MULTIPASS] &&
                            !ctx->opt[PGW_OPT_FULL_COLUMN] && !a->local_p_ref && !a->i_reinterp;
     if ((rc = plev_table(ctx, a->nplev, a->plev))) return rc;
-    void *evap = nullptr;
-    if ((rc = ws_get(ctx, 0, (size_t)ntime * N * ncol * es, &evap))) return rc;
+    void *evap = nullptr;      // PGW level arrays (evap, 4-D outputs): float64 in reference-dtype mode
+    if ((rc = ws_get(ctx, 0, (size_t)ntime * N * ncol * elem_size(ref ? PGW_F64 : dtype), &evap))) return rc;
     Levels lv = levels_of(ctx);
     const int check_top = a->ignore_top ? 0 : 1;
-    auto top_check = [&]() -> int {                       // functions.py:417-425
-        if (!check_top) return PGW_OK;
-        DevStatus *h = ctx->h_status;
-        if (!h->nan_seen && h->min_targ_bits != ~0ull && h->min_src_bits != ~0ull) {
-            double mt, ms;
-            memcpy(&mt, &h->min_targ_bits, 8);
-            memcpy(&ms, &h->min_src_bits, 8);
-            if (mt < ms) { ctx->err = status_text(PGW_ERR_TOP_PRESSURE); ctx->err_col = -1; return PGW_ERR_TOP_PRESSURE; }
-        }
-        return PGW_OK;
-    };
+    // each delta file has its own time axis in the reference (load_delta per variable): own bracket, own abscissae
+    const double zx_hi = a->per_var_time ? a->zg_x_hi : a->x_hi, zx_new = a->per_var_time ? a->zg_x_new : a->x_new;
 
     // ---- surface riders (step_03:103-146)
     if (a->FR_SEA_ICE && a->siconc_b && a->FR_SEA_ICE_out) {
@@ -1745,19 +1690,16 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
         for (int s = 0; s < a->nsoil; ++s) st.w[s] = exp(-a->soil_depth[s] / 2.8);      // step_03:140
         long long n = (long long)ntime * ncol;
         Prof pr(ctx, PGW_K_SURFACE);
-        DISPATCH_TLV(dtype, ref, 1, {
-            // each delta file has its own time axis in the reference (load_delta per variable): own bracket, own abscissae
-            const double sx = a->per_var_time ? a->siconc_x_hi : a->x_hi, sn = a->per_var_time ? a->siconc_x_new : a->x_new;
-            const double tx = a->per_var_time ? a->ts_x_hi : a->x_hi, tn = a->per_var_time ? a->ts_x_new : a->x_new;
-            const double ox = a->per_var_time ? a->tos_x_hi : a->x_hi, on = a->per_var_time ? a->tos_x_new : a->x_new;
-            DeltaSrc<T> dsic{(const T *)a->siconc_b, sx == 0.0 ? nullptr : (const T *)a->siconc_a, sx, sn};
-            DeltaSrc<T> dts{(const T *)a->ts_b, tx == 0.0 ? nullptr : (const T *)a->ts_a, tx, tn};
-            DeltaSrc<T> dtos{(const T *)a->tos_b, ox == 0.0 ? nullptr : (const T *)a->tos_a, ox, on};
-            hipLaunchKernelGGL((k_surface_update_lerp<T, REF>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, ntime, ncol, st,
-                               (const T *)a->FR_SEA_ICE, dsic, dtos, dts, (const T *)a->FR_LAND, (const T *)a->ts_clim,
+        with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
+            using T = decltype(t_);
+            const bool own = a->per_var_time != 0;
+            const DeltaSrc<T> dsic = delta_src<T>(a->siconc_b, a->siconc_a, own ? a->siconc_x_hi : a->x_hi, own ? a->siconc_x_new : a->x_new);
+            const DeltaSrc<T> dts = delta_src<T>(a->ts_b, a->ts_a, own ? a->ts_x_hi : a->x_hi, own ? a->ts_x_new : a->x_new);
+            const DeltaSrc<T> dtos = delta_src<T>(a->tos_b, a->tos_a, own ? a->tos_x_hi : a->x_hi, own ? a->tos_x_new : a->x_new);
+            hipLaunchKernelGGL((k_surface_update_lerp<T, decltype(ref_)::value>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream,
+                               ntime, ncol, st, (const T *)a->FR_SEA_ICE, dsic, dtos, dts, (const T *)a->FR_LAND, (const T *)a->ts_clim,
                                (const T *)a->T_SKIN, (const T *)a->T_SO, (T *)a->FR_SEA_ICE_out, (T *)a->T_SKIN_out,
                                (T *)a->T_SO_out);
-            (void)V;
         });
     }
 
@@ -1786,55 +1728,47 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
                 if ((rc = loop_state(ctx, (long long)ntime * ncol, &ls))) return rc;
                 if ((rc = ws_get(ctx, 6, (size_t)ntime * ncol * MULTI_MAX_PASS * sizeof(double), &dps_hist))) return rc;
                 // blocks 1 (errors of the kernel's ERA-state scan) and 2 (pass 1) of the device status
-                DevStatus *blank = ctx->h_status + 2 + MULTI_MAX_PASS;     // (run_ps_loop's zero blocks: same content)
-                for (int k = 0; k < 2; ++k) {
-                    memset(&blank[k], 0, sizeof(DevStatus));
-                    blank[k].col = ~0ull; blank[k].min_targ_bits = ~0ull; blank[k].min_src_bits = ~0ull;
-                }
-                HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + 1, blank, 2 * sizeof(DevStatus), hipMemcpyHostToDevice, ctx->stream));
+                HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + 1, blank_blocks(ctx, 2), 2 * sizeof(DevStatus), hipMemcpyHostToDevice, ctx->stream));
             }
             {
                 Prof pr(ctx, PGW_K_QUAD_DELTA);
-#define LAUNCH_QUAD(OT, LERP_)   do { if (fuse) LAUNCH_QUAD_(OT, LERP_, (sizeof(T) == 8)); else LAUNCH_QUAD_(OT, LERP_, false); } while (0)
-#define LAUNCH_QUAD_(OT, LERP_, FUSE_)                                                                                \
-                    hipLaunchKernelGGL((k_delta_quad<T, TL, QUAD_U, QUAD_TPB, OT, LERP_, REF, FUSE_>), dim3(nblocks((long long)ntime * ncol, QUAD_TPB)), \
-                                       dim3(QUAD_TPB), qlds, ctx->stream, ctx->plev_tab, lv, ntime, ncol, (const T *)a->T,     \
-                                       (const T *)a->QV, (const T *)a->U, (const T *)a->V, (const T *)a->PS, dth, ds, ph, \
-                                       dwd, check_top, (TL *)a->T_out, (TL *)evap, (TL *)a->hur_pgw_out, (TL *)a->U_out,      \
-                                       (TL *)a->V_out, (TL *)a->QV_out, qv_done, ctx->n_pure, ctx->d_status, a->p_ref, d_ff)
-                DISPATCH_TLV(dtype, ref, 1, {
-                    const double zx = a->per_var_time ? a->zg_x_hi : a->x_hi, zn = a->per_var_time ? a->zg_x_new : a->x_new;
-                    const bool fuse = fused_first;
-                    const FusedFirst<T> ff{a->adj_factor, (const T *)a->FIS,
-                                           {(const T *)a->zg_b, zx == 0.0 ? nullptr : (const T *)a->zg_a, zx, zn},
+                hipError_t copied = hipSuccess;
+                with_flow(dtype, ref, [&](auto t_, auto l_, auto ref_) {
+                    using T = decltype(t_); using TL = decltype(l_);
+                    const FusedFirst<T> ff{a->adj_factor, (const T *)a->FIS, delta_src<T>(a->zg_b, a->zg_a, zx_hi, zx_new),
                                            ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, (double *)dps_hist, ls.era_flags,
                                            ctx->d_status + 1, ctx->d_status + 2};
                     // the kernel reads the block from device memory (the host copy is free again after this file's read-back)
                     static_assert(sizeof(FusedFirst<T>) <= FUSED_BLOCKS * sizeof(DevStatus), "FusedFirst block");
                     FusedFirst<T> *h_ff = (FusedFirst<T> *)(ctx->h_status + 2 + 2 * MULTI_MAX_PASS);
                     const FusedFirst<T> *d_ff = (const FusedFirst<T> *)(ctx->d_status + 2 + MULTI_MAX_PASS);
-                    if (fuse) {
+                    if (fused_first) {
                         *h_ff = ff;
-                        if (hipMemcpyAsync((void *)d_ff, h_ff, sizeof(ff), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-                            return fail(ctx, PGW_ERR_HIP, "hipMemcpyAsync (FusedFirst block)");
+                        copied = hipMemcpyAsync((void *)d_ff, h_ff, sizeof(ff), hipMemcpyHostToDevice, ctx->stream);
+                        if (copied != hipSuccess) return;
                     }
-                    PairSrc<T> dth{{(const T *)a->ta_b, exact ? nullptr : (const T *)a->ta_a, a->x_hi, a->x_new},
-                                   {(const T *)a->hur_b, exact ? nullptr : (const T *)a->hur_a, a->x_hi, a->x_new}};
-                    PairSrc<T> ds{{(const T *)a->tas_b, exact ? nullptr : (const T *)a->tas_a, a->x_hi, a->x_new},
-                                  {(const T *)a->hurs_b, exact ? nullptr : (const T *)a->hurs_a, a->x_hi, a->x_new}};
-                    DeltaSrc<T> ph{(const T *)a->pshist_b, exact ? nullptr : (const T *)a->pshist_a, a->x_hi, a->x_new};
-                    PairSrc<T> dwd{{(const T *)a->ua_b, exact ? nullptr : (const T *)a->ua_a, a->x_hi, a->x_new},
-                                   {(const T *)a->va_b, exact ? nullptr : (const T *)a->va_a, a->x_hi, a->x_new}};
-                    // arrays below 4 GiB (a 0.25 deg L137 field is 1.1 GB): 32-bit byte offsets from uniform bases
+                    const PairSrc<T> dth = pair_src<T>(a->ta_b, a->ta_a, a->hur_b, a->hur_a, a->x_hi, a->x_new);
+                    const PairSrc<T> ds = pair_src<T>(a->tas_b, a->tas_a, a->hurs_b, a->hurs_a, a->x_hi, a->x_new);
+                    const DeltaSrc<T> ph = delta_src<T>(a->pshist_b, a->pshist_a, a->x_hi, a->x_new);
+                    const PairSrc<T> dwd = pair_src<T>(a->ua_b, a->ua_a, a->va_b, a->va_a, a->x_hi, a->x_new);
+                    // O: arrays below 4 GiB (a 0.25 deg L137 field is 1.1 GB): 32-bit byte offsets from uniform bases
+                    // LERP: the instant lies between two records (false: it is a record); FUSE: fused_first
+                    auto launch = [&](auto o_, auto lerp_, auto fuse_) {
+                        hipLaunchKernelGGL((k_delta_quad<T, TL, QUAD_U, QUAD_TPB, decltype(o_), decltype(lerp_)::value != 0, decltype(ref_)::value, decltype(fuse_)::value>),
+                                           dim3(nblocks((long long)ntime * ncol, QUAD_TPB)), dim3(QUAD_TPB), qlds, ctx->stream, ctx->plev_tab,
+                                           lv, ntime, ncol, (const T *)a->T, (const T *)a->QV, (const T *)a->U, (const T *)a->V,
+                                           (const T *)a->PS, dth, ds, ph, dwd, check_top, (TL *)a->T_out, (TL *)evap,
+                                           (TL *)a->hur_pgw_out, (TL *)a->U_out, (TL *)a->V_out, (TL *)a->QV_out, qv_done, ctx->n_pure,
+                                           ctx->d_status, a->p_ref, d_ff);
+                    };
                     const bool o32 = !ctx->opt[PGW_OPT_FORCE_OFF64] &&
                                      (unsigned long long)ntime * (N > S ? N : S) * ncol * sizeof(TL) < (1ull << 32);
-                    // LERP: the instant lies between two records (false: it is a record, `exact`)
-                    if (o32) { if (exact) LAUNCH_QUAD(boff32, false); else LAUNCH_QUAD(boff32, true); }
-                    else { if (exact) LAUNCH_QUAD(boff64, false); else LAUNCH_QUAD(boff64, true); }
-                    (void)V;
+                    with_offsets(o32, [&](auto o_) { with_int<2>(a->x_hi != 0.0, [&](auto lerp_) {
+                        if constexpr (sizeof(T) == 8) { if (fused_first) return launch(o_, lerp_, std::true_type()); }
+                        launch(o_, lerp_, std::false_type());
+                    }); });
                 });
-#undef LAUNCH_QUAD
-#undef LAUNCH_QUAD_
+                if (copied != hipSuccess) return fail(ctx, PGW_ERR_HIP, "hipMemcpyAsync (FusedFirst block)");
             }
             HIPCHK(ctx, hipGetLastError());
         } else {
@@ -1842,37 +1776,34 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
             // cross-check of the same arithmetic: tests/test_hip_parity.py::test_kernel_variants_are_bit_identical)
             const size_t lds = (size_t)2 * N * sizeof(double);            // akm | bkm
             const unsigned int grid = nblocks((long long)ntime * ncol, 128);
-#define LAUNCH_PAIR(THERMO, FA, FB, D3, DS, PH, OA, OB, OH)                                                                   \
-        hipLaunchKernelGGL((k_delta_pair<T, 1, THERMO, (THERMO ? 2 : PAIR_U), 128>), dim3(grid), dim3(128), lds, ctx->stream,  \
-                           ctx->plev_tab, lv, ntime, ncol, FA, FB, (const T *)a->PS, D3, DS, PH, check_top, OA, OB, OH, \
-                           ctx->d_status)
             {
                 Prof pr(ctx, PGW_K_THERMO_DELTA);
-                DISPATCH_T(dtype, {
-                    PairSrc<T> d3{{(const T *)a->ta_b, exact ? nullptr : (const T *)a->ta_a, a->x_hi, a->x_new},
-                                  {(const T *)a->hur_b, exact ? nullptr : (const T *)a->hur_a, a->x_hi, a->x_new}};
-                    PairSrc<T> ds{{(const T *)a->tas_b, exact ? nullptr : (const T *)a->tas_a, a->x_hi, a->x_new},
-                                  {(const T *)a->hurs_b, exact ? nullptr : (const T *)a->hurs_a, a->x_hi, a->x_new}};
-                    DeltaSrc<T> ph{(const T *)a->pshist_b, exact ? nullptr : (const T *)a->pshist_a, a->x_hi, a->x_new};
-                    LAUNCH_PAIR(true, (const T *)a->T, (const T *)a->QV, d3, ds, ph, (T *)a->T_out, (T *)evap, (T *)a->hur_pgw_out);
+                with_type(dtype, [&](auto t_) {
+                    using T = decltype(t_);
+                    hipLaunchKernelGGL((k_delta_pair<T, 1, true, 2, 128>), dim3(grid), dim3(128), lds, ctx->stream, ctx->plev_tab, lv, ntime,
+                                       ncol, (const T *)a->T, (const T *)a->QV, (const T *)a->PS,
+                                       pair_src<T>(a->ta_b, a->ta_a, a->hur_b, a->hur_a, a->x_hi, a->x_new),
+                                       pair_src<T>(a->tas_b, a->tas_a, a->hurs_b, a->hurs_a, a->x_hi, a->x_new),
+                                       delta_src<T>(a->pshist_b, a->pshist_a, a->x_hi, a->x_new), check_top, (T *)a->T_out, (T *)evap,
+                                       (T *)a->hur_pgw_out, ctx->d_status);
                 });
             }
             {
                 Prof pr(ctx, PGW_K_WIND_DELTA);
-                DISPATCH_T(dtype, {
-                    PairSrc<T> d3{{(const T *)a->ua_b, exact ? nullptr : (const T *)a->ua_a, a->x_hi, a->x_new},
-                                  {(const T *)a->va_b, exact ? nullptr : (const T *)a->va_a, a->x_hi, a->x_new}};
-                    PairSrc<T> ds{{nullptr, nullptr, 0.0, 0.0}, {nullptr, nullptr, 0.0, 0.0}};
-                    DeltaSrc<T> ph{nullptr, nullptr, 0.0, 0.0};
-                    LAUNCH_PAIR(false, (const T *)a->U, (const T *)a->V, d3, ds, ph, (T *)a->U_out, (T *)a->V_out, (T *)nullptr);
+                with_type(dtype, [&](auto t_) {
+                    using T = decltype(t_);
+                    hipLaunchKernelGGL((k_delta_pair<T, 1, false, PAIR_U, 128>), dim3(grid), dim3(128), lds, ctx->stream, ctx->plev_tab, lv,
+                                       ntime, ncol, (const T *)a->U, (const T *)a->V, (const T *)a->PS,
+                                       pair_src<T>(a->ua_b, a->ua_a, a->va_b, a->va_a, a->x_hi, a->x_new),
+                                       pair_src<T>(nullptr, nullptr, nullptr, nullptr, 0.0, 0.0), delta_src<T>(nullptr, nullptr, 0.0, 0.0),
+                                       check_top, (T *)a->U_out, (T *)a->V_out, (T *)nullptr, ctx->d_status);
                 });
             }
-#undef LAUNCH_PAIR
             HIPCHK(ctx, hipGetLastError());
         }
         if (!defer) {
             if ((rc = status_check(ctx))) return rc;            // (latitude-band mode: pgw_step03_file meets the other bands)
-            if ((rc = top_check())) return rc;
+            if ((rc = top_pressure_check(ctx, a->ignore_top))) return rc;
         }
     }
 
@@ -1880,11 +1811,19 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     a->n_iter = 0;
     for (int i = 0; i < 32; ++i) a->max_err_hist[i] = NAN;
     if (a->local_p_ref) NEED(ctx, a->zg3_b != nullptr, "local_p_ref needs the full zg records (zg3_b / zg3_a)");
-    rc = run_ps_loop(ctx, dtype, ntime, ncol, a->PS, a->FIS, a->T, a->QV, a->T_out, evap,
-                     a->local_p_ref ? a->zg3_b : a->zg_b, a->local_p_ref ? a->zg3_a : a->zg_a,
-                     a->per_var_time ? a->zg_x_hi : a->x_hi, a->per_var_time ? a->zg_x_new : a->x_new, a->p_ref, a->adj_factor, a->thresh, a->max_n_iter, a->PS_out, a->QV_out, &a->n_iter,
-                     a->max_err_hist, 32, a->local_p_ref ? a->nplev : 0, a->plev,
-                     !check_top && !a->local_p_ref, qv_done, ref, fused_first);
+    PsLoopArgs la;
+    la.dtype = dtype; la.ntime = ntime; la.ncol = ncol;
+    la.PS = a->PS; la.FIS = a->FIS; la.T = a->T; la.QV = a->QV;
+    la.ta_pgw = a->T_out; la.evap = evap;
+    la.dzg_b = a->local_p_ref ? a->zg3_b : a->zg_b; la.dzg_a = a->local_p_ref ? a->zg3_a : a->zg_a;
+    la.x_hi = zx_hi; la.x_new = zx_new;
+    la.p_ref = a->p_ref; la.adj_factor = a->adj_factor; la.thresh = a->thresh; la.max_n_iter = a->max_n_iter;
+    la.ps_pgw = a->PS_out; la.hus_pgw = a->QV_out;
+    la.n_iter = &a->n_iter; la.max_err_hist = a->max_err_hist; la.hist_len = 32;
+    if (a->local_p_ref) { la.local_nplev = a->nplev; la.plev_file = a->plev; }
+    la.status_armed = !check_top && !a->local_p_ref;
+    la.qv_done_levels = qv_done; la.ref = ref; la.fused_first = fused_first;
+    rc = run_ps_loop(ctx, la);
     a->levels_touched = ctx->last_levels_touched;
     a->passes_launched = ctx->last_passes_launched;
     return rc;
@@ -1932,8 +1871,11 @@ extern "C" int pgw_harmonic_smooth(pgw_ctx *ctx, int dtype, int ntime, long long
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // the host tables may be freed after the call
     {
         Prof pr(ctx, PGW_K_HARMONIC);
-        DISPATCH_T(dtype, hipLaunchKernelGGL((k_harmonic_smooth<T, 8>), dim3(nblocks(inner, BLOCK)), dim3(BLOCK), lds, ctx->stream,
-                                             ntime, inner, (const double *)tab, (const T *)in, (T *)out));
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_harmonic_smooth<T, 8>), dim3(nblocks(inner, BLOCK)), dim3(BLOCK), lds, ctx->stream, ntime, inner,
+                               (const double *)tab, (const T *)in, (T *)out);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -2019,8 +1961,7 @@ extern "C" int pgw_byteswap(pgw_ctx *ctx, int elem_bytes, long long n, const voi
     const bool al16 = ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0;
     const long long n16 = al16 ? n / (16 / elem_bytes) : 0;
     const long long work = al16 ? (n16 ? n16 : 1) : n;
-    unsigned int nb = nblocks(work, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
+    const unsigned int nb = flat_grid(work);
     {
         Prof pr(ctx, PGW_K_BYTESWAP);
         if (elem_bytes == 4)
@@ -2039,8 +1980,7 @@ extern "C" int pgw_narrow_f64_f32(pgw_ctx *ctx, long long n, const double *src, 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool al = ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 8) == 0;
     const long long n2 = al ? n / 2 : 0;
-    unsigned int nb = nblocks(n2 ? n2 : n, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
+    const unsigned int nb = flat_grid(n2 ? n2 : n);
     {
         Prof pr(ctx, PGW_K_BYTESWAP);
         if (big_endian) hipLaunchKernelGGL((k_narrow_f64_f32<true>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n2, n, src, (unsigned int *)dst);
@@ -2106,30 +2046,30 @@ extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, in
     tb.lon_lo = di + 3 * nlat_t; tb.lon_hi = tb.lon_lo + nlon_t; tb.lon_oob = tb.lon_lo + 2 * nlon_t;
     {
         Prof pr(ctx, PGW_K_REGRID);
-        DISPATCH_T(dtype, {
-            if (south_row >= 0 || north_row >= 0)
+        if (south_row >= 0 || north_row >= 0)
+            with_type(dtype, [&](auto t_) {
+                using T = decltype(t_);
                 hipLaunchKernelGGL((k_zonal_mean_rows<T>), dim3(nblocks(nfield * 2 * 64, BLOCK)), dim3(BLOCK), 0, ctx->stream, nfield,
                                    nlat_s, nlon_s, (const T *)src, south_row, north_row, dpole);
-            // two target longitudes per thread (one 16-B / 8-B store per plane) when the row length and the output
-            // alignment allow; z-slices: enough blocks to fill 256 CUs several times over even for small target grids
-            const int W = (nlon_t % 2 == 0 && ((uintptr_t)out % (2 * sizeof(T))) == 0 && !ctx->opt[PGW_OPT_FORCE_VEC1]) ? 2 : 1;
-            const unsigned int bx = nblocks(nlon_t, BLOCK * W);
-            long long xy = (long long)bx * nlat_t;
-            long long want = (8192 + xy - 1) / xy;
-            unsigned int gz = (unsigned int)(want < 1 ? 1 : (want > nfield ? nfield : want));
-            // z-slices in multiples of 8 where there are planes for it: one XCD per slice group (k_regrid)
-            if (nfield >= 8) gz = (gz + 7u) / 8u * 8u;
-            if (gz > nfield) gz = (unsigned int)nfield;
-            NEED(ctx, xy * gz < (1ll << 31), "regrid: too many blocks");
-            const unsigned int nb = (unsigned int)(xy * gz);
+            });
+        // two target longitudes per thread (one 16-B / 8-B store per plane) when the row length and the output
+        // alignment allow; z-slices: enough blocks to fill 256 CUs several times over even for small target grids
+        const int W = (nlon_t % 2 == 0 && ((uintptr_t)out % (2 * elem_size(dtype))) == 0 && !ctx->opt[PGW_OPT_FORCE_VEC1]) ? 2 : 1;
+        const unsigned int bx = nblocks(nlon_t, BLOCK * W);
+        long long xy = (long long)bx * nlat_t;
+        long long want = (8192 + xy - 1) / xy;
+        unsigned int gz = (unsigned int)(want < 1 ? 1 : (want > nfield ? nfield : want));
+        // z-slices in multiples of 8 where there are planes for it: one XCD per slice group (k_regrid)
+        if (nfield >= 8) gz = (gz + 7u) / 8u * 8u;
+        if (gz > nfield) gz = (unsigned int)nfield;
+        NEED(ctx, xy * gz < (1ll << 31), "regrid: too many blocks");
+        const unsigned int nb = (unsigned int)(xy * gz);
+        with_type(dtype, [&](auto t_) { with_int<2>(W - 1, [&](auto w_) {
+            using T = decltype(t_);
             // 4 planes per step (2: 6 % slower, 8: the same)
-            if (W == 2)
-                hipLaunchKernelGGL((k_regrid<T, 4, 2>), dim3(nb), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s,
-                                   nlon_s, nlat_t, nlon_t, bx, gz, (const T *)src, tb, dpole, (T *)out);
-            else
-                hipLaunchKernelGGL((k_regrid<T, 4, 1>), dim3(nb), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s,
-                                   nlon_s, nlat_t, nlon_t, bx, gz, (const T *)src, tb, dpole, (T *)out);
-        });
+            hipLaunchKernelGGL((k_regrid<T, 4, decltype(w_)::value + 1>), dim3(nb), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s,
+                               nlat_t, nlon_t, bx, gz, (const T *)src, tb, dpole, (T *)out);
+        }); });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -2142,8 +2082,11 @@ extern "C" int pgw_integrate_tos(pgw_ctx *ctx, int dtype, long long n, const voi
     NEED(ctx, n >= 1 && tos && ts && land && ice && out, "bad argument");
     {
         Prof pr(ctx, PGW_K_SURFACE);
-        DISPATCH_T(dtype, hipLaunchKernelGGL((k_integrate_tos<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n,
-                                             (const T *)tos, (const T *)ts, (const T *)land, (const T *)ice, (T *)out));
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_integrate_tos<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, (const T *)tos,
+                               (const T *)ts, (const T *)land, (const T *)ice, (T *)out);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -2165,10 +2108,12 @@ extern "C" int pgw_surface_update(pgw_ctx *ctx, int dtype, int ntime, long long 
     long long n = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_SURFACE);
-        DISPATCH_T(dtype, hipLaunchKernelGGL((k_surface_update<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, ntime, ncol,
-                                              st, (const T *)sic, (const T *)dsic, (const T *)dtos, (const T *)dts, (const T *)land,
-                                              (const T *)ts_clim, (const T *)tskin, (const T *)tso, (T *)sic_out, (T *)dts_comb_out,
-                                              (T *)tskin_out, (T *)tso_out));
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_surface_update<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, ntime, ncol, st,
+                               (const T *)sic, (const T *)dsic, (const T *)dtos, (const T *)dts, (const T *)land, (const T *)ts_clim,
+                               (const T *)tskin, (const T *)tso, (T *)sic_out, (T *)dts_comb_out, (T *)tskin_out, (T *)tso_out);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -2178,13 +2123,7 @@ extern "C" int pgw_surface_update(pgw_ctx *ctx, int dtype, int ntime, long long 
 // settings.function_dtype_flow = 'reference': one dtype tag per operand, nothing is cast up front; the kernels reproduce
 // numpy's promotion through the cited reference lines (include/pgw_hip.h).  A tag combination that is not instantiated is
 // PGW_ERR_ARG with a message, never another instantiation.
-#define TAG_OK(t) ((t) == PGW_F32 || (t) == PGW_F64)
-template <typename F> static inline void with_type(int tag, F &&f) { if (tag == PGW_F64) f(double()); else f(float()); }
-template <typename F> static inline void with_vec(int vec, F &&f) {
-    if (vec == 4) f(std::integral_constant<int, 4>());
-    else if (vec == 2) f(std::integral_constant<int, 2>());
-    else f(std::integral_constant<int, 1>());
-}
+
 // Elements per thread of a kernel whose rows differ in element size: the narrowest row loads as one 16-byte (V = 4 float32)
 // or 8-byte (V = 2) access per lane, a float64 row beside it as V / 2 16-byte accesses; all rows float64: V = 2 as in
 // pick_vec.  PGW_OPT_MIXED_VEC caps V (A/B knob of tools/function_flow_time.py).
@@ -2192,10 +2131,7 @@ static int pick_vec_mixed(pgw_ctx *ctx, bool any_f32, long long ncol, std::initi
     int v = any_f32 ? 4 : 2;
     if (v > ctx->opt[PGW_OPT_MIXED_VEC]) v = ctx->opt[PGW_OPT_MIXED_VEC] < 1 ? 1 : ctx->opt[PGW_OPT_MIXED_VEC];
     if (v == 3) v = 2;
-    if (ctx->opt[PGW_OPT_FORCE_VEC1]) return 1;
-    for (const void *p : ptrs) if (!aligned16(p)) return 1;
-    while (v > 1 && ncol % v != 0) v >>= 1;
-    return v;
+    return fit_vec(ctx, v, ncol, ptrs);
 }
 
 extern "C" int pgw_integ_geopot_mixed(pgw_ctx *ctx, int dt_pa_hl, int dt_zgs, int dt_ta, int dt_hus, int ntime, int nlev,
@@ -2230,8 +2166,7 @@ template <int WHICH>
 static void launch_humidity_mixed(pgw_ctx *ctx, int dt_a, int dt_b, int dt_c, long long n, const void *a, const void *b,
                                   const void *c, void *out) {
     const int vec = pick_vec_mixed(ctx, true, n, {a, b, c, out}) == 4 ? 4 : 1;
-    unsigned int nb = nblocks(n / vec, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
+    const unsigned int nb = flat_grid(n / vec);
     with_type(dt_a, [&](auto a_) { with_type(dt_b, [&](auto b_) { with_type(dt_c, [&](auto c_) { with_vec(vec, [&](auto v_) {
         using TA = decltype(a_); using TB = decltype(b_); using TC = decltype(c_);
         constexpr int V = decltype(v_)::value;
@@ -2254,15 +2189,7 @@ extern "C" int pgw_humidity_mixed(pgw_ctx *ctx, int which, int dt_a, int dt_b, i
     if (which < 5) dt_c = dt_a;
     {
         Prof pr(ctx, which == 6 ? PGW_K_RH_TO_Q : PGW_K_Q_TO_RH);
-        switch (which) {
-            case 0: launch_humidity_mixed<0>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
-            case 1: launch_humidity_mixed<1>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
-            case 2: launch_humidity_mixed<2>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
-            case 3: launch_humidity_mixed<3>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
-            case 4: launch_humidity_mixed<4>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
-            case 5: launch_humidity_mixed<5>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
-            default: launch_humidity_mixed<6>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); break;
-        }
+        with_int<7>(which, [&](auto w_) { launch_humidity_mixed<decltype(w_)::value>(ctx, dt_a, dt_b, dt_c, n, a, b, c, out); });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -2283,19 +2210,12 @@ extern "C" int pgw_interp_logp_4d_mixed(pgw_ctx *ctx, int dt_var, int dt_p, int 
     const long long total = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_INTERP_LOGP);
-        with_type(dt_var, [&](auto v_) {
+        with_type(dt_var, [&](auto v_) { with_int<4>(extrapolate, [&](auto m_) {
             using TV = decltype(v_);
-#define INTERP_M(M) hipLaunchKernelGGL((k_interp_logp_stream<TV, double, double, M>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0,  \
-                                       ctx->stream, ntime, nsrc, ntarg, ncol, (const TV *)var, (const double *)source_P,           \
-                                       (const double *)targ_P, out, logp_in, ctx->d_status)
-            switch (extrapolate) {
-                case 0: INTERP_M(0); break;
-                case 1: INTERP_M(1); break;
-                case 2: INTERP_M(2); break;
-                default: INTERP_M(3); break;
-            }
-#undef INTERP_M
-        });
+            hipLaunchKernelGGL((k_interp_logp_stream<TV, double, double, decltype(m_)::value>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
+                               0, ctx->stream, ntime, nsrc, ntarg, ncol, (const TV *)var, (const double *)source_P,
+                               (const double *)targ_P, out, logp_in, ctx->d_status);
+        }); });
     }
     HIPCHK(ctx, hipGetLastError());
     return status_check(ctx);
@@ -2326,18 +2246,18 @@ extern "C" int pgw_vert_interp_delta_mixed(pgw_ctx *ctx, int dt_delta, int dt_sf
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
         with_type(dt_delta, [&](auto d_) { with_type(dt_add, [&](auto a_) {
             using TD = decltype(d_); using TA = decltype(a_);
-            DeltaSrc<TD> d{(const TD *)delta, nullptr, 0.0, 0.0};
+            const DeltaSrc<TD> d = delta_src<TD>(delta, nullptr, 0.0, 0.0);           // the records of the instant itself
             if (!delta_sfc) {
-                DeltaSrc<TD> s{nullptr, nullptr, 0.0, 0.0};
-                DeltaSrc<double> p{nullptr, nullptr, 0.0, 0.0};
+                const DeltaSrc<TD> s = delta_src<TD>(nullptr, nullptr, 0.0, 0.0);
+                const DeltaSrc<double> p = delta_src<double>(nullptr, nullptr, 0.0, 0.0);
                 hipLaunchKernelGGL((k_vert_interp_delta<TD, double, double, false, TA, TD, double>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
                                    0, ctx->stream, ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const double *)targ_P,
                                    (const double *)nullptr, ignore_top ? 0 : 1, (const TA *)add_to, out, ctx->d_status);
             } else {
                 with_type(dt_sfc, [&](auto s_) { with_type(dt_pshist, [&](auto h_) {
                     using TS = decltype(s_); using TH = decltype(h_);
-                    DeltaSrc<TS> s{(const TS *)delta_sfc, nullptr, 0.0, 0.0};
-                    DeltaSrc<TH> p{(const TH *)ps_hist, nullptr, 0.0, 0.0};
+                    const DeltaSrc<TS> s = delta_src<TS>(delta_sfc, nullptr, 0.0, 0.0);
+                    const DeltaSrc<TH> p = delta_src<TH>(ps_hist, nullptr, 0.0, 0.0);
                     hipLaunchKernelGGL((k_vert_interp_delta<TD, double, double, true, TA, TS, TH>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
                                        0, ctx->stream, ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const double *)targ_P,
                                        (const double *)nullptr, ignore_top ? 0 : 1, (const TA *)add_to, out, ctx->d_status);
@@ -2359,14 +2279,7 @@ extern "C" int pgw_replace_delta_sfc_mixed(pgw_ctx *ctx, int dt_delta, int dt_sf
     NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV, "nplev must be in [1, 64]");
     NEED(ctx, plev_asc && delta && delta_sfc && ps_hist && out_P && out_delta, "null pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    PlevTable t;
-    memset(&t, 0, sizeof(t));
-    t.n = nplev; t.pmax = -INFINITY; t.pmin = INFINITY;
-    for (int i = 0; i < nplev; ++i) {
-        t.p[i] = plev_asc[i];
-        if (t.p[i] > t.pmax) t.pmax = t.p[i];
-        if (t.p[i] < t.pmin) t.pmin = t.p[i];
-    }
+    const PlevTable t = ascending_plev_table(nplev, plev_asc);
     int rc = status_reset(ctx);
     if (rc) return rc;
     const long long total = (long long)ntime * ncol;
@@ -2389,8 +2302,7 @@ extern "C" int pgw_time_lerp_mixed(pgw_ctx *ctx, int dt_before, int dt_after, lo
     NEED(ctx, n >= 1 && v_before && v_after && out, "bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int vec = pick_vec_mixed(ctx, dt_before == PGW_F32 || dt_after == PGW_F32, n, {v_before, v_after, out}) >= 2 ? 2 : 1;
-    unsigned int nb = nblocks(n / vec, BLOCK);
-    if (nb > 256 * 16) nb = 256 * 16;
+    const unsigned int nb = flat_grid(n / vec);
     {
         Prof pr(ctx, PGW_K_TIME_LERP);
         with_type(dt_before, [&](auto b_) { with_type(dt_after, [&](auto a_) { with_vec(vec, [&](auto v_) {
