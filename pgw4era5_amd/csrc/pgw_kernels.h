@@ -1046,17 +1046,146 @@ struct DeltaSrc {
         const T ra = ld_off(a, byte_off);
         return ((double)ra - (double)rb) / x_hi * x_new + (double)rb;
     }
-    // same, addressed by byte offset (ld_off); the division by the kernel-wide x_hi goes through a reciprocal the
-    // caller computed once (SharedDivisor: same quotient bits)
-    // LERP is the compile-time form of `a != nullptr` (all records of a file share the instant, so it is one
-    // property of the launch): no per-source null test - those tests were uniform 64-bit masks kept in spilled SGPRs
-    template <bool LERP, bool REF, typename O>
-    __device__ __forceinline__ double get_at(O byte_off, const SharedDivisor &by_x_hi) const {
-        const T rb = ld_off(b, byte_off);
-        if (!LERP) return (double)rb;
-        const T ra = ld_off(a, byte_off);
+    // get<REF>() of one raw record pair the caller loaded itself (all loads of a bracket change go out before the first
+    // use); the division by the kernel-wide x_hi goes through a reciprocal the caller computed once (SharedDivisor: same
+    // quotient bits).  `lerp` is `a != nullptr`, one property of the launch (all records of a file share the instant):
+    // no per-source null test - those tests were uniform 64-bit masks kept in spilled SGPRs
+    template <bool REF>
+    __device__ __forceinline__ double lerp_pair(bool lerp, T rb, T ra, const SharedDivisor &by_x_hi) const {
+        if (!lerp) return (double)rb;                             // :282-283
         const double diff = REF ? (double)(T)(ra - rb) : (double)ra - (double)rb;
-        return by_x_hi.divide(diff) * x_new + (double)rb;
+        return by_x_hi.divide(diff) * x_new + (double)rb;         // :288-292
+    }
+};
+
+// ---- rules every delta kernel follows: one statement each ------------------------------------------------------------
+// The top-pressure check (functions.py:417-420) for one block: minimum target and source pressure and the NaN flags of
+// its NW waves into DevStatus; the host compares the two minima.  The three LDS arrays hold one entry per wave.
+template <int NW>
+__device__ __forceinline__ void top_pressure_report(double min_t, double min_s, int nanflag, double (&s_mint)[NW],
+                                                    double (&s_mins)[NW], int (&s_nan)[NW], DevStatus *st) {
+    double wt = wave_min(min_t), ws = wave_min(min_s);
+    int wn = nanflag;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) wn |= __shfl_xor(wn, off, 64);
+    int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_mint[w] = wt; s_mins[w] = ws; s_nan[w] = wn; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double mt = s_mint[0], ms = s_mins[0];
+        int nn = s_nan[0];
+        for (int i = 1; i < NW; ++i) { mt = fmin(mt, s_mint[i]); ms = fmin(ms, s_mins[i]); nn |= s_nan[i]; }
+        // pressures are compared as ordered bit patterns; negative values (unphysical) map to 0
+        if (mt < __builtin_inf()) atomicMin(&st->min_targ_bits, mt > 0 ? dbits(mt) : 0ull);
+        if (ms < __builtin_inf()) atomicMin(&st->min_src_bits, ms > 0 ? dbits(ms) : 0ull);
+        if (nn) atomicOr(&st->nan_seen, nn);
+    }
+}
+
+// One table of the by-value PlevTable (p or lnp) into LDS, for lanes that index it with their own (divergent) scan
+// position.  The caller synchronises afterwards.
+__device__ __forceinline__ void stage_plev(const double (&tab)[MAX_PLEV], double *lds, int nthreads) {
+    for (int i = threadIdx.x; i < MAX_PLEV; i += nthreads) lds[i] = tab[i];
+}
+
+// replace_delta_sfc (functions.py:356-365) for one column: the source level `ksfc` that moves to ps_hist (-1: none) and
+// whether the levels below it take the surface delta (`fill`).  A ps_hist above the file's top level is status 15 for
+// column `col`; such a column inserts nothing: ksfc = -1 AND fill = false, for every caller.
+// `p` is the caller's copy of the ascending pressures (an LDS array: lanes scan it with a divergent index).
+// k_delta_pair and k_delta_quad keep their own text of this rule, on pt.p (uniform index: scalar loads): every form of the
+// helper tried there (struct or reference results, table or scalars passed) changed the instruction counts of the tuned
+// kernels' per-column preamble.  They follow the same statement, `fill` cleared included.  k_delta_pair keeps its
+// source minimum too, for the same reason; k_delta_quad takes source_min (same opcode counts and registers).
+struct SfcLevel { int ksfc; bool fill; };
+template <typename P>
+__device__ __forceinline__ SfcLevel sfc_level(const PlevTable &pt, const P &p, double pshv, DevStatus *st, long long col) {
+    const int S = pt.n;
+    SfcLevel r{-1, false};
+    bool bad = false;
+    if (pshv > pt.pmax) r.ksfc = S - 1;                            // :356-359
+    else if (pshv < pt.pmin) bad = true;                          // :360-361
+    else {                                                        // :362-365
+        for (int i = 0; i < S; ++i) if (pshv > p[i]) r.ksfc = i;
+        if (r.ksfc < 0) bad = true;                               // np.max of empty argwhere
+        r.fill = true;
+    }
+    if (bad) { report(st, 15, col); r.ksfc = -1; r.fill = false; }
+    return r;
+}
+// np.min(source_P) of the column (:417) after that insertion, folded into the lane's min_s / nanflag; `p` as above
+template <bool HAS_SFC, typename P>
+__device__ __forceinline__ void source_min(int S, const P &p, int ksfc, double pshv, double &min_s, int &nanflag) {
+    double m = min_s;                      // folded in locals: the loop compiles to selects, as written in a kernel
+    int nf = nanflag;
+    for (int i = 0; i < S; ++i) {
+        double v = (HAS_SFC && i == ksfc) ? pshv : p[i];
+        if (v != v) nf |= 2; else m = fmin(m, v);
+    }
+    min_s = m;
+    nanflag = nf;
+}
+
+// One variable of one column on the source axis of vert_interp_delta (functions.py:343-431): ln(plev) with level ksfc
+// moved to ln(ps_hist), the delta records of the file with the surface delta at and (fill) below it; the scan position
+// and the cached bracket of interp_extrap_1d ('constant', :527-578) as the caller walks its target levels.
+// DY32: the reference's dtype flow takes `src_y[i2] - src_y[i1]` in float32 (numba, :575-578).
+template <typename TD, bool HAS_SFC, bool DY32>
+struct DeltaColumn {
+    const DeltaSrc<TD> &dsrc;
+    const double *s_lnp;
+    const int S;
+    const long long dbase, ncol;         // delta records are (ntime, S, ncol), file order
+    SfcLevel sl{-1, false};
+    double d_sfc = 0.0, lnps = 0.0;
+    int j = 0;                           // first source index with srcx >= x
+    double xprev = -__builtin_inf();
+    int ci = -2;                         // cached bracket index: values y[ci], y[ci+1]
+    double y_lo = 0.0, y_hi = 0.0;
+
+    // surface insertion from (sfc, psh) of column `flat`, and with check_top the column's source minimum
+    template <typename TS, typename TH, typename P>
+    __device__ __forceinline__ void insert_sfc(const PlevTable &pt, const P &s_p, const DeltaSrc<TS> &sfc, const DeltaSrc<TH> &psh,
+                                               long long flat, const double *logtab, int check_top, double &min_s,
+                                               int &nanflag, DevStatus *st) {
+        double pshv = 0.0;
+        if (HAS_SFC) {
+            pshv = psh.get(flat);
+            d_sfc = sfc.get(flat);
+            if constexpr (sizeof(TS) > sizeof(TD)) d_sfc = (double)(TD)d_sfc;     // stored in the delta's dtype
+            sl = sfc_level(pt, s_p, pshv, st, flat);
+            lnps = pgw_log_tab(pshv, logtab);
+        }
+        if (check_top) source_min<HAS_SFC>(S, s_p, sl.ksfc, pshv, min_s, nanflag);
+    }
+    __device__ __forceinline__ double srcx(int i) const { return (HAS_SFC && i == sl.ksfc) ? lnps : s_lnp[i]; }
+    __device__ __forceinline__ double srcy(int i) const {
+        if (HAS_SFC && sl.ksfc >= 0 && (i == sl.ksfc || (sl.fill && i > sl.ksfc))) return d_sfc;
+        return dsrc.get(dbase + (long long)(S - 1 - i) * ncol);
+    }
+    // the delta at ln-pressure x; a descending or NaN target restarts the scan
+    __device__ __forceinline__ double interp(double x) {
+        if (!(x >= xprev)) j = 0;
+        while (j < S) {
+            double xs = srcx(j);
+            if (xs == x || xs > x) break;
+            ++j;
+        }
+        double y;
+        if (j >= S) {                                   // above range, constant :558-560
+            y = srcy(S - 1);
+        } else {
+            double xs = srcx(j);
+            if (xs == x) y = srcy(j);                   // exact :540-543
+            else if (j == 0) y = srcy(0);               // below range, constant :534-536
+            else {
+                if (ci != j - 1) { y_lo = srcy(j - 1); y_hi = srcy(j); ci = j - 1; }
+                double x1 = srcx(j - 1);
+                if constexpr (DY32) y = y_lo + (x - x1) * (double)((float)y_hi - (float)y_lo) / (xs - x1);
+                else y = y_lo + (x - x1) * (y_hi - y_lo) / (xs - x1);    // :575-578
+            }
+        }
+        xprev = (x == x) ? x : __builtin_inf();
+        return y;
     }
 };
 
@@ -1084,59 +1213,20 @@ __global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PlevTable pt, Level
     lt.logtab = s_lev + 2 * (MAX_NLEV + 1) + 2 * MAX_NLEV;
     if (!trgP) lt = stage_levels<false, true>(lv, s_lev, BLOCK);
     else stage_log_table(s_lev + 2 * (MAX_NLEV + 1) + 2 * MAX_NLEV, BLOCK);
-    const int S = pt.n;
-    if (threadIdx.x < MAX_PLEV) {
-        s_p[threadIdx.x] = pt.p[threadIdx.x];
-        s_lnp[threadIdx.x] = pt.lnp[threadIdx.x];
-    }
+    stage_plev(pt.p, s_p, BLOCK);
+    stage_plev(pt.lnp, s_lnp, BLOCK);
     __syncthreads();
     long long flat = (long long)blockIdx.x * BLOCK + threadIdx.x;
     double min_t = __builtin_inf(), min_s = __builtin_inf();
     int nanflag = 0;
     if (flat < (long long)ntime * ncol) {
         long long t = flat / ncol, c = flat - t * ncol;
-        long long c2 = flat;
-        long long dbase = t * S * ncol + c;      // delta records are (ntime, S, ncol), file order
-        int ksfc = -1;                           // level moved to ps_hist
-        bool fill_below = false;
-        double d_sfc = 0.0, lnps = 0.0, pshv = 0.0;
-        bool bad = false;
-        if (HAS_SFC) {
-            pshv = psh.get(c2);
-            d_sfc = sfc.get(c2);
-            if constexpr (sizeof(TS) > sizeof(TD)) d_sfc = (double)(TD)d_sfc;     // stored in the delta's dtype
-            if (pshv > pt.pmax) {                                  // :356-359
-                ksfc = S - 1;
-            } else if (pshv < pt.pmin) {                           // :360-361
-                bad = true;
-            } else {                                               // :362-365
-                for (int i = 0; i < S; ++i) if (pshv > s_p[i]) ksfc = i;
-                if (ksfc < 0) bad = true;                          // np.max of empty argwhere
-                fill_below = true;
-            }
-            if (bad) { report(st, 15, flat); ksfc = -1; }
-            lnps = pgw_log_tab(pshv, lt.logtab);
-        }
-        auto srcx = [&](int i) -> double { return (HAS_SFC && i == ksfc) ? lnps : s_lnp[i]; };
-        auto srcy = [&](int i) -> double {
-            if (HAS_SFC && ksfc >= 0 && (i == ksfc || (fill_below && i > ksfc))) return d_sfc;
-            return dsrc.get(dbase + (long long)(S - 1 - i) * ncol);
-        };
-        if (check_top) {
-            // np.min(source_P) over this column (:417)
-            for (int i = 0; i < S; ++i) {
-                double p = (HAS_SFC && i == ksfc) ? pshv : s_p[i];
-                if (p != p) nanflag |= 2; else min_s = fmin(min_s, p);
-            }
-        }
+        DeltaColumn<TD, HAS_SFC, DY32> col{dsrc, s_lnp, pt.n, t * pt.n * ncol + c, ncol};
+        col.insert_sfc(pt, s_p, sfc, psh, flat, lt.logtab, check_top, min_s, nanflag, st);
         double psv = 0.0;
         const TP *ptg = nullptr;
-        if (trgP) ptg = trgP + t * N * ncol + c; else psv = (double)ps[c2];
+        if (trgP) ptg = trgP + t * N * ncol + c; else psv = (double)ps[flat];
         long long obase = t * N * ncol + c;
-        int j = 0;
-        double xprev = -__builtin_inf();
-        int ci = -2;                 // cached bracket index: values y[ci], y[ci+1]
-        double y_lo = 0.0, y_hi = 0.0;
         // chunks of 4 target levels: the next chunk's target pressures and addends are in flight while this one is
         // interpolated (one memory latency per chunk instead of per level; each element is touched once: streaming forms)
         constexpr int U = 4;
@@ -1165,51 +1255,13 @@ __global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PlevTable pt, Level
             if (l >= N) break;
             double p = ptg ? cp_[u] : (lt.akm[l] + psv * lt.bkm[l]);
             if (check_top) { if (p != p) nanflag |= 1; else min_t = fmin(min_t, p); }
-            double x = pgw_log_tab(p, lt.logtab);
-            if (!(x >= xprev)) j = 0;
-            while (j < S) {
-                double xs = srcx(j);
-                if (xs == x || xs > x) break;
-                ++j;
-            }
-            double y;
-            if (j >= S) {                                   // above range, constant :558-560
-                y = srcy(S - 1);
-            } else {
-                double xs = srcx(j);
-                if (xs == x) y = srcy(j);                   // exact :540-543
-                else if (j == 0) y = srcy(0);               // below range, constant :534-536
-                else {
-                    if (ci != j - 1) { y_lo = srcy(j - 1); y_hi = srcy(j); ci = j - 1; }
-                    double x1 = srcx(j - 1);
-                    if constexpr (DY32) y = y_lo + (x - x1) * (double)((float)y_hi - (float)y_lo) / (xs - x1);
-                    else y = y_lo + (x - x1) * (y_hi - y_lo) / (xs - x1);    // :575-578
-                }
-            }
+            double y = col.interp(pgw_log_tab(p, lt.logtab));
             if (add_to) y = ca_[u] + y;                                        // step_03:170-173
             SIG_ST((TO)y, out + obase + (long long)l * ncol);
-            xprev = (x == x) ? x : __builtin_inf();
         }
         }
     }
-    if (check_top) {
-        double wt = wave_min(min_t), ws = wave_min(min_s);
-        int wn = nanflag;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wn |= __shfl_xor(wn, off, 64);
-        int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { s_mint[w] = wt; s_mins[w] = ws; s_nan[w] = wn; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double mt = s_mint[0], ms = s_mins[0];
-            int nn = s_nan[0];
-            for (int i = 1; i < BLOCK / 64; ++i) { mt = fmin(mt, s_mint[i]); ms = fmin(ms, s_mins[i]); nn |= s_nan[i]; }
-            // pressures are compared as ordered bit patterns; negative values (unphysical) map to 0
-            if (mt < __builtin_inf()) atomicMin(&st->min_targ_bits, mt > 0 ? dbits(mt) : 0ull);
-            if (ms < __builtin_inf()) atomicMin(&st->min_src_bits, ms > 0 ? dbits(ms) : 0ull);
-            if (nn) atomicOr(&st->nan_seen, nn);
-        }
-    }
+    if (check_top) top_pressure_report<BLOCK / 64>(min_t, min_s, nanflag, s_mint, s_mins, s_nan, st);
 }
 
 // settings.i_reinterp = 1 (step_03_apply_to_era.py:202-216, 330-343), one variable, one pass, one kernel:
@@ -1232,50 +1284,18 @@ __global__ __launch_bounds__(BLOCK) void k_reinterp_field(PlevTable pt, Levels l
     __shared__ double s_p[MAX_PLEV], s_lnp[MAX_PLEV];
     __shared__ double s_lev[LEVTAB_DOUBLES];
     LevTab lt = stage_levels<false, true>(lv, s_lev, BLOCK);
-    const int S = pt.n, N = lv.nlev;
-    if (threadIdx.x < MAX_PLEV) {
-        s_p[threadIdx.x] = pt.p[threadIdx.x];
-        s_lnp[threadIdx.x] = pt.lnp[threadIdx.x];
-    }
+    const int N = lv.nlev;
+    stage_plev(pt.p, s_p, BLOCK);
+    stage_plev(pt.lnp, s_lnp, BLOCK);
     __syncthreads();
     long long flat = (long long)blockIdx.x * BLOCK + threadIdx.x;
     double min_t = __builtin_inf(), min_s = __builtin_inf();
     int nanflag = 0;
     if (flat < (long long)ntime * ncol) {
         long long t = flat / ncol, c = flat - t * ncol;
-        long long c2 = flat;
-        long long dbase = t * S * ncol + c;      // delta records are (ntime, S, ncol), file order
-        int ksfc = -1;                           // level moved to ps_hist
-        bool fill_below = false;
-        double d_sfc = 0.0, lnps = 0.0, pshv = 0.0;
-        bool bad = false;
-        if (HAS_SFC) {
-            pshv = psh.get(c2);
-            d_sfc = sfc.get(c2);
-            if (pshv > pt.pmax) {                                  // functions.py:356-359
-                ksfc = S - 1;
-            } else if (pshv < pt.pmin) {                           // :360-361
-                bad = true;
-            } else {                                               // :362-365
-                for (int i = 0; i < S; ++i) if (pshv > s_p[i]) ksfc = i;
-                if (ksfc < 0) bad = true;
-                fill_below = true;
-            }
-            if (bad) { report(st, 15, flat); ksfc = -1; }
-            lnps = pgw_log_tab(pshv, lt.logtab);
-        }
-        auto srcx = [&](int i) -> double { return (HAS_SFC && i == ksfc) ? lnps : s_lnp[i]; };
-        auto srcy = [&](int i) -> double {
-            if (HAS_SFC && ksfc >= 0 && (i == ksfc || (fill_below && i > ksfc))) return d_sfc;
-            return dsrc.get(dbase + (long long)(S - 1 - i) * ncol);
-        };
-        if (check_top) {
-            for (int i = 0; i < S; ++i) {                          // np.min(source_P) over this column (:417)
-                double p = (HAS_SFC && i == ksfc) ? pshv : s_p[i];
-                if (p != p) nanflag |= 2; else min_s = fmin(min_s, p);
-            }
-        }
-        const double pse = (double)ps_era[c2], psv = (double)ps_pgw[c2];
+        DeltaColumn<T, HAS_SFC, false> col{dsrc, s_lnp, pt.n, t * pt.n * ncol + c, ncol};
+        col.insert_sfc(pt, s_p, sfc, psh, flat, lt.logtab, check_top, min_s, nanflag, st);
+        const double pse = (double)ps_era[flat], psv = (double)ps_pgw[flat];
         const long long obase = t * (long long)N * ncol + c;
         const T *pf = era_field + obase;
         // ---- window over the ERA column: (wxm, wym) level wj - 1, (wxj, wyj) level wj, and the raw values of levels
@@ -1290,15 +1310,11 @@ __global__ __launch_bounds__(BLOCK) void k_reinterp_field(PlevTable pt, Levels l
             q0 = wload(1); q1 = wload(2); q2 = wload(3); q3 = wload(4);
         };
         wreset();
-        int j = 0;
-        double xprev = -__builtin_inf();
-        int ci = -2;                 // cached bracket index of the delta: values y[ci], y[ci+1]
-        double y_lo = 0.0, y_hi = 0.0;
         for (int l = 0; l < N; ++l) {
             const double p = lt.akm[l] + psv * lt.bkm[l];                                   // step_03:196-197
             if (check_top) { if (p != p) nanflag |= 1; else min_t = fmin(min_t, p); }
             const double x = pgw_log_tab(p, lt.logtab);
-            if (__builtin_expect(!(x >= xprev), 0)) { j = 0; wreset(); }                    // descending / NaN target: both scans restart
+            if (__builtin_expect(!(x >= col.xprev), 0)) wreset();                           // descending / NaN target: both scans restart (the delta's in interp)
             // -- the ERA field at this pressure (interp_extrap_1d, 'constant')
             while (wj < N && !(wxj == x || wxj > x)) {
                 wxm = wxj; wym = wyj;
@@ -1314,45 +1330,11 @@ __global__ __launch_bounds__(BLOCK) void k_reinterp_field(PlevTable pt, Levels l
             else if (wxj == x || wj == 0) e = wyj;                  // exact :540-543 / before the first: its value :534-536
             else e = wym + (x - wxm) * (wyj - wym) / (wxj - wxm);   // :575-578
             // -- the climate delta at this pressure (as k_vert_interp_delta)
-            while (j < S) {
-                double xs = srcx(j);
-                if (xs == x || xs > x) break;
-                ++j;
-            }
-            double y;
-            if (j >= S) {
-                y = srcy(S - 1);
-            } else {
-                double xs = srcx(j);
-                if (xs == x) y = srcy(j);
-                else if (j == 0) y = srcy(0);
-                else {
-                    if (ci != j - 1) { y_lo = srcy(j - 1); y_hi = srcy(j); ci = j - 1; }
-                    double x1 = srcx(j - 1);
-                    y = y_lo + (x - x1) * (y_hi - y_lo) / (xs - x1);
-                }
-            }
+            const double y = col.interp(x);
             SIG_ST((T)(e + y), out + obase + (long long)l * ncol);                          // vars_era + deltas  :216
-            xprev = (x == x) ? x : __builtin_inf();
         }
     }
-    if (check_top) {
-        double wt = wave_min(min_t), ws = wave_min(min_s);
-        int wn = nanflag;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wn |= __shfl_xor(wn, off, 64);
-        int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { s_mint[w] = wt; s_mins[w] = ws; s_nan[w] = wn; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double mt = s_mint[0], ms = s_mins[0];
-            int nn = s_nan[0];
-            for (int i = 1; i < BLOCK / 64; ++i) { mt = fmin(mt, s_mint[i]); ms = fmin(ms, s_mins[i]); nn |= s_nan[i]; }
-            if (mt < __builtin_inf()) atomicMin(&st->min_targ_bits, mt > 0 ? dbits(mt) : 0ull);
-            if (ms < __builtin_inf()) atomicMin(&st->min_src_bits, ms > 0 ? dbits(ms) : 0ull);
-            if (nn) atomicOr(&st->nan_seen, nn);
-        }
-    }
+    if (check_top) top_pressure_report<BLOCK / 64>(min_t, min_s, nanflag, s_mint, s_mins, s_nan, st);
 }
 
 // settings.i_reinterp = 1, TWO variables that share both pressure axes in one kernel (ta + hur, whose surface insertion
@@ -1418,10 +1400,8 @@ __global__ __launch_bounds__(BLOCK, (EVAP ? RP_MINW_EVAP : RP_MINW)) void k_rein
     double *s_akm = lds_rp, *s_bkm = lds_rp + N;
     stage_log_table(s_logt, BLOCK);
     for (int i = threadIdx.x; i < N; i += BLOCK) { s_akm[i] = lv.akm[i]; s_bkm[i] = lv.bkm[i]; }
-    if (threadIdx.x < MAX_PLEV) {
-        s_p[threadIdx.x] = pt.p[threadIdx.x];
-        s_lnp[threadIdx.x] = pt.lnp[threadIdx.x];
-    }
+    stage_plev(pt.p, s_p, BLOCK);
+    stage_plev(pt.lnp, s_lnp, BLOCK);
     __syncthreads();
     long long flat = (long long)blockIdx.x * BLOCK + threadIdx.x;
     double min_t = __builtin_inf(), min_s = __builtin_inf();
@@ -1430,45 +1410,24 @@ __global__ __launch_bounds__(BLOCK, (EVAP ? RP_MINW_EVAP : RP_MINW)) void k_rein
         long long t = flat / ncol, c = flat - t * ncol;
         const O row = (O)((unsigned long long)ncol * sizeof(T));
         const O dbase = (O)((unsigned long long)(t * S * ncol + c) * sizeof(T));      // delta records are (ntime, S, ncol), file order
-        int ksfc = -1;                                 // level moved to ps_hist
-        bool fill_below = false;
+        SfcLevel sl{-1, false};                        // level moved to ps_hist
         double d_sfc0 = 0.0, d_sfc1 = 0.0, lnps = 0.0, pshv = 0.0;
         if (HAS_SFC) {
-            bool bad = false;
             pshv = psh.template get<REF>(flat);
             d_sfc0 = rv.sfc[0].template get<REF>(flat);
             d_sfc1 = rv.sfc[1].template get<REF>(flat);
-            if (pshv > pt.pmax) {                                  // functions.py:356-359
-                ksfc = S - 1;
-            } else if (pshv < pt.pmin) {                           // :360-361
-                bad = true;
-            } else {                                               // :362-365
-                for (int i = 0; i < S; ++i) if (pshv > s_p[i]) ksfc = i;
-                if (ksfc < 0) bad = true;
-                fill_below = true;
-            }
-            if (bad) { report(st, 15, flat); ksfc = -1; }
+            sl = sfc_level(pt, s_p, pshv, st, flat);
             lnps = pgw_log_tab(pshv, s_logt);
         }
-        auto srcx = [&](int i) -> double { return (HAS_SFC && i == ksfc) ? lnps : s_lnp[i]; };
-        auto is_sfc = [&](int i) -> bool { return HAS_SFC && ksfc >= 0 && (i == ksfc || (fill_below && i > ksfc)); };
-        if (check_top) {
-            for (int i = 0; i < S; ++i) {                          // np.min(source_P) over this column (:417)
-                double p = (HAS_SFC && i == ksfc) ? pshv : s_p[i];
-                if (p != p) nanflag |= 2; else min_s = fmin(min_s, p);
-            }
-        }
+        auto srcx = [&](int i) -> double { return (HAS_SFC && i == sl.ksfc) ? lnps : s_lnp[i]; };
+        auto is_sfc = [&](int i) -> bool { return HAS_SFC && sl.ksfc >= 0 && (i == sl.ksfc || (sl.fill && i > sl.ksfc)); };
+        if (check_top) source_min<HAS_SFC>(S, s_p, sl.ksfc, pshv, min_s, nanflag);
         // delta records of the bracket (ci, ci + 1) of both variables; all loads of a change before the first use
         int ci = -2;
         double a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;
         const bool lerp = rv.d[0].a != nullptr;          // one instant for every record of the launch
-        const double x_new = rv.d[0].x_new;
         const SharedDivisor by_x_hi(lerp ? rv.d[0].x_hi : 1.0);
-        auto tl = [&](T rb, T ra) -> double {             // DeltaSrc::get (functions.py:282-292)
-            if (!lerp) return (double)rb;
-            const double diff = REF ? (double)(T)(ra - rb) : (double)ra - (double)rb;
-            return by_x_hi.divide(diff) * x_new + (double)rb;
-        };
+        auto tl = [&](T rb, T ra) -> double { return rv.d[0].template lerp_pair<REF>(lerp, rb, ra, by_x_hi); };
         // value differences of the column interpolations (functions.py:575-578) in the dtype numba sees them in
         auto ydiff = [&](double hi, double lo) -> double { return (REF && !lerp) ? (double)((float)hi - (float)lo) : hi - lo; };
         auto ediff0 = [](double hi, double lo) -> double { return (REF && sizeof(TE0) == 4) ? (double)((float)hi - (float)lo) : hi - lo; };
@@ -1617,23 +1576,7 @@ __global__ __launch_bounds__(BLOCK, (EVAP ? RP_MINW_EVAP : RP_MINW)) void k_rein
             }
         }
     }
-    if (check_top) {
-        double wt = wave_min(min_t), ws = wave_min(min_s);
-        int wn = nanflag;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wn |= __shfl_xor(wn, off, 64);
-        int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { s_mint[w] = wt; s_mins[w] = ws; s_nan[w] = wn; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double mt = s_mint[0], ms = s_mins[0];
-            int nn = s_nan[0];
-            for (int i = 1; i < BLOCK / 64; ++i) { mt = fmin(mt, s_mint[i]); ms = fmin(ms, s_mins[i]); nn |= s_nan[i]; }
-            if (mt < __builtin_inf()) atomicMin(&st->min_targ_bits, mt > 0 ? dbits(mt) : 0ull);
-            if (ms < __builtin_inf()) atomicMin(&st->min_src_bits, ms > 0 ? dbits(ms) : 0ull);
-            if (nn) atomicOr(&st->nan_seen, nn);
-        }
-    }
+    if (check_top) top_pressure_report<BLOCK / 64>(min_t, min_s, nanflag, s_mint, s_mins, s_nan, st);
 }
 
 // =====================================================================================
@@ -1682,7 +1625,7 @@ __global__ __launch_bounds__(TPB, THERMO ? 4 : 1) void k_delta_pair(PlevTable pt
     const int S = pt.n;
     double *s_akm = lds_pair, *s_bkm = s_akm + lv.nlev;
     stage_log_table(s_logt, TPB);
-    for (int i = threadIdx.x; i < MAX_PLEV; i += TPB) s_lnp[i] = pt.lnp[i];
+    stage_plev(pt.lnp, s_lnp, TPB);
     for (int i = threadIdx.x; i < lv.nlev; i += TPB) {
         s_akm[i] = lv.akm[i];
         s_bkm[i] = lv.bkm[i];
@@ -1834,23 +1777,7 @@ __global__ __launch_bounds__(TPB, THERMO ? 4 : 1) void k_delta_pair(PlevTable pt
             }
         }
     }
-    if (check_top) {
-        double wt = wave_min(min_t), ws = wave_min(min_s);
-        int wn = nanflag;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wn |= __shfl_xor(wn, off, 64);
-        int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { s_mint[w] = wt; s_mins[w] = ws; s_nan[w] = wn; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double mt = s_mint[0], ms = s_mins[0];
-            int nn = s_nan[0];
-            for (int i = 1; i < TPB / 64; ++i) { mt = fmin(mt, s_mint[i]); ms = fmin(ms, s_mins[i]); nn |= s_nan[i]; }
-            if (mt < __builtin_inf()) atomicMin(&st->min_targ_bits, mt > 0 ? dbits(mt) : 0ull);
-            if (ms < __builtin_inf()) atomicMin(&st->min_src_bits, ms > 0 ? dbits(ms) : 0ull);
-            if (nn) atomicOr(&st->nan_seen, nn);
-        }
-    }
+    if (check_top) top_pressure_report<TPB / 64>(min_t, min_s, nanflag, s_mint, s_mins, s_nan, st);
 }
 
 // -------------------------------------------------------------------------------------
@@ -1926,7 +1853,7 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
     double *s_akm = lds_quad, *s_bkm = lds_quad + lv.nlev, *s_lnpa = lds_quad + 2 * lv.nlev;
     double *s_ak = lds_quad + 3 * lv.nlev, *s_bk = s_ak + lv.nlev + 1;
     stage_log_table(s_logt, TPB);
-    for (int i = threadIdx.x; i < MAX_PLEV; i += TPB) s_lnp[i] = pt.lnp[i];
+    stage_plev(pt.lnp, s_lnp, TPB);
     for (int i = threadIdx.x; i < lv.nlev; i += TPB) { s_akm[i] = lv.akm[i]; s_bkm[i] = lv.bkm[i]; }
     if (FUSE) {
         for (int i = threadIdx.x; i <= lv.nlev; i += TPB) { s_ak[i] = lv.ak[i]; s_bk[i] = lv.bk[i]; }
@@ -1973,12 +1900,7 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
             if (bad) { report(st, 15, flat); ksfc = -1; fill = false; }
         }
         const double lnps = pgw_log_tab(pshv, s_logt);
-        if (check_top) {                                                      // np.min(source_P), :417
-            for (int i = 0; i < S; ++i) {
-                double p = (i == ksfc) ? pshv : pt.p[i];
-                if (p != p) nanflag |= 2; else min_s = fmin(min_s, p);
-            }
-        }
+        if (check_top) source_min<true>(S, pt.p, ksfc, pshv, min_s, nanflag);
         // modified axis: unconditional LDS read + select (the compiler otherwise wraps the read in a divergent branch;
         // the empty asm keeps the load where it is; 8 of 82 exec-mask regions of the loop gone, 2.28 -> 2.25 ms)
         auto sx1 = [&](int i) -> double { double v = s_lnp[i]; asm("" : "+v"(v)); return (i == ksfc) ? lnps : v; };
@@ -1991,11 +1913,7 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
         // issued back to back BEFORE the first use (raw values into registers, then the time interpolation): one exposed
         // memory latency per change instead of one per value (the first version waited after every record pair - 2 to 4
         // serial round trips per change, the largest part of the kernel's 0.51 s_waitcnt share).
-        auto tl = [&](const DeltaSrc<T> &sv, T rb, T ra) -> double {          // load_delta's time interpolation of one value
-            if (!LERP) return (double)rb;
-            const double diff = REF ? (double)(T)(ra - rb) : (double)ra - (double)rb;
-            return by_x_hi.divide(diff) * sv.x_new + (double)rb;
-        };
+        auto tl = [&](const DeltaSrc<T> &sv, T rb, T ra) -> double { return sv.template lerp_pair<REF>(LERP, rb, ra, by_x_hi); };
         auto off_of = [&](int i) -> O { return dbase + (O)(S - 1 - i) * row; };
         auto fetch1 = [&](int i1) {
             if (ci1 == i1) return;
@@ -2206,23 +2124,7 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
         const double wm = wave_max(abs_err);
         if ((threadIdx.x & 63) == 0 && wm >= 0.0) { DevStatus *sp = ffp->st_pass; atomicMax(&sp->max_bits, dbits(wm)); atomicAdd(&sp->valid, 1ull); }
     }
-    if (check_top) {
-        double wt = wave_min(min_t), ws = wave_min(min_s);
-        int wn = nanflag;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wn |= __shfl_xor(wn, off, 64);
-        int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { s_mint[w] = wt; s_mins[w] = ws; s_nan[w] = wn; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double mt = s_mint[0], ms = s_mins[0];
-            int nn = s_nan[0];
-            for (int i = 1; i < TPB / 64; ++i) { mt = fmin(mt, s_mint[i]); ms = fmin(ms, s_mins[i]); nn |= s_nan[i]; }
-            if (mt < __builtin_inf()) atomicMin(&st->min_targ_bits, mt > 0 ? dbits(mt) : 0ull);
-            if (ms < __builtin_inf()) atomicMin(&st->min_src_bits, ms > 0 ? dbits(ms) : 0ull);
-            if (nn) atomicOr(&st->nan_seen, nn);
-        }
-    }
+    if (check_top) top_pressure_report<TPB / 64>(min_t, min_s, nanflag, s_mint, s_mins, s_nan, st);
 }
 
 // =====================================================================================
@@ -2499,27 +2401,19 @@ __global__ __launch_bounds__(BLOCK) void k_replace_delta_sfc(PlevTable pt, int n
                                                              T *__restrict__ outD, DevStatus *st) {
     __shared__ double s_p[MAX_PLEV];
     const int S = pt.n;
-    if (threadIdx.x < MAX_PLEV) s_p[threadIdx.x] = pt.p[threadIdx.x];
+    stage_plev(pt.p, s_p, BLOCK);
     __syncthreads();
     long long flat = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (flat >= (long long)ntime * ncol) return;
     long long t = flat / ncol, c = flat - t * ncol;
     long long base = t * S * ncol + c;
     double ps = (double)pshist[flat], ds = (double)dsfc[flat];
-    int k = -1;
-    bool fill = false;
-    if (ps > pt.pmax) k = S - 1;                                   // :356-359
-    else if (ps < pt.pmin) { report(st, 15, flat); }               // :360-361
-    else {                                                         // :362-365
-        for (int i = 0; i < S; ++i) if (ps > s_p[i]) k = i;
-        if (k < 0) report(st, 15, flat);
-        fill = true;
-    }
+    const SfcLevel sl = sfc_level(pt, s_p, ps, st, flat);
     for (int i = 0; i < S; ++i) {
         double P = s_p[i], D = (double)delta[base + (long long)i * ncol];
-        if (k >= 0) {
-            if (i == k) { P = ps; D = ds; }
-            else if (fill && i > k) D = ds;
+        if (sl.ksfc >= 0) {
+            if (i == sl.ksfc) { P = ps; D = ds; }
+            else if (sl.fill && i > sl.ksfc) D = ds;
         }
         outP[base + (long long)i * ncol] = (TP)P;
         outD[base + (long long)i * ncol] = (T)D;

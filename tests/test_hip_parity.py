@@ -262,6 +262,67 @@ def test_vert_interp_delta_vs_oracle(F, with_sfc):
         assert str(e.value) == ''
 
 
+def _single_column_top_inputs():
+    """(plev, delta, delta_sfc, ps_hist, [(target_P, raises), ...]) of test_top_pressure_check_sees_a_single_column:
+    1 time step, 5 x 13 = 65 columns (one block; the second wave has one live lane, column 64), N = 4 target levels."""
+    rng = np.random.default_rng(417)
+    plev = np.array([100000.0, 85000.0, 50000.0, 20000.0, 10000.0])          # file order; min(plev) = 10000
+    delta = rng.normal(size=(1, plev.size, 5, 13))
+    dsfc = rng.normal(size=(1, 5, 13))
+    psh = rng.uniform(90000.0, 99000.0, size=(1, 5, 13))
+    ok = np.sort(rng.uniform(10000.5, 101000.0, size=(1, 4, 5, 13)), axis=1)   # every level >= min(plev)
+    below = np.nextafter(plev.min(), 0.0)                                       # one ulp below min(plev)
+    inputs = []
+    for col, top, raises in [(64, below, True), (0, below, True), (64, plev.min(), False)]:
+        pa = ok.copy()
+        pa.reshape(4, 65)[0, col] = top
+        assert (pa.reshape(4, 65)[0] < plev.min()).sum() == (1 if raises else 0)
+        inputs.append((pa, raises))
+    return plev, delta, dsfc, psh, inputs
+
+
+def test_top_pressure_check_sees_a_single_column(F):
+    """The top-pressure check (functions.py:417-420) decided by ONE column: every target pressure >= min(plev) except the
+    top level of the last column of the block (the single live lane of the second wave), or of the first, one ulp below it
+    -> the reference's ValueError; exactly equal -> none (the comparison is strict).  The oracle must decide each input the
+    same way.  Then the file paths that carry the check (quad kernel, pair kernels, i_reinterp): all raise without -t,
+    all return with it."""
+    plev, delta, dsfc, psh, inputs = _single_column_top_inputs()
+    msg = 'ERA5 top pressure is lower than climate delta top pressure'
+    for sfc in [(dsfc, psh), (None, None)]:
+        for pa, raises in inputs:
+            if raises:
+                with pytest.raises(ValueError) as e:
+                    O.vert_interp_delta(delta, plev, pa, *sfc, ignore_top_pressure_error=False)
+                assert msg in str(e.value)
+                with pytest.raises(ValueError) as e:
+                    F.vert_interp_delta(delta, pa, *sfc, ignore_top_pressure_error=False, plev=plev)
+                assert msg in str(e.value)
+            else:
+                want = O.vert_interp_delta(delta, plev, pa, *sfc, ignore_top_pressure_error=False)
+                got = F.vert_interp_delta(delta, pa, *sfc, ignore_top_pressure_error=False, plev=plev)
+                np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-13)
+    from pgw4era5_amd import step_03_apply_to_era as s3
+    from pgw4era5_amd.device import default_context
+    ctx = default_context()
+    c = _case(8, 12, 27, seed=81)                                  # model top above the delta top
+    args = (c['era'], c['deltas'], c['delta_times'], c['plev'], c['target_dt'])
+    with pytest.raises(ValueError) as e:
+        O.pgw_for_era5_arrays(*args, ignore_top_pressure_error=False)
+    assert msg in str(e.value)
+    for opts, kw in [({}, {}), (dict(quad=0), {}), ({}, dict(i_reinterp=True))]:
+        old = {k: ctx.set_option(k, v) for k, v in opts.items()}
+        try:
+            with pytest.raises(ValueError) as e:
+                s3.pgw_for_era5_arrays(*args, ignore_top_pressure_error=False, **kw)
+            assert msg in str(e.value), (opts, kw)
+            out = s3.pgw_for_era5_arrays(*args, ignore_top_pressure_error=True, **kw)
+            assert np.isfinite(out['PS']).all() and out['n_iter'] >= 1, (opts, kw)
+        finally:
+            for k, v in old.items():
+                ctx.set_option(k, v)
+
+
 def test_time_lerp_vs_oracle(F):
     rng = np.random.default_rng(8)
     b, a = rng.normal(size=(3, 4, 5)), rng.normal(size=(3, 4, 5))
