@@ -64,7 +64,8 @@ enum pgw_kernel_id {
     PGW_K_THERMO_DELTA = 11, PGW_K_WIND_DELTA = 12, PGW_K_PHI_REF_HYBRID = 13, PGW_K_QUAD_DELTA = 14,
     PGW_K_BYTESWAP = 15, PGW_K_HARMONIC = 16, PGW_K_GAUSS_INTERP = 17, PGW_K_PS_LOOP_MULTI = 18,
     PGW_K_HYBRID_TO_PLEV = 19, PGW_K_MAGNUS_RH = 20, PGW_K_HUR_MERGE = 21,
-    PGW_K_COUNT = 22
+    PGW_K_CLIM_ACCUMULATE = 22, PGW_K_FIELD_SUB = 23, PGW_K_CLIM_READ = 24,
+    PGW_K_COUNT = 25
 };
 
 /* per-context options (pgw_set_option).  Defaults come from the environment variables named below, which are read
@@ -605,6 +606,28 @@ int pgw_magnus_rh(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol,
 int pgw_hur_merge_levels(pgw_ctx *ctx, int dtype_amon, int ntime, int nplev, int namon, long long ncol, const double *hur,
                          const void *amon, const int *copy_from, const int *e_above, const int *e_below,
                          const int *a_above, const int *a_below, double *out);
+
+/* s4 multi-year mean of the records of one calendar bin  step_01_extract_deltas/extract_climate_delta.sh:153-159, 217-219
+ * (`cdo ymonmean` / `cdo ydaymean` of the `-selyear` series; run a second time on the computed hur series, :235-238).
+ * x (nrec, inner): device array of dtype_in, the bin's records in time order, NaN = missing value.  Per cell i, in record
+ * order:  if (!isnan(x[r][i])) { sum += (double)x[r][i]; cnt += 1; }  - the sequential float64 sum, bit for bit.
+ *  first != 0: start from zero, sum / cnt are not read; otherwise continue from sum (inner) float64 and cnt (inner) int32.
+ *  last != 0: write mean[i] = (dtype_out)(sum / cnt), NaN where cnt == 0 (IEEE division), and NO state; otherwise write
+ *    sum and cnt back and leave mean alone.
+ *  With both set sum and cnt may be NULL and no accumulator exists in memory (a day-of-year bin of 30 years is one launch
+ *  over 30 records); a month bin of daily data goes through in chunks that carry the state.
+ *  dtype_out: dtype_in, or PGW_F64 for PGW_F32 input.  cdo's mean skips missing values the same way; parity with cdo's
+ *  own summation order is not pinned (kind U). */
+int pgw_clim_accumulate(pgw_ctx *ctx, int dtype_in, int dtype_out, int nrec, long long inner, const void *x, int first,
+                        int last, double *sum, int *cnt, void *mean);
+
+/* s5 `cdo sub` of two climatology files                  step_01_extract_deltas/extract_climate_delta.sh:244-249
+ * out[i] = (dtype)((double)a[i] - (double)b[i]) on n elements; NaN (missing) in either operand gives NaN. */
+int pgw_field_sub(pgw_ctx *ctx, int dtype, long long n, const void *a, const void *b, void *out);
+
+/* Diagnostic: the loads of pgw_clim_accumulate on x (nrec, inner) and nothing else, on the same grid, timed under
+ * PGW_K_CLIM_READ - what the card gives this access pattern (tools/clim_time.py); no reference counterpart. */
+int pgw_test_read_records(pgw_ctx *ctx, int dtype, int nrec, long long inner, const void *x);
 
 #ifdef __cplusplus
 }

@@ -768,6 +768,78 @@ extern "C" int pgw_hur_merge_levels(pgw_ctx *ctx, int dtype_amon, int ntime, int
     return PGW_OK;
 }
 
+// ------------------------------------------------------------------ step_01: climatologies and their difference
+// Shape of a launch over the records x (nrec, inner): cells per thread and the byte-offset type of x
+struct ClimForm { int vec; bool o32; };
+static ClimForm clim_form(pgw_ctx *ctx, int dtype_in, int nrec, long long inner, std::initializer_list<const void *> ptrs) {
+    const unsigned long long big = (unsigned long long)nrec * (unsigned long long)inner * elem_size(dtype_in);
+    return ClimForm{pick_vec(ctx, dtype_in, inner, ptrs), big < (1ull << 32) && !ctx->opt[PGW_OPT_FORCE_OFF64]};
+}
+
+extern "C" int pgw_clim_accumulate(pgw_ctx *ctx, int dtype_in, int dtype_out, int nrec, long long inner, const void *x,
+                                   int first, int last, double *sum, int *cnt, void *mean) {
+    CHECK_COMMON(ctx, dtype_in, nrec, inner);
+    NEED(ctx, dtype_out == dtype_in || dtype_out == PGW_F64, "dtype_out must be dtype_in or PGW_F64");
+    NEED(ctx, x, "null pointer");
+    const bool carried = !(first && last);
+    NEED(ctx, !carried || (sum && cnt), "sum and cnt are needed unless first and last are both set");
+    NEED(ctx, !last || mean, "mean is needed with last");
+    const ClimForm f = clim_form(ctx, dtype_in, nrec, inner, {x, carried ? sum : nullptr, carried ? cnt : nullptr, last ? mean : nullptr});
+    {
+        Prof pr(ctx, PGW_K_CLIM_ACCUMULATE);
+        auto launch = [&](auto ti_, auto to_) { with_offsets(f.o32, [&](auto o_) {
+            using TI = decltype(ti_); using TO = decltype(to_); using O = decltype(o_);
+            auto form = [&](auto v_) {
+                constexpr int V = decltype(v_)::value;
+                hipLaunchKernelGGL((k_clim_accumulate<TI, TO, V, O>), dim3(nblocks(inner / V, BLOCK)), dim3(BLOCK), 0, ctx->stream, nrec,
+                                   inner, (const TI *)x, first ? 1 : 0, last ? 1 : 0, sum, cnt, (TO *)mean);
+            };
+            if constexpr (sizeof(TI) == 8) { if (f.vec >= 2) form(int_c<2>()); else form(int_c<1>()); }
+            else with_vec(f.vec, form);
+        }); };
+        if (dtype_in == PGW_F64) launch(double(), double());
+        else if (dtype_out == PGW_F64) launch(float(), double());
+        else launch(float(), float());
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_test_read_records(pgw_ctx *ctx, int dtype, int nrec, long long inner, const void *x) {
+    CHECK_COMMON(ctx, dtype, nrec, inner);
+    NEED(ctx, x, "null pointer");
+    const ClimForm f = clim_form(ctx, dtype, nrec, inner, {x});
+    {
+        Prof pr(ctx, PGW_K_CLIM_READ);
+        with_type_vec(dtype, f.vec, [&](auto t_, auto v_) { with_offsets(f.o32, [&](auto o_) {
+            using T = decltype(t_); using O = decltype(o_);
+            constexpr int V = decltype(v_)::value;
+            hipLaunchKernelGGL((k_clim_read<T, V, O>), dim3(nblocks(inner / V, BLOCK)), dim3(BLOCK), 0, ctx->stream, nrec, inner,
+                               (const T *)x, (T *)nullptr);
+        }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_field_sub(pgw_ctx *ctx, int dtype, long long n, const void *a, const void *b, void *out) {
+    NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
+    NEED(ctx, n >= 1 && a && b && out, "bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int vec = pick_vec(ctx, dtype, n, {a, b, out});
+    const unsigned int nb = flat_grid(n / vec);
+    {
+        Prof pr(ctx, PGW_K_FIELD_SUB);
+        with_type_vec(dtype, vec, [&](auto t_, auto v_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_field_sub<T, decltype(v_)::value>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, (const T *)a,
+                               (const T *)b, (T *)out);
+        });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
 // ------------------------------------------------------------------ time lerp
 extern "C" int pgw_time_lerp(pgw_ctx *ctx, int dtype, long long n, const void *v_before, const void *v_after,
                              double x_hi, double x_new, void *out) {

@@ -987,6 +987,131 @@ __global__ __launch_bounds__(BLOCK) void k_hur_merge_levels(int ntime, int nplev
 }
 
 // =====================================================================================
+// s4  multi-year mean of one calendar bin      step_01_extract_deltas/extract_climate_delta.sh:153-159, 217-219, 235-238
+// (`cdo ymonmean` / `cdo ydaymean` after `-selyear`: the records of one month or one day of the year, missing values
+// skipped).  x (nrec, inner): the bin's records in time order, NaN = missing.  Per cell, in record order,
+//   if (!isnan(x[r][i])) { sum += (double)x[r][i]; cnt += 1; }
+// `first`: start from zero without reading sum / cnt; `last`: write mean = (TO)(sum / cnt) (NaN where cnt == 0, IEEE
+// division) and no state.  The order of the additions IS the definition (the sequential float64 sum, bit for bit): one
+// accumulator per cell, no tree.  What is unrolled is the LOADS: CLIM_UNROLL records of a cell group are in flight before
+// the first of them is added.  One thread per V cells (16 B per lane), byte offsets of type O into x as in ld_off.
+// =====================================================================================
+constexpr int CLIM_UNROLL = 8;
+template <typename T, int V, typename O>
+__device__ __forceinline__ void clim_ld(const T *__restrict__ base, O byte_off, T (&out)[V]) {
+    if constexpr (V == 1) out[0] = ld_off_nt<T, O>(base, byte_off);
+    else {
+        using VT = typename VecOf<T, V>::type;                 // V * sizeof(T) <= 16
+        const VT t = ld_off_nt<VT, O>(reinterpret_cast<const VT *>(base), byte_off);
+#pragma unroll
+        for (int v = 0; v < V; ++v) out[v] = t[v];
+    }
+}
+template <typename TI, typename TO, int V, typename O>
+__global__ __launch_bounds__(BLOCK) void k_clim_accumulate(int nrec, long long inner, const TI *__restrict__ x, int first,
+                                                           int last, double *__restrict__ sum, int *__restrict__ cnt,
+                                                           TO *__restrict__ mean) {
+    static_assert(V * sizeof(TI) <= 16, "one access per record and lane");
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= inner / V) return;                                // V | inner
+    const long long i = g * V;
+    double s[V];
+    Pack<int, V> c;
+    if (first) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) { s[v] = 0.0; c.v[v] = 0; }
+    } else {
+        loadv16<double, V>(sum + i, s);
+        c = *reinterpret_cast<const Pack<int, V> *>(cnt + i);
+    }
+    const O rowb = (O)((unsigned long long)inner * sizeof(TI));
+    O off = (O)((unsigned long long)i * sizeof(TI));
+    auto add = [&](const TI (&b)[V]) {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+            if (b[v] == b[v]) { s[v] += (double)b[v]; c.v[v] += 1; }
+    };
+    int r = 0;
+    for (; r + CLIM_UNROLL <= nrec; r += CLIM_UNROLL) {
+        TI b[CLIM_UNROLL][V];
+#pragma unroll
+        for (int u = 0; u < CLIM_UNROLL; ++u) clim_ld<TI, V, O>(x, off + (O)u * rowb, b[u]);
+        off += (O)CLIM_UNROLL * rowb;
+#pragma unroll
+        for (int u = 0; u < CLIM_UNROLL; ++u) add(b[u]);
+    }
+    for (; r < nrec; ++r) {
+        TI b[V];
+        clim_ld<TI, V, O>(x, off, b);
+        off += rowb;
+        add(b);
+    }
+    if (last) {
+        double m[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) m[v] = c.v[v] > 0 ? s[v] / (double)c.v[v] : __builtin_nan("");
+        storev16<TO, V>(mean + i, m);
+    } else {
+        storev16<double, V>(sum + i, s);
+        *reinterpret_cast<Pack<int, V> *>(cnt + i) = c;
+    }
+}
+
+// The loads of k_clim_accumulate and nothing else, on the same grid (diagnostic entry pgw_test_read_records: what the card
+// gives this access pattern, tools/clim_time.py).  `sink` is null in every call; it keeps the loads alive.
+template <typename TI, int V, typename O>
+__global__ __launch_bounds__(BLOCK) void k_clim_read(int nrec, long long inner, const TI *__restrict__ x, TI *__restrict__ sink) {
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= inner / V) return;
+    const O rowb = (O)((unsigned long long)inner * sizeof(TI));
+    O off = (O)((unsigned long long)(g * V) * sizeof(TI));
+    TI keep[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) keep[v] = 0;
+    auto take = [&](const TI (&b)[V]) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) keep[v] = b[v] > keep[v] ? b[v] : keep[v];
+    };
+    int r = 0;
+    for (; r + CLIM_UNROLL <= nrec; r += CLIM_UNROLL) {
+        TI b[CLIM_UNROLL][V];
+#pragma unroll
+        for (int u = 0; u < CLIM_UNROLL; ++u) clim_ld<TI, V, O>(x, off + (O)u * rowb, b[u]);
+        off += (O)CLIM_UNROLL * rowb;
+#pragma unroll
+        for (int u = 0; u < CLIM_UNROLL; ++u) take(b[u]);
+    }
+    for (; r < nrec; ++r) {
+        TI b[V];
+        clim_ld<TI, V, O>(x, off, b);
+        off += rowb;
+        take(b);
+    }
+    if (sink) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) sink[g * V + v] = keep[v];
+    }
+}
+
+// =====================================================================================
+// s5  difference of two climatologies (`cdo sub`)              step_01_extract_deltas/extract_climate_delta.sh:244-249
+// out = (T)((double)a - (double)b) on a flat grid; NaN (missing) in either operand gives NaN.
+// =====================================================================================
+template <typename T, int V>
+__global__ __launch_bounds__(BLOCK) void k_field_sub(long long n, const T *__restrict__ a, const T *__restrict__ b,
+                                                     T *__restrict__ out) {
+    const long long stride = (long long)gridDim.x * BLOCK;
+    for (long long g = (long long)blockIdx.x * BLOCK + threadIdx.x; g * V < n; g += stride) {
+        double x[V], y[V], r[V];
+        loadv_nt<T, V>(a + g * V, x);
+        loadv_nt<T, V>(b + g * V, y);
+#pragma unroll
+        for (int v = 0; v < V; ++v) r[v] = x[v] - y[v];
+        storev_nt<T, V>(out + g * V, r);
+    }
+}
+
+// =====================================================================================
 // a7  time lerp of load_delta                                  functions.py:288-292
 // =====================================================================================
 // TB / TA / TO: storage types of the two records and of the result.  REF (settings.function_dtype_flow = 'reference'):

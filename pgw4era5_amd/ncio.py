@@ -158,6 +158,49 @@ def decode_cf_time(values, units, calendar='standard'):
     return np.array(out, dtype='datetime64[s]').reshape(np.shape(values))
 
 
+_CUM366 = np.array([0, 31, 60, 91, 121, 152, 182, 213, 244, 274, 305, 335, 366])
+
+
+def cf_year_month_day(values, units, calendar='standard'):
+    """CF 'X since Y' numbers -> integer (year, month, day) arrays IN THE FILE'S OWN CALENDAR (what `cdo ymonmean` /
+    `ydaymean` / `selyear` bin by): standard / gregorian / proleptic_gregorian (the proleptic Gregorian calendar of
+    numpy), noleap / 365_day, all_leap / 366_day, 360_day.  Nothing is mapped or clipped: 360_day yields Feb 29 and
+    Feb 30, all_leap a Feb 29 in every year.  Times are rounded to whole seconds first, like decode_cf_time."""
+    m = _UNITS.match(units)
+    if not m:
+        raise ValueError('cannot parse time units %r' % units)
+    unit = m.group(1).lower()
+    if unit not in _SECONDS:
+        raise ValueError('unsupported time unit %r' % unit)
+    y, mo, d = int(m.group(2)), int(m.group(3)), int(m.group(4))
+    hh, mi = int(m.group(5) or 0), int(m.group(6) or 0)
+    ss = float(m.group(7) or 0)
+    vals = np.asarray(values, dtype=np.float64)
+    secs = np.round(vals * _SECONDS[unit]).astype(np.int64)
+    cal = (calendar or 'standard').lower()
+    if cal in ('standard', 'gregorian', 'proleptic_gregorian'):
+        t = np.datetime64('%04d-%02d-%02dT%02d:%02d:%02d' % (y, mo, d, hh, mi, int(ss)), 's') + secs.astype('timedelta64[s]')
+        t_y, t_m, t_d = t.astype('datetime64[Y]'), t.astype('datetime64[M]'), t.astype('datetime64[D]')
+        year = t_y.astype(np.int64) + 1970
+        month = (t_m - t_y.astype('datetime64[M]')).astype(np.int64) + 1
+        day = (t_d - t_m.astype('datetime64[D]')).astype(np.int64) + 1
+        return year, month, day
+    base_secs = hh * 3600 + mi * 60 + int(round(ss))
+    if cal in ('noleap', '365_day', 'all_leap', '366_day'):
+        cum = _CUM365 if cal in ('noleap', '365_day') else _CUM366
+        ylen = int(cum[-1])
+        days = (y * ylen + int(cum[mo - 1]) + (d - 1)) + (base_secs + secs) // 86400
+        year, doy = days // ylen, days % ylen
+        month = np.searchsorted(cum, doy, side='right').astype(np.int64)
+        day = doy - cum[month - 1] + 1
+        return year, month, day
+    if cal == '360_day':
+        days = (y * 360 + (mo - 1) * 30 + (d - 1)) + (base_secs + secs) // 86400
+        year, doy = days // 360, days % 360
+        return year, doy // 30 + 1, doy % 30 + 1
+    raise ValueError('unsupported calendar %r' % calendar)
+
+
 # ------------------------------------------------------------------------------ CF mask and scale
 def _float_dtype_for(dtype, has_offset):
     """xarray.coding.variables._choose_float_dtype (2022.12): the dtype packed / masked data decode to."""

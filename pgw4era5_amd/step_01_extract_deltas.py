@@ -1,5 +1,5 @@
 """
-step_01: the two array programs of the reference's step_01_extract_deltas directory on MI355X.
+step_01: the array programs of the reference's step_01_extract_deltas directory on MI355X.
 
 * `CFday_interp_to_plev.py:86-154`: daily CMIP6 `CFday` fields on the GCM's hybrid model levels (`ap`, `b`, `ps` in the
   file) interpolated to a fixed list of pressure levels -> `interp_to_plev` / `interp_file` / sub-command `interp_to_plev`.
@@ -11,7 +11,17 @@ step_01: the two array programs of the reference's step_01_extract_deltas direct
   formula of the reference's functions.py), then the coarse `Amon` hur carried onto the finer `Emon` levels with weights
   taken from the computed hur (`merge_hur_levels`) -> `hus_to_hur_file` / sub-command `hus_to_hur`.
 
-The shell templates of step_01 (`cdo`, `wget`) are site scripts and stay out of scope.
+* `extract_climate_delta.sh:153-159, 217-219, 235-238, 244-249`: the array program inside the shell template - `cdo -cat`,
+  `-selyear`, `ymonmean` / `ydaymean` of the historical and of the scenario series and `cdo sub` of the two ->
+  `calendar_bins` / `climatology` / `climatology_files` / `delta_files`, sub-commands `climatology` and `delta`.  The mean
+  of a bin is the sequential float64 sum of its records in time order, missing values skipped, divided by their count
+  (`pgw_clim_accumulate`); the difference is `pgw_field_sub`.  `cdo` itself is not available to this project and the
+  reference has no program text for this step: the definition of correct is that statement plus cdo's documented
+  conventions (date of the last contributing record, records sorted by month / day key); bit parity with cdo is unpinned
+  (kind U).
+
+The rest of the shell templates of step_01 (site paths, `sellonlatbox`, the Emon model-top merge, `wget`) are site scripts
+and stay out of scope.
 
 Array kinds as in `functions.py`: numpy, `ncio.Field` (labels re-wrapped) or `DeviceArray` in, the same kind out.
 Files are NetCDF-3 through `ncio` like everywhere in this package.
@@ -124,9 +134,12 @@ def load_target_plev(path):
 
 def records_per_block(ctx, nrec, S, N, ncol, s_in, s_out, max_records=None):
     """Time records per launch: what fits into 80 % of the card's free memory (`pgw_mem_info`), at most `max_records`."""
-    per = (S * s_in + s_in + N * s_out) * ncol
+    return _fit_records(ctx, nrec, (S * s_in + s_in + N * s_out) * ncol, max_records)
+
+
+def _fit_records(ctx, nrec, bytes_per_record, max_records=None):
     free, _ = ctx.mem_info()
-    n = max(1, min(int(nrec), int(0.8 * free) // max(per, 1)))
+    n = max(1, min(int(nrec), int(0.8 * free) // max(bytes_per_record, 1)))
     if max_records:
         n = max(1, min(n, int(max_records)))
     return n
@@ -322,10 +335,314 @@ def hus_to_hur_file(hus_file, ta_file, hur_file, amon_hur_file):
     return hur_file
 
 
+# ------------------------------------------------------------------------------- climatologies and climate deltas
+CLIM_MODES = ('ymonmean', 'ydaymean')
+
+
+def calendar_bins(time_values, units, calendar, mode, years=None):
+    """The bins of `cdo ymonmean` (key = month) / `cdo ydaymean` (key = month * 100 + day; Feb 29 is a bin of its own with
+    fewer samples, which is why functions.load_delta drops a leap day) for the raw time coordinate of a file, in the
+    file's own calendar (`ncio.cf_year_month_day`).  years=(y0, y1): only records with y0 <= year <= y1 (`cdo selyear`).
+    Returns (keys, bin_of_record): the keys that occur, ascending, and per record the index of its key, -1 for records
+    outside `years`."""
+    if mode not in CLIM_MODES:
+        raise ValueError('mode must be one of %s, got %r' % (CLIM_MODES, mode))
+    year, month, day = ncio.cf_year_month_day(np.asarray(time_values).reshape(-1), units, calendar)
+    key = month if mode == 'ymonmean' else month * 100 + day
+    use = np.ones(key.shape, dtype=bool)
+    if years is not None:
+        y0, y1 = int(years[0]), int(years[1])
+        use = (year >= y0) & (year <= y1)
+    keys = np.unique(key[use]).astype(np.int64)
+    bins = np.where(use, np.searchsorted(keys, key), -1).astype(np.int64) if len(keys) else np.full(key.shape, -1, dtype=np.int64)
+    return keys, bins
+
+
+def _clim_dtypes(in_dtype, out_dtype):
+    dt = _F32 if np.dtype(in_dtype) == _F32 else _F64
+    odt = dt if out_dtype is None else np.dtype(out_dtype)
+    if odt not in (_F32, _F64) or (odt == _F32 and dt != _F32):
+        raise ValueError('out_dtype: the input dtype, or float64 for float32 input')
+    return dt, odt
+
+
+def _launch_clim(ctx, d_x, first, last, d_sum, d_cnt, d_mean, odt):
+    """pgw_clim_accumulate over the records d_x (nrec, ...)."""
+    inner = int(np.prod(d_x.shape[1:], dtype=np.int64))
+    ctx._check(ctx.lib.pgw_clim_accumulate(ctx.handle, dtype_tag(d_x.dtype), dtype_tag(odt), d_x.shape[0], inner, d_x.ptr,
+                                           1 if first else 0, 1 if last else 0, d_sum.ptr if d_sum is not None else None,
+                                           d_cnt.ptr if d_cnt is not None else None, d_mean.ptr if d_mean is not None else None))
+
+
+class _BinMean:
+    """The mean of one bin after another through one chunk buffer of `nb` records: `fill(d_chunk, records)` puts the given
+    records (indices into the series, time order) into the leading slots of the buffer, or returns another device array
+    that already holds them.  A bin that fits the buffer is ONE launch with `first` and `last` both set and no accumulator
+    in memory; a longer one goes through in chunks that carry sum / cnt on the device."""
+
+    def __init__(self, ctx, rec_shape, dt, odt, nb):
+        self.ctx, self.rec_shape, self.dt, self.odt, self.nb = ctx, tuple(rec_shape), dt, odt, int(nb)
+        self.chunk = ctx.empty((self.nb,) + self.rec_shape, dt)
+        self.sum = self.cnt = None
+
+    def run(self, records, fill, d_mean):
+        n = len(records)
+        for r0 in range(0, n, self.nb):
+            part = records[r0:r0 + self.nb]
+            first, last = r0 == 0, r0 + len(part) == n
+            if not (first and last) and self.sum is None:
+                self.sum, self.cnt = self.ctx.empty(self.rec_shape, _F64), self.ctx.empty(self.rec_shape, np.int32)
+            d_x = fill(self.chunk, part)
+            if d_x is None:
+                d_x = self.chunk if len(part) == self.nb else DeviceArray(self.ctx, (len(part),) + self.rec_shape, self.dt,
+                                                                         ptr=self.chunk.ptr, owner=self.chunk)
+            _launch_clim(self.ctx, d_x, first, last, None if (first and last) else self.sum,
+                         None if (first and last) else self.cnt, d_mean if last else None, self.odt)
+
+
+def _records_of_bins(bin_of_record, nbin):
+    b = np.asarray(bin_of_record).reshape(-1)
+    if len(b) and (b.max() >= nbin or b.min() < -1):
+        raise ValueError('bin_of_record must lie in [-1, nbin)')
+    return [np.nonzero(b == k)[0] for k in range(int(nbin))]
+
+
+def climatology(x, bin_of_record, nbin, out_dtype=None, max_records=None):
+    """`cdo ymonmean` / `ydaymean` on arrays: x (time, ...) -> (nbin, ...), record k of the result the mean over the records
+    r with bin_of_record[r] == k (`calendar_bins`), in time order, NaN = missing value skipped, float64 accumulation;
+    cells without a sample (and bins without a record) are NaN.  Records with bin -1 are not read.
+    out_dtype: the input's (default), or float64 for float32 input.  max_records caps the records per launch (a longer
+    bin carries its sum on the device; the results do not depend on it).
+    numpy, `ncio.Field` (labels re-wrapped, without the time coordinate) or `DeviceArray` in, the same kind out."""
+    rx = _raw(x)
+    if len(rx.shape) < 1 or rx.shape[0] != len(np.asarray(bin_of_record).reshape(-1)):
+        raise ValueError('bin_of_record must have one entry per record of x')
+    nbin = int(nbin)
+    if nbin < 1:
+        raise ValueError('nbin must be positive')
+    dt, odt = _clim_dtypes(rx.dtype, out_dtype)
+    rec_shape = tuple(rx.shape[1:])
+    inner = int(np.prod(rec_shape, dtype=np.int64))
+    if inner < 1:
+        raise ValueError('empty records')
+    recs = _records_of_bins(bin_of_record, nbin)
+    ctx = default_context()
+    on_device = isinstance(rx, DeviceArray)
+    if on_device and rx.dtype != dt:
+        raise TypeError('device arrays must be float32 or float64, got %s' % rx.dtype)
+    out = ctx.empty((nbin,) + rec_shape, odt)
+    longest = max(len(r) for r in recs)
+    if longest:
+        nb = _fit_records(ctx, longest, inner * dt.itemsize, max_records)
+        acc = _BinMean(ctx, rec_shape, dt, odt, nb)
+        rec_bytes = inner * dt.itemsize
+        host = None if on_device else np.empty((nb,) + rec_shape, dtype=dt)
+
+        def fill(d_chunk, part):
+            if on_device:
+                if len(part) == 1 or np.all(np.diff(part) == 1):  # consecutive records: read where they are
+                    return DeviceArray(ctx, (len(part),) + rec_shape, dt, ptr=rx.ptr + int(part[0]) * rec_bytes, owner=rx)
+                for i, r in enumerate(part):
+                    ctx._check(ctx.lib.pgw_memcpy_d2d(ctx.handle, d_chunk.ptr + i * rec_bytes, rx.ptr + int(r) * rec_bytes, rec_bytes))
+                return None
+            for i, r in enumerate(part):
+                host[i] = rx[r]
+            DeviceArray(ctx, (len(part),) + rec_shape, dt, ptr=d_chunk.ptr, owner=d_chunk).copy_from(host[:len(part)])
+            return None
+    nan_rec = None
+    for k, part in enumerate(recs):
+        if len(part):
+            acc.run(part, fill, out.slab(k))
+        else:
+            nan_rec = np.full(rec_shape, np.nan, dtype=odt) if nan_rec is None else nan_rec
+            out.slab(k).copy_from(nan_rec)
+    if on_device:
+        return out
+    res = out.numpy()
+    if _is_labelled(x):
+        dims = tuple(x.dims)
+        coords = {d: v for d, v in getattr(x, 'coords', {}).items() if d in dims[1:]}
+        return ncio.Field(res, dims, coords, dict(getattr(x, 'attrs', {})), getattr(x, 'name', None))
+    return res
+
+
+_FILL_KEYS = ('_FillValue', 'missing_value')
+_PACK_KEYS = ('scale_factor', 'add_offset')
+
+
+def _open_series(path, var_name):
+    """(everything of the file but the variable's data, taken raw; a RecordReader of the variable)."""
+    ds = ncio.open_dataset(path, decode_times=False, skip=(var_name,))
+    if var_name not in ds:
+        raise KeyError(var_name)
+    return ds, ncio.RecordReader(path, var_name, decode_times=False)
+
+
+def _time_axis(ds, reader, path):
+    tdim = reader.dims[0]
+    if tdim not in ds or 'units' not in ds[tdim].attrs:
+        raise ValueError('%s: the first dimension %r has no coordinate with time units' % (path, tdim))
+    t = ds[tdim]
+    return tdim, np.asarray(t.values).reshape(-1), str(t.attrs['units']), str(t.attrs.get('calendar', 'standard'))
+
+
+def _encoded(values, raw_attrs):
+    """The decoded array as it goes into the file: NaN -> the input's `_FillValue` / `missing_value` when it has one
+    (`ncio.to_netcdf` writes arrays as they are); the fill attributes in the array's dtype, packing attributes dropped
+    (the values are the decoded ones)."""
+    attrs = {k: v for k, v in raw_attrs.items() if k not in _PACK_KEYS}
+    fill = None
+    for k in _FILL_KEYS:
+        if k in attrs:
+            f = np.asarray(attrs[k]).reshape(-1)[0].astype(values.dtype)
+            attrs[k] = f
+            if fill is None and f == f:
+                fill = f
+    if fill is not None:
+        values[np.isnan(values)] = fill
+    return values, attrs
+
+
+def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=None, out_dtype=None):
+    """extract_climate_delta.sh:194-219 without its `sellonlatbox`: `cdo -cat` of the files `inputs` (one path, or a list in
+    time order - CMIP series come in multi-year pieces), `-selyear` (years=(y0, y1)), `ymonmean` / `ydaymean` (mode) of
+    `var_name` -> `out_path`.
+    The files must share the time units, the calendar and the record shape (ValueError).  Bin by bin (`calendar_bins`) the
+    records are read in time order (`ncio.RecordReader`), uploaded in chunks of what fits into 80 % of the card's free
+    memory, at most `max_records` (the results do not depend on it), and accumulated; records outside `years` are never
+    read.  Output: the variable on (time = number of bins, ...) with the input's attributes in its decoded dtype
+    (out_dtype='float64' widens a float32 series), every variable without the time dimension carried over, `time` = the raw
+    time value of the LAST contributing record of each bin (cdo's convention for ymon* / yday*) with the input's units /
+    calendar, records in key order.  Cells without a sample hold the input's `_FillValue` / `missing_value` (NaN if it has
+    none).  NetCDF-3 in and out like everywhere in this package; the result loads through `functions.load_delta`."""
+    if mode not in CLIM_MODES:
+        raise ValueError('mode must be one of %s, got %r' % (CLIM_MODES, mode))
+    paths = [inputs] if isinstance(inputs, (str, os.PathLike)) else list(inputs)
+    if not paths:
+        raise ValueError('no input file')
+    opened = []
+    try:
+        for p in paths:
+            opened.append(_open_series(p, var_name))
+        ds0, r0 = opened[0]
+        tdim, _, units, cal = _time_axis(ds0, r0, paths[0])
+        times, where = [], []
+        for k, (ds, rd) in enumerate(opened):
+            td, t, u, c = _time_axis(ds, rd, paths[k])
+            if (td, u, c.lower()) != (tdim, units, cal.lower()):
+                raise ValueError('%s: time axis %r (%s, %s) differs from %r (%s, %s) of %s' % (paths[k], td, u, c, tdim, units, cal, paths[0]))
+            if rd.rec_shape != r0.rec_shape or rd.dims != r0.dims or rd.dtype != r0.dtype:
+                raise ValueError('%s: records %s %s %s differ from %s %s %s of %s'
+                                 % (paths[k], rd.dims, rd.rec_shape, rd.dtype, r0.dims, r0.rec_shape, r0.dtype, paths[0]))
+            if len(t) != rd.nrec:
+                raise ValueError('%s: %d time values for %d records' % (paths[k], len(t), rd.nrec))
+            times.append(t)
+            where += [(k, i) for i in range(rd.nrec)]
+        times = np.concatenate(times)
+        keys, bins = calendar_bins(times, units, cal, mode, years)
+        if not len(keys):
+            raise ValueError('no record lies within the years %s' % (years,))
+        dt, odt = _clim_dtypes(r0.dtype, out_dtype)
+        rec_shape = r0.rec_shape
+        inner = int(np.prod(rec_shape, dtype=np.int64))
+        recs = _records_of_bins(bins, len(keys))
+        ctx = default_context()
+        nb = _fit_records(ctx, max(len(r) for r in recs), inner * dt.itemsize, max_records)
+        acc = _BinMean(ctx, rec_shape, dt, odt, nb)
+        host = np.empty((nb,) + rec_shape, dtype=dt)
+        d_mean = ctx.empty(rec_shape, odt)
+        result = np.empty((len(keys),) + rec_shape, dtype=odt)
+
+        def fill(d_chunk, part):
+            for i, r in enumerate(part):
+                k, j = where[r]
+                host[i] = opened[k][1].read_record(j)
+            DeviceArray(ctx, (len(part),) + rec_shape, dt, ptr=d_chunk.ptr, owner=d_chunk).copy_from(host[:len(part)])
+
+        for k, part in enumerate(recs):
+            acc.run(part, fill, d_mean)
+            result[k] = d_mean.numpy()
+        t_out = np.array([times[part[-1]] for part in recs], dtype=times.dtype)
+    finally:
+        for _, rd in opened:
+            rd.close()
+    result, vattrs = _encoded(result, ds0[var_name].attrs)
+    out = ncio.Dataset(attrs=dict(ds0.attrs), record_dim=ds0.record_dim)
+    coords = {d: ds0[d].values for d in r0.dims[1:] if d in ds0}
+    coords[tdim] = t_out
+    for name, f in ds0.variables.items():
+        if name == var_name:
+            out[name] = ncio.Field(result, r0.dims, coords, vattrs)
+        elif name == tdim:
+            out[name] = ncio.Field(t_out, (tdim,), {tdim: t_out}, {k: v for k, v in f.attrs.items() if k != 'bounds'})
+        elif tdim not in f.dims:
+            out[name] = ncio.Field(f.values, f.dims, f.coords, dict(f.attrs))
+    ncio.to_netcdf(out, out_path)
+    return out_path
+
+
+def _month_day_keys(ds, reader, path):
+    tdim, t, units, cal = _time_axis(ds, reader, path)
+    _, month, day = ncio.cf_year_month_day(t, units, cal)
+    daily = len(np.unique(month)) < len(month)                    # several records per month: a day-of-year file
+    return month, day, daily
+
+
+def delta_files(scen_path, hist_path, out_path, var_name):
+    """extract_climate_delta.sh:244-249, `cdo sub scenario historical delta`: the difference of two climatology files
+    (`pgw_field_sub`, NaN / missing in either gives missing).  Both must have the same number of records, the same record
+    shape and dtype and the same bin keys - the months of their time axes, and the days too in a day-of-year file -
+    (ValueError).  Metadata and the time axis come from the scenario file, as cdo takes them from its first operand."""
+    ds_s, rs = _open_series(scen_path, var_name)
+    ds_h, rh = _open_series(hist_path, var_name)
+    try:
+        if rs.nrec != rh.nrec or rs.rec_shape != rh.rec_shape or rs.dtype != rh.dtype:
+            raise ValueError('%s (%d records of %s %s) and %s (%d records of %s %s) do not match'
+                             % (scen_path, rs.nrec, rs.rec_shape, rs.dtype, hist_path, rh.nrec, rh.rec_shape, rh.dtype))
+        ms, dys, daily_s = _month_day_keys(ds_s, rs, scen_path)
+        mh, dyh, daily_h = _month_day_keys(ds_h, rh, hist_path)
+        if not np.array_equal(ms, mh) or daily_s != daily_h or (daily_s and not np.array_equal(dys, dyh)):
+            raise ValueError('%s and %s do not hold the same months / days of the year' % (scen_path, hist_path))
+        dt, _ = _clim_dtypes(rs.dtype, None)
+        nrec, rec_shape = rs.nrec, rs.rec_shape
+        inner = int(np.prod(rec_shape, dtype=np.int64))
+        ctx = default_context()
+        nb = _fit_records(ctx, nrec, 3 * inner * dt.itemsize)
+        d_a, d_b, d_o = (ctx.empty((nb,) + rec_shape, dt) for _ in range(3))
+        h_a, h_b = np.empty((nb,) + rec_shape, dtype=dt), np.empty((nb,) + rec_shape, dtype=dt)
+        result = np.empty((nrec,) + rec_shape, dtype=dt)
+        for r0 in range(0, nrec, nb):
+            n = min(nb, nrec - r0)
+            for i in range(n):
+                h_a[i], h_b[i] = rs.read_record(r0 + i), rh.read_record(r0 + i)
+            a, b, o = (DeviceArray(ctx, (n,) + rec_shape, dt, ptr=d.ptr, owner=d) for d in (d_a, d_b, d_o))
+            a.copy_from(h_a[:n]); b.copy_from(h_b[:n])
+            ctx._check(ctx.lib.pgw_field_sub(ctx.handle, dtype_tag(dt), n * inner, a.ptr, b.ptr, o.ptr))
+            result[r0:r0 + n] = o.numpy()
+    finally:
+        rs.close(); rh.close()
+    result, vattrs = _encoded(result, ds_s[var_name].attrs)
+    out = ncio.Dataset(attrs=dict(ds_s.attrs), record_dim=ds_s.record_dim)
+    for name, f in ds_s.variables.items():
+        out[name] = ncio.Field(result, rs.dims, f.coords, vattrs) if name == var_name else ncio.Field(f.values, f.dims, f.coords, dict(f.attrs))
+    ncio.to_netcdf(out, out_path)
+    return out_path
+
+
+def _parse_years(text):
+    if text is None:
+        return None
+    parts = text.replace(',', '/').split('/')
+    if len(parts) != 2:
+        raise ValueError('years must be given as FIRST/LAST, e.g. 1985/2014')
+    return int(parts[0]), int(parts[1])
+
+
 # ------------------------------------------------------------------------------- command line
 def build_parser():
     p = argparse.ArgumentParser(prog='python -m pgw4era5_amd.step_01_extract_deltas',
-                                description='PGW for ERA5 step_01 on MI355X: CFday model levels to pressure levels, Emon hus to hur.')
+                                description='PGW for ERA5 step_01 on MI355X: CFday model levels to pressure levels, Emon hus to hur, '
+                                            'climatologies and climate deltas.')
     sub = p.add_subparsers(dest='command', required=True)
     a = sub.add_parser('interp_to_plev', help='Interpolate CFday output to pressure levels (CFday_interp_to_plev.py)')
     a.add_argument('-i', '--input', type=str, required=True,
@@ -341,6 +658,20 @@ def build_parser():
     h.add_argument('ta_file', type=str)
     h.add_argument('hur_file', type=str)
     h.add_argument('-a', '--amon_hur_file', type=str, required=True, help='Amon relative humidity file')
+    c = sub.add_parser('climatology', help='Multi-year monthly / day-of-year mean of a series (cdo -cat, -selyear, ymonmean / ydaymean)')
+    c.add_argument('-i', '--input', type=str, required=True, nargs='+',
+                   help='NetCDF-3 input files in time order; {} is replaced by the variable name')
+    c.add_argument('-o', '--output', type=str, required=True, help='output file; {} is replaced by the variable name')
+    c.add_argument('-v', '--var_names', type=str, required=True, help='comma separated variable names, e.g. ta,hur,ua,va')
+    c.add_argument('-m', '--mode', type=str, required=True, choices=list(CLIM_MODES))
+    c.add_argument('-y', '--years', type=str, default=None, help='first and last year to use, e.g. 1985/2014 (cdo selyear)')
+    c.add_argument('--max_records', type=int, default=None, help='at most this many time records per launch')
+    c.add_argument('--out_dtype', type=str, default=None, choices=['float32', 'float64'])
+    d = sub.add_parser('delta', help='Scenario climatology minus historical climatology (cdo sub)')
+    d.add_argument('scen_file', type=str, help='{} is replaced by the variable name (also in the other two paths)')
+    d.add_argument('hist_file', type=str)
+    d.add_argument('delta_file', type=str)
+    d.add_argument('-v', '--var_names', type=str, required=True, help='comma separated variable names')
     return p
 
 
@@ -356,8 +687,23 @@ def main(argv=None):
             print('Process input file: \n{}\nto output file: \n{}'.format(inp, out))
             done.append(interp_file(inp, out, name, args.target_p, extrapolate=args.extrapolate,
                                     max_records=args.max_records, out_dtype=args.out_dtype))
-    else:
+    elif args.command == 'hus_to_hur':
         done.append(hus_to_hur_file(args.hus_file, args.ta_file, args.hur_file, args.amon_hur_file))
+    elif args.command == 'climatology':
+        names = args.var_names.split(',')
+        if len(names) > 1 and ('{}' not in args.output or not all('{}' in i for i in args.input)):
+            raise ValueError('several variables need {} in the input and the output paths')
+        years = _parse_years(args.years)
+        for name in names:
+            done.append(climatology_files([i.replace('{}', name) for i in args.input], args.output.replace('{}', name), name,
+                                          args.mode, years=years, max_records=args.max_records, out_dtype=args.out_dtype))
+    else:
+        names = args.var_names.split(',')
+        paths = (args.scen_file, args.hist_file, args.delta_file)
+        if len(names) > 1 and not all('{}' in p for p in paths):
+            raise ValueError('several variables need {} in all three paths')
+        for name in names:
+            done.append(delta_files(*[p.replace('{}', name) for p in paths], name))
     return done
 
 
