@@ -1221,6 +1221,8 @@ __device__ __forceinline__ void stage_plev(const double (&tab)[MAX_PLEV], double
 // helper tried there (struct or reference results, table or scalars passed) changed the instruction counts of the tuned
 // kernels' per-column preamble.  They follow the same statement, `fill` cleared included.  k_delta_pair keeps its
 // source minimum too, for the same reason; k_delta_quad takes source_min (same opcode counts and registers).
+// tests/test_surface_rule_edges.py holds the three texts together: ps_hist on a level, one ulp beside it, above all levels,
+// on min(plev) and NaN, and NaN deltas below the ground, through every kernel that carries the rule.
 struct SfcLevel { int ksfc; bool fill; };
 template <typename P>
 __device__ __forceinline__ SfcLevel sfc_level(const PlevTable &pt, const P &p, double pshv, DevStatus *st, long long col) {
