@@ -10,118 +10,27 @@ Accepted array kinds, everywhere a field is expected:
   * `pgw4era5_amd.device.DeviceArray`      -> used in place, result stays on the device
   * labelled arrays (`pgw4era5_amd.ncio.Field`, or any object with `.values`, `.dims`,
     `.coords`)                             -> like ndarray, result re-wrapped with the labels
-4-D fields are C-order `(time, level, lat, lon)`.
+(`operands.py` holds these rules.)  4-D fields are C-order `(time, level, lat, lon)`.
 """
 import ctypes as C
-import datetime as _dt
+import datetime
 import os
 
 import numpy as np
 
-from . import _lib
+from ._lib import _dp, _ip
 from .constants import CON_G, CON_RD, CON_MW_MD   # noqa: F401  (re-exported like the reference)
 from .device import DeviceArray, default_context, dtype_tag, ptr
+from .operands import (F64, aligned, check_extrapolate, common_dtype, dev, dev_own, fit, float_dtype, is_labelled, out_like,
+                       raw, shape4)
 from .settings import (                      # noqa: F401
     i_debug, i_use_xesmf_regridding, file_name_bases,
     TIME_ERA, LEV_ERA, HLEV_ERA, LON_ERA, LAT_ERA,
     TIME_GCM, PLEV_GCM, LON_GCM, LAT_GCM, LON_GCM_OCEAN, LAT_GCM_OCEAN,
 )
 
-_dp = C.POINTER(C.c_double)
-_ip = C.POINTER(C.c_int)
-
-
-# ------------------------------------------------------------------------------- helpers
-def _is_labelled(x):
-    return hasattr(x, 'values') and hasattr(x, 'dims') and not isinstance(x, DeviceArray)
-
-
-def _raw(x):
-    """ndarray / DeviceArray behind any accepted input."""
-    if isinstance(x, DeviceArray):
-        return x
-    if _is_labelled(x):
-        return np.asarray(x.values)
-    return np.asarray(x)
-
-
-def _common_dtype(*xs):
-    for x in xs:
-        if x is None:
-            continue
-        r = _raw(x)
-        if r.dtype == np.float64:
-            return np.dtype('float64')
-        if r.dtype not in (np.dtype('float32'),):
-            if not isinstance(r, DeviceArray) and r.dtype.kind in 'iu':
-                return np.dtype('float64')
-    return np.dtype('float32')
-
-
-def _dev(ctx, x, dtype, shape=None):
-    """Device array of `x` in `dtype` (no copy if it already is one of that dtype)."""
-    if x is None:
-        return None
-    r = _raw(x)
-    if isinstance(r, DeviceArray):
-        if r.dtype != dtype:
-            raise TypeError('device arrays of mixed dtype: got %s, expected %s' % (r.dtype, dtype))
-        return r if shape is None else r.view(shape)
-    a = np.ascontiguousarray(r, dtype=dtype)
-    if shape is not None:
-        a = a.reshape(shape)
-    return ctx.to_device(a, dtype)
-
-
-def _out(ctx, dev, like):
-    """Return `dev` in the kind of `like`: DeviceArray as it is; a labelled array re-wrapped with `like`'s dimension
-    names and coordinates - `ncio.Field.like(data)`, or `.copy(data=...)` of an `xarray.DataArray` (and anything else
-    that offers it), so that the reference's own next line, e.g. `.transpose(TIME_ERA, LEV_ERA, LAT_ERA, LON_ERA)`
-    (step_03_apply_to_era.py:91-94), keeps working; a plain ndarray otherwise."""
-    if isinstance(like, DeviceArray):
-        return dev
-    host = dev.numpy()
-    if _is_labelled(like):
-        if hasattr(like, 'like'):
-            return like.like(host)
-        if hasattr(like, 'copy') and tuple(getattr(like, 'shape', ())) == host.shape:
-            try:
-                return like.copy(data=host)
-            except TypeError:
-                pass
-    return host
-
-
-def _aligned(x, like):
-    """A labelled operand whose dimensions are those of `like` in another order is transposed to `like`'s order (xarray
-    aligns operands by dimension NAME; the kernels take positions).  Anything else passes through."""
-    if x is None or not (_is_labelled(x) and _is_labelled(like)):
-        return x
-    dx, dl = tuple(x.dims), tuple(like.dims)
-    if dx != dl and sorted(dx) == sorted(dl) and hasattr(x, 'transpose'):
-        return x.transpose(*dl)
-    return x
-
-
-def _fit(x, shape, name):
-    """Operand `x` for a kernel that indexes it as `shape` (the leading operand's): a host array is broadcast to it like the
-    reference's numpy arithmetic would (ValueError when it cannot be), a DeviceArray must have exactly that shape.  Called
-    before anything is uploaded or launched: a shorter operand would otherwise be read past its end."""
-    shape = tuple(int(n) for n in shape)
-    r = _raw(x)
-    if isinstance(r, DeviceArray):
-        if r.shape != shape:
-            raise ValueError('%s: device array of shape %s, expected %s' % (name, r.shape, shape))
-        return r
-    try:
-        return np.broadcast_to(r, shape)
-    except ValueError:
-        raise ValueError('%s: shape %s does not broadcast to %s' % (name, r.shape, shape)) from None
-
 
 # ------------------------------------------------------------------------------- dtype flow
-_F32, _F64 = np.dtype('float32'), np.dtype('float64')
-
 # per function of settings.function_dtype_flow = 'reference': (operands that go to the device in their own dtype, operands
 # that must be float64, result).  The result is 'promote' (numpy's promoted type of all operands), the name of the operand
 # whose dtype it takes, 'float64', or a tuple of those for a function with several results.
@@ -155,13 +64,6 @@ def _flow():
     return _check_flow(S.function_dtype_flow)
 
 
-def _float_dtype(dt):
-    """float32 / float64 as they are; anything else (integers, bool) as the float64 numpy's promotion with a python float
-    gives."""
-    dt = np.dtype(dt)
-    return dt if dt in (_F32, _F64) else _F64
-
-
 def reference_dtype_flow(function, **dtypes):
     """What settings.function_dtype_flow = 'reference' does with operands of the given dtypes, without touching a GPU:
     `(tags, result)` - `tags[operand]` is the C-ABI dtype tag (`_lib.PGW_F32` / `PGW_F64`) the operand is handed over with, in
@@ -176,9 +78,9 @@ def reference_dtype_flow(function, **dtypes):
     unknown = set(dtypes) - set(own) - set(need64)
     if unknown:
         raise TypeError('%s: unknown operand(s) %s' % (function, sorted(unknown)))
-    given = {k: _float_dtype(v) for k, v in dtypes.items() if v is not None}
+    given = {k: float_dtype(v) for k, v in dtypes.items() if v is not None}
     for name in need64:
-        if name in given and given[name] != _F64:
+        if name in given and given[name] != F64:
             raise NotImplementedError(
                 "%s: a float32 `%s` would make the reference take its logarithm in float32; that flow is not built - use "
                 "settings.function_dtype_flow = 'common' (or hand `%s` over as float64)" % (function, name, name))
@@ -186,7 +88,7 @@ def reference_dtype_flow(function, **dtypes):
 
     def res(rule):
         if rule == 'float64':
-            return _F64
+            return F64
         if rule == 'promote':
             have = [given[k] for k in own if k in given]
             return np.result_type(*have) if have else None
@@ -194,127 +96,95 @@ def reference_dtype_flow(function, **dtypes):
     return tags, (tuple(res(r) for r in result) if isinstance(result, tuple) else res(result))
 
 
-def _own(x):
-    """ndarray (float32 / float64 as it is, anything else as float64) or DeviceArray behind an operand: no cast."""
-    r = _raw(x)
-    if isinstance(r, DeviceArray):
-        return r
-    return r if r.dtype in (_F32, _F64) else r.astype(_F64)
+class OperandPlan:
+    """How the named operands `xs` of one call of `function` reach its kernel, decided once and before anything is uploaded:
+    `reference` - the call runs under settings.function_dtype_flow = 'reference' (read here, and only for a function of
+    `_FLOW_RULES`): every operand goes in its own dtype, as `reference_dtype_flow` says (its NotImplementedError is raised
+    here); otherwise every operand is cast to one dtype - `common` where the entry fixes it, else `common_dtype` of the
+    operands.  `result` is the dtype of the result (a pair for replace_delta_sfc).  Operands that are None stay None."""
 
+    def __init__(self, ctx, function, common=None, **xs):
+        self.ctx, self.xs = ctx, xs
+        self.reference = function in _FLOW_RULES and _flow() == 'reference'
+        if self.reference:
+            self.tags, self.result = reference_dtype_flow(
+                function, **{n: None if x is None else raw(x).dtype for n, x in xs.items()})
+        else:
+            self.dtype = common_dtype(*xs.values()) if common is None else np.dtype(common)
+            rule = _FLOW_RULES.get(function)
+            self.result = (self.dtype,) * len(rule[2]) if rule and isinstance(rule[2], tuple) else self.dtype
 
-def _dev_own(ctx, x, shape=None):
-    """Device array of `x` in ITS OWN dtype (the 'reference' flow: host arrays are uploaded as they are)."""
-    if x is None:
-        return None
-    r = _own(x)
-    if isinstance(r, DeviceArray):
-        return r if shape is None else r.view(shape)
-    a = np.ascontiguousarray(r)
-    if shape is not None:
-        a = a.reshape(shape)
-    return ctx.to_device(a, a.dtype)
+    def dev(self, name, shape=None):
+        """The operand on the device (viewed / uploaded as `shape`): in its own dtype, or cast to the common one - where a
+        DeviceArray of another dtype is a TypeError."""
+        if self.reference:
+            return dev_own(self.ctx, self.xs[name], shape)
+        return dev(self.ctx, self.xs[name], self.dtype, shape)
 
-
-def _dt(x):
-    return None if x is None else _own(x).dtype
-
-
-def _shape4(x):
-    s = _raw(x).shape
-    if len(s) != 4:
-        raise ValueError('expected a 4-D (time, level, lat, lon) array, got shape %s' % (s,))
-    return s
+    def tag(self, name):
+        """C-ABI dtype tag of the operand: its own (0 when it is absent), or the one common tag."""
+        return self.tags.get(name, 0) if self.reference else dtype_tag(self.dtype)
 
 
 # ------------------------------------------------------------------------------- humidity
+def _humidity(function, which, **xs):
+    """Entry `which` of the humidity family on the operands `xs`: the reference's argument names, the leading operand first
+    (the others are aligned and broadcast to it, and the result comes back in its kind).  `xs` keeps the caller's keyword
+    order, which is the C argument order.  C entries reached: `pgw_humidity_mixed` (reference flow, every `which`),
+    `pgw_humidity_leaf` (which 0-4: the one- and two-operand leaves), and for the two three-operand wrappers (which 5, 6)
+    the entry of their own name, `pgw_specific_to_relative_humidity` / `pgw_relative_to_specific_humidity`."""
+    ctx = default_context()
+    names = list(xs)
+    lead = xs[names[0]]
+    shp = raw(lead).shape
+    ops = OperandPlan(ctx, function, **{n: fit(aligned(x, lead), shp, n) if n != names[0] else x for n, x in xs.items()})
+    d = [ops.dev(n) for n in names] + [None, None]
+    out = ctx.empty(shp, ops.result)
+    if ops.reference:
+        t = [ops.tag(n) for n in names] + [0, 0]
+        rc = ctx.lib.pgw_humidity_mixed(ctx.handle, which, t[0], t[1], t[2], out.size, d[0].ptr, ptr(d[1]), ptr(d[2]), out.ptr)
+    elif which < 5:
+        rc = ctx.lib.pgw_humidity_leaf(ctx.handle, ops.tag(names[0]), which, out.size, d[0].ptr, ptr(d[1]), out.ptr)
+    else:
+        rc = getattr(ctx.lib, 'pgw_' + function)(ctx.handle, ops.tag(names[0]), out.size, d[0].ptr, d[1].ptr, d[2].ptr, out.ptr)
+    ctx._check(rc)
+    return out_like(out, lead)
+
+
 def specific_to_relative_humidity(hus, pa, ta):
     """RH [%] from specific humidity (IFS 7.92/7.93).  reference functions.py:107-116."""
-    ctx = default_context()
-    pa, ta = _aligned(pa, hus), _aligned(ta, hus)
-    if _flow() == 'reference':
-        return _humidity_ref('specific_to_relative_humidity', 5, ('hus', 'pa', 'ta'), (hus, pa, ta), hus)
-    dt = _common_dtype(hus, pa, ta)
-    shp = _raw(hus).shape
-    pa_, ta_ = _fit(pa, shp, 'pa'), _fit(ta, shp, 'ta')
-    dh, dp_, dt_ = _dev(ctx, hus, dt), _dev(ctx, pa_, dt), _dev(ctx, ta_, dt)
-    out = ctx.empty(shp, dt)
-    ctx._check(ctx.lib.pgw_specific_to_relative_humidity(ctx.handle, dtype_tag(dt), out.size, dh.ptr, dp_.ptr, dt_.ptr, out.ptr))
-    return _out(ctx, out, hus)
+    return _humidity('specific_to_relative_humidity', 5, hus=hus, pa=pa, ta=ta)
 
 
 def relative_to_specific_humidity(hur, pa, ta):
     """Specific humidity from RH [%].  reference functions.py:118-125."""
-    ctx = default_context()
-    pa, ta = _aligned(pa, hur), _aligned(ta, hur)
-    if _flow() == 'reference':
-        return _humidity_ref('relative_to_specific_humidity', 6, ('hur', 'pa', 'ta'), (hur, pa, ta), hur)
-    dt = _common_dtype(hur, pa, ta)
-    shp = _raw(hur).shape
-    pa_, ta_ = _fit(pa, shp, 'pa'), _fit(ta, shp, 'ta')
-    dh, dp_, dt_ = _dev(ctx, hur, dt), _dev(ctx, pa_, dt), _dev(ctx, ta_, dt)
-    out = ctx.empty(shp, dt)
-    ctx._check(ctx.lib.pgw_relative_to_specific_humidity(ctx.handle, dtype_tag(dt), out.size, dh.ptr, dp_.ptr, dt_.ptr, out.ptr))
-    return _out(ctx, out, hur)
-
-
-def _humidity_ref(function, which, names, operands, like):
-    """The humidity functions under settings.function_dtype_flow = 'reference' (`pgw_humidity_mixed`)."""
-    ctx = default_context()
-    shp = _raw(operands[0]).shape
-    fitted = [operands[0]] + [_fit(x, shp, n) for n, x in zip(names[1:], operands[1:])]
-    tags, res = reference_dtype_flow(function, **{n: _dt(x) for n, x in zip(names, fitted)})
-    d = [_dev_own(ctx, x) for x in fitted] + [None, None]
-    t = [tags[n] for n in names] + [0, 0]
-    out = ctx.empty(shp, res)
-    ctx._check(ctx.lib.pgw_humidity_mixed(ctx.handle, which, t[0], t[1], t[2], out.size, d[0].ptr, ptr(d[1]), ptr(d[2]), out.ptr))
-    return _out(ctx, out, like)
-
-
-_LEAF_NAMES = {0: ('specific_humidity_to_vapor_pressure', ('hus', 'pa')), 1: ('vapor_pressure_to_specific_humidity', ('vapp', 'pa')),
-               2: ('saturation_vapor_pressure_water_or_ice', ('ta',)), 3: ('saturation_vapor_pressure_water_or_ice', ('ta',)),
-               4: ('saturation_vapor_pressure_water_and_ice', ('ta',))}
-
-
-def _humidity_leaf(which, a, b, like):
-    if _flow() == 'reference':
-        fn, names = _LEAF_NAMES[which]
-        return _humidity_ref(fn, which, names, (a,) if b is None else (a, _aligned(b, a)), like)
-    ctx = default_context()
-    dt = _common_dtype(a) if b is None else _common_dtype(a, b)
-    shp = _raw(a).shape
-    b_ = None if b is None else _fit(_aligned(b, a), shp, 'pa')
-    da = _dev(ctx, a, dt)
-    db = None if b_ is None else _dev(ctx, b_, dt)
-    out = ctx.empty(shp, dt)
-    ctx._check(ctx.lib.pgw_humidity_leaf(ctx.handle, dtype_tag(dt), which, out.size, da.ptr, db.ptr if db is not None else None, out.ptr))
-    return _out(ctx, out, like)
+    return _humidity('relative_to_specific_humidity', 6, hur=hur, pa=pa, ta=ta)
 
 
 def specific_humidity_to_vapor_pressure(hus, pa):
     """e = hus * pa / (0.622 + 0.378 * hus).  reference functions.py:58-64."""
-    return _humidity_leaf(0, hus, pa, hus)
+    return _humidity('specific_humidity_to_vapor_pressure', 0, hus=hus, pa=pa)
 
 
 def vapor_pressure_to_specific_humidity(vapp, pa):
     """hus = 0.622 * vapp / (pa - 0.378 * vapp).  reference functions.py:66-72."""
-    return _humidity_leaf(1, vapp, pa, vapp)
+    return _humidity('vapor_pressure_to_specific_humidity', 1, vapp=vapp, pa=pa)
 
 
 def saturation_vapor_pressure_water_or_ice(pa, ta, water=True):
     """IFS (7.93) saturation vapour pressure over water or over ice; `pa` is unused, as in the reference (functions.py:74-89)."""
-    return _humidity_leaf(2 if water else 3, ta, None, ta)
+    return _humidity('saturation_vapor_pressure_water_or_ice', 2 if water else 3, ta=ta)
 
 
 def saturation_vapor_pressure_water_and_ice(pa, ta):
     """IFS (7.92) mixed-phase saturation vapour pressure.  reference functions.py:91-105."""
-    return _humidity_leaf(4, ta, None, ta)
+    return _humidity('saturation_vapor_pressure_water_and_ice', 4, ta=ta)
 
 
 def dt64_to_dt(dt64):
     """numpy datetime64 -> python datetime (UTC).  reference functions.py:38-51."""
-    import datetime as _datetime
     timestamp = (np.datetime64(dt64, 's') - np.datetime64('1970-01-01T00:00:00')) / np.timedelta64(1, 's')
-    return _datetime.datetime.utcfromtimestamp(float(timestamp))
+    return datetime.datetime.utcfromtimestamp(float(timestamp))
 
 
 # ------------------------------------------------------------------------------- pressure
@@ -323,17 +193,17 @@ def hybrid_pressure(ak, bk, ps, akm=None, bkm=None):
     this is what BASELINE.json calls "integ_pressure").  ps (time, lat, lon) -> (pa_hl, pa)."""
     ctx = default_context()
     ctx.set_levels(ak, bk, akm, bkm)
-    dt = _common_dtype(ps)
-    s = _raw(ps).shape
+    ops = OperandPlan(ctx, 'hybrid_pressure', ps=ps)
+    s = raw(ps).shape
     if len(s) != 3:
         raise ValueError('ps must be (time, lat, lon)')
     nt, ncol, n = s[0], s[1] * s[2], ctx.nlev
-    dps = _dev(ctx, ps, dt)
+    dps = ops.dev('ps')
     # the kernel's two write streams in different stretches of the card's memory when the context places its level arrays
     # (settings.placement; Context.level_array falls back to plain memory): 0.34 instead of 0.41 ms at 0.25 deg L137
-    pa_hl = ctx.level_array((nt, n + 1, s[1], s[2]), dt, cls=0)
-    pa = ctx.level_array((nt, n, s[1], s[2]), dt, cls=1)
-    ctx._check(ctx.lib.pgw_pressure_levels(ctx.handle, dtype_tag(dt), nt, ncol, dps.ptr, pa_hl.ptr, pa.ptr))
+    pa_hl = ctx.level_array((nt, n + 1, s[1], s[2]), ops.result, cls=0)
+    pa = ctx.level_array((nt, n, s[1], s[2]), ops.result, cls=1)
+    ctx._check(ctx.lib.pgw_pressure_levels(ctx.handle, ops.tag('ps'), nt, ncol, dps.ptr, pa_hl.ptr, pa.ptr))
     if isinstance(ps, DeviceArray):
         return pa_hl, pa
     return pa_hl.numpy(), pa.numpy()
@@ -343,64 +213,50 @@ def hybrid_pressure(ak, bk, ps, akm=None, bkm=None):
 def integ_geopot(pa_hl, zgs, ta, hus, level1, p_ref, full_column=True):
     """Geopotential at p_ref by hydrostatic integration from the surface.
     reference functions.py:128-189.  `level1` = half-level labels (its length must be N+1).
-    p_ref: scalar or (time, lat, lon) field.  Returns (time, lat, lon)."""
+    p_ref: scalar or (time, lat, lon) field.  Returns (time, lat, lon).
+    Under settings.function_dtype_flow = 'reference': phi_hl in the dtype of zgs, tav in the promoted dtype of (ta, hus),
+    float64 pressures, float64 result."""
     ctx = default_context()
-    hus = _aligned(hus, ta)
-    s = _shape4(pa_hl)
-    st = _shape4(ta)
-    if len(level1) != s[1] or st[1] != s[1] - 1 or _shape4(hus) != st:
+    hus = aligned(hus, ta)
+    s = shape4(pa_hl)
+    st = shape4(ta)
+    if len(level1) != s[1] or st[1] != s[1] - 1 or shape4(hus) != st:
         raise ValueError('level dimensions are inconsistent')
-    if _flow() == 'reference':
-        return _integ_geopot_ref(ctx, pa_hl, zgs, ta, hus, p_ref, full_column, s, st)
-    dt = _common_dtype(pa_hl, zgs, ta, hus)
-    nt, n, ncol = s[0], st[1], s[2] * s[3]
-    ta_, hus_ = _fit(ta, (nt, n, s[2], s[3]), 'ta'), _fit(hus, (nt, n, s[2], s[3]), 'hus')
-    d_p, d_z, d_t, d_q = _dev(ctx, pa_hl, dt), _dev(ctx, zgs, dt, (nt, s[2], s[3])), _dev(ctx, ta_, dt), _dev(ctx, hus_, dt)
-    pref_field = None
-    pref_scalar = 0.0
-    pr = _raw(p_ref) if not np.isscalar(p_ref) else None
-    if pr is not None and (isinstance(pr, DeviceArray) or pr.ndim > 0):
-        pref_field = _dev(ctx, p_ref, dt, (nt, s[2], s[3]))
-    else:
-        pref_scalar = float(p_ref)
-    out = ctx.empty((nt, s[2], s[3]), dt)
-    ctx._check(ctx.lib.pgw_integ_geopot(ctx.handle, dtype_tag(dt), nt, n, ncol, d_p.ptr, d_z.ptr, d_t.ptr, d_q.ptr,
-                                        pref_scalar, ptr(pref_field), out.ptr, 1 if full_column else 0))
-    return _out(ctx, out, zgs)
-
-
-def _integ_geopot_ref(ctx, pa_hl, zgs, ta, hus, p_ref, full_column, s, st):
-    """integ_geopot under settings.function_dtype_flow = 'reference' (`pgw_integ_geopot_mixed`): phi_hl in the dtype of zgs,
-    tav in the promoted dtype of (ta, hus), float64 pressures, float64 result."""
-    nt, n, ncol = s[0], st[1], s[2] * s[3]
-    ta_, hus_ = _fit(ta, (nt, n, s[2], s[3]), 'ta'), _fit(hus, (nt, n, s[2], s[3]), 'hus')
-    pr = _raw(p_ref) if not np.isscalar(p_ref) else None
+    nt, n, ncol, s3 = s[0], st[1], s[2] * s[3], (s[0], s[2], s[3])
+    ta_, hus_ = fit(ta, (nt, n, s[2], s[3]), 'ta'), fit(hus, (nt, n, s[2], s[3]), 'hus')
+    pr = raw(p_ref) if not np.isscalar(p_ref) else None
     is_field = pr is not None and (isinstance(pr, DeviceArray) or pr.ndim > 0)
-    tags, res = reference_dtype_flow('integ_geopot', pa_hl=_dt(pa_hl), zgs=_dt(zgs), ta=_dt(ta_), hus=_dt(hus_),
-                                     p_ref=_dt(p_ref) if is_field else None)
-    d_p, d_z = _dev_own(ctx, pa_hl), _dev_own(ctx, zgs, (nt, s[2], s[3]))
-    d_t, d_q = _dev_own(ctx, ta_), _dev_own(ctx, hus_)
-    pref_field = _dev_own(ctx, p_ref, (nt, s[2], s[3])) if is_field else None
-    pref_scalar = 0.0 if is_field else float(p_ref)
-    out = ctx.empty((nt, s[2], s[3]), res)
-    ctx._check(ctx.lib.pgw_integ_geopot_mixed(ctx.handle, tags['pa_hl'], tags['zgs'], tags['ta'], tags['hus'], nt, n, ncol,
-                                              d_p.ptr, d_z.ptr, d_t.ptr, d_q.ptr, pref_scalar, ptr(pref_field), out.ptr,
-                                              1 if full_column else 0))
-    return _out(ctx, out, zgs)
+    # a p_ref field follows the common dtype of the other four, it has no say in it
+    ops = OperandPlan(ctx, 'integ_geopot', common=common_dtype(pa_hl, zgs, ta, hus),
+                      pa_hl=pa_hl, zgs=zgs, ta=ta_, hus=hus_, p_ref=p_ref if is_field else None)
+    d_p, d_z, d_t, d_q, d_ref = ops.dev('pa_hl'), ops.dev('zgs', s3), ops.dev('ta'), ops.dev('hus'), ops.dev('p_ref', s3)
+    out = ctx.empty(s3, ops.result)
+    tail = (nt, n, ncol, d_p.ptr, d_z.ptr, d_t.ptr, d_q.ptr, 0.0 if is_field else float(p_ref), ptr(d_ref), out.ptr,
+            1 if full_column else 0)
+    if ops.reference:
+        rc = ctx.lib.pgw_integ_geopot_mixed(ctx.handle, ops.tag('pa_hl'), ops.tag('zgs'), ops.tag('ta'), ops.tag('hus'), *tail)
+    else:
+        rc = ctx.lib.pgw_integ_geopot(ctx.handle, ops.tag('pa_hl'), *tail)
+    ctx._check(rc)
+    return out_like(out, zgs)
 
 
 # ------------------------------------------------------------------------------- interpolation
-def _check_extrapolate(extrapolate):
-    if extrapolate not in _lib.EXTRAP:
-        raise ValueError('Invalid input value for "extrapolate"')
-    return _lib.EXTRAP[extrapolate]
+def _interp_logp(ops, var, targ, dims, d_v, d_s, d_t, mode, is_logp, out):
+    """Status of `pgw_interp_logp_4d` (`_mixed` in the reference flow, which takes the tags of the operands named `var` and
+    `targ`) for dims = (nt, S, N, ncol)."""
+    ctx = ops.ctx
+    tail = dims + (d_v.ptr, d_s.ptr, d_t.ptr, mode, is_logp, out.ptr)
+    if ops.reference:
+        return ctx.lib.pgw_interp_logp_4d_mixed(ctx.handle, ops.tag(var), ops.tag(targ), *tail)
+    return ctx.lib.pgw_interp_logp_4d(ctx.handle, ops.tag(var), *tail)
 
 
 def interp_logp_4d(var, source_P, targ_P, extrapolate='off', time_key=None, lat_key=None, lon_key=None):
     """Column-wise linear interpolation in ln(p).  reference functions.py:434-477.
     var, source_P (time, S, lat, lon); targ_P (time, N, lat, lon) -> (time, N, lat, lon)."""
-    mode = _check_extrapolate(extrapolate)
-    sv, ss, st = _shape4(var), _shape4(source_P), _shape4(targ_P)
+    mode = check_extrapolate(extrapolate)
+    sv, ss, st = shape4(var), shape4(source_P), shape4(targ_P)
     if (sv[0] != ss[0]) or (sv[0] != st[0]):
         raise ValueError('Time dimension of input files is inconsistent!')
     if (sv[2] != ss[2]) or (sv[2] != st[2]):
@@ -410,64 +266,35 @@ def interp_logp_4d(var, source_P, targ_P, extrapolate='off', time_key=None, lat_
     if sv[1] != ss[1]:
         raise ValueError('Level dimension of var and source_P is inconsistent!')
     ctx = default_context()
-    if _flow() == 'reference':
-        tags, res = reference_dtype_flow('interp_logp_4d', var=_dt(var), source_P=_dt(source_P), targ_P=_dt(targ_P))
-        d_v, d_s, d_t = _dev_own(ctx, var), _dev_own(ctx, source_P), _dev_own(ctx, targ_P)
-        out = ctx.empty(st, res)
-        ctx._check(ctx.lib.pgw_interp_logp_4d_mixed(ctx.handle, tags['var'], tags['targ_P'], st[0], sv[1], st[1], st[2] * st[3],
-                                                    d_v.ptr, d_s.ptr, d_t.ptr, mode, 0, out.ptr))
-        return _out(ctx, out, targ_P)
-    dt = _common_dtype(var, source_P, targ_P)
-    d_v, d_s, d_t = _dev(ctx, var, dt), _dev(ctx, source_P, dt), _dev(ctx, targ_P, dt)
-    out = ctx.empty(st, dt)
-    ctx._check(ctx.lib.pgw_interp_logp_4d(ctx.handle, dtype_tag(dt), st[0], sv[1], st[1], st[2] * st[3],
-                                          d_v.ptr, d_s.ptr, d_t.ptr, mode, 0, out.ptr))
-    return _out(ctx, out, targ_P)
+    ops = OperandPlan(ctx, 'interp_logp_4d', var=var, source_P=source_P, targ_P=targ_P)
+    d_v, d_s, d_t = ops.dev('var'), ops.dev('source_P'), ops.dev('targ_P')
+    out = ctx.empty(st, ops.result)
+    ctx._check(_interp_logp(ops, 'var', 'targ_P', (st[0], sv[1], st[1], st[2] * st[3]), d_v, d_s, d_t, mode, 0, out))
+    return out_like(out, targ_P)
 
 
 def interp_1d_for_timelatlon(orig_array, src_p, targ_p, interp_array, ntime, nlat, nlon, extrapolate):
     """reference functions.py:479-508: inputs already hold ln(p); fills `interp_array` in place."""
-    mode = _check_extrapolate(extrapolate)
+    mode = check_extrapolate(extrapolate)
     ctx = default_context()
-    dt = np.dtype('float64')
-    if _flow() == 'reference':
-        tags, res = reference_dtype_flow('interp_1d_for_timelatlon', orig_array=_dt(orig_array), src_p=_dt(src_p), targ_p=_dt(targ_p))
-        d_v, d_s, d_t = _dev_own(ctx, orig_array), _dev_own(ctx, src_p), _dev_own(ctx, targ_p)
-        out = ctx.empty(d_t.shape, res)
-        ctx._check(ctx.lib.pgw_interp_logp_4d_mixed(ctx.handle, tags['orig_array'], tags['targ_p'], ntime, d_s.shape[1], d_t.shape[1],
-                                                    nlat * nlon, d_v.ptr, d_s.ptr, d_t.ptr, mode, 1, out.ptr))
-        interp_array[...] = out.numpy()
-        return
-    d_v, d_s, d_t = _dev(ctx, orig_array, dt), _dev(ctx, src_p, dt), _dev(ctx, targ_p, dt)
-    out = ctx.empty(d_t.shape, dt)
-    ctx._check(ctx.lib.pgw_interp_logp_4d(ctx.handle, dtype_tag(dt), ntime, d_s.shape[1], d_t.shape[1], nlat * nlon,
-                                          d_v.ptr, d_s.ptr, d_t.ptr, mode, 1, out.ptr))
+    ops = OperandPlan(ctx, 'interp_1d_for_timelatlon', common=F64, orig_array=orig_array, src_p=src_p, targ_p=targ_p)
+    d_v, d_s, d_t = ops.dev('orig_array'), ops.dev('src_p'), ops.dev('targ_p')
+    out = ctx.empty(d_t.shape, ops.result)
+    ctx._check(_interp_logp(ops, 'orig_array', 'targ_p', (ntime, d_s.shape[1], d_t.shape[1], nlat * nlon), d_v, d_s, d_t, mode, 1, out))
     interp_array[...] = out.numpy()
 
 
 def interp_extrap_1d(src_x, src_y, targ_x, extrapolate):
     """reference functions.py:511-580 for one column (abscissae as given, e.g. ln p)."""
-    mode = _check_extrapolate(extrapolate)
+    mode = check_extrapolate(extrapolate)
     ctx = default_context()
-    dt = np.dtype('float64')
     S, N = len(src_x), len(targ_x)
-    if _flow() == 'reference':
-        tags, res = reference_dtype_flow('interp_extrap_1d', src_x=_dt(src_x), src_y=_dt(src_y), targ_x=_dt(targ_x))
-        d_s, d_v, d_t = _dev_own(ctx, src_x, (1, S, 1, 1)), _dev_own(ctx, src_y, (1, S, 1, 1)), _dev_own(ctx, targ_x, (1, N, 1, 1))
-        out = ctx.empty((1, N, 1, 1), res)
-        rc = ctx.lib.pgw_interp_logp_4d_mixed(ctx.handle, tags['src_y'], tags['targ_x'], 1, S, N, 1, d_v.ptr, d_s.ptr, d_t.ptr, mode, 1,
-                                              out.ptr)
-        ctx._check(0 if rc in (10, 11) else rc)             # no ascending pre-check in the 1-D function (see below)
-        return out.numpy().reshape(N)
-    d_s = _dev(ctx, np.asarray(src_x, dtype=dt).reshape(1, S, 1, 1), dt)
-    d_v = _dev(ctx, np.asarray(src_y, dtype=dt).reshape(1, S, 1, 1), dt)
-    d_t = _dev(ctx, np.asarray(targ_x, dtype=dt).reshape(1, N, 1, 1), dt)
-    out = ctx.empty((1, N, 1, 1), dt)
-    rc = ctx.lib.pgw_interp_logp_4d(ctx.handle, dtype_tag(dt), 1, S, N, 1, d_v.ptr, d_s.ptr, d_t.ptr, mode, 1, out.ptr)
+    ops = OperandPlan(ctx, 'interp_extrap_1d', common=F64, src_x=src_x, src_y=src_y, targ_x=targ_x)
+    d_s, d_v, d_t = ops.dev('src_x', (1, S, 1, 1)), ops.dev('src_y', (1, S, 1, 1)), ops.dev('targ_x', (1, N, 1, 1))
+    out = ctx.empty((1, N, 1, 1), ops.result)
+    rc = _interp_logp(ops, 'src_y', 'targ_x', (1, S, N, 1), d_v, d_s, d_t, mode, 1, out)
     # the 1-D function has no ascending pre-check (that lives in interp_1d_for_timelatlon)
-    if rc in (10, 11):
-        rc = 0
-    ctx._check(rc)
+    ctx._check(0 if rc in (10, 11) else rc)
     return out.numpy().reshape(N)
 
 
@@ -476,51 +303,41 @@ def time_lerp(v_before, v_after, x_hi, x_new):
     """(v_after - v_before)/x_hi * x_new + v_before: the arithmetic under load_delta's
     `.interp(time=...)` (reference functions.py:288-292; scipy interp1d linear)."""
     ctx = default_context()
-    if _flow() == 'reference':
-        v_after_ = _fit(v_after, _raw(v_before).shape, 'v_after')
-        tags, res = reference_dtype_flow('time_lerp', v_before=_dt(v_before), v_after=_dt(v_after_))
-        d_b, d_a = _dev_own(ctx, v_before), _dev_own(ctx, v_after_)
-        out = ctx.empty(d_b.shape, res)
-        ctx._check(ctx.lib.pgw_time_lerp_mixed(ctx.handle, tags['v_before'], tags['v_after'], out.size, d_b.ptr, d_a.ptr,
-                                               float(x_hi), float(x_new), out.ptr))
-        return _out(ctx, out, v_before)
-    dt = _common_dtype(v_before, v_after)
-    v_after_ = _fit(v_after, _raw(v_before).shape, 'v_after')
-    d_b, d_a = _dev(ctx, v_before, dt), _dev(ctx, v_after_, dt)
-    out = ctx.empty(d_b.shape, dt)
-    ctx._check(ctx.lib.pgw_time_lerp(ctx.handle, dtype_tag(dt), out.size, d_b.ptr, d_a.ptr, float(x_hi), float(x_new), out.ptr))
-    return _out(ctx, out, v_before)
+    ops = OperandPlan(ctx, 'time_lerp', v_before=v_before, v_after=fit(v_after, raw(v_before).shape, 'v_after'))
+    d_b, d_a = ops.dev('v_before'), ops.dev('v_after')
+    out = ctx.empty(d_b.shape, ops.result)
+    tail = (out.size, d_b.ptr, d_a.ptr, float(x_hi), float(x_new), out.ptr)
+    if ops.reference:
+        rc = ctx.lib.pgw_time_lerp_mixed(ctx.handle, ops.tag('v_before'), ops.tag('v_after'), *tail)
+    else:
+        rc = ctx.lib.pgw_time_lerp(ctx.handle, ops.tag('v_before'), *tail)
+    ctx._check(rc)
+    return out_like(out, v_before)
 
 
 def replace_delta_sfc(source_P, ps_hist, delta, delta_sfc):
     """reference functions.py:343-366 for one ascending-pressure column."""
     ctx = default_context()
-    dt = np.dtype('float64')
-    if _flow() == 'reference':
-        S = len(source_P)
-        tags, (res_p, res_d) = reference_dtype_flow('replace_delta_sfc', source_P=_dt(source_P), delta=_dt(delta),
-                                                    delta_sfc=_dt(delta_sfc), ps_hist=_dt(ps_hist))
-        P = np.ascontiguousarray(_own(source_P))
-        d_d, d_s, d_p = _dev_own(ctx, delta, (1, S, 1)), _dev_own(ctx, delta_sfc, (1, 1)), _dev_own(ctx, ps_hist, (1, 1))
-        oP, oD = ctx.empty((1, S, 1), res_p), ctx.empty((1, S, 1), res_d)
-        ctx._check(ctx.lib.pgw_replace_delta_sfc_mixed(ctx.handle, tags['delta'], tags['delta_sfc'], tags['ps_hist'], 1, S, 1,
-                                                       P.ctypes.data_as(_dp), d_d.ptr, d_s.ptr, d_p.ptr, oP.ptr, oD.ptr))
-        return oP.numpy().reshape(S), oD.numpy().reshape(S)
-    P = np.ascontiguousarray(source_P, dtype=dt)
+    ops = OperandPlan(ctx, 'replace_delta_sfc', common=F64, source_P=source_P, delta=delta, delta_sfc=delta_sfc, ps_hist=ps_hist)
+    if ops.reference:                                       # a column without len() (DeviceArray, Field) fails here in this
+        len(source_P)                                       # flow and in the cast below in the other: each keeps its own
+    P = np.ascontiguousarray(source_P, dtype=F64)           # read on the host; float64 in both flows
     S = len(P)
-    d_d = _dev(ctx, np.asarray(delta, dtype=dt).reshape(1, S, 1), dt)
-    d_s = _dev(ctx, np.asarray([[delta_sfc]], dtype=dt), dt)
-    d_p = _dev(ctx, np.asarray([[ps_hist]], dtype=dt), dt)
-    oP, oD = ctx.empty((1, S, 1), dt), ctx.empty((1, S, 1), dt)
-    ctx._check(ctx.lib.pgw_replace_delta_sfc(ctx.handle, dtype_tag(dt), 1, S, 1, P.ctypes.data_as(_dp),
-                                             d_d.ptr, d_s.ptr, d_p.ptr, oP.ptr, oD.ptr))
+    d_d, d_s, d_p = ops.dev('delta', (1, S, 1)), ops.dev('delta_sfc', (1, 1)), ops.dev('ps_hist', (1, 1))
+    oP, oD = (ctx.empty((1, S, 1), dt) for dt in ops.result)
+    tail = (1, S, 1, P.ctypes.data_as(_dp), d_d.ptr, d_s.ptr, d_p.ptr, oP.ptr, oD.ptr)
+    if ops.reference:
+        rc = ctx.lib.pgw_replace_delta_sfc_mixed(ctx.handle, ops.tag('delta'), ops.tag('delta_sfc'), ops.tag('ps_hist'), *tail)
+    else:
+        rc = ctx.lib.pgw_replace_delta_sfc(ctx.handle, ops.tag('delta'), *tail)
+    ctx._check(rc)
     return oP.numpy().reshape(S), oD.numpy().reshape(S)
 
 
 def _plev_of(delta, plev):
     if plev is not None:
         return np.ascontiguousarray(plev, dtype=np.float64)
-    if _is_labelled(delta) and PLEV_GCM in getattr(delta, 'coords', {}):
+    if is_labelled(delta) and PLEV_GCM in getattr(delta, 'coords', {}):
         return np.ascontiguousarray(delta.coords[PLEV_GCM], dtype=np.float64)
     raise ValueError('vert_interp_delta needs the plev coordinate (labelled delta or plev=...)')
 
@@ -533,36 +350,28 @@ def vert_interp_delta(delta, target_P, delta_sfc=None, ps_hist=None, ignore_top_
     target_P (time, N, lat, lon); delta_sfc, ps_hist (time, lat, lon) or None."""
     ctx = default_context()
     pl = _plev_of(delta, plev)
-    sd, st = _shape4(delta), _shape4(target_P)
+    sd, st = shape4(delta), shape4(target_P)
     if sd[0] != st[0] or sd[2:] != st[2:]:
         raise ValueError()
     if (delta_sfc is None) != (ps_hist is None):
         raise ValueError('delta_sfc and ps_hist must be given together')
-    nt, S, ncol, N = sd[0], sd[1], sd[2] * sd[3], st[1]
-    add_ = _fit(add_to, st, 'add_to') if add_to is not None else None
-    if _flow() == 'reference':
-        tags, res = reference_dtype_flow('vert_interp_delta', delta=_dt(delta), target_P=_dt(target_P), delta_sfc=_dt(delta_sfc),
-                                         ps_hist=_dt(ps_hist), add_to=_dt(add_))
-        d_d, d_t = _dev_own(ctx, delta), _dev_own(ctx, target_P)
-        d_s, d_p = _dev_own(ctx, delta_sfc, (nt, sd[2], sd[3])), _dev_own(ctx, ps_hist, (nt, sd[2], sd[3]))
-        d_add = _dev_own(ctx, add_)
-        out = ctx.empty(st, res)
-        ctx._check(ctx.lib.pgw_vert_interp_delta_mixed(
-            ctx.handle, tags['delta'], tags.get('delta_sfc', 0), tags.get('ps_hist', 0), tags['target_P'], tags.get('add_to', 0),
-            nt, S, N, ncol, pl.ctypes.data_as(_dp), d_d.ptr, ptr(d_s), ptr(d_p), d_t.ptr,
-            1 if ignore_top_pressure_error else 0, ptr(d_add), out.ptr))
-        return _out(ctx, out, target_P)
-    dt = _common_dtype(delta, target_P, delta_sfc, ps_hist, add_to)
-    d_d, d_t = _dev(ctx, delta, dt), _dev(ctx, target_P, dt)
-    d_s = _dev(ctx, delta_sfc, dt, (nt, sd[2], sd[3])) if delta_sfc is not None else None
-    d_p = _dev(ctx, ps_hist, dt, (nt, sd[2], sd[3])) if ps_hist is not None else None
-    d_add = _dev(ctx, add_, dt) if add_ is not None else None
-    out = ctx.empty(st, dt)
-    ctx._check(ctx.lib.pgw_vert_interp_delta(
-        ctx.handle, dtype_tag(dt), nt, S, N, ncol, pl.ctypes.data_as(_dp),
-        d_d.ptr, None, 0.0, 0.0, ptr(d_s), None, ptr(d_p), None,
-        d_t.ptr, None, 1 if ignore_top_pressure_error else 0, ptr(d_add), out.ptr))
-    return _out(ctx, out, target_P)
+    nt, S, ncol, N, s3 = sd[0], sd[1], sd[2] * sd[3], st[1], (sd[0], sd[2], sd[3])
+    # the common dtype is decided on the caller's add_to: `fit` keeps an operand's dtype, so the fitted one decides the same
+    ops = OperandPlan(ctx, 'vert_interp_delta', delta=delta, target_P=target_P, delta_sfc=delta_sfc, ps_hist=ps_hist,
+                      add_to=None if add_to is None else fit(add_to, st, 'add_to'))
+    d_d, d_t, d_s, d_p, d_add = ops.dev('delta'), ops.dev('target_P'), ops.dev('delta_sfc', s3), ops.dev('ps_hist', s3), ops.dev('add_to')
+    out = ctx.empty(st, ops.result)
+    top = 1 if ignore_top_pressure_error else 0
+    if ops.reference:
+        rc = ctx.lib.pgw_vert_interp_delta_mixed(
+            ctx.handle, ops.tag('delta'), ops.tag('delta_sfc'), ops.tag('ps_hist'), ops.tag('target_P'), ops.tag('add_to'),
+            nt, S, N, ncol, pl.ctypes.data_as(_dp), d_d.ptr, ptr(d_s), ptr(d_p), d_t.ptr, top, ptr(d_add), out.ptr)
+    else:
+        rc = ctx.lib.pgw_vert_interp_delta(
+            ctx.handle, ops.tag('delta'), nt, S, N, ncol, pl.ctypes.data_as(_dp),
+            d_d.ptr, None, 0.0, 0.0, ptr(d_s), None, ptr(d_p), None, d_t.ptr, None, top, ptr(d_add), out.ptr)
+    ctx._check(rc)
+    return out_like(out, target_P)
 
 
 def determine_p_ref(p_min_era, p_min_pgw, p_ref_opts, p_ref_last=None):
@@ -578,21 +387,17 @@ def integrate_tos(tos_field, ts_field, land_frac, ice_frac):
     """Blend SST and skin-temperature deltas by land + sea-ice fraction.
     reference functions.py:1145-1186."""
     ctx = default_context()
-    shp = _raw(tos_field).shape
-    if _flow() == 'reference':
-        names = ('tos_field', 'ts_field', 'land_frac', 'ice_frac')
-        ops = (tos_field, ts_field, land_frac, ice_frac)
-        tags, res = reference_dtype_flow('integrate_tos', **{n: _dt(x) for n, x in zip(names, ops)})
-        d = [_dev_own(ctx, x) for x in ops]
-        out = ctx.empty(shp, res)
-        ctx._check(ctx.lib.pgw_integrate_tos_mixed(ctx.handle, *[tags[n] for n in names], out.size, d[0].ptr, d[1].ptr, d[2].ptr,
-                                                   d[3].ptr, out.ptr))
-        return _out(ctx, out, tos_field)
-    dt = _common_dtype(tos_field, ts_field, land_frac, ice_frac)
-    d = [_dev(ctx, x, dt) for x in (tos_field, ts_field, land_frac, ice_frac)]
-    out = ctx.empty(shp, dt)
-    ctx._check(ctx.lib.pgw_integrate_tos(ctx.handle, dtype_tag(dt), out.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, out.ptr))
-    return _out(ctx, out, tos_field)
+    names = ('tos_field', 'ts_field', 'land_frac', 'ice_frac')
+    ops = OperandPlan(ctx, 'integrate_tos', **dict(zip(names, (tos_field, ts_field, land_frac, ice_frac))))
+    d = [ops.dev(n) for n in names]
+    out = ctx.empty(raw(tos_field).shape, ops.result)
+    tail = (out.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, out.ptr)
+    if ops.reference:
+        rc = ctx.lib.pgw_integrate_tos_mixed(ctx.handle, *[ops.tag(n) for n in names], *tail)
+    else:
+        rc = ctx.lib.pgw_integrate_tos(ctx.handle, ops.tag(names[0]), *tail)
+    ctx._check(rc)
+    return out_like(out, tos_field)
 
 
 # ------------------------------------------------------------------------------- ps loop
@@ -608,17 +413,16 @@ def adjust_ps_loop(ak, bk, PS, FIS, T, QV, ta_pgw, hur_pgw, dzg_pref, akm=None, 
     max_n_iter = S.max_n_iter if max_n_iter is None else max_n_iter
     ctx = default_context()
     ctx.set_levels(ak, bk, akm, bkm)
-    s = _shape4(ta_pgw)
-    dt = _common_dtype(PS, FIS, T, QV, ta_pgw, hur_pgw, dzg_pref)
+    s = shape4(ta_pgw)
+    ops = OperandPlan(ctx, 'adjust_ps_loop', PS=PS, FIS=FIS, T=T, QV=QV, ta=ta_pgw, hur=hur_pgw, dzg=dzg_pref)
     nt, ncol = s[0], s[2] * s[3]
     s3 = (nt, s[2], s[3])
-    d = dict(PS=_dev(ctx, PS, dt, s3), FIS=_dev(ctx, FIS, dt, s3), T=_dev(ctx, T, dt), QV=_dev(ctx, QV, dt),
-             ta=_dev(ctx, ta_pgw, dt), hur=_dev(ctx, hur_pgw, dt), dzg=_dev(ctx, dzg_pref, dt, s3))
-    ps_out = ctx.empty(s3, dt)
-    hus_out = ctx.empty(s, dt) if want_hus else None
+    d = {n: ops.dev(n, s3 if n in ('PS', 'FIS', 'dzg') else None) for n in ('PS', 'FIS', 'T', 'QV', 'ta', 'hur', 'dzg')}
+    ps_out = ctx.empty(s3, ops.result)
+    hus_out = ctx.empty(s, ops.result) if want_hus else None
     n_iter = C.c_int(0)
     hist = (C.c_double * int(max_n_iter))()
-    rc = ctx.lib.pgw_adjust_ps_loop(ctx.handle, dtype_tag(dt), nt, ncol, d['PS'].ptr, d['FIS'].ptr, d['T'].ptr,
+    rc = ctx.lib.pgw_adjust_ps_loop(ctx.handle, ops.tag('ta'), nt, ncol, d['PS'].ptr, d['FIS'].ptr, d['T'].ptr,
                                     d['QV'].ptr, d['ta'].ptr, d['hur'].ptr, d['dzg'].ptr, float(p_ref),
                                     float(adj_factor), float(thresh), int(max_n_iter), ps_out.ptr, ptr(hus_out),
                                     C.byref(n_iter), hist)
@@ -699,24 +503,23 @@ def regrid_field(field, src_lat, src_lon, targ_lat, targ_lon):
     """Bilinear (lat, then lon) regridding of field (..., nlat_s, nlon_s) on the GPU."""
     ctx = default_context()
     tb = regrid_tables(src_lat, src_lon, targ_lat, targ_lon)
-    r = _raw(field)
-    shp = r.shape
-    dt = _common_dtype(field)
+    shp = raw(field).shape
+    ops = OperandPlan(ctx, 'regrid_field', field=field)
     nlat_s, nlon_s = shp[-2], shp[-1]
     if nlat_s != len(src_lat) or nlon_s != len(src_lon):
         raise ValueError('field shape does not match the source coordinates')
     nfield = int(np.prod(shp[:-2], dtype=np.int64)) if len(shp) > 2 else 1
-    d_src = _dev(ctx, field, dt)
-    out = ctx.empty(shp[:-2] + (len(targ_lat), len(targ_lon)), dt)
+    d_src = ops.dev('field')
+    out = ctx.empty(shp[:-2] + (len(targ_lat), len(targ_lon)), ops.result)
     c = {k: np.ascontiguousarray(v) for k, v in tb.items() if isinstance(v, np.ndarray)}
     ctx._check(ctx.lib.pgw_regrid_bilinear(
-        ctx.handle, dtype_tag(dt), nfield, nlat_s, nlon_s, len(targ_lat), len(targ_lon), d_src.ptr,
+        ctx.handle, ops.tag('field'), nfield, nlat_s, nlon_s, len(targ_lat), len(targ_lon), d_src.ptr,
         c['lat_lo'].ctypes.data_as(_ip), c['lat_hi'].ctypes.data_as(_ip), c['lat_dx'].ctypes.data_as(_dp),
         c['lat_Dx'].ctypes.data_as(_dp), c['lat_oob'].ctypes.data_as(_ip),
         c['lon_lo'].ctypes.data_as(_ip), c['lon_hi'].ctypes.data_as(_ip), c['lon_dx'].ctypes.data_as(_dp),
         c['lon_Dx'].ctypes.data_as(_dp), c['lon_oob'].ctypes.data_as(_ip),
         tb['south_row'], tb['north_row'], out.ptr))
-    return _out(ctx, out, field)
+    return out_like(out, field)
 
 
 # ------------------------------------------------------------------------------- delta files
@@ -825,18 +628,18 @@ def smooth_annual_cycle(diff):
     the array form of filter_data (reference functions.py:603-669).  Returns the kind of `diff` (host array, labelled
     array or DeviceArray), same dtype."""
     ctx = default_context()
-    r = _raw(diff)
+    r = raw(diff)
     if len(r.shape) not in (3, 4):
         raise ValueError('Wrong dimensions of input file should be 3 or 4-D')          # :648
-    dtype = _common_dtype(diff)
+    ops = OperandPlan(ctx, 'smooth_annual_cycle', diff=diff)
     lt = int(r.shape[0])
     inner = int(np.prod(r.shape[1:], dtype=np.int64))
     cos_t, sin_t = harmonic_tables(max(lt, 1))
-    d_in = _dev(ctx, diff, dtype)
-    d_out = ctx.empty(r.shape, dtype)
-    ctx._check(ctx.lib.pgw_harmonic_smooth(ctx.handle, dtype_tag(dtype), lt, inner, cos_t.ctypes.data_as(_lib._dp),
-                                           sin_t.ctypes.data_as(_lib._dp), d_in.ptr, d_out.ptr))
-    return _out(ctx, d_out, diff)
+    d_in = ops.dev('diff')
+    d_out = ctx.empty(r.shape, ops.result)
+    ctx._check(ctx.lib.pgw_harmonic_smooth(ctx.handle, ops.tag('diff'), lt, inner, cos_t.ctypes.data_as(_dp),
+                                           sin_t.ctypes.data_as(_dp), d_in.ptr, d_out.ptr))
+    return out_like(d_out, diff)
 
 
 def harmonic_ac_analysis(ts):

@@ -290,7 +290,7 @@ def _worker(rank, world, func, tasks, queue):
         queue.put((rank, [], '%s: %s' % (type(e).__name__, e)))
 
 
-def _dist_env():
+def dist_env():
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     return rank, world
@@ -337,7 +337,7 @@ class IterMP:
 
     def run(self, func, fargs={}, step_args=None):
         tasks = _merge(fargs, step_args or [])
-        rank, world = _dist_env()
+        rank, world = dist_env()
         if world > 1:
             self.output = self._run_distributed(func, tasks, rank, world)
         elif self.njobs > 1 and len(tasks) > 1:

@@ -27,25 +27,21 @@ Array kinds as in `functions.py`: numpy, `ncio.Field` (labels re-wrapped) or `De
 Files are NetCDF-3 through `ncio` like everywhere in this package.
 """
 import argparse
-import ctypes as C
 import os
 
 import numpy as np
 
 from . import _lib, ncio
 from .device import DeviceArray, default_context, dtype_tag
-from .functions import _check_extrapolate, _dev, _is_labelled, _raw
+from ._lib import _dp, _ip
+from .operands import F32, F64, check_extrapolate, dev, is_labelled, out_like, raw
 from .settings import LAT_GCM, LEV_GCM, LON_GCM, PLEV_GCM, TIME_GCM
-
-_dp = C.POINTER(C.c_double)
-_ip = C.POINTER(C.c_int)
-_F32, _F64 = np.dtype('float32'), np.dtype('float64')
 
 MAX_LEVELS = 256          # nsrc, ntarg, nplev limit of the kernels (include/pgw_hip.h)
 
 
 def _f64(x, name):
-    a = np.ascontiguousarray(_raw(x), dtype=np.float64)
+    a = np.ascontiguousarray(raw(x), dtype=np.float64)
     if a.ndim != 1:
         raise ValueError('%s must be one-dimensional' % name)
     return a
@@ -81,9 +77,9 @@ def _hybrid_args(var_dtype, ps_dtype, S, ap, b, targ_plev, out_dtype):
     if not 1 <= len(targ) <= MAX_LEVELS:
         raise ValueError('between 1 and %d target levels are supported, got %d' % (MAX_LEVELS, len(targ)))
     # float32 var with float32 ps is the CFday file's dtype flow; anything mixed is computed in float64
-    dt = _F32 if (np.dtype(var_dtype) == _F32 and np.dtype(ps_dtype) == _F32) else _F64
-    odt = _F64 if out_dtype is None else np.dtype(out_dtype)
-    if odt not in (_F32, _F64) or (odt == _F32 and dt != _F32):
+    dt = F32 if (np.dtype(var_dtype) == F32 and np.dtype(ps_dtype) == F32) else F64
+    odt = F64 if out_dtype is None else np.dtype(out_dtype)
+    if odt not in (F32, F64) or (odt == F32 and dt != F32):
         raise ValueError('out_dtype: float64, or float32 for float32 input')
     return ap, b, targ, dt, odt
 
@@ -102,8 +98,8 @@ def interp_to_plev(var, ps, ap, b, targ_plev, extrapolate='constant', lev_descen
     out_dtype='float32' (float32 input only) narrows that float64 result on the store: half the output, not the
     reference's bits.
     Labelled input comes back as `ncio.Field` on (time, plev, lat, lon) with the `plev` coordinate."""
-    mode = _check_extrapolate(extrapolate)
-    rv, rp = _raw(var), _raw(ps)
+    mode = check_extrapolate(extrapolate)
+    rv, rp = raw(var), raw(ps)
     if len(rv.shape) != 4:
         raise ValueError('expected a 4-D (time, lev, lat, lon) array, got shape %s' % (rv.shape,))
     nt, S, nlat, nlon = rv.shape
@@ -112,13 +108,13 @@ def interp_to_plev(var, ps, ap, b, targ_plev, extrapolate='constant', lev_descen
     ap, b, targ, dt, odt = _hybrid_args(rv.dtype, rp.dtype, S, ap, b, targ_plev, out_dtype)
     src_rev = levels_descend(ap, b) if lev_descending is None else bool(lev_descending)
     ctx = default_context()
-    d_var, d_ps = _dev(ctx, var, dt), _dev(ctx, ps, dt)
+    d_var, d_ps = dev(ctx, var, dt), dev(ctx, ps, dt)
     out = ctx.empty((nt, len(targ), nlat, nlon), odt)
     _launch_hybrid(ctx, d_var, d_ps, ap, b, targ, mode, src_rev, plev_descending, out)
     if isinstance(rv, DeviceArray):
         return out
     host = out.numpy()
-    if _is_labelled(var):
+    if is_labelled(var):
         dims = tuple(var.dims)
         coords = {d: var.coords[d] for d in (dims[0], dims[2], dims[3]) if d in getattr(var, 'coords', {})}
         coords[PLEV_GCM] = targ[::-1].copy() if plev_descending else targ
@@ -153,7 +149,7 @@ def interp_file(inp_path, out_path, var_name, targ_plev, extrapolate='constant',
 
     The file goes through in blocks of time records (`ncio.RecordReader`), so it may be larger than the card's memory;
     `max_records` caps the block (the results do not depend on it)."""
-    mode = _check_extrapolate(extrapolate)
+    mode = check_extrapolate(extrapolate)
     targ = load_target_plev(targ_plev) if isinstance(targ_plev, (str, os.PathLike)) else np.sort(_f64(targ_plev, 'targ_plev'))
     ds = ncio.open_dataset(inp_path, decode_times=False, skip=(var_name, 'ps'))
     for need in (var_name, 'ps', 'ap', 'b'):
@@ -207,11 +203,11 @@ def specific_to_relative_humidity(QV, P, T):
     first, :53-55; a 4-D P whose columns all hold that list is accepted and reduced to it).  The result is float64 as
     numpy gives it with a float64 P: on float32 QV / T the exponent, exp and the reciprocal are float32 operations, the
     products float64."""
-    rq, rt = _raw(QV), _raw(T)
+    rq, rt = raw(QV), raw(T)
     if tuple(rq.shape) != tuple(rt.shape) or len(rq.shape) != 4:
         raise ValueError('QV and T must be 4-D (time, plev, lat, lon) arrays of one shape')
     nt, nplev, nlat, nlon = rq.shape
-    p = np.asarray(_raw(P), dtype=np.float64) if not isinstance(_raw(P), DeviceArray) else _raw(P).numpy().astype(np.float64)
+    p = np.asarray(raw(P), dtype=np.float64) if not isinstance(raw(P), DeviceArray) else raw(P).numpy().astype(np.float64)
     if p.ndim == 4:
         if p.shape != tuple(rq.shape) or not np.array_equal(p, np.broadcast_to(p[0, :, 0, 0][None, :, None, None], p.shape), equal_nan=True):
             raise ValueError('a 4-D P must hold the same pressure list in every column')
@@ -219,15 +215,12 @@ def specific_to_relative_humidity(QV, P, T):
     p = np.ascontiguousarray(p.reshape(-1))
     if len(p) != nplev or nplev > MAX_LEVELS:
         raise ValueError('P must hold the %d pressure levels of QV (at most %d)' % (nplev, MAX_LEVELS))
-    dt = _F32 if (rq.dtype == _F32 and rt.dtype == _F32) else _F64
+    dt = F32 if (rq.dtype == F32 and rt.dtype == F32) else F64
     ctx = default_context()
-    d_q, d_t = _dev(ctx, QV, dt), _dev(ctx, T, dt)
-    out = ctx.empty(rq.shape, _F64)
+    d_q, d_t = dev(ctx, QV, dt), dev(ctx, T, dt)
+    out = ctx.empty(rq.shape, F64)
     ctx._check(ctx.lib.pgw_magnus_rh(ctx.handle, dtype_tag(dt), nt, nplev, nlat * nlon, d_q.ptr, _cdp(p), d_t.ptr, out.ptr))
-    if isinstance(rq, DeviceArray):
-        return out
-    host = out.numpy()
-    return QV.like(host) if (_is_labelled(QV) and hasattr(QV, 'like')) else host
+    return out_like(out, QV)
 
 
 def merge_level_table(plev, amon_plev):
@@ -281,9 +274,9 @@ def merge_hur_levels(hur, plev, amon_hur, amon_plev):
         plev = hur.coords[PLEV_GCM]
     if amon_plev is None:
         amon_plev = amon_hur.coords[PLEV_GCM]
-    if _is_labelled(hur) and _is_labelled(amon_hur):
+    if is_labelled(hur) and is_labelled(amon_hur):
         _same_coords(hur, amon_hur, 'merge_hur_levels')
-    rh, ra = _raw(hur), _raw(amon_hur)
+    rh, ra = raw(hur), raw(amon_hur)
     if len(rh.shape) != 4 or len(ra.shape) != 4:
         raise ValueError('hur and amon_hur must be 4-D (time, plev, lat, lon)')
     nt, nplev, nlat, nlon = rh.shape
@@ -292,17 +285,14 @@ def merge_hur_levels(hur, plev, amon_hur, amon_plev):
     tabs = merge_level_table(plev, amon_plev)
     if len(tabs[0]) != nplev or len(_f64(amon_plev, 'amon_plev')) != ra.shape[1] or nplev > MAX_LEVELS:
         raise ValueError('plev / amon_plev do not match the level axes of the fields')
-    adt = _F32 if ra.dtype == _F32 else _F64
+    adt = F32 if ra.dtype == F32 else F64
     ctx = default_context()
-    d_h, d_a = _dev(ctx, hur, _F64), _dev(ctx, amon_hur, adt)
-    out = ctx.empty(rh.shape, _F64)
+    d_h, d_a = dev(ctx, hur, F64), dev(ctx, amon_hur, adt)
+    out = ctx.empty(rh.shape, F64)
     ti = [np.ascontiguousarray(t, dtype=np.int32) for t in tabs]
     ctx._check(ctx.lib.pgw_hur_merge_levels(ctx.handle, dtype_tag(adt), nt, nplev, ra.shape[1], nlat * nlon, d_h.ptr, d_a.ptr,
                                             *[t.ctypes.data_as(_ip) for t in ti], out.ptr))
-    if isinstance(rh, DeviceArray):
-        return out
-    host = out.numpy()
-    return hur.like(host) if (_is_labelled(hur) and hasattr(hur, 'like')) else host
+    return out_like(out, hur)
 
 
 def hus_to_hur_file(hus_file, ta_file, hur_file, amon_hur_file):
@@ -359,9 +349,9 @@ def calendar_bins(time_values, units, calendar, mode, years=None):
 
 
 def _clim_dtypes(in_dtype, out_dtype):
-    dt = _F32 if np.dtype(in_dtype) == _F32 else _F64
+    dt = F32 if np.dtype(in_dtype) == F32 else F64
     odt = dt if out_dtype is None else np.dtype(out_dtype)
-    if odt not in (_F32, _F64) or (odt == _F32 and dt != _F32):
+    if odt not in (F32, F64) or (odt == F32 and dt != F32):
         raise ValueError('out_dtype: the input dtype, or float64 for float32 input')
     return dt, odt
 
@@ -391,7 +381,7 @@ class _BinMean:
             part = records[r0:r0 + self.nb]
             first, last = r0 == 0, r0 + len(part) == n
             if not (first and last) and self.sum is None:
-                self.sum, self.cnt = self.ctx.empty(self.rec_shape, _F64), self.ctx.empty(self.rec_shape, np.int32)
+                self.sum, self.cnt = self.ctx.empty(self.rec_shape, F64), self.ctx.empty(self.rec_shape, np.int32)
             d_x = fill(self.chunk, part)
             if d_x is None:
                 d_x = self.chunk if len(part) == self.nb else DeviceArray(self.ctx, (len(part),) + self.rec_shape, self.dt,
@@ -414,7 +404,7 @@ def climatology(x, bin_of_record, nbin, out_dtype=None, max_records=None):
     out_dtype: the input's (default), or float64 for float32 input.  max_records caps the records per launch (a longer
     bin carries its sum on the device; the results do not depend on it).
     numpy, `ncio.Field` (labels re-wrapped, without the time coordinate) or `DeviceArray` in, the same kind out."""
-    rx = _raw(x)
+    rx = raw(x)
     if len(rx.shape) < 1 or rx.shape[0] != len(np.asarray(bin_of_record).reshape(-1)):
         raise ValueError('bin_of_record must have one entry per record of x')
     nbin = int(nbin)
@@ -459,7 +449,7 @@ def climatology(x, bin_of_record, nbin, out_dtype=None, max_records=None):
     if on_device:
         return out
     res = out.numpy()
-    if _is_labelled(x):
+    if is_labelled(x):
         dims = tuple(x.dims)
         coords = {d: v for d, v in getattr(x, 'coords', {}).items() if d in dims[1:]}
         return ncio.Field(res, dims, coords, dict(getattr(x, 'attrs', {})), getattr(x, 'name', None))

@@ -23,10 +23,9 @@ import numpy as np
 
 from . import _lib
 from . import settings as S
+from ._lib import _dp
 from .constants import CON_G, CON_RD   # noqa: F401
 from .device import DeviceArray, default_context, dtype_tag, ptr
-
-_dp = C.POINTER(C.c_double)
 
 
 # ----------------------------------------------------------------------------------------
@@ -1073,8 +1072,8 @@ def _cli(argv=None):
 
 def _run_banded(fargs, step_args):
     """`--bands`: all ranks of the torch.distributed.run launch work on ONE file at a time, in latitude bands."""
-    from .parallel import _dist_env, band_max_hook, bind_rank_to_numa
-    rank, world = _dist_env()
+    from .parallel import band_max_hook, dist_env, bind_rank_to_numa
+    rank, world = dist_env()
     if fargs.get('debug_mode') is not None:
         raise NotImplementedError('debug_mode is a validation aid of the reference and not part of the MI355X hot path')
     if world == 1:

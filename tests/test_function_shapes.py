@@ -1,76 +1,22 @@
 """CPU tests of the operand-shape checks of the functions.py mirror.  The flat and column kernels are sized by one operand
 and index every other one as if it had the same shape, so a shorter operand would be read past its end on the device.
-A stand-in context (no GPU) records every library call and every upload: a bad shape must raise ValueError before any of
-them, and a host operand that broadcasts must reach the kernel entry at full size, as numpy's arithmetic would see it."""
-import ctypes as C
+A stand-in context (no GPU, tests/function_recorder.py) records every library call and every upload: a bad shape must raise
+ValueError before any of them, and a host operand that broadcasts must reach the kernel entry at full size, as numpy's
+arithmetic would see it."""
+import os
+import sys
 
 import numpy as np
 import pytest
 
-
-class _Lib:
-    """Records every pgw_* call; the copies move bytes between host memory and the stand-in's buffers."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-
-    def pgw_memcpy_d2h(self, handle, dst, src, nbytes):
-        buf = self.ctx.mem[src]
-        C.memmove(dst, buf.ctypes.data, nbytes)
-        return 0
-
-    def __getattr__(self, name):
-        if not name.startswith('pgw_'):
-            raise AttributeError(name)
-
-        def call(*args):
-            self.ctx.calls.append((name, args))
-            return 0
-        return call
-
-
-class _Ctx:
-    """Device memory is a dict of host arrays keyed by a fake address (16-byte aligned, never 0)."""
-
-    def __init__(self):
-        self.handle, self._live, self.nlev = 1, 0, 0
-        self.lib = _Lib(self)
-        self.mem, self.calls, self.uploads = {}, [], []
-        self._next = 4096
-
-    def _alloc(self, host):
-        from pgw4era5_amd.device import DeviceArray
-        p = self._next
-        self._next += (host.nbytes + 15) // 16 * 16 + 16
-        self.mem[p] = host
-        return DeviceArray(self, host.shape, host.dtype, ptr=p, owner=self)
-
-    def _check(self, rc):
-        assert rc == 0
-
-    def sync(self):
-        pass
-
-    def empty(self, shape, dtype):
-        return self._alloc(np.zeros(shape, dtype))
-
-    def to_device(self, host, dtype=None):
-        host = np.array(host, dtype=dtype or host.dtype, order='C')
-        self.uploads.append(host.shape)
-        return self._alloc(host)
-
-    def device(self, shape, dtype=np.float64):
-        """A DeviceArray operand made by the test itself (not counted as an upload of the call under test)."""
-        return self._alloc(np.ones(shape, dtype))
-
-    def entries(self):
-        return [n for n, _ in self.calls]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from function_recorder import RecordingContext                                       # noqa: E402
 
 
 @pytest.fixture
 def ctx(monkeypatch):
     from pgw4era5_amd import functions
-    c = _Ctx()
+    c = RecordingContext()
     monkeypatch.setattr(functions, 'default_context', lambda: c)
     return c
 

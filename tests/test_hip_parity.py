@@ -503,7 +503,7 @@ def test_regrid_full_size_config4_properties_and_band(F):
 class FakeDataArray:
     """Stand-in for xarray.DataArray (not installable here): `.values/.dims/.coords/.shape/.dtype`, `.copy(data=)`,
     `.transpose(*dims)`, `.isel`, `len()` - what the reference's step_03 lines touch on the results of the functions
-    below.  NOT an ncio.Field: no `.like`, so functions._out must take the `.copy(data=)` route."""
+    below.  NOT an ncio.Field: no `.like`, so operands.out_like must take the `.copy(data=)` route."""
 
     def __init__(self, values, dims, coords=None):
         self.values = np.asarray(values)

@@ -44,6 +44,7 @@ def main():
     a = p.parse_args()
     from pgw4era5_amd import step_01_extract_deltas as s1
     from pgw4era5_amd.device import DeviceArray, default_context
+    from pgw4era5_amd.operands import check_extrapolate
     ctx = default_context()
     if a.vec1:
         ctx.set_option('force_vec1', 1)
@@ -55,7 +56,7 @@ def main():
     rng = np.random.default_rng(0)
     res = dict(device=ctx.device_name(), S=S, N=N, ncol=ncol, runs=a.runs, ps='random' if a.random_ps else 'smooth',
                force_vec1=bool(a.vec1), cases={})
-    mode = s1._check_extrapolate('constant')
+    mode = check_extrapolate('constant')
     for tag, dt, odt in (('F32->F64', np.float32, np.float64), ('F64->F64', np.float64, np.float64)):
         s_in, s_out = np.dtype(dt).itemsize, np.dtype(odt).itemsize
         nrec = int(np.ceil(a.gbytes * 1e9 / (S * ncol * s_in)))
