@@ -64,8 +64,8 @@ enum pgw_kernel_id {
     PGW_K_THERMO_DELTA = 11, PGW_K_WIND_DELTA = 12, PGW_K_PHI_REF_HYBRID = 13, PGW_K_QUAD_DELTA = 14,
     PGW_K_BYTESWAP = 15, PGW_K_HARMONIC = 16, PGW_K_GAUSS_INTERP = 17, PGW_K_PS_LOOP_MULTI = 18,
     PGW_K_HYBRID_TO_PLEV = 19, PGW_K_MAGNUS_RH = 20, PGW_K_HUR_MERGE = 21,
-    PGW_K_CLIM_ACCUMULATE = 22, PGW_K_FIELD_SUB = 23, PGW_K_CLIM_READ = 24,
-    PGW_K_COUNT = 25
+    PGW_K_CLIM_ACCUMULATE = 22, PGW_K_FIELD_SUB = 23, PGW_K_CLIM_READ = 24, PGW_K_DELTA_FIELDS = 25,
+    PGW_K_COUNT = 26
 };
 
 /* per-context options (pgw_set_option).  Defaults come from the environment variables named below, which are read
@@ -423,6 +423,40 @@ int pgw_surface_update(pgw_ctx *ctx, int dtype, int ntime, long long ncol, int n
                        const void *sic, const void *dsic, const void *dtos, const void *dts,
                        const void *land, const void *ts_clim, const void *tskin, const void *tso,
                        void *sic_out, void *dts_comb_out, void *tskin_out, void *tso_out);
+
+/* ---------------------------------------------------------------- debug mode --------- */
+/* step_03 --debug_mode interpolate_full (step_03_apply_to_era.py:350-361): the deltas the reference writes instead of the
+ * ERA5 file, as arrays.  Both entries are synchronous function-level calls beside the whole-file entry; the whole-file entry
+ * does not use them.
+ *
+ * The four deltas of load_delta_interp (functions.py:306-340) on the model-level pressures akm + ps*bkm (tables of
+ * the last set_levels call), one kernel: the values the whole-file entry adds to T, RELHUM, U, V, with its
+ * expressions (time interpolation of the records, surface insertion for ta / hur from tas / hurs / ps_hist, the column
+ * interpolation in ln p), so `era + delta` in numpy reproduces its outputs bit for bit.  Records (ntime, nplev, ncol) /
+ * (ntime, ncol) in `dtype`, `*_a` unused when x_hi == 0 (the instant is a record); ps in `dtype`: PS of the file, or the
+ * converged ps_pgw under settings.i_reinterp = 1 (step_03:212-216, 336-343).  ref_dtype = 1 (dtype PGW_F32 only): the
+ * reference's dtype flow on float32 files.  Outputs (ntime, nlev, ncol) are float64 for every dtype
+ * (xr.zeros_like(targ_P), functions.py:472-473).  Status codes and error columns as vert_interp_delta reports them for ta / hur:
+ * PGW_ERR_PS_HIST_ABOVE_TOP (ps_hist not above min(plev), or NaN), PGW_ERR_TOP_PRESSURE unless ignore_top; target levels
+ * that do not ascend restart the scan as there. */
+int pgw_delta_fields(pgw_ctx *ctx, int dtype, int ref_dtype, int ntime, int nlev, int nplev, long long ncol,
+                     const double *plev, const void *ps,
+                     const void *ta_b, const void *ta_a, const void *hur_b, const void *hur_a,
+                     const void *ua_b, const void *ua_a, const void *va_b, const void *va_a,
+                     const void *tas_b, const void *tas_a, const void *hurs_b, const void *hurs_a,
+                     const void *pshist_b, const void *pshist_a, double x_hi, double x_new, int ignore_top,
+                     double *dta, double *dhur, double *dua, double *dva);
+
+/* delta_ts_combined = integrate_tos(delta_tos, delta_ts, land, clip(sic + delta_siconc/100, 0, 1) of time 0)
+ * (step_03:103-125) and delta_soilt[s] = clim + exp(-soil_depth[s]/2.8) * (delta_ts_combined - clim) (:139-143), float64
+ * (ntime, ncol) and (ntime, nsoil, ncol); delta_soilt may be NULL.  The three 2-D deltas come as record pairs, each with the
+ * abscissae of its own time axis, and are interpolated in the kernel as the whole-file entry does. */
+int pgw_surface_deltas(pgw_ctx *ctx, int dtype, int ref_dtype, int ntime, long long ncol, int nsoil,
+                       const double *soil_depth, const void *sic,
+                       const void *siconc_b, const void *siconc_a, double siconc_x_hi, double siconc_x_new,
+                       const void *tos_b, const void *tos_a, double tos_x_hi, double tos_x_new,
+                       const void *ts_b, const void *ts_a, double ts_x_hi, double ts_x_new,
+                       const void *land, const void *ts_clim, double *dts_comb, double *delta_soilt);
 
 /* Spectral smoothing of a daily annual cycle, step_02 `smoothing`: filter_data / harmonic_ac_analysis,
  * functions.py:603-740.  in / out: (ntime, inner) C-order, inner = product of the non-time dimensions; every

@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -935,6 +936,50 @@ extern "C" int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int npl
     HIPCHK(ctx, hipGetLastError());
     rc = status_check(ctx);
     if (rc) return rc;
+    return top_pressure_check(ctx, ignore_top);
+}
+
+// step_03 --debug_mode interpolate_full: the four deltas of load_delta_interp on the model levels of `ps`, one launch
+extern "C" int pgw_delta_fields(pgw_ctx *ctx, int dtype, int ref_dtype, int ntime, int nlev, int nplev, long long ncol,
+                                const double *plev, const void *ps, const void *ta_b, const void *ta_a, const void *hur_b,
+                                const void *hur_a, const void *ua_b, const void *ua_a, const void *va_b, const void *va_a,
+                                const void *tas_b, const void *tas_a, const void *hurs_b, const void *hurs_a,
+                                const void *pshist_b, const void *pshist_a, double x_hi, double x_new, int ignore_top,
+                                double *dta, double *dhur, double *dua, double *dva) {
+    CHECK_COMMON(ctx, dtype, ntime, ncol);
+    const bool ref = ref_dtype != 0;
+    NEED(ctx, !ref || dtype == PGW_F32, "ref_dtype = 1 is the float32-file mode: dtype must be PGW_F32");
+    NEED(ctx, ctx->nlev > 0 && nlev == ctx->nlev, "nlev must match pgw_set_levels");
+    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, plev && ps && ta_b && hur_b && ua_b && va_b && tas_b && hurs_b && pshist_b, "null pointer");
+    NEED(ctx, x_hi == 0.0 || (ta_a && hur_a && ua_a && va_a && tas_a && hurs_a && pshist_a), "record after the instant is NULL");
+    NEED(ctx, dta && dhur && dua && dva, "output pointer is NULL");
+    int rc = plev_table(ctx, nplev, plev);
+    if (rc) return rc;
+    if ((rc = status_reset(ctx))) return rc;
+    const Levels lv = levels_of(ctx);
+    const long long total = (long long)ntime * ncol;
+    // O: 32-bit byte offsets while the largest array (a float64 output, or the records) stays below 4 GiB
+    const unsigned long long big = (unsigned long long)ntime * ncol *
+                                   std::max((unsigned long long)nlev * sizeof(double), (unsigned long long)nplev * elem_size(dtype));
+    const bool o32 = !ctx->opt[PGW_OPT_FORCE_OFF64] && big < (1ull << 32);
+    {
+        Prof pr(ctx, PGW_K_DELTA_FIELDS);
+        with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
+            using T = decltype(t_);
+            const PairSrc<T> dth = pair_src<T>(ta_b, ta_a, hur_b, hur_a, x_hi, x_new);
+            const PairSrc<T> ds = pair_src<T>(tas_b, tas_a, hurs_b, hurs_a, x_hi, x_new);
+            const DeltaSrc<T> ph = delta_src<T>(pshist_b, pshist_a, x_hi, x_new);
+            const PairSrc<T> dwd = pair_src<T>(ua_b, ua_a, va_b, va_a, x_hi, x_new);
+            with_offsets(o32, [&](auto o_) { with_int<2>(x_hi != 0.0, [&](auto lerp_) {
+                hipLaunchKernelGGL((k_delta_fields<T, decltype(o_), decltype(lerp_)::value != 0, decltype(ref_)::value>),
+                                   dim3(nblocks(total, FIELDS_TPB)), dim3(FIELDS_TPB), 0, ctx->stream, ctx->plev_tab, lv, ntime, ncol,
+                                   (const T *)ps, dth, ds, ph, dwd, ignore_top ? 0 : 1, dta, dhur, dua, dva, ctx->n_pure, ctx->d_status);
+            }); });
+        });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if ((rc = status_check(ctx))) return rc;
     return top_pressure_check(ctx, ignore_top);
 }
 
@@ -2185,6 +2230,41 @@ extern "C" int pgw_surface_update(pgw_ctx *ctx, int dtype, int ntime, long long 
             hipLaunchKernelGGL((k_surface_update<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, ntime, ncol, st,
                                (const T *)sic, (const T *)dsic, (const T *)dtos, (const T *)dts, (const T *)land, (const T *)ts_clim,
                                (const T *)tskin, (const T *)tso, (T *)sic_out, (T *)dts_comb_out, (T *)tskin_out, (T *)tso_out);
+        });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// step_03 --debug_mode interpolate_full: delta_ts_combined (step_03:118-125) and delta_soilt (:139-143) as float64 arrays,
+// every 2-D delta on its own time axis as in pgw_step03_file
+extern "C" int pgw_surface_deltas(pgw_ctx *ctx, int dtype, int ref_dtype, int ntime, long long ncol, int nsoil,
+                                  const double *soil_depth, const void *sic, const void *siconc_b, const void *siconc_a,
+                                  double siconc_x_hi, double siconc_x_new, const void *tos_b, const void *tos_a,
+                                  double tos_x_hi, double tos_x_new, const void *ts_b, const void *ts_a, double ts_x_hi,
+                                  double ts_x_new, const void *land, const void *ts_clim, double *dts_comb,
+                                  double *delta_soilt) {
+    CHECK_COMMON(ctx, dtype, ntime, ncol);
+    const bool ref = ref_dtype != 0;
+    NEED(ctx, !ref || dtype == PGW_F32, "ref_dtype = 1 is the float32-file mode: dtype must be PGW_F32");
+    NEED(ctx, nsoil >= 0 && nsoil <= MAX_SOIL, "nsoil must be in [0, 16]");
+    NEED(ctx, sic && siconc_b && tos_b && ts_b && land && dts_comb, "null pointer");
+    NEED(ctx, (siconc_x_hi == 0.0 || siconc_a) && (tos_x_hi == 0.0 || tos_a) && (ts_x_hi == 0.0 || ts_a),
+         "record after the instant is NULL");
+    NEED(ctx, !delta_soilt || (ts_clim && soil_depth && nsoil > 0), "ts_clim, soil_depth required for delta_soilt");
+    SoilTable st;
+    memset(&st, 0, sizeof(st));
+    st.n = nsoil;
+    for (int s = 0; s < nsoil; ++s) st.w[s] = exp(-soil_depth[s] / 2.8);      // step_03:140
+    const long long n = (long long)ntime * ncol;
+    {
+        Prof pr(ctx, PGW_K_SURFACE);
+        with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_surface_deltas<T, decltype(ref_)::value>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream,
+                               ntime, ncol, st, (const T *)sic, delta_src<T>(siconc_b, siconc_a, siconc_x_hi, siconc_x_new),
+                               delta_src<T>(tos_b, tos_a, tos_x_hi, tos_x_new), delta_src<T>(ts_b, ts_a, ts_x_hi, ts_x_new),
+                               (const T *)land, (const T *)ts_clim, dts_comb, delta_soilt);
         });
     }
     HIPCHK(ctx, hipGetLastError());

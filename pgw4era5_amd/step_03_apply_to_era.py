@@ -932,7 +932,13 @@ def pgw_for_era5(inp_era_file_path, out_era_file_path, delta_input_dir, era_step
     """Apply the PGW deltas to one ERA5 file (reference step_03_apply_to_era.py:44-381).
     Returns the number of loop passes.  When many files are processed through IterMP the three
     stages below run as a pipeline (read of file i+1 and write of file i-1 overlap the GPU work of
-    file i; SURVEY.md section 8 f rank 1)."""
+    file i; SURVEY.md section 8 f rank 1).
+    debug_mode = 'interpolate_full' (step_03:350-361): the same computation, then the seven deltas are written instead of
+    the ERA5 file - step_03_debug.debug_interpolate_full, synchronous, outside the stages (which refuse a debug mode)."""
+    if debug_mode == 'interpolate_full':
+        from .step_03_debug import debug_interpolate_full
+        return debug_interpolate_full(inp_era_file_path, out_era_file_path, delta_input_dir, era_step_dt,
+                                      ignore_top_pressure_error, debug_mode)
     return _stage_store(_stage_download(_stage_compute(_stage_upload(_stage_load(
         inp_era_file_path, out_era_file_path, delta_input_dir, era_step_dt, ignore_top_pressure_error, debug_mode)))))
 
@@ -1032,9 +1038,12 @@ def _cli(argv=None):
     p.add_argument('-t', '--ignore_top_pressure_error', action='store_true',
                    help='do not fail if ERA5 reaches higher than the climate deltas')
     p.add_argument('-D', '--debug_mode', type=str, default=None,
-                   help='interpolate_time | interpolate_full: the reference dumps the deltas instead of the ERA5 files '
-                        '(step_03_apply_to_era.py:350-361, 387-414) - a validation aid, NOT built here: the run stops with '
-                        'NotImplementedError')
+                   help='write the climate deltas instead of the ERA5 files, to compare with the reference\'s -D output '
+                        '(tools/compare_deltas.py).  interpolate_time: every delta interpolated in time only, '
+                        'delta_{var}_{file} for tos, tas, hurs, ps, ta, hur, ua, va, zg (step_03_apply_to_era.py:387-414).  '
+                        'interpolate_full: the deltas the run adds, on the model levels, {VAR}_delta_{file} for PS, T, RELHUM, '
+                        'U, V, T_SO, T_SKIN (:350-361).  NetCDF-3 files beside the output path; one file at a time per rank; '
+                        'not with --bands')
     p.add_argument('--bands', action='store_true',
                    help='latency mode: EVERY file is split over all ranks in latitude bands (each rank reads, computes and '
                         'writes its rows; one MAX all-reduce per loop launch) instead of file i -> rank i mod W.  Needs the '
@@ -1065,8 +1074,13 @@ def _cli(argv=None):
                       era_step_dt=s) for s in steps]
     if args.bands:
         return _run_banded(fargs, step_args)
+    func = pgw_for_era5
+    if args.debug_mode is not None:                         # step_03:630-635; functions without `stages`: never pipelined
+        from . import step_03_debug
+        func = (step_03_debug.debug_interpolate_time if args.debug_mode == 'interpolate_time'
+                else step_03_debug.debug_interpolate_full)
     imp = IterMP(njobs=args.n_par, run_async=True)
-    imp.run(pgw_for_era5, fargs, step_args)
+    imp.run(func, fargs, step_args)
     return imp.output
 
 
