@@ -65,7 +65,8 @@ enum pgw_kernel_id {
     PGW_K_BYTESWAP = 15, PGW_K_HARMONIC = 16, PGW_K_GAUSS_INTERP = 17, PGW_K_PS_LOOP_MULTI = 18,
     PGW_K_HYBRID_TO_PLEV = 19, PGW_K_MAGNUS_RH = 20, PGW_K_HUR_MERGE = 21,
     PGW_K_CLIM_ACCUMULATE = 22, PGW_K_FIELD_SUB = 23, PGW_K_CLIM_READ = 24, PGW_K_DELTA_FIELDS = 25,
-    PGW_K_COUNT = 26
+    PGW_K_CELL_LOCATE = 26, PGW_K_REGRID_SPARSE = 27,
+    PGW_K_COUNT = 28
 };
 
 /* per-context options (pgw_set_option).  Defaults come from the environment variables named below, which are read
@@ -92,7 +93,9 @@ enum pgw_option {
     PGW_OPT_MIXED_VEC = 8,    /* columns / elements per thread of the `_mixed` entries (operands of different element size), cap:
                                  4 (default): a float32 row is one 16-byte access per lane, a float64 row beside it two; 2: 8 and
                                  16 bytes; 1: scalar.  A/B knob of tools/function_flow_time.py                                       */
-    PGW_OPT_COUNT = 9
+    PGW_OPT_SPARSE_DIRECT = 9, /* test knob, default 0: pgw_regrid_sparse stages a block's source window in LDS when it fits; 1: every
+                                 block gathers from memory.  Same bits either way                                                     */
+    PGW_OPT_COUNT = 10
 };
 
 /* ---------------------------------------------------------------- context ------------ */
@@ -412,6 +415,35 @@ int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, i
                         const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
                         const int *lon_oob,
                         int south_row, int north_row, void *out);
+
+/* regrid_lat_lon, xESMF branch (functions.py:797-810, settings.py:117-129): what `xe.Regridder(ds_in, ds_era5, "bilinear",
+ * periodic=periodic_lon)` (:799-800) asks ESMF for and `regridder(ds_in[var_name])` (:802) applies, for source grids with
+ * 2-D coordinates (rotated-pole, curvilinear).  Bilinear on the unit sphere in 3-D Cartesian space, cell edges being chords;
+ * the definition (patch, Newton solve, Cramer order, tolerances, pole caps, lowest accepting cell) is written out above
+ * k_cell_locate in pgw4era5_amd/csrc/pgw_kernels.h and restated in numpy in tests/test_regrid_curvilinear_host.py.  Parity
+ * with ESMF itself is unpinned.  PRECONDITIONS: cells are convex and smaller than a hemisphere; concave
+ * cells are not detected.  All pointers are DEVICE pointers except n_unmapped.
+ *
+ * Locate (:799-800), once per grid pair.  P (ntarg, 3): target unit vectors.  X (ny*nx, 3), or (ny*nx + 2, 3) when
+ * periodic: source node unit vectors (cos lat cos lon, cos lat sin lon, sin lat), formed by the caller; when periodic, the
+ * two appended vectors are the poles of the caps, normalise(sum_i X[je, i]) of row je = 0 and of row ny - 1.  Buckets: a
+ * uniform nb^3 grid over [-1, 1]^3, bucket id = (bx * nb + by) * nb + bz with b = clamp((int)((x + 1) * 0.5 * nb), 0, nb - 1);
+ * bucket_start (nb^3 + 1), bucket_cells: per bucket, ASCENDING, every cell whose bounding box - enlarged by the radial bulge
+ * of its patch and the acceptance tolerance - touches it (pgw4era5_amd.functions.curvilinear_buckets).  Cells: quads
+ * j * ncx + i (ncx = nx when periodic, else nx - 1), then the nx cap triangles of row 0 and those of row ny - 1 (periodic
+ * only).  Results: idx (ntarg, 4) source node of each entry, -1 = absent (never read), ny*nx / ny*nx + 1 = the pole nodes;
+ * w (ntarg, 4); *n_unmapped = targets no cell accepts (four -1).  Synchronous. */
+int pgw_bilinear_locate(pgw_ctx *ctx, long long ntarg, const double *P, int ny, int nx, int periodic, const double *X,
+                        int nb, const int *bucket_start, const int *bucket_cells, int *idx, double *w,
+                        long long *n_unmapped);
+
+/* Apply (:802).  src (nfield, ny, nx), out (nfield, ntarg) in `dtype`; out[f, g] = w0*v0, then + wk*vk over the present
+ * entries in order, in float64 on the stored values, stored in `dtype`; NaN in a present entry gives NaN (xESMF
+ * skipna=False); an unmapped target gets 0.0 (xESMF 0.6.2, environment.yml:177), NaN with unmapped_nan != 0.  A pole node's
+ * value is the plain mean of its row, (sum_i v[je, i]) / nx in index order, NaN propagating.  Entries outside
+ * [-1, ny*nx + 2) count as absent. */
+int pgw_regrid_sparse(pgw_ctx *ctx, int dtype, long long nfield, int ny, int nx, long long ntarg, const void *src,
+                      const int *idx, const double *w, int unmapped_nan, void *out);
 
 /* ---------------------------------------------------------------- surface riders ----- */
 /* a9 step_03_apply_to_era.py:103-146 + integrate_tos functions.py:1145-1186, 2-D fields (n = ntime*ncol)

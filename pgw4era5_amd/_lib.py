@@ -24,10 +24,11 @@ EXTRAP = {'off': 0, 'linear': 1, 'constant': 2, 'nan': 3}
 KERNEL_IDS = dict(pressure=0, q_to_rh=1, rh_to_q=2, integ_geopot=3, interp_logp=4, time_lerp=5,
                   vert_interp_delta=6, adjust_ps_step=7, regrid=8, surface=9, finalize=10,
                   thermo_delta=11, wind_delta=12, phi_ref_hybrid=13, quad_delta=14, byteswap=15, harmonic=16, gauss_interp=17, ps_loop_multi=18,
-                  hybrid_to_plev=19, magnus_rh=20, hur_merge=21, clim_accumulate=22, field_sub=23, clim_read=24, delta_fields=25)
+                  hybrid_to_plev=19, magnus_rh=20, hur_merge=21, clim_accumulate=22, field_sub=23, clim_read=24, delta_fields=25,
+                  cell_locate=26, regrid_sparse=27)
 
 # enum pgw_option (include/pgw_hip.h)
-OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7, mixed_vec=8)
+OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7, mixed_vec=8, sparse_direct=9)
 
 PGW_OK = 0
 PGW_ERR_HIP = 1
@@ -156,6 +157,9 @@ SIGNATURES['pgw_test_read_records'] = (_i, [_vp, _i, _i, _ll, _vp])
 SIGNATURES['pgw_delta_fields'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _dp, _vp] + [_vp] * 14 + [_d, _d, _i, _vp, _vp, _vp, _vp])
 SIGNATURES['pgw_surface_deltas'] = (_i, [_vp, _i, _i, _i, _ll, _i, _dp, _vp, _vp, _vp, _d, _d, _vp, _vp, _d, _d, _vp, _vp, _d, _d,
                                          _vp, _vp, _vp, _vp])
+# regrid_lat_lon's xESMF branch: locate once per grid pair, apply per variable
+SIGNATURES['pgw_bilinear_locate'] = (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_ll)])
+SIGNATURES['pgw_regrid_sparse'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _vp, _vp, _i, _vp])
 
 _lib = None
 

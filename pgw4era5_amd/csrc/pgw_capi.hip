@@ -276,6 +276,7 @@ extern "C" int pgw_ctx_create(int device, pgw_ctx **out) {
     c->opt[PGW_OPT_TEST_FAIL] = 0;
     c->opt[PGW_OPT_FUSED_FIRST] = env_flag("PGW_FUSED_FIRST", 1);
     c->opt[PGW_OPT_MIXED_VEC] = 4;
+    c->opt[PGW_OPT_SPARSE_DIRECT] = 0;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc(&c->d_status, (2 + MULTI_MAX_PASS + FUSED_BLOCKS) * sizeof(DevStatus)) != hipSuccess ||
         hipHostMalloc(&c->h_status, (2 + 2 * MULTI_MAX_PASS + FUSED_BLOCKS) * sizeof(DevStatus)) != hipSuccess ||
@@ -2187,6 +2188,72 @@ extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, in
             hipLaunchKernelGGL((k_regrid<T, 4, decltype(w_)::value + 1>), dim3(nb), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s,
                                nlat_t, nlon_t, bx, gz, (const T *)src, tb, dpole, (T *)out);
         }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// regrid_lat_lon, xESMF branch (functions.py:797-810): locate once per grid pair ...
+extern "C" int pgw_bilinear_locate(pgw_ctx *ctx, long long ntarg, const double *P, int ny, int nx, int periodic, const double *X,
+                                   int nb, const int *bucket_start, const int *bucket_cells, int *idx, double *w,
+                                   long long *n_unmapped) {
+    NEED(ctx, ntarg >= 1 && ntarg < (1ll << 29), "ntarg must be in [1, 2^29)");
+    NEED(ctx, ny >= 2 && nx >= 2 && (long long)ny * nx < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
+    NEED(ctx, nb >= 1 && nb <= 512, "nb must be in [1, 512]");
+    NEED(ctx, P && X && bucket_start && bucket_cells && idx && w && n_unmapped, "null pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    void *ws = nullptr;
+    int rc = ws_get(ctx, 3, 64, &ws);
+    if (rc) return rc;
+    unsigned int *d_count = (unsigned int *)ws;
+    HIPCHK(ctx, hipMemsetAsync(d_count, 0, sizeof(unsigned int), ctx->stream));
+    {
+        Prof pr(ctx, PGW_K_CELL_LOCATE);
+        hipLaunchKernelGGL(k_cell_locate, dim3(nblocks(ntarg, BLOCK)), dim3(BLOCK), 0, ctx->stream, ntarg, P, ny, nx, periodic ? 1 : 0, X,
+                           nb, bucket_start, bucket_cells, idx, w, d_count);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    unsigned int h_count = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&h_count, d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *n_unmapped = (long long)h_count;
+    return PGW_OK;
+}
+
+// ... and apply to every plane (regridder(ds_in[var_name]), functions.py:802)
+extern "C" int pgw_regrid_sparse(pgw_ctx *ctx, int dtype, long long nfield, int ny, int nx, long long ntarg, const void *src,
+                                 const int *idx, const double *w, int unmapped_nan, void *out) {
+    NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
+    NEED(ctx, nfield >= 1 && ntarg >= 1 && ntarg < (1ll << 29), "nfield >= 1 and ntarg in [1, 2^29)");
+    NEED(ctx, ny >= 2 && nx >= 2 && (long long)ny * nx < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
+    NEED(ctx, src && idx && w && out, "null pointer");
+    NEED(ctx, ((uintptr_t)src % elem_size(dtype)) == 0 && ((uintptr_t)out % elem_size(dtype)) == 0, "pointers must be element-aligned");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    void *ws = nullptr;
+    int rc = ws_get(ctx, 3, 64 + sizeof(double) * 2 * (size_t)nfield, &ws);
+    if (rc) return rc;
+    double *dpole = (double *)((char *)ws + 64);
+    // 16 bytes of a plane per thread when the plane length and the output's alignment allow
+    const int wide = (int)(16 / elem_size(dtype));
+    const int W = (ntarg % wide == 0 && aligned16(out) && !ctx->opt[PGW_OPT_FORCE_VEC1]) ? wide : 1;
+    const unsigned int bx = nblocks(ntarg, BLOCK * W);
+    // z-slices: enough blocks to fill 256 CUs several times over even for few targets
+    long long want = (8192 + (long long)bx - 1) / bx;
+    unsigned int gz = (unsigned int)(want < 1 ? 1 : (want > nfield ? nfield : want));
+    if (gz > 65535u) gz = 65535u;
+    {
+        Prof pr(ctx, PGW_K_REGRID_SPARSE);
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_row_mean_plain<T>), dim3(nblocks(nfield * 2 * 64, BLOCK)), dim3(BLOCK), 0, ctx->stream, nfield, ny, nx,
+                               (const T *)src, dpole);
+            auto form = [&](auto w_) {
+                hipLaunchKernelGGL((k_regrid_sparse<T, decltype(w_)::value>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield,
+                                   (long long)ny * nx, ntarg, gz, (const T *)src, idx, w, dpole, unmapped_nan ? 1 : 0,
+                                   ctx->opt[PGW_OPT_SPARSE_DIRECT] ? 1 : 0, (T *)out);
+            };
+            if (W == 1) form(int_c<1>()); else form(int_c<(int)(16 / sizeof(T))>());
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;

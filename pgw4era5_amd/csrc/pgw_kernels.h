@@ -3491,4 +3491,231 @@ __global__ void k_log_table(int n, const double *in, double *out) {
     if (i < n) out[i] = pgw_log_tab(in[i], s_tab);
 }
 
+
+// =====================================================================================
+// a10b  bilinear regridding from curvilinear / rotated source grids       functions.py:797-810
+// =====================================================================================
+// What `xe.Regridder(ds_in, ds_era5, "bilinear", periodic=...)` asks ESMF for, stated natively: bilinear weights on the unit
+// sphere in 3-D Cartesian space, a cell edge being the straight chord between its corners (ESMF's default line type for the
+// non-conservative methods).  Two phases like a Regridder: k_cell_locate (geometry, once per grid pair) and k_regrid_sparse
+// (every plane).  Preconditions: cells are convex and smaller than a hemisphere; concave cells are not detected.
+//
+// Nodes X[j*nx + i] and targets P are unit vectors the host forms in numpy; the kernels do no trigonometry and no square
+// root, so every value below is IEEE + - * / in the order written (contraction is off) and numpy restates it bit for bit
+// (locate_statement / apply_statement of tests/test_regrid_curvilinear_host.py; tests/test_regrid_curvilinear_hip.py compares).
+//
+//   det3(a, b, c) = ((a0 * (b1*c2 - b2*c1)) - (a1 * (b0*c2 - b2*c0))) + (a2 * (b0*c1 - b1*c0))
+//
+// Quad (A, B, C, D), patch p(s,t) = A + s(B-A) + t(D-A) + s t E, E = ((A - B) + C) - D.  Newton on p(s,t) - r P = 0 from
+// s = t = 0.5, r = 1, at most CELL_NEWTON_MAX steps:
+//   F  = (((A + s*ab) + t*ad) + (s*t)*E) - r*P           ab = B - A, ad = D - A
+//   c1 = ab + t*E, c2 = ad + s*E, c3 = -P, det = det3(c1, c2, c3)          reject: det == 0 or not finite
+//   ds = det3(F, c2, c3) / det, dt = det3(c1, F, c3) / det, dr = det3(c1, c2, F) / det;  s -= ds, t -= dt, r -= dr
+//   reject: s, t or r not finite;  converged: |ds| <= 1e-14 and |dt| <= 1e-14
+// reject: not converged, r <= 0, s or t outside [-1e-10, 1 + 1e-10].  Clamp s, t to [0, 1];
+// weights (A, B, C, D) = (1-s)*(1-t), s*(1-t), s*t, (1-s)*t.
+//
+// Cap triangle (N, X1, X2):  e1 = X1 - N, e2 = X2 - N, c3 = -P, rhs = -N, det = det3(e1, e2, c3) (reject as above),
+//   u = det3(rhs, e2, c3) / det, v = det3(e1, rhs, c3) / det, r = det3(e1, e2, rhs) / det
+// reject: not finite, u or v < -1e-10, u + v > 1 + 1e-10, r <= 0.  Clamp: u = min(max(u, 0), 1), v = min(max(v, 0), 1 - u);
+// weights (N, X1, X2) = (1 - u) - v, u, v.
+constexpr int CELL_NEWTON_MAX = 20;
+constexpr double CELL_STEP_TOL = 1e-14, CELL_ACCEPT_TOL = 1e-10;
+
+struct Vec3 { double x, y, z; };
+__device__ __forceinline__ Vec3 v3_load(const double *__restrict__ p, long long i) { return Vec3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+__device__ __forceinline__ Vec3 v3_sub(const Vec3 &a, const Vec3 &b) { return Vec3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ Vec3 v3_add(const Vec3 &a, const Vec3 &b) { return Vec3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ Vec3 v3_scale(double s, const Vec3 &a) { return Vec3{s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ Vec3 v3_neg(const Vec3 &a) { return Vec3{-a.x, -a.y, -a.z}; }
+__device__ __forceinline__ double det3(const Vec3 &a, const Vec3 &b, const Vec3 &c) {
+    return ((a.x * (b.y * c.z - b.z * c.y)) - (a.y * (b.x * c.z - b.z * c.x))) + (a.z * (b.x * c.y - b.y * c.x));
+}
+__device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }    // false for NaN
+
+__device__ __forceinline__ bool cell_solve_quad(const Vec3 &A, const Vec3 &B, const Vec3 &Cc, const Vec3 &D, const Vec3 &P,
+                                                double (&w)[4]) {
+    const Vec3 ab = v3_sub(B, A), ad = v3_sub(D, A), E = v3_sub(v3_add(v3_sub(A, B), Cc), D), c3 = v3_neg(P);
+    double s = 0.5, t = 0.5, r = 1.0;
+    bool conv = false;
+    for (int it = 0; it < CELL_NEWTON_MAX; ++it) {
+        const Vec3 F = v3_sub(v3_add(v3_add(v3_add(A, v3_scale(s, ab)), v3_scale(t, ad)), v3_scale(s * t, E)), v3_scale(r, P));
+        const Vec3 c1 = v3_add(ab, v3_scale(t, E)), c2 = v3_add(ad, v3_scale(s, E));
+        const double det = det3(c1, c2, c3);
+        if (det == 0.0 || !finite_d(det)) return false;
+        const double ds = det3(F, c2, c3) / det, dt = det3(c1, F, c3) / det, dr = det3(c1, c2, F) / det;
+        s = s - ds; t = t - dt; r = r - dr;
+        if (!(finite_d(s) && finite_d(t) && finite_d(r))) return false;
+        if (fabs(ds) <= CELL_STEP_TOL && fabs(dt) <= CELL_STEP_TOL) { conv = true; break; }
+    }
+    if (!conv) return false;
+    if (!(r > 0.0)) return false;
+    if (!(s >= -CELL_ACCEPT_TOL && s <= 1.0 + CELL_ACCEPT_TOL && t >= -CELL_ACCEPT_TOL && t <= 1.0 + CELL_ACCEPT_TOL)) return false;
+    s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
+    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    const double os = 1.0 - s, ot = 1.0 - t;
+    w[0] = os * ot; w[1] = s * ot; w[2] = s * t; w[3] = os * t;
+    return true;
+}
+
+__device__ __forceinline__ bool cell_solve_tri(const Vec3 &N, const Vec3 &X1, const Vec3 &X2, const Vec3 &P, double (&w)[4]) {
+    const Vec3 e1 = v3_sub(X1, N), e2 = v3_sub(X2, N), c3 = v3_neg(P), rhs = v3_neg(N);
+    const double det = det3(e1, e2, c3);
+    if (det == 0.0 || !finite_d(det)) return false;
+    double u = det3(rhs, e2, c3) / det, v = det3(e1, rhs, c3) / det;
+    const double r = det3(e1, e2, rhs) / det;
+    if (!(finite_d(u) && finite_d(v) && finite_d(r))) return false;
+    if (!(u >= -CELL_ACCEPT_TOL && v >= -CELL_ACCEPT_TOL && u + v <= 1.0 + CELL_ACCEPT_TOL && r > 0.0)) return false;
+    u = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
+    const double vmax = 1.0 - u;
+    v = v < 0.0 ? 0.0 : (v > vmax ? vmax : v);
+    w[0] = (1.0 - u) - v; w[1] = u; w[2] = v; w[3] = 0.0;
+    return true;
+}
+
+// Bucket of a point of [-1, 1]^3 in the uniform nb^3 grid; the host's builder (functions.curvilinear_buckets) evaluates the
+// same expression on the corners of every cell's enlarged box, and it is monotone in each coordinate.
+__device__ __forceinline__ int bucket_coord(double x, int nb) {
+    const int b = (int)((x + 1.0) * 0.5 * (double)nb);
+    return b < 0 ? 0 : (b > nb - 1 ? nb - 1 : b);
+}
+
+// One target per thread.  Cells: quads j * ncx + i (ncx = nx when periodic: column i + 1 wraps and closes the seam, else
+// nx - 1), then - periodic grids only - the cap triangles (pole, X[je, i], X[je, i+1]) of row 0 and of row ny - 1; the poles
+// are the virtual nodes ny*nx and ny*nx + 1 whose unit vectors the host appends to X.  `bucket_cells` lists, ascending per
+// bucket, every cell whose enlarged bounding box touches the bucket, so the first accepting candidate is the lowest
+// accepting cell of all.  idx = -1: entry absent (never read); no accepting cell: four -1 and a count in *n_unmapped.
+__global__ __launch_bounds__(BLOCK) void k_cell_locate(long long ntarg, const double *__restrict__ P, int ny, int nx, int periodic,
+                                                       const double *__restrict__ X, int nb, const int *__restrict__ bucket_start,
+                                                       const int *__restrict__ bucket_cells, int *__restrict__ idx,
+                                                       double *__restrict__ w, unsigned int *__restrict__ n_unmapped) {
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= ntarg) return;
+    const Vec3 p = v3_load(P, g);
+    int id[4] = {-1, -1, -1, -1};
+    double wt[4] = {0.0, 0.0, 0.0, 0.0};
+    bool found = false;
+    if (p.x == p.x && p.y == p.y && p.z == p.z) {
+        const int ncx = periodic ? nx : nx - 1, nq = (ny - 1) * ncx, nsrc = ny * nx;
+        const long long b = ((long long)bucket_coord(p.x, nb) * nb + bucket_coord(p.y, nb)) * nb + bucket_coord(p.z, nb);
+        const int k1 = bucket_start[b + 1];
+        for (int k = bucket_start[b]; k < k1 && !found; ++k) {
+            const int c = bucket_cells[k];
+            if (c < 0 || c >= nq + (periodic ? 2 * nx : 0)) continue;      // not a cell: nothing is read for it
+            if (c < nq) {
+                const int j = c / ncx, i = c - j * ncx, ip = (i + 1 == nx) ? 0 : i + 1;
+                const int a = j * nx + i, bb = j * nx + ip, cc = (j + 1) * nx + ip, d = (j + 1) * nx + i;
+                if (cell_solve_quad(v3_load(X, a), v3_load(X, bb), v3_load(X, cc), v3_load(X, d), p, wt)) {
+                    id[0] = a; id[1] = bb; id[2] = cc; id[3] = d; found = true;
+                }
+            } else {
+                const int tri = c - nq, which = tri >= nx ? 1 : 0, i = tri - which * nx, ip = (i + 1 == nx) ? 0 : i + 1;
+                const int row = which ? (ny - 1) * nx : 0;
+                if (cell_solve_tri(v3_load(X, nsrc + which), v3_load(X, row + i), v3_load(X, row + ip), p, wt)) {
+                    id[0] = nsrc + which; id[1] = row + i; id[2] = row + ip; id[3] = -1; found = true;
+                }
+            }
+        }
+    }
+    if (!found) atomicAdd(n_unmapped, 1u);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { idx[4 * g + k] = id[k]; w[4 * g + k] = found ? wt[k] : 0.0; }
+}
+
+// Plain mean of the two edge rows of every plane, the value of the virtual pole nodes: (sum_i v[je, i]) / nx summed in index
+// order, NaN propagating (a sibling of k_zonal_mean_rows, whose mean skips NaN and sums per lane).  One wave per
+// (plane, row): 64 values per coalesced load, then every lane adds them in index order.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_row_mean_plain(long long nfield, int ny, int nx, const T *__restrict__ src,
+                                                          double *__restrict__ pole /* [nfield][2] */) {
+    const long long wv = ((long long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (wv >= nfield * 2) return;
+    const long long f = wv >> 1;
+    const int which = (int)(wv & 1);
+    const T *r = src + (f * ny + (which ? ny - 1 : 0)) * (long long)nx;
+    double sum = 0.0;
+    for (int i0 = 0; i0 < nx; i0 += 64) {
+        const double v = (i0 + lane < nx) ? (double)r[i0 + lane] : 0.0;
+        const int n = nx - i0 < 64 ? nx - i0 : 64;
+        for (int k = 0; k < n; ++k) sum = sum + __shfl(v, k, 64);
+    }
+    if (lane == 0) pole[f * 2 + which] = sum / (double)nx;
+}
+
+// Apply: out[f, g] = w0*v0, then + wk*vk for the present entries in order (values read in T, widened, stored in T); NaN in a
+// present entry gives NaN; an unmapped target gets 0.0, or NaN with `unmapped_nan`.  Entries >= ny*nx are the pole values of
+// k_row_mean_plain.  Write-dominated like k_regrid (1.9 of ~2.0 GB at production size), so: a thread owns W consecutive
+// targets (16 bytes of a plane where the row length allows), keeps their idx / w in registers and walks the planes of its
+// z-slice with streaming stores.  A block covers BLOCK * W consecutive targets; when the source elements they touch span at
+// most SPARSE_WIN consecutive elements of a plane, the block stages that window per plane in LDS (coalesced loads, two
+// buffers: one barrier per plane) and reads its entries from there instead of four uncoalesced gathers per output - what
+// held the first k_regrid at 2.4 TB/s; a wider window (coarse, unsorted or seam-crossing targets) gathers directly.  Both
+// forms read the same T values and do the same arithmetic: same bits.  `force_direct` is the test knob for the second form.
+constexpr int SPARSE_WIN = 2048;
+
+template <typename T, int W>
+__global__ __launch_bounds__(BLOCK) void k_regrid_sparse(long long nfield, long long nsrc, long long ntarg, unsigned int gz,
+                                                         const T *__restrict__ src, const int *__restrict__ idx,
+                                                         const double *__restrict__ w, const double *__restrict__ pole,
+                                                         int unmapped_nan, int force_direct, T *__restrict__ out) {
+    __shared__ T s_win[2][SPARSE_WIN];
+    __shared__ int s_lo, s_hi;
+    const long long g0 = ((long long)blockIdx.x * BLOCK + threadIdx.x) * W;
+    const bool active = g0 < ntarg;                           // W | ntarg when W > 1: a thread's targets are all in range or none
+    int id[W][4];
+    double wt[W][4];
+    if (threadIdx.x == 0) { s_lo = 0x7fffffff; s_hi = -1; }
+    __syncthreads();
+    int lo = 0x7fffffff, hi = -1;
+#pragma unroll
+    for (int u = 0; u < W; ++u)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            id[u][k] = active ? idx[4 * (g0 + u) + k] : -1;
+            if (id[u][k] >= nsrc + 2) id[u][k] = -1;           // nothing beyond the two pole nodes is ever read
+            wt[u][k] = active ? w[4 * (g0 + u) + k] : 0.0;
+            if (id[u][k] >= 0 && id[u][k] < nsrc) { lo = id[u][k] < lo ? id[u][k] : lo; hi = id[u][k] > hi ? id[u][k] : hi; }
+        }
+    if (hi >= 0) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
+    __syncthreads();
+    const int w0 = s_lo, span = s_hi - s_lo + 1;              // span <= 0: the block reads no source element
+    const bool staged = !force_direct && span > 0 && span <= SPARSE_WIN;
+    const long long per = (nfield + gz - 1) / gz;
+    const long long f0 = (long long)blockIdx.y * per, f1 = f0 + per < nfield ? f0 + per : nfield;
+    const double miss = unmapped_nan ? __builtin_nan("") : 0.0;
+    auto combine = [&](long long f, auto &&value) {
+        double r[W];
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            double acc = miss;
+            bool have = false;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (id[u][k] >= 0) {
+                    const double v = id[u][k] >= nsrc ? pole[f * 2 + (id[u][k] - nsrc)] : value(id[u][k]);
+                    const double term = wt[u][k] * v;
+                    acc = have ? acc + term : term;
+                    have = true;
+                }
+            r[u] = acc;
+        }
+        if (active) storev_nt<T, W>(out + f * ntarg + g0, r);
+    };
+    if (staged) {
+        int buf = 0;
+        for (long long f = f0; f < f1; ++f, buf ^= 1) {
+            const T *sp = src + f * nsrc + w0;
+            for (int c = threadIdx.x; c < span; c += BLOCK) s_win[buf][c] = sp[c];
+            __syncthreads();                                  // the other buffer is last read one plane back, before this barrier
+            combine(f, [&](int i) { return (double)s_win[buf][i - w0]; });
+        }
+    } else {
+        for (long long f = f0; f < f1; ++f) {
+            const T *sp = src + f * nsrc;
+            combine(f, [&](int i) { return (double)sp[i]; });
+        }
+    }
+}
+
 }  // namespace pgw

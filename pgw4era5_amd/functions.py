@@ -522,6 +522,179 @@ def regrid_field(field, src_lat, src_lon, targ_lat, targ_lon):
     return out_like(out, field)
 
 
+# ------------------------------------------------------------------------------- regridding, 2-D source coordinates
+def unit_vectors(lat_deg, lon_deg):
+    """(..., 3) unit vectors (cos lat cos lon, cos lat sin lon, sin lat) of points in degrees, float64: the only
+    trigonometry of the curvilinear regridding; the kernels work on these."""
+    la = np.deg2rad(np.asarray(lat_deg, dtype=np.float64))
+    lo = np.deg2rad(np.asarray(lon_deg, dtype=np.float64))
+    return np.stack([np.cos(la) * np.cos(lo), np.cos(la) * np.sin(lo), np.sin(la)], axis=-1)
+
+
+def pole_vector(row):
+    """normalise(sum_i row[i]) of an edge row of node vectors (nx, 3), summed in index order."""
+    s = np.add.accumulate(np.asarray(row, dtype=np.float64), axis=0)[-1]
+    return s / np.sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2])
+
+
+def periodic_lon_rule(lon):
+    """`periodic_lon` of regrid_lat_lon (reference functions.py:778-789) for 1-D or 2-D longitudes: np.diff along the
+    last axis, its median, global max / min."""
+    lon = np.asarray(lon, dtype=np.float64)
+    return bool((np.median(np.diff(lon)) + np.max(lon) - np.min(lon)) >= 359.9)
+
+
+def curvilinear_cells(X, periodic):
+    """Corners of every cell of the node grid X (ny, nx, 3) in cell-number order: quads j * ncx + i (A, B, C, D), then -
+    periodic only - the cap triangles of row 0 and of row ny - 1 as (pole, X_i, X_i+1, X_i+1).  Returns (ncell, 4, 3)."""
+    ny, nx = X.shape[:2]
+    ncx = nx if periodic else nx - 1
+    ip = (np.arange(ncx) + 1) % nx
+    i0 = np.arange(ncx)
+    quads = np.stack([X[:-1][:, i0], X[:-1][:, ip], X[1:][:, ip], X[1:][:, i0]], axis=2).reshape(-1, 4, 3)
+    if not periodic:
+        return quads
+    tris = []
+    for je in (0, ny - 1):
+        n = np.broadcast_to(pole_vector(X[je]), (nx, 3))
+        tris.append(np.stack([n, X[je][i0], X[je][ip], X[je][ip]], axis=1))
+    return np.concatenate([quads] + tris, axis=0)
+
+
+def curvilinear_buckets(X, periodic, nb=None):
+    """The candidate lists of k_cell_locate: a uniform nb^3 bucket grid over [-1, 1]^3 (only the shell around the sphere is
+    occupied), every cell listed - ascending - in each bucket its bounding box touches.  The box is enlarged because a target
+    P of the cell is the OUTWARD projection of a patch point p (a convex combination of the corners, so inside their box and
+    inside the sphere): |P - p| = 1 - |p|, and with d the largest corner distance |p|^2 = sum w_k w_l X_k.X_l >=
+    1 - d^2 / 2, so the radial bulge is at most 1 - sqrt(1 - d^2 / 2); plus 1e-8 for the acceptance tolerance (1e-10 in
+    s, t moves p by less than 1e-9) and rounding.  A cell with a NaN corner accepts nothing and is listed nowhere.
+    Returns (nb, bucket_start (nb^3 + 1) int32, bucket_cells int32)."""
+    cells = curvilinear_cells(np.asarray(X, dtype=np.float64), periodic)
+    ncell = len(cells)
+    if nb is None:
+        nb = int(min(max(int(np.sqrt(ncell / 2.0)), 1), 128))
+    ok = np.isfinite(cells).all(axis=(1, 2))
+    cid = np.nonzero(ok)[0]
+    c = cells[ok]
+    d2 = np.zeros(len(c))
+    for a in range(4):
+        for b in range(a + 1, 4):
+            d2 = np.maximum(d2, ((c[:, a] - c[:, b]) ** 2).sum(axis=1))
+    pad = (1.0 - np.sqrt(np.maximum(0.0, 1.0 - 0.5 * d2))) * (1.0 + 1e-6) + 1e-8
+
+    def coord(x):
+        return np.clip(((x + 1.0) * 0.5 * nb).astype(np.int64), 0, nb - 1)      # bucket_coord of pgw_kernels.h
+    lo = coord(np.maximum(c.min(axis=1) - pad[:, None], -1.0))
+    hi = coord(np.minimum(c.max(axis=1) + pad[:, None], 1.0))
+    ext = hi - lo + 1
+    cnt = ext.prod(axis=1)
+    first = np.concatenate([[0], np.cumsum(cnt)])
+    owner = np.repeat(np.arange(len(c)), cnt)
+    k = np.arange(first[-1]) - first[owner]
+    ez, ey = ext[owner, 2], ext[owner, 1]
+    bz = lo[owner, 2] + k % ez
+    by = lo[owner, 1] + (k // ez) % ey
+    bx = lo[owner, 0] + k // (ez * ey)
+    bucket = (bx * nb + by) * nb + bz
+    order = np.lexsort((cid[owner], bucket))
+    bucket_start = np.searchsorted(bucket[order], np.arange(nb ** 3 + 1)).astype(np.int32)
+    return nb, bucket_start, np.ascontiguousarray(cid[owner][order].astype(np.int32))
+
+
+class CurvilinearWeights:
+    """Result of the locate phase: device-resident idx (ntarg, 4) int32 and w (ntarg, 4) float64, the unmapped count, and
+    the shapes `regrid_curvilinear` needs."""
+
+    def __init__(self, idx, w, n_unmapped, src_shape, targ_shape, periodic):
+        self.idx, self.w, self.n_unmapped = idx, w, int(n_unmapped)
+        self.src_shape, self.targ_shape, self.periodic = tuple(src_shape), tuple(targ_shape), bool(periodic)
+
+
+def _mesh(lat, lon, what):
+    lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
+    if lat.ndim == 1 and lon.ndim == 1:
+        return np.meshgrid(lat, lon, indexing='ij')
+    if lat.ndim == 2 and lat.shape == lon.shape:
+        return lat, lon
+    raise ValueError('%s coordinates must be 1-D lat and lon or 2-D arrays of one shape' % what)
+
+
+def locate_points(X, P, periodic, nb=None):
+    """The locate phase on given vectors: nodes X (ny, nx, 3), targets P (ntarg, 3).  Returns CurvilinearWeights with a
+    flat target shape."""
+    ctx = default_context()
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    P = np.ascontiguousarray(P, dtype=np.float64).reshape(-1, 3)
+    if X.ndim != 3 or X.shape[2] != 3 or X.shape[0] < 2 or X.shape[1] < 2:
+        raise ValueError('the source grid must be at least 2 x 2 nodes')
+    if len(P) == 0:
+        raise ValueError('no target points')
+    ny, nx = X.shape[:2]
+    nb, bstart, bcells = curvilinear_buckets(X, periodic, nb)
+    nodes = X.reshape(-1, 3)
+    if periodic:
+        nodes = np.concatenate([nodes, pole_vector(X[0])[None], pole_vector(X[ny - 1])[None]], axis=0)
+    f64 = np.dtype('float64')
+    d_P, d_X = ctx.to_device(P, f64), ctx.to_device(np.ascontiguousarray(nodes), f64)
+    d_bs = ctx.empty(bstart.shape, np.int32).copy_from(bstart)
+    d_bc = ctx.empty((max(len(bcells), 1),), np.int32).copy_from(bcells if len(bcells) else np.zeros(1, np.int32))
+    idx, w = ctx.empty((len(P), 4), np.int32), ctx.empty((len(P), 4), f64)
+    n_un = C.c_longlong(0)
+    ctx._check(ctx.lib.pgw_bilinear_locate(ctx.handle, len(P), d_P.ptr, ny, nx, 1 if periodic else 0, d_X.ptr, nb, d_bs.ptr,
+                                           d_bc.ptr, idx.ptr, w.ptr, C.byref(n_un)))
+    return CurvilinearWeights(idx, w, n_un.value, (ny, nx), (len(P),), periodic)
+
+
+_WEIGHTS_CACHE = {}
+
+
+def curvilinear_weights(src_lat, src_lon, targ_lat, targ_lon, periodic):
+    """Locate phase of the bilinear regridding from a logically rectangular source grid with 1-D or 2-D coordinates onto
+    target points with 1-D or 2-D coordinates (1-D pairs are meshed): what `xe.Regridder(ds_in, ds_era5, "bilinear",
+    periodic=periodic)` computes (reference functions.py:799-800).  Cached per coordinate arrays, so the variables and files
+    of one step_02 run locate once."""
+    import hashlib
+    from . import settings as S
+    ctx = default_context()
+    digest = hashlib.blake2b(digest_size=16)
+    shapes = []
+    for a in (src_lat, src_lon, targ_lat, targ_lon):          # the coordinates as given: nothing is meshed or copied on a hit
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        shapes.append(a.shape)
+        digest.update(a.data)
+    key = (id(ctx), bool(periodic), tuple(shapes), digest.digest())
+    hit = _WEIGHTS_CACHE.get(key)
+    if hit is None:
+        sla, slo = _mesh(src_lat, src_lon, 'source')
+        tla, tlo = _mesh(targ_lat, targ_lon, 'target')
+        hit = locate_points(unit_vectors(sla, slo), unit_vectors(tla, tlo).reshape(-1, 3), periodic)
+        hit.targ_shape = tla.shape
+        _WEIGHTS_CACHE.clear()                                 # one grid pair at a time: the tables of a big pair are ~50 MB
+        _WEIGHTS_CACHE[key] = hit
+        if S.i_debug >= 1:
+            print('Regridding: %d of %d target points lie in no source cell (unmapped).'
+                  % (hit.n_unmapped, int(np.prod(hit.targ_shape))))
+    return hit
+
+
+def regrid_curvilinear(field, weights):
+    """Apply phase: field (..., ny, nx) -> (...,) + target shape on the GPU, dtype and array kind as `regrid_field`.
+    Unmapped targets get 0.0, or NaN with settings.xesmf_unmapped_to_nan."""
+    from . import settings as S
+    ctx = default_context()
+    shp = raw(field).shape
+    if len(shp) < 2 or tuple(shp[-2:]) != weights.src_shape:
+        raise ValueError('field shape does not match the source coordinates')
+    ops = OperandPlan(ctx, 'regrid_curvilinear', field=field)
+    nfield = int(np.prod(shp[:-2], dtype=np.int64)) if len(shp) > 2 else 1
+    ntarg = int(np.prod(weights.targ_shape, dtype=np.int64))
+    d_src = ops.dev('field')
+    out = ctx.empty(tuple(shp[:-2]) + weights.targ_shape, ops.result)
+    ctx._check(ctx.lib.pgw_regrid_sparse(ctx.handle, ops.tag('field'), nfield, shp[-2], shp[-1], ntarg, d_src.ptr,
+                                         weights.idx.ptr, weights.w.ptr, 1 if S.xesmf_unmapped_to_nan else 0, out.ptr))
+    return out_like(out, field)
+
+
 # ------------------------------------------------------------------------------- delta files
 _DATASET_CACHE = {}
 
@@ -580,14 +753,59 @@ def load_delta_interp(delta_input_dir, var_name, target_P, era5_date_time, targe
 
 
 # ------------------------------------------------------------------------------- step_02
+def _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name):
+    """The xESMF branch of regrid_lat_lon (reference functions.py:797-810) on the GPU."""
+    from . import ncio
+    from . import settings as S
+    src_lat, src_lon = np.asarray(ds_gcm[LAT_GCM].values), np.asarray(ds_gcm[LON_GCM].values)
+    periodic_lon = periodic_lon_rule(src_lon)                   # :778-789
+    if periodic_lon and S.i_debug >= 1:
+        print('Regridding: Use periodic boundary conditions for GCM input data as it appears to be periodic in '
+              'longitudinal direction.')
+    hdims = tuple(ds_gcm[LAT_GCM].dims) if src_lat.ndim == 2 else (LAT_GCM, LON_GCM)
+    f = ds_gcm[var_name]
+    if tuple(f.dims[-2:]) != hdims:
+        raise ValueError('%s has dimensions %s; its last two must be the horizontal dimensions %s of the source grid'
+                         % (var_name, tuple(f.dims), hdims))
+    t_lat, t_lon = ds_era5[LAT_ERA], ds_era5[LON_ERA]
+    targ_lat, targ_lon = np.asarray(t_lat.values, dtype=np.float64), np.asarray(t_lon.values, dtype=np.float64)
+    weights = curvilinear_weights(src_lat, src_lon, targ_lat, targ_lon, periodic_lon)          # xe.Regridder  :799-800
+    vals = f.values                                            # float32 / float64 of either byte order keep their width
+    vals = vals.astype(vals.dtype.newbyteorder('=') if vals.dtype.kind == 'f' and vals.dtype.itemsize in (4, 8) else np.float64,
+                       copy=False)
+    res = regrid_curvilinear(np.ascontiguousarray(vals), weights)                              # regridder(...)  :802
+    lead = tuple(f.dims[:-2])
+    out = ncio.Dataset(attrs=ds_gcm.attrs)                                                     # :810
+    for d in lead:
+        if d in ds_gcm:
+            out[d] = ds_gcm[d]
+    if targ_lat.ndim == 2:
+        tdims = tuple(t_lat.dims)
+        out[LAT_GCM] = ncio.Field(targ_lat, tdims, {}, None, LAT_GCM)
+        out[LON_GCM] = ncio.Field(targ_lon, tdims, {}, None, LON_GCM)
+        coords = {d: f.coords[d] for d in lead if d in f.coords}
+    else:
+        tdims = (LAT_GCM, LON_GCM)
+        out[LAT_GCM] = ncio.Field(targ_lat, (LAT_GCM,), {LAT_GCM: targ_lat}, None, LAT_GCM)
+        out[LON_GCM] = ncio.Field(targ_lon, (LON_GCM,), {LON_GCM: targ_lon}, None, LON_GCM)
+        coords = dict({d: f.coords[d] for d in lead if d in f.coords}, **{LAT_GCM: targ_lat, LON_GCM: targ_lon})
+    out[var_name] = ncio.Field(res, lead + tdims, coords, None, var_name)
+    if 'height' in ds_gcm and 'height' not in out:
+        out['height'] = ds_gcm['height']
+    for name in [var_name, TIME_GCM, PLEV_GCM, LAT_GCM, LON_GCM, 'height']:                   # :805-808
+        if name in ds_gcm and name in out:
+            out[name] = ncio.Field(out[name].values, out[name].dims, out[name].coords, ds_gcm[name].attrs, name)
+    return out
+
+
 def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
-    """Bilinear regridding of every lat/lon variable of `ds_gcm` onto the ERA5 grid of
-    `ds_era5` (xarray branch of reference functions.py:748-898; the xESMF branch is not part of
-    this build - SURVEY.md section 8c).  Returns a new Dataset on the target grid."""
+    """Bilinear regridding onto the ERA5 grid of `ds_era5` (reference functions.py:748-898).  i_use_xesmf = 0: the xarray
+    branch, every lat/lon variable of `ds_gcm` through the separable kernel (1-D coordinates).  i_use_xesmf = 1: the xESMF
+    branch (:797-810) for source grids with 2-D coordinates (rotated-pole, curvilinear; 1-D ones are meshed), `var_name`
+    through the cell-locate and sparse-apply kernels.  Returns a new Dataset on the target grid."""
     from . import ncio
     if i_use_xesmf:
-        raise NotImplementedError('the xESMF regridding branch (functions.py:797-810) is out of scope; '
-                                  'set i_use_xesmf_regridding = 0')
+        return _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name)
     targ_lon = np.asarray(ds_era5[LON_ERA].values, dtype=np.float64)
     targ_lat = np.asarray(ds_era5[LAT_ERA].values, dtype=np.float64)
     src_lon = np.asarray(ds_gcm[LON_GCM].values, dtype=np.float64)

@@ -20,8 +20,14 @@ var_name_map = dict(
     ps='PS', hus='QV', zgs='FIS', ts='T_SKIN', st='T_SO', sftlf='FR_LAND', sic='FR_SEA_ICE',
 )
 
-# step_02 regridding (:120-129).  The xESMF branch is not part of this build.
+# step_02 regridding (:120-129).  0: separable bilinear regridding, for deltas on a regular lat/lon grid (1-D coordinates).
+# 1: the reference's xESMF branch (functions.py:797-810), built natively - bilinear on the sphere from a source grid with
+# 2-D coordinates (rotated-pole regional models, curvilinear grids; 1-D coordinates work too) - use it whenever the GCM / RCM
+# deltas are not on a regular lat/lon grid.  Neither xESMF nor ESMF is needed.
 i_use_xesmf_regridding = 0
+# not in the reference: a target point that lies in no source cell gets 0.0 with xESMF 0.6.2 (environment.yml:177), which is
+# the default here; True makes it NaN instead
+xesmf_unmapped_to_nan = False
 nan_interp_kernel_radius = 1000000
 nan_interp_sharpness = 4
 

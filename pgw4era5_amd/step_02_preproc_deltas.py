@@ -4,7 +4,8 @@ step_02: regrid GCM climate deltas (and HIST climatologies) to the ERA5 grid on 
 Command line of the reference's step_02_preproc_deltas.py (:27-87): positional
 {smoothing,regridding}, -i, -o, -e, -v.  For every variable both `{var}_historical.nc` and
 `{var}_delta.nc` are processed (:116-119).  `regridding` runs the bilinear lat-then-lon kernel
-(functions.regrid_lat_lon); `smoothing` runs the annual-cycle filter for daily deltas
+(functions.regrid_lat_lon), or with settings.i_use_xesmf_regridding = 1 the cell-locate / sparse-apply kernels for source
+grids with 2-D coordinates; `smoothing` runs the annual-cycle filter for daily deltas
 (functions.filter_data, reference functions.py:603-740); tos / siconc on the ocean grid go through the
 NaN-ignoring Gaussian-kernel interpolation (functions.nan_ignoring_interp, reference functions.py:900-1060).
 """
@@ -14,7 +15,8 @@ from pathlib import Path
 
 from . import ncio
 from .functions import filter_data, interp_wrapper
-from .settings import file_name_bases, i_use_xesmf_regridding, nan_interp_kernel_radius, nan_interp_sharpness
+from . import settings
+from .settings import file_name_bases, nan_interp_kernel_radius, nan_interp_sharpness
 
 DEFAULT_VARS = 'ta,hur,ua,va,zg,hurs,tas,ps,tos,ts,siconc'
 
@@ -55,7 +57,7 @@ def main(argv=None):
             if not os.path.exists(inp):
                 raise ValueError('Files for variable ' + var_name + ' are missing')
             ds_gcm = ncio.open_dataset(inp)
-            ds_out = interp_wrapper(ds_gcm, ds_era5, var_name, i_use_xesmf=i_use_xesmf_regridding,
+            ds_out = interp_wrapper(ds_gcm, ds_era5, var_name, i_use_xesmf=settings.i_use_xesmf_regridding,
                                     nan_interp_kernel_radius=nan_interp_kernel_radius,
                                     nan_interp_sharpness=nan_interp_sharpness)
             ncio.to_netcdf(ds_out, out)

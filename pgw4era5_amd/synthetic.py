@@ -173,6 +173,48 @@ def make_gcm_grid_case(nlat_src=48, nlon_src=96, nlat=37, nlon=72, nplev=5, ntim
     return dict(field=f, src_lat=src_lat, src_lon=src_lon, targ_lat=targ_lat, targ_lon=targ_lon)
 
 
+def rotated_pole_grid(nrlat=24, nrlon=48, pole_lat=39.25, pole_lon=-162.0, rlat_range=(-14.0, 14.0), rlon_range=(-22.0, 22.0)):
+    """A rotated-pole regional grid like a EURO-CORDEX one: regular in the rotated coordinates (rlat, rlon), whose north
+    pole lies at (pole_lat, pole_lon) geographic, so that the domain - around the rotated equator - has nearly square cells.
+    Returns (rlat (nrlat), rlon (nrlon), lat (nrlat, nrlon), lon (nrlat, nrlon)), geographic degrees, lon in (-180, 180]."""
+    rlat = np.linspace(rlat_range[0], rlat_range[1], nrlat)
+    rlon = np.linspace(rlon_range[0], rlon_range[1], nrlon)
+    la, lo = np.deg2rad(rlat)[:, None], np.deg2rad(rlon)[None, :]
+    x, y, z = np.cos(la) * np.cos(lo), np.cos(la) * np.sin(lo), np.sin(la) * np.ones_like(lo)
+    # rotate the rotated frame's pole (0, 0, 1) to (pole_lat, pole_lon): about y by the co-latitude, then about z
+    th, ph = np.deg2rad(90.0 - pole_lat), np.deg2rad(pole_lon + 180.0)
+    x1, z1 = x * np.cos(th) - z * np.sin(th), x * np.sin(th) + z * np.cos(th)
+    x2, y2 = x1 * np.cos(ph) - y * np.sin(ph), x1 * np.sin(ph) + y * np.cos(ph)
+    lat = np.rad2deg(np.arcsin(np.clip(z1, -1.0, 1.0)))
+    lon = np.rad2deg(np.arctan2(y2, x2))
+    return rlat, rlon, lat, lon
+
+
+def make_rotated_delta(nrlat=24, nrlon=48, nplev=3, ntime=2, seed=0, dtype=np.float64, var_name='ta', **grid):
+    """An atmospheric climate delta of a rotated-pole regional model, as step_02 `regridding` meets it with
+    settings.i_use_xesmf_regridding = 1: `var_name` (time, plev, rlat, rlon) with 2-D `lat` / `lon` over (rlat, rlon),
+    values smooth in space plus noise, attributes on the variable, the coordinates and the file.  Returns an ncio.Dataset."""
+    from . import ncio
+    rng = np.random.default_rng(seed)
+    rlat, rlon, lat, lon = rotated_pole_grid(nrlat, nrlon, **grid)
+    plev = np.array([85000.0, 50000.0, 20000.0, 10000.0, 5000.0][:nplev])
+    times = np.array(['1995-%02d-15T12:00:00' % (m + 1) for m in range(ntime)], dtype='datetime64[s]')
+    pat = 1.0 + 0.5 * np.cos(np.deg2rad(lat)) * np.sin(np.deg2rad(2 * lon) + 0.3)
+    vals = (1 + 0.1 * np.arange(ntime))[:, None, None, None] * (1 + np.arange(nplev))[None, :, None, None] * pat[None, None]
+    vals = (vals + 0.05 * rng.standard_normal(vals.shape)).astype(dtype)
+    F = ncio.Field
+    ds = ncio.Dataset(attrs=dict(title='synthetic rotated-pole delta', source='pgw4era5_amd.synthetic'))
+    ds['time'] = F(times, ('time',), attrs=dict(long_name='time'))
+    ds['plev'] = F(plev, ('plev',), attrs=dict(units='Pa', positive='down'))
+    ds['rlat'] = F(rlat, ('rlat',), attrs=dict(units='degrees', standard_name='grid_latitude'))
+    ds['rlon'] = F(rlon, ('rlon',), attrs=dict(units='degrees', standard_name='grid_longitude'))
+    ds['lat'] = F(lat, ('rlat', 'rlon'), attrs=dict(units='degrees_north', standard_name='latitude'))
+    ds['lon'] = F(lon, ('rlat', 'rlon'), attrs=dict(units='degrees_east', standard_name='longitude'))
+    ds[var_name] = F(vals, ('time', 'plev', 'rlat', 'rlon'), {'time': times, 'plev': plev, 'rlat': rlat, 'rlon': rlon},
+                     dict(units='K', long_name='%s delta' % var_name))
+    return ds
+
+
 def make_ocean_grid_case(nj=40, ni=60, ntime=12, seed=0, land_patches=3):
     """An ocean-model-like delta for step_02's NaN-ignoring interpolation (tos / siconc): curvilinear grid with 2-D
     `latitude` / `longitude` coordinates (a regular grid sheared and stretched so that rows are not parallels, longitudes
