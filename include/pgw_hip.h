@@ -95,7 +95,17 @@ enum pgw_option {
                                  16 bytes; 1: scalar.  A/B knob of tools/function_flow_time.py                                       */
     PGW_OPT_SPARSE_DIRECT = 9, /* test knob, default 0: pgw_regrid_sparse stages a block's source window in LDS when it fits; 1: every
                                  block gathers from memory.  Same bits either way                                                     */
-    PGW_OPT_COUNT = 10
+    PGW_OPT_QV_FROM_PASS = 10, /* 1 (default): the last pass of every multi-pass loop launch (fixed p_ref) also stores the QV it forms
+                                 below p_ref into hus_pgw; when that pass is the converged one - the host predicts it with
+                                 PGW_OPT_LOOP_GUESS - the finalize kernel computes only the levels above it (pgw_last_qv_from_pass),
+                                 otherwise all of them as with 0.  Same bits either way for every divisor pm - 0.378 e that is a finite
+                                 pressure of normal range and every e >= 0 that is 0 or of normal range; outside that - a divisor of
+                                 exactly 0 or inf, denormal-scale operands, e = -0 - the pass's scale-free quotient can differ from
+                                 the finalize kernel's IEEE division (NaN for inf, +0 for -0), as k_delta_quad's QV of the
+                                 pure-pressure levels already does.  Takes effect with PGW_OPT_MULTIPASS = 1,
+                                 PGW_OPT_FULL_COLUMN = 0, a fixed p_ref, i_reinterp = 0, in pgw_step03_file with PGW_OPT_QUAD = 1, and
+                                 for float64 level arrays (float64 files, float32 files in reference-dtype mode)  [PGW_QV_FROM_PASS] */
+    PGW_OPT_COUNT = 11
 };
 
 /* ---------------------------------------------------------------- context ------------ */
@@ -322,6 +332,12 @@ int pgw_adjust_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol,
 /* sum over columns and passes of the full levels the last pgw_adjust_ps_loop actually read
  * (the pass kernel stops a wave above p_ref); used for the bytes-moved accounting. */
 unsigned long long pgw_last_levels_touched(pgw_ctx *ctx);
+
+/* PGW_OPT_QV_FROM_PASS: 1 when the finalize kernel of the last pgw_adjust_ps_loop / pgw_step03_file took the QV below p_ref from
+ * the converged pass (that pass was the last one of its launch), else 0.  *skipped (may be NULL): the level-columns of hus_pgw
+ * the finalize kernel then left alone, summed over columns - it read e and wrote QV on the other
+ * (nlev - qv_done_levels) * ntime * ncol - *skipped. */
+int pgw_last_qv_from_pass(pgw_ctx *ctx, unsigned long long *skipped);
 
 /* ---------------------------------------------------------------- whole file ---------- */
 /* The per-file compute path of pgw_for_era5 (reference step_03_apply_to_era.py:62-346 with

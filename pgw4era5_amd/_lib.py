@@ -28,7 +28,7 @@ KERNEL_IDS = dict(pressure=0, q_to_rh=1, rh_to_q=2, integ_geopot=3, interp_logp=
                   cell_locate=26, regrid_sparse=27)
 
 # enum pgw_option (include/pgw_hip.h)
-OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7, mixed_vec=8, sparse_direct=9)
+OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7, mixed_vec=8, sparse_direct=9, qv_from_pass=10)
 
 PGW_OK = 0
 PGW_ERR_HIP = 1
@@ -96,6 +96,7 @@ SIGNATURES = {
     'pgw_adjust_ps_loop': (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _i,
                                 _vp, _vp, _ip, _dp]),
     'pgw_last_levels_touched': (C.c_ulonglong, [_vp]),
+    'pgw_last_qv_from_pass': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     'pgw_regrid_bilinear': (_i, [_vp, _i, _ll, _i, _i, _i, _i, _vp, _ip, _ip, _dp, _dp, _ip,
                                  _ip, _ip, _dp, _dp, _ip, _i, _i, _vp]),
     'pgw_surface_update': (_i, [_vp, _i, _i, _ll, _i, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -57,6 +57,10 @@ struct pgw_ctx {
     double prof_ms[PGW_K_COUNT];
     hipEvent_t t0 = nullptr, t1 = nullptr;
     unsigned long long last_levels_touched = 0;
+    // PGW_OPT_QV_FROM_PASS: did the last file's finalize kernel use the marks of the converged pass, and how many
+    // level-columns of QV did that leave it to skip
+    bool last_qv_from_pass = false;
+    unsigned long long last_qv_skipped = 0;
 };
 
 static const size_t SMALL_BYTES = 64 * 1024;
@@ -275,6 +279,7 @@ extern "C" int pgw_ctx_create(int device, pgw_ctx **out) {
     c->opt[PGW_OPT_FORCE_OFF64] = 0;
     c->opt[PGW_OPT_TEST_FAIL] = 0;
     c->opt[PGW_OPT_FUSED_FIRST] = env_flag("PGW_FUSED_FIRST", 1);
+    c->opt[PGW_OPT_QV_FROM_PASS] = env_flag("PGW_QV_FROM_PASS", 1);
     c->opt[PGW_OPT_MIXED_VEC] = 4;
     c->opt[PGW_OPT_SPARSE_DIRECT] = 0;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -1380,9 +1385,10 @@ static void launch_local_p_ref(pgw_ctx *ctx, int dtype, bool ref, const PlevTabl
 }
 
 // ps_pgw = PS + dps and hus_pgw from e on the final levels (:262-266, 370); the first qv_done_levels levels of hus_pgw are
-// already written
+// already written, and with `marks` so are each column's levels from its mark on (by the converged loop pass)
 static void launch_finalize(pgw_ctx *ctx, int dtype, bool ref, int ntime, long long ncol, const void *PS, const double *dps,
-                            const void *evap, void *ps_pgw, void *hus_pgw, int qv_done_levels) {
+                            const void *evap, void *ps_pgw, void *hus_pgw, int qv_done_levels,
+                            const unsigned short *marks = nullptr) {
     int vec = pick_vec(ctx, dtype, ncol, {PS, evap, ps_pgw, hus_pgw, dps});
     Levels lv = levels_of(ctx);
     Prof pr(ctx, PGW_K_FINALIZE);
@@ -1391,7 +1397,7 @@ static void launch_finalize(pgw_ctx *ctx, int dtype, bool ref, int ntime, long l
         constexpr int V = decltype(v_)::value;
         hipLaunchKernelGGL((k_finalize_ps_hus<T, TL, V, decltype(ref_)::value>), dim3(nblocks((long long)ntime * ncol / V, BLOCK)),
                            dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)PS, dps, (const TL *)evap, (T *)ps_pgw,
-                           (TL *)hus_pgw, qv_done_levels);
+                           (TL *)hus_pgw, qv_done_levels, marks);
     });
 }
 
@@ -1427,6 +1433,9 @@ struct PsLoopArgs {
     // first launch is then two: pass 1 for the flagged groups alone (k_ps_loop_multi<.., FLAGGED>), and passes 2 .. np for
     // all columns as a continuation launch.
     bool fused_first = false;
+    // PGW_OPT_QV_FROM_PASS may apply.  pgw_step03_file with PGW_OPT_QUAD = 0 says no: the pair kernels are kept as an independent
+    // cross-check of the production path, and so is the QV their files get - all of it from the finalize kernel's division
+    bool qv_from_pass = true;
 };
 
 static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
@@ -1464,6 +1473,20 @@ static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
         DevStatus *mst = ctx->d_status + 2;                                // device per-pass blocks
         DevStatus *hback = ctx->h_status + 1;                              // [0] = block 0 (ERA-state scan / earlier kernels), [1..] passes
         DevStatus *hzero = blank_blocks(ctx, MULTI_MAX_PASS);
+        // PGW_OPT_QV_FROM_PASS: the last pass of every launch of the FLAGGED = false, fixed-p_ref kernel stores the QV it
+        // forms below p_ref into hus_pgw and marks how far each column got.  When that pass turns out to be the converged one
+        // (the host predicts it: loop_guess), the finalize kernel has only the levels above the marks left; otherwise it
+        // runs over all of them as before and overwrites what was speculated.  hus_pgw must not be an array the loop reads.
+        unsigned short *marks = nullptr;
+        if (ctx->opt[PGW_OPT_QV_FROM_PASS] && a.qv_from_pass && !local && a.hus_pgw && a.hus_pgw != a.QV && a.hus_pgw != a.T && a.hus_pgw != a.ta_pgw &&
+            a.hus_pgw != a.evap) {
+            void *m = nullptr;
+            if ((rc = ws_get(ctx, 4, (size_t)n2 * sizeof(unsigned short), &m))) return rc;
+            marks = (unsigned short *)m;
+        }
+        int stored_k = -1;             // pass index, within the launch just read back, of the pass that stored QV (-1: none)
+        bool marks_valid = false;
+        ctx->last_qv_from_pass = false; ctx->last_qv_skipped = 0;
         if (!a.status_armed && (rc = status_reset(ctx))) return rc;
         int it = 1;
         bool first = true;
@@ -1484,7 +1507,8 @@ static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
             {
                 // one column per lane (two columns: 168 VGPRs + scratch; measured 1.36 vs 1.39 ms before the log table)
                 constexpr int MULTI_MAXV = 1;
-                int vec = pick_vec(ctx, dtype, ncol, {a.ta_pgw, a.evap, a.T, a.QV, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, dps_hist}, MULTI_MAXV);
+                int vec = pick_vec(ctx, dtype, ncol, {a.ta_pgw, a.evap, a.T, a.QV, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, dps_hist,
+                                                       marks ? a.hus_pgw : nullptr /* the storing pass writes V-wide rows */}, MULTI_MAXV);
                 Levels lv = levels_of(ctx);
                 Prof pr(ctx, PGW_K_PS_LOOP_MULTI);
                 const LocalPRef loc{ptf, ctx->h_akN, ctx->h_bkN, ls.pref_f, ls.pref_idx};
@@ -1492,13 +1516,18 @@ static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
                     using T = decltype(t_); using TL = decltype(l_);
                     constexpr int V = decltype(v_)::value;
                     // `n` passes from the state as it stands (init: from the ERA state) into `blocks` and the rows of `hist`
+                    constexpr bool qv_pass = QV_FROM_PASS<TL, decltype(ref_)::value>;
+                    stored_k = -1;
                     auto launch = [&](auto local_, auto flagged_, double p_ref, int init, int n, DevStatus *blocks, double *hist,
                                       unsigned char *flags, DevStatus *st_era) {
+                        const bool store = qv_pass && marks && !decltype(local_)::value && !decltype(flagged_)::value;
+                        if (store) stored_k = (int)(blocks - mst) + n - 1;
                         hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, decltype(ref_)::value, decltype(local_)::value, decltype(flagged_)::value>),
                                            dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)a.T,
                                            (const T *)a.QV, (const TL *)a.ta_pgw, (const TL *)a.evap, (const T *)a.PS, (const T *)a.FIS,
                                            delta_src<T>(a.dzg_b, a.dzg_a, a.x_hi, a.x_new), ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps,
-                                           hist, p_ref, a.adj_factor, init, n, ctx->d_status, blocks, loc, flags, st_era);
+                                           hist, p_ref, a.adj_factor, init, n, ctx->d_status, blocks, loc, flags, st_era,
+                                           store ? (TL *)a.hus_pgw : nullptr, a.qv_done_levels, marks);
                     };
                     constexpr std::true_type yes{};
                     constexpr std::false_type no{};
@@ -1556,7 +1585,11 @@ static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
                     ctx->err_col = -1;
                     return PGW_ERR_NOT_CONVERGED;
                 }
-                if (!(err_k > a.thresh)) conv = dps_hist + (size_t)k * n2; // :189  (NaN stops the loop too)
+                if (!(err_k > a.thresh)) {                                 // :189  (NaN stops the loop too)
+                    conv = dps_hist + (size_t)k * n2;
+                    marks_valid = k == stored_k;                           // hus_pgw holds this pass's QV from the marks on
+                    if (marks_valid) ctx->last_qv_skipped = h.qv_stored;
+                }
             }
             first = false;
         }
@@ -1565,11 +1598,14 @@ static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
         ctx->last_levels_touched = touched;
         ctx->last_passes_launched = launched;
         if (a.n_iter) *a.n_iter = it - 1;
+        ctx->last_qv_from_pass = marks_valid;
         if (a.ps_pgw || a.hus_pgw)
-            launch_finalize(ctx, dtype, a.ref, ntime, ncol, a.PS, conv, a.evap, a.ps_pgw, a.hus_pgw, a.qv_done_levels);
+            launch_finalize(ctx, dtype, a.ref, ntime, ncol, a.PS, conv, a.evap, a.ps_pgw, a.hus_pgw, a.qv_done_levels,
+                            marks_valid ? marks : nullptr);
         HIPCHK(ctx, hipGetLastError());
         return PGW_OK;
     }
+    ctx->last_qv_from_pass = false; ctx->last_qv_skipped = 0;
 
     double phi_ref_max_error = INFINITY;                                   // :186
     int it = 1;                                                            // :188
@@ -1823,6 +1859,7 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
 
     if (a->i_reinterp) {                                  // settings.i_reinterp = 1: the loop re-interpolates in every pass
         a->levels_touched = 0; a->passes_launched = 0;
+        ctx->last_qv_from_pass = false; ctx->last_qv_skipped = 0;
         return run_reinterp_file(ctx, a, check_top);
     }
 
@@ -1941,6 +1978,7 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     if (a->local_p_ref) { la.local_nplev = a->nplev; la.plev_file = a->plev; }
     la.status_armed = !check_top && !a->local_p_ref;
     la.qv_done_levels = qv_done; la.ref = ref; la.fused_first = fused_first;
+    la.qv_from_pass = ctx->opt[PGW_OPT_QUAD] != 0;
     rc = run_ps_loop(ctx, la);
     a->levels_touched = ctx->last_levels_touched;
     a->passes_launched = ctx->last_passes_launched;
@@ -1948,6 +1986,11 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
 }
 
 extern "C" unsigned long long pgw_last_levels_touched(pgw_ctx *ctx) { return ctx->last_levels_touched; }
+
+extern "C" int pgw_last_qv_from_pass(pgw_ctx *ctx, unsigned long long *skipped) {
+    if (skipped) *skipped = ctx->last_qv_from_pass ? ctx->last_qv_skipped : 0;
+    return ctx->last_qv_from_pass ? 1 : 0;
+}
 
 extern "C" int pgw_test_exp(pgw_ctx *ctx, long long n, const double *in, double *out, double *ref) {
     NEED(ctx, n >= 1 && in && out && ref, "bad argument");

@@ -27,6 +27,7 @@ struct DevStatus {
     unsigned long long min_targ_bits;  // min target pressure (bits of positive double)
     unsigned long long min_src_bits;   // min source pressure
     unsigned long long levels_touched; // sum over columns of levels read (early-exit kernels)
+    unsigned long long qv_stored;      // sum over columns of levels whose QV the pass stored (k_ps_loop_multi, last pass of a launch)
 };
 
 template <typename T, int V> struct alignas(sizeof(T) * V) Pack { T v[V]; };

@@ -432,12 +432,21 @@ done:
 // already in flight (software pipeline; ~2*U KiB per wave outstanding).
 // TL = storage type of the two level arrays.  REF (reference-dtype mode, float32 files): phi rounded to float32 per
 // level; for the ERA state (SECOND_IS_Q, float32 T and QV) tav and CON_RD*tav are float32 products.
-template <typename TL, int V, int U, bool SECOND_IS_Q, bool REF>
+// QMODE 2 = STORE_Q (loop pass only): the pass also stores the q it forms, as TL, for every level lc >= l_lim it processes (l_lim =
+// nlev: none), lanes with `live` only, into the array of pe's shape that lies `qdiff` bytes behind it (hus_pgw: one uniform
+// register pair instead of a second per-lane address); `low` returns the lowest level index the wave processed (the stop
+// is wave-uniform: the same for all 64 lanes).  See k_ps_loop_multi.
+// QMODE 1: a pass of that kernel that does not store (only the start value of phi is pinned, see below); 0: neither.
+template <typename TL, int V, int U, bool SECOND_IS_Q, bool REF, int QMODE = 0>
 __device__ __forceinline__ void scan_columns(const Levels &lv, const LevTab &lt, long long ncol, const TL *__restrict__ pt,
                                              const TL *__restrict__ pe, const double (&ps)[V], const double (&z)[V],
                                              const double (&pref)[V], int full_column, DevStatus *st, long long c2,
-                                             double (&phi_ref)[V], double (&tlow)[V], int &touched) {
+                                             double (&phi_ref)[V], double (&tlow)[V], int &touched,
+                                             long long qdiff = 0, int l_lim = 0, bool live = false, int *low = nullptr) {
+    constexpr bool STORE_Q = QMODE == 2;
+    static_assert(QMODE == 0 || !SECOND_IS_Q, "the stored q is the loop pass's");
     const int N = lv.nlev;
+    int lowest = N;
     // the ERA-state scan (SECOND_IS_Q) reads its rows once per file; the loop passes re-read theirs (keep those cacheable)
 #define SCAN_LOADV(p, o) do { if constexpr (SECOND_IS_Q) loadv_nt<TL, V>(p, o); else loadv<TL, V>(p, o); } while (0)
     GeoAcc acc[V];
@@ -459,6 +468,14 @@ __device__ __forceinline__ void scan_columns(const Levels &lv, const LevTab &lt,
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) tlow[v] = tn[0][v];             // ta at the lowest full level, :303
+    // phi's start value has to be IN its register here.  In k_ps_loop_multi it is the surface geopotential, which lives in
+    // scratch between the passes; when its reload was still in flight at the loop's entry, its first use inside the loop
+    // became an s_waitcnt vmcnt(0) in the middle of every iteration, which also waits for the rows just requested
+    // (+0.09 ms per float64 file)
+    if constexpr (QMODE != 0) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) asm volatile("" : "+v"(acc[v].phi));
+    }
     for (int l = N - 1; l >= 0; l -= U) {
         double t[U][V], e[U][V];
 #pragma unroll
@@ -478,6 +495,7 @@ __device__ __forceinline__ void scan_columns(const Levels &lv, const LevTab &lt,
             int lc = l - u;
             if (lc >= 0) {
                 double am = lt.akm[lc], bm = lt.bkm[lc], a = lt.ak[lc], b = lt.bk[lc];
+                double qs[V];
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
                     double rtv;
@@ -492,8 +510,26 @@ __device__ __forceinline__ void scan_columns(const Levels &lv, const LevTab &lt,
                         const double pm = am + ps[v] * bm;
                         double q = SharedDivisor(pm - (1 - CON_MW_MD) * e[u][v]).divide(CON_MW_MD * e[u][v]);
                         rtv = CON_RD * (t[u][v] * (1 + 0.61 * q));
+                        if (STORE_Q) qs[v] = q;
                     }
                     geo_layer<REF, true>(acc[v], lc, rtv, a + ps[v] * b, pref[v], lt.logtab);
+                }
+                if constexpr (STORE_Q) {
+                    // hus_pgw is not read again by this library: streaming store
+                    if (lc >= l_lim) {
+                        // the row's address as the lane's own `pe` plus ONE uniform byte offset (kept opaque: re-associated into
+                        // a second per-lane base it costs the two VGPRs that spill a loop-carried value, and the reload's wait).
+                        // This steps from one allocation (e) into another (hus_pgw) and drops pe's const: outside what C++
+                        // defines, relied on as flat global addressing of gfx950 (addresses are plain 64-bit integers); pe's
+                        // __restrict__ is not violated in effect, because nothing is ever read back through the new pointer and
+                        // the host refuses a hus_pgw that is one of the arrays the loop reads
+                        const long long ob = (long long)lc * ncol * (long long)sizeof(TL) + qdiff;
+                        const unsigned int olo = __builtin_amdgcn_readfirstlane((unsigned int)ob);
+                        const unsigned int ohi = __builtin_amdgcn_readfirstlane((unsigned int)((unsigned long long)ob >> 32));
+                        const long long ou = (long long)(((unsigned long long)ohi << 32) | olo);
+                        if (live) storev_nt<TL, V>((TL *)((char *)const_cast<TL *>(pe) + ou), qs);
+                    }
+                    lowest = lc;
                 }
                 touched += V;
             }
@@ -507,6 +543,7 @@ __device__ __forceinline__ void scan_columns(const Levels &lv, const LevTab &lt,
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) phi_ref[v] = geo_finish(acc[v], pref[v], st, c2 + v);
+    if constexpr (STORE_Q) *low = lowest;
 }
 
 // step_03:192-193.  REF: delta_ps is a float32 array updated in place (`delta_ps += adj_ps` casts the float64 sum back,
@@ -532,7 +569,7 @@ __global__ __launch_bounds__(BLOCK) void k_adjust_ps_step(Levels lv, int ntime, 
     if (clear && blockIdx.x == 0 && threadIdx.x == 0) {       // status block of the NEXT pass
         DevStatus z;
         z.code = 0; z.nan_seen = 0; z.col = ~0ull; z.max_bits = 0; z.valid = 0;
-        z.min_targ_bits = ~0ull; z.min_src_bits = ~0ull; z.levels_touched = 0;
+        z.min_targ_bits = ~0ull; z.min_src_bits = ~0ull; z.levels_touched = 0; z.qv_stored = 0;
         *clear = z;
     }
     LevTab lt = stage_levels<true, true>(lv, s_lev, BLOCK);
@@ -626,11 +663,16 @@ __global__ __launch_bounds__(BLOCK) void k_phi_ref_hybrid(Levels lv, int ntime, 
 }
 
 // final outputs of the loop: ps_pgw = PS + delta_ps (step_03:193,369), hus_pgw from e (:262-266,370)
+// `marks` (PGW_OPT_QV_FROM_PASS, the converged pass was the storing pass of k_ps_loop_multi): per column the lowest level
+// whose QV that pass has stored with this delta_ps - only the levels above it are left.  The V columns of a thread lie in
+// one wave of that kernel and carry the same mark; the largest is taken all the same, and a level written twice gets the
+// same bits twice.
 template <typename T, typename TL, int V, bool REF>
 __global__ __launch_bounds__(BLOCK) void k_finalize_ps_hus(Levels lv, int ntime, long long ncol,
                                                            const T *__restrict__ PS, const double *__restrict__ delta_ps,
                                                            const TL *__restrict__ evap, T *__restrict__ ps_out,
-                                                           TL *__restrict__ hus_out, int l_start) {
+                                                           TL *__restrict__ hus_out, int l_start,
+                                                           const unsigned short *__restrict__ marks) {
     __shared__ double s_lev[LEVTAB_DOUBLES];
     LevTab lt = stage_levels<false, true>(lv, s_lev, BLOCK);
     long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -647,9 +689,16 @@ __global__ __launch_bounds__(BLOCK) void k_finalize_ps_hus(Levels lv, int ntime,
     if (hus_out) {
         const int N = lv.nlev;
         long long base = ix.t * N * ncol + ix.c;
+        int l_end = N;
+        if (marks) {
+            int m = 0;
+#pragma unroll
+            for (int v = 0; v < V; ++v) m = marks[c2 + v] > m ? marks[c2 + v] : m;
+            l_end = m < N ? m : N;
+        }
         // e is read for the last time and QV is not read again by this library: streaming loads / stores
 #pragma unroll 4
-        for (int l = l_start; l < N; ++l) {            // levels < l_start were written by k_delta_quad
+        for (int l = l_start; l < l_end; ++l) {        // levels < l_start were written by k_delta_quad
             double e[V], r[V];
             loadv_nt<TL, V>(evap + base + (long long)l * ncol, e);
             double am = lt.akm[l], bm = lt.bkm[l];
@@ -2855,6 +2904,11 @@ __global__ __launch_bounds__(BLOCK) void k_dphi_clim(long long n, DeltaSrc<T> z,
 // run as a continuation launch (first = 0) of the unchanged FLAGGED = false instantiation.
 // -------------------------------------------------------------------------------------
 constexpr int MULTI_MAX_PASS = 8;
+// Storage flows whose loop kernel takes the speculative QV store of PGW_OPT_QV_FROM_PASS (TL = storage type of the PGW level
+// arrays, REF = reference-dtype mode); an excluded flow compiles the parent's kernel.  DESIGN.md section 4 has the figures.
+// float32 fast mode is excluded: its loop kernel lost more (1.18 -> 1.30 ms) than its finalize kernel, which moves half the
+// bytes, gained (0.13 -> 0.06 ms).
+template <typename TL, bool REF> constexpr bool QV_FROM_PASS = sizeof(TL) == 8;
 #ifndef MULTI_MINW
 #define MULTI_MINW 4      // 128 VGPRs (12 bytes of scratch per lane): 1.28 -> 1.21 ms against 3 waves / 136 VGPRs; 5 waves spill 132 bytes and lose
 #endif
@@ -2879,14 +2933,31 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
                                                          DevStatus *st0 /* errors of the ERA-state scan */,
                                                          DevStatus *st /* [npass] */, LocalPRef loc,
                                                          const unsigned char *__restrict__ flags = nullptr,
-                                                         const DevStatus *st_era = nullptr) {
+                                                         const DevStatus *st_era = nullptr,
+                                                         TL *__restrict__ hus_out = nullptr, int l_start = 0,
+                                                         unsigned short *__restrict__ marks = nullptr) {
     static_assert(!LOCAL || V == 1, "local p_ref: one column per lane");
     static_assert(!FLAGGED || !LOCAL, "the fused first pass needs a fixed p_ref");
+    constexpr bool QVP = QV_FROM_PASS<TL, REF> && !LOCAL && !FLAGGED;
+    if constexpr (FLAGGED) {
+        // Nothing is staged before the flags are read: after a fused delta kernel almost every block finds none of its waves
+        // flagged and leaves here, without the tables and their barrier (all this launch did for 52 us).
+        long long gf = (long long)blockIdx.x * BLOCK + threadIdx.x;
+        const long long ngf = (long long)ntime * ncol / V;
+        if (gf >= ngf) gf = ngf - 1;
+        bool flagged = false;
+#pragma unroll
+        for (int v = 0; v < V; ++v) flagged = flagged || flags[(gf * V + v) >> 6] != 0;
+        if (blockIdx.x == 0 && threadIdx.x == 0 && st_era->code != 0) report(st0, st_era->code, (long long)st_era->col);
+        if (!__syncthreads_or(flagged)) return;
+    }
     __shared__ unsigned long long s_max[MULTI_MAX_PASS];          // per pass: max |err| as ordered bits, #valid, levels read
     __shared__ unsigned int s_valid[MULTI_MAX_PASS];
     __shared__ unsigned long long s_touched[MULTI_MAX_PASS];
     __shared__ double s_lev[LEVTAB_DOUBLES];
+    __shared__ unsigned long long s_stored;                       // QVP: level-columns of QV this block's last pass stored
     if (threadIdx.x < MULTI_MAX_PASS) { s_max[threadIdx.x] = 0ull; s_valid[threadIdx.x] = 0u; s_touched[threadIdx.x] = 0ull; }
+    if constexpr (QVP) { if (threadIdx.x == 0) s_stored = 0ull; }
     LevTab lt = stage_levels<true, true>(lv, s_lev, BLOCK);        // ends with a barrier
     const long long n2 = (long long)ntime * ncol;
     long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -2904,7 +2975,6 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
 #pragma unroll
         for (int v = 0; v < V; ++v) flagged = flagged || flags[(c2 + v) >> 6] != 0;
         run = __any(flagged);
-        if (blockIdx.x == 0 && threadIdx.x == 0 && st_era->code != 0) report(st0, st_era->code, (long long)st_era->col);
     }
     if (run) {
         ColIdx ix = col_index(g, V, ncol);
@@ -2940,6 +3010,7 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
             loadv<double, V>(adj_ps + c2, adj);
             if (LOCAL) { pref[0] = loc.p_ref_col[c2]; idx = loc.p_idx_col[c2]; }
         }
+        int low = N;                                               // QVP: lowest level index the last pass processed
         for (int k = 0; k < npass; ++k) {
             double ps[V];
 #pragma unroll
@@ -2971,8 +3042,19 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
                 }
             }
             int touched = 0;
-            scan_columns<TL, V, U, false, REF>(lv, lt, ncol, ta + lbase, evap + lbase, ps, z, pref, 0, st + k, c2, phi_ref, tlow,
-                                               touched);
+            if constexpr (QVP) {
+                // the last pass of the launch also stores its q into hus_pgw (see above), in an instantiation of its own: the
+                // other passes keep the parent's loop.  (One body with l_lim = N for them measured the same per file, 3.2345
+                // vs 3.2355 ms, but needs 28 bytes of scratch against 20: DESIGN.md section 4.)
+                const bool last = k == npass - 1 && hus_out;
+                const long long qdiff = (const char *)hus_out - (const char *)evap;
+                if (last) scan_columns<TL, V, U, false, REF, 2>(lv, lt, ncol, ta + lbase, evap + lbase, ps, z, pref, 0, st + k, c2,
+                                                                phi_ref, tlow, touched, qdiff, l_start, live, &low);
+                else scan_columns<TL, V, U, false, REF, 1>(lv, lt, ncol, ta + lbase, evap + lbase, ps, z, pref, 0, st + k, c2, phi_ref,
+                                                           tlow, touched);
+            } else
+                scan_columns<TL, V, U, false, REF>(lv, lt, ncol, ta + lbase, evap + lbase, ps, z, pref, 0, st + k, c2, phi_ref, tlow,
+                                                   touched);
             double amax = -1.0;
 #pragma unroll
             for (int v = 0; v < V; ++v) {
@@ -2995,6 +3077,19 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
             storev<double, V>(delta_ps + c2, dps);        // state after the last pass: a continuation launch resumes here
             storev<double, V>(adj_ps + c2, adj);
         }
+        if constexpr (QVP) {
+            if (hus_out) {
+                // the levels low .. N-1 (from l_start on) of these columns now hold the q of pass npass-1; the stop is
+                // wave-uniform, so one lane speaks for the wave's live columns
+                if (live) {
+#pragma unroll
+                    for (int v = 0; v < V; ++v) marks[c2 + v] = (unsigned short)low;
+                }
+                const int stored = N - (low > l_start ? low : l_start);
+                const unsigned long long nlive = __popcll(__ballot(live));
+                if ((threadIdx.x & 63) == 0 && stored > 0) atomicAdd(&s_stored, nlive * V * (unsigned long long)stored);
+            }
+        }
         if (LOCAL && live) {
             loc.p_ref_col[c2] = pref[0]; loc.p_idx_col[c2] = idx;
             phi_ref_era[c2] = phi_era[0]; dphi_clim[c2] = dphi[0];
@@ -3008,6 +3103,9 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
             atomicAdd(&st[k].valid, 1ull);
         }
         atomicAdd(&st[k].levels_touched, s_touched[k]);
+    }
+    if constexpr (QVP) {
+        if (threadIdx.x == 0 && hus_out && s_stored) atomicAdd(&st[npass - 1].qv_stored, s_stored);
     }
 }
 

@@ -419,7 +419,7 @@ class Context:
         self._check(self.lib.pgw_sync(self.handle))
 
     def set_option(self, name, value):
-        """Per-context option of include/pgw_hip.h `enum pgw_option` ('quad', 'full_column', 'force_vec1', 'multipass', 'loop_guess', 'force_off64', 'test_fail', 'fused_first', 'mixed_vec', 'sparse_direct');
+        """Per-context option of include/pgw_hip.h `enum pgw_option` ('quad', 'full_column', 'force_vec1', 'multipass', 'loop_guess', 'force_off64', 'test_fail', 'fused_first', 'mixed_vec', 'sparse_direct', 'qv_from_pass');
         returns the previous value."""
         old = self.get_option(name)
         self._check(self.lib.pgw_set_option(self.handle, _lib.OPTIONS[name], int(value)))
@@ -429,6 +429,13 @@ class Context:
         v = C.c_int(0)
         self._check(self.lib.pgw_get_option(self.handle, _lib.OPTIONS[name], C.byref(v)))
         return v.value
+
+    def last_qv_from_pass(self):
+        """(used, skipped) of the last file or `adjust_ps` loop on this context (`pgw_last_qv_from_pass`): whether its finalize
+        kernel took the QV below p_ref from the converged pass, and the level-columns it skipped because of that."""
+        n = C.c_ulonglong(0)
+        used = self.lib.pgw_last_qv_from_pass(self.handle, C.byref(n))
+        return bool(used), int(n.value)
 
     def device_name(self):
         buf = C.create_string_buffer(256)
