@@ -707,6 +707,26 @@ int pgw_clim_accumulate(pgw_ctx *ctx, int dtype_in, int dtype_out, int nrec, lon
  * out[i] = (dtype)((double)a[i] - (double)b[i]) on n elements; NaN (missing) in either operand gives NaN. */
 int pgw_field_sub(pgw_ctx *ctx, int dtype, long long n, const void *a, const void *b, void *out);
 
+/* s6 level list, lon-lat box and model-top merge          step_01_extract_deltas/extract_climate_delta.sh:194-208 and
+ * CFday_cut_subdomain.sh:28-30 (`cdo sellonlatbox,$box`), Emon_add_top_from_Amon.sh:45-56 (`cdo sellevel` twice and
+ * `cdo -O merge`).  A copy of words:
+ *   dst[r, lev_dst0 + k, i, j] = src[r, lev_index[k], lat0 + i, (lon0 + j) % nlon_src]
+ * src (nrec, nlev_src, nlat_src, nlon_src), dst (nrec, nlev_dst, nlat_sel, nlon_sel): device arrays of elements of
+ * `elem_bytes` = 2, 4 or 8 bytes (NetCDF-3 short, int / float, double), copied as unsigned integers of that size - no
+ * arithmetic and no dtype tag, so raw big-endian file bytes go through as well as decoded arrays, and every NaN payload,
+ * `_FillValue` and packed value is kept bit for bit.  Only levels lev_dst0 .. lev_dst0 + nlev_sel - 1 of dst are written:
+ * two calls with different lev_dst0 into one dst are the merge.  A variable without a level axis passes nlev_src = 1;
+ * leading dimensions fold into nrec.
+ *  lev_index (nlev_sel, HOST, any order, nlev_sel <= 256; NULL = 0 .. nlev_sel - 1): source level of each output level.
+ *  lat0, nlat_sel: the source rows lat0 .. lat0 + nlat_sel - 1.  lon0 in [0, nlon_src), nlon_sel in [1, nlon_src]: the
+ *  cyclic run of source columns (lon0 + j) mod nlon_src.  src and dst must not overlap.
+ * A lane moves 16, 8, 4 or 2 bytes - the widest word that divides nlon_src, nlon_sel and lon0 in bytes and both addresses
+ * (PGW_OPT_FORCE_VEC1: one element); byte offsets are 32-bit when both arrays are below 4 GiB (PGW_OPT_FORCE_OFF64: 64-bit).
+ * The same bytes in every form.  Not timed by the launch profiler (pgw_timer_start / _stop around the call do). */
+int pgw_select_box(pgw_ctx *ctx, int elem_bytes, int nrec, int nlev_src, int nlat_src, int nlon_src, const void *src,
+                   int nlev_sel, const int *lev_index, int lat0, int nlat_sel, int lon0, int nlon_sel, int nlev_dst,
+                   int lev_dst0, void *dst);
+
 /* Diagnostic: the loads of pgw_clim_accumulate on x (nrec, inner) and nothing else, on the same grid, timed under
  * PGW_K_CLIM_READ - what the card gives this access pattern (tools/clim_time.py); no reference counterpart. */
 int pgw_test_read_records(pgw_ctx *ctx, int dtype, int nrec, long long inner, const void *x);

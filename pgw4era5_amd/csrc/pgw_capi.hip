@@ -847,6 +847,59 @@ extern "C" int pgw_field_sub(pgw_ctx *ctx, int dtype, long long n, const void *a
     return PGW_OK;
 }
 
+// ------------------------------------------------------------------ step_01: level list, lon-lat box, model-top merge
+extern "C" int pgw_select_box(pgw_ctx *ctx, int elem_bytes, int nrec, int nlev_src, int nlat_src, int nlon_src, const void *src,
+                              int nlev_sel, const int *lev_index, int lat0, int nlat_sel, int lon0, int nlon_sel, int nlev_dst,
+                              int lev_dst0, void *dst) {
+    NEED(ctx, elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8, "elem_bytes must be 2, 4 or 8");
+    NEED(ctx, nrec >= 1 && nlev_src >= 1 && nlat_src >= 1 && nlon_src >= 1, "nrec, nlev_src, nlat_src and nlon_src must be positive");
+    NEED(ctx, src && dst, "null pointer");
+    NEED(ctx, nlev_sel >= 1 && nlev_sel <= SEL_MAX_LEVELS, "nlev_sel must be in [1, 256]");
+    NEED(ctx, lev_index || nlev_sel <= nlev_src, "without lev_index nlev_sel must not exceed nlev_src");
+    SelLevels tab;
+    for (int k = 0; k < nlev_sel; ++k) {
+        tab.lev[k] = lev_index ? lev_index[k] : k;
+        NEED(ctx, tab.lev[k] >= 0 && tab.lev[k] < nlev_src, "lev_index must lie in [0, nlev_src)");
+    }
+    NEED(ctx, lat0 >= 0 && nlat_sel >= 1 && (long long)lat0 + nlat_sel <= nlat_src, "lat0 .. lat0 + nlat_sel must lie within [0, nlat_src]");
+    NEED(ctx, lon0 >= 0 && lon0 < nlon_src, "lon0 must lie in [0, nlon_src)");
+    NEED(ctx, nlon_sel >= 1 && nlon_sel <= nlon_src, "nlon_sel must be in [1, nlon_src]");
+    NEED(ctx, lev_dst0 >= 0 && nlev_dst >= 1 && (long long)lev_dst0 + nlev_sel <= nlev_dst, "lev_dst0 + nlev_sel must not exceed nlev_dst");
+    const unsigned long long eb = (unsigned long long)elem_bytes;
+    const unsigned long long src_bytes = (unsigned long long)nrec * nlev_src * nlat_src * nlon_src * eb;
+    const unsigned long long dst_bytes = (unsigned long long)nrec * nlev_dst * nlat_sel * nlon_sel * eb;
+    const uintptr_t ps = (uintptr_t)src, pd = (uintptr_t)dst;
+    NEED(ctx, ps % eb == 0 && pd % eb == 0, "src and dst must be aligned to elem_bytes");
+    NEED(ctx, ps + src_bytes <= pd || pd + dst_bytes <= ps, "src and dst must not overlap");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // bytes per lane: the widest word (16, 8, 4, 2) that divides both row lengths, the first column - and with it the place
+    // where the window wraps, nlon_src - lon0 - and both base addresses; every row then starts on such a word
+    unsigned long long wb = ctx->opt[PGW_OPT_FORCE_VEC1] ? eb : 16;
+    while (wb > eb && ((nlon_src * eb) % wb || (nlon_sel * eb) % wb || (lon0 * eb) % wb || ps % wb || pd % wb)) wb >>= 1;
+    const unsigned long long per = wb / eb, nsel_w = (unsigned long long)nlon_sel / per;
+    const unsigned int lpr = (unsigned int)std::min<unsigned long long>(nsel_w, BLOCK), rpb = BLOCK / lpr;
+    const unsigned long long nrows = (unsigned long long)nrec * nlev_sel * nlat_sel;
+    const unsigned long long tile_rows = (unsigned long long)rpb * SEL_ROWS;
+    const unsigned int grid = (unsigned int)std::min<unsigned long long>((nrows + tile_rows - 1) / tile_rows, 256ull * 16);
+    const bool o32 = src_bytes < (1ull << 32) && dst_bytes < (1ull << 32) && !ctx->opt[PGW_OPT_FORCE_OFF64];
+    with_offsets(o32, [&](auto o_) {
+        using O = decltype(o_);
+        const SelBox<O> a = {(O)nrows, (unsigned int)nlev_sel, (unsigned int)nlat_sel, (O)nlev_src, (O)nlat_src,
+                             (O)((unsigned long long)nlon_src / per), (O)lat0, (O)((unsigned long long)lon0 / per), (O)nsel_w,
+                             (O)nlev_dst, (O)lev_dst0, lpr, rpb};
+        auto launch = [&](auto w_) {
+            using W = decltype(w_);
+            hipLaunchKernelGGL((k_select_box<W, O>), dim3(grid), dim3(BLOCK), 0, ctx->stream, a, tab, (const W *)src, (W *)dst);
+        };
+        if (wb == 16) launch(VecOf<unsigned int, 4>::type());
+        else if (wb == 8) launch((unsigned long long)0);
+        else if (wb == 4) launch((unsigned int)0);
+        else launch((unsigned short)0);
+    });
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
 // ------------------------------------------------------------------ time lerp
 extern "C" int pgw_time_lerp(pgw_ctx *ctx, int dtype, long long n, const void *v_before, const void *v_after,
                              double x_hi, double x_new, void *out) {

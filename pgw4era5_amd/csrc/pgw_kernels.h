@@ -1161,6 +1161,67 @@ __global__ __launch_bounds__(BLOCK) void k_field_sub(long long n, const T *__res
 }
 
 // =====================================================================================
+// s6  level list, lon-lat box and model-top merge      step_01_extract_deltas/extract_climate_delta.sh:194-208,
+//     (`cdo sellonlatbox`, `cdo sellevel`, `cdo -O merge`)      CFday_cut_subdomain.sh:28-30, Emon_add_top_from_Amon.sh:45-56
+//   dst[r, lev_dst0 + k, i, j] = src[r, lev[k], lat0 + i, (lon0 + j) % nlon_src]
+// A copy of words, no arithmetic: W is an unsigned word of 2, 4, 8 or 16 bytes, so NaN payloads, fill values, packed
+// integers and raw big-endian file bytes go through bit for bit.  The host picks the widest W that divides the row lengths,
+// lon0 (hence the place where the window wraps) and both base addresses, and hands over every longitude count in units of
+// W: the wide forms ARE the scalar form on a coarser word, which is why all forms give the same bytes.
+// Lanes run along the output longitude: `lpr` lanes per output row, BLOCK / lpr rows side by side in a block (a short row
+// does not leave most of a wave idle), a row longer than the block is walked in steps of lpr.  Each lane takes SEL_ROWS
+// rows per pass, their loads issued before the first store; blocks stride over the row tiles, so the number of rows has no
+// grid limit.  The level list comes in the kernel arguments and is staged in LDS (a lane-dependent index into it).
+// O: row index and byte offsets (pgw_device.h ld_off), 32-bit when source and destination are smaller than 4 GiB.
+// =====================================================================================
+constexpr int SEL_MAX_LEVELS = MAX_NLEV;
+constexpr int SEL_ROWS = 4;                // 8 / 16 rows per lane for the 4-byte form of the example box: 0.087 / 0.074 ms against 0.075
+struct SelLevels { int lev[SEL_MAX_LEVELS]; };
+template <typename O> struct SelBox {
+    O nrows;                               // nrec * nlev_sel * nlat_sel output rows
+    unsigned int nlev_sel, nlat_sel;
+    O nlev_src, nlat_src, nlon_src;        // nlon_*, lon0 in words W
+    O lat0, lon0, nlon_sel;
+    O nlev_dst, lev_dst0;
+    unsigned int lpr, rpb;                 // lanes per row, rows per block: lpr * rpb <= BLOCK
+};
+template <typename W, typename O>
+__global__ __launch_bounds__(BLOCK) void k_select_box(SelBox<O> a, SelLevels tab, const W *__restrict__ src, W *__restrict__ dst) {
+    __shared__ int s_lev[SEL_MAX_LEVELS];
+    for (unsigned int k = threadIdx.x; k < a.nlev_sel; k += BLOCK) s_lev[k] = tab.lev[k];
+    __syncthreads();
+    const unsigned int sub = threadIdx.x / a.lpr, lane = threadIdx.x - sub * a.lpr;
+    if (sub >= a.rpb) return;                                  // BLOCK is not a multiple of lpr: the rest of the block idles
+    const O tile_rows = (O)(a.rpb * SEL_ROWS);
+    const O ntiles = (a.nrows + tile_rows - 1) / tile_rows;
+    for (O tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        O soff[SEL_ROWS], doff[SEL_ROWS];
+        bool ok[SEL_ROWS];
+#pragma unroll
+        for (int u = 0; u < SEL_ROWS; ++u) {
+            const O row = tile * tile_rows + (O)(u * a.rpb + sub);
+            ok[u] = row < a.nrows;
+            const O rk = row / a.nlat_sel, i = row - rk * a.nlat_sel;
+            const O r = rk / a.nlev_sel, k = rk - r * a.nlev_sel;
+            const O lev = (O)s_lev[k];
+            soff[u] = ((r * a.nlev_src + lev) * a.nlat_src + a.lat0 + i) * a.nlon_src * (O)sizeof(W);
+            doff[u] = ((r * a.nlev_dst + a.lev_dst0 + k) * a.nlat_sel + i) * a.nlon_sel * (O)sizeof(W);
+        }
+        for (O j = lane; j < a.nlon_sel; j += a.lpr) {
+            O js = a.lon0 + j;                                 // lon0 < nlon_src and j < nlon_sel <= nlon_src: one wrap at most
+            if (js >= a.nlon_src) js -= a.nlon_src;
+            W v[SEL_ROWS];
+#pragma unroll
+            for (int u = 0; u < SEL_ROWS; ++u)
+                if (ok[u]) v[u] = ld_off_nt<W, O>(src, soff[u] + js * (O)sizeof(W));
+#pragma unroll
+            for (int u = 0; u < SEL_ROWS; ++u)
+                if (ok[u]) st_off_nt<W, O>(dst, doff[u] + j * (O)sizeof(W), v[u]);
+        }
+    }
+}
+
+// =====================================================================================
 // a7  time lerp of load_delta                                  functions.py:288-292
 // =====================================================================================
 // TB / TA / TO: storage types of the two records and of the result.  REF (settings.function_dtype_flow = 'reference'):

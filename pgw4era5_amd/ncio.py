@@ -501,10 +501,35 @@ class RecordReader:
                     self.coords[d] = arr
             probe, self.attrs = mask_and_scale(np.zeros(1, dtype=v['dtype']), dict(v['attrs']))
             self.dtype = probe.dtype
+            self.file_dtype, self.file_attrs = v['dtype'], dict(v['attrs'])   # the NetCDF type and the attributes as stored
         finally:
             os.close(fd)
         self._fd = None
         self._lock = __import__('threading').Lock()
+
+    def read_record_raw(self, r, out=None):
+        """Record r as the file holds it: the `pread` alone, no byte swap and no decoding.  -> array of `rec_shape` in the
+        file's big-endian dtype ('>f4', '>i2', ...; `file_dtype` with the byte order of the file), a view of `out` when a
+        writable C-contiguous buffer of the record's size is given."""
+        import os
+        r = int(r)
+        if not 0 <= r < self.nrec:
+            raise IndexError(r)
+        v = self._v
+        with self._lock:
+            if self._fd is None:
+                self._fd = os.open(self.path, os.O_RDONLY)
+        if out is None:
+            buf = np.empty(self._inner, dtype=np.uint8)
+        else:
+            buf = out.reshape(-1).view(np.uint8)
+            if buf.size != self._inner or not np.shares_memory(buf, out):
+                raise ValueError('out must be a C-contiguous buffer of %d bytes' % self._inner)
+        # a record variable's records are `recsize` apart; a fixed-size variable's first dimension is contiguous
+        off = v['begin'] + (r * self._recsize if v['record'] else r * self._inner)
+        if self._inner:
+            _pread_into(self._fd, buf, off)
+        return buf.view(v['dtype'].newbyteorder('>') if v['dtype'].itemsize > 1 else v['dtype']).reshape(self.rec_shape)
 
     def read_record(self, r):
         import os

@@ -20,14 +20,22 @@ step_01: the array programs of the reference's step_01_extract_deltas directory 
   conventions (date of the last contributing record, records sorted by month / day key); bit parity with cdo is unpinned
   (kind U).
 
-The rest of the shell templates of step_01 (site paths, `sellonlatbox`, the Emon model-top merge, `wget`) are site scripts
-and stay out of scope.
+* `extract_climate_delta.sh:194-208`, `CFday_cut_subdomain.sh:28-30` (`cdo sellonlatbox,$box`) and
+  `Emon_add_top_from_Amon.sh:45-56` (`cdo sellevel` twice, `cdo -O merge`): a level list, a latitude x cyclic-longitude
+  window and the concatenation of two files' levels -> `lonlat_box` / `level_indices` / `select` / `select_file` /
+  `merge_levels_files`, sub-commands `select` and `merge_levels`, and `climatology_files(box=...)`.  One kernel that moves
+  words (`pgw_select_box`): the variable goes through the card as the raw bytes of the file, so its NetCDF type, fill
+  values and packing are kept bit for bit.  Parity with cdo is unpinned here too; the docstrings are the contract.
+
+The rest of the shell templates of step_01 (site paths, `wget`) are site scripts and stay out of scope (DESIGN.md
+section 7).
 
 Array kinds as in `functions.py`: numpy, `ncio.Field` (labels re-wrapped) or `DeviceArray` in, the same kind out.
 Files are NetCDF-3 through `ncio` like everywhere in this package.
 """
 import argparse
 import os
+import sys
 
 import numpy as np
 
@@ -325,6 +333,354 @@ def hus_to_hur_file(hus_file, ta_file, hur_file, amon_hur_file):
     return hur_file
 
 
+# ------------------------------------------------------------------------------- level list, lon-lat box, model-top merge
+def lonlat_box(lat, lon, box):
+    """`cdo sellonlatbox,lon1,lon2,lat1,lat2` on 1-D coordinates -> (lat0, nlat_sel, lon0, nlon_sel, lon_out): the rows
+    lat0 .. lat0 + nlat_sel - 1 and the cyclic run of columns (lon0 + j) % len(lon), j < nlon_sel; `lon_out` their
+    longitudes shifted into the box.
+    box = (lon1, lon2, lat1, lat2) with lon1 < lon2 and lon2 - lon1 <= 360.  Rows with min(lat1, lat2) <= lat <= max(lat1,
+    lat2) are kept in file order (north to south or south to north).  Column i is selected when lon1 <= lon[i] + 360 k <=
+    lon2 for an integer k; the smallest such k is taken, so a column appears once, and the columns are ordered by that
+    shifted longitude ascending - for the strictly ascending `lon` required here that is one cyclic run.  A box across 0
+    deg on a 0 ... 360 grid (-73, 37) therefore gives negative, then positive longitudes; (0, 360, -90, 90) on a 0 ... <360
+    grid is the identity.  ValueError: coordinates that are not 1-D (2-D curvilinear coordinates are not supported here),
+    `lon` not strictly ascending, a bad box, rows that do not form one contiguous run (`lat` not monotonic), nothing
+    selected."""
+    lat, lon = np.asarray(raw(lat)), np.asarray(raw(lon))
+    if lat.ndim != 1 or lon.ndim != 1:
+        raise ValueError('lonlat_box needs 1-D lat and lon; 2-D (curvilinear) coordinates are not supported here')
+    out_dtype = lon.dtype if lon.dtype.kind == 'f' else F64
+    lat, lon = lat.astype(np.float64), lon.astype(np.float64)
+    if len(lon) > 1 and not np.all(np.diff(lon) > 0):
+        raise ValueError('lon must be strictly ascending')
+    try:
+        lon1, lon2, lat1, lat2 = (float(b) for b in box)
+    except (TypeError, ValueError):
+        raise ValueError('box must be (lon1, lon2, lat1, lat2), got %r' % (box,)) from None
+    if not lon1 < lon2 or lon2 - lon1 > 360.0:
+        raise ValueError('box needs lon1 < lon2 and lon2 - lon1 <= 360, got %r, %r' % (lon1, lon2))
+    rows = np.nonzero((lat >= min(lat1, lat2)) & (lat <= max(lat1, lat2)))[0]
+    if not len(rows):
+        raise ValueError('no latitude lies within [%r, %r]' % (min(lat1, lat2), max(lat1, lat2)))
+    if rows[-1] - rows[0] + 1 != len(rows):
+        raise ValueError('the selected latitudes are not one contiguous run of rows: lat must be monotonic')
+    k = np.ceil((lon1 - lon) / 360.0)                             # the smallest k with lon + 360 k >= lon1 ...
+    k += (lon + 360.0 * k) < lon1                                 # ... whatever the division rounded to
+    k -= (lon + 360.0 * (k - 1.0)) >= lon1
+    shifted = lon + 360.0 * k
+    cols = np.nonzero(shifted <= lon2)[0]
+    if not len(cols):
+        raise ValueError('no longitude lies within [%r, %r]' % (lon1, lon2))
+    cols = cols[np.argsort(shifted[cols], kind='stable')]
+    if not np.array_equal(cols, (cols[0] + np.arange(len(cols))) % len(lon)):
+        raise ValueError('the selected longitudes are not one cyclic run of columns (does lon span more than 360 degrees?)')
+    return int(rows[0]), int(len(rows)), int(cols[0]), int(len(cols)), shifted[cols].astype(out_dtype)
+
+
+def level_indices(plev, levels):
+    """`cdo sellevel,levels`: the indices into `plev` of the requested values IN FILE ORDER (cdo keeps the file's order
+    whatever the order of the request).  Exact equality.  ValueError: a requested level that is absent (named), a level
+    requested twice."""
+    plev = np.asarray(raw(plev)).astype(np.float64).reshape(-1)
+    want = np.atleast_1d(np.asarray(levels, dtype=np.float64)).reshape(-1)
+    if not len(want):
+        raise ValueError('no level requested')
+    for i, v in enumerate(want):
+        if not np.any(plev == v):
+            raise ValueError('level %r is not in the file (levels: %s)' % (float(v), plev.tolist()))
+        if np.any(want[:i] == v):
+            raise ValueError('level %r is requested twice' % float(v))
+    return np.nonzero(np.isin(plev, want))[0].astype(np.int32)
+
+
+def _launch_select(ctx, itemsize, nrec, nlev_src, nlat_src, nlon_src, src_ptr, lev_idx, rows, cols, nlev_dst, lev_dst0, dst_ptr):
+    """pgw_select_box: lev_idx (int array, or None = all nlev_src levels), rows = (lat0, nlat_sel), cols = (lon0, nlon_sel)."""
+    if lev_idx is None:
+        nsel, p_lev = nlev_src, None
+    else:
+        lev_idx = np.ascontiguousarray(lev_idx, dtype=np.int32)
+        nsel, p_lev = len(lev_idx), lev_idx.ctypes.data_as(_ip)
+    ctx._check(ctx.lib.pgw_select_box(ctx.handle, int(itemsize), int(nrec), int(nlev_src), int(nlat_src), int(nlon_src), src_ptr,
+                                      int(nsel), p_lev, int(rows[0]), int(rows[1]), int(cols[0]), int(cols[1]), int(nlev_dst),
+                                      int(lev_dst0), dst_ptr))
+
+
+def _upload_words(ctx, d, host):
+    """host -> the DeviceArray d as it is: no cast and no byte-order conversion (`DeviceArray.copy_from` converts)."""
+    host = np.ascontiguousarray(host)
+    if host.nbytes != d.nbytes:
+        raise ValueError('upload of %d bytes into a device array of %d' % (host.nbytes, d.nbytes))
+    if d.nbytes:
+        ctx._check(ctx.lib.pgw_memcpy_h2d(ctx.handle, d.ptr, host.ctypes.data, d.nbytes))
+        ctx.sync()                                                # pageable source
+
+
+def _word_size(dtype):
+    n = np.dtype(dtype).itemsize
+    if n not in (2, 4, 8):
+        raise ValueError('elements of 2, 4 or 8 bytes (NetCDF short, int / float, double) can be selected, got %s' % np.dtype(dtype))
+    return n
+
+
+def select(field, levels=None, box=None, plev=None, lat=None, lon=None):
+    """`cdo sellevel` and / or `cdo sellonlatbox` on an array (..., [plev,] lat, lon): a numpy array, an `ncio.Field` or a
+    `DeviceArray` in, the same kind and the same dtype out (elements of 2, 4 or 8 bytes are moved as words, any byte
+    order).  levels: the level values to keep (`level_indices`, file order); box = (lon1, lon2, lat1, lat2)
+    (`lonlat_box`).  plev / lat / lon: the 1-D coordinates; a labelled input brings its own and comes back with the cut /
+    shifted ones.  The array has a level axis - third from the end - when `plev` is given or a labelled input names it."""
+    r = raw(field)
+    shape = tuple(r.shape)
+    labelled = is_labelled(field)
+    coords = dict(getattr(field, 'coords', {})) if labelled else {}
+    dims = tuple(field.dims) if labelled else None
+    if labelled:
+        if len(dims) < 2 or dims[-2:] != (LAT_GCM, LON_GCM):
+            raise ValueError('the dimensions must end in ([%s,] %s, %s), got %s' % (PLEV_GCM, LAT_GCM, LON_GCM, dims))
+        has_lev = len(dims) >= 3 and dims[-3] == PLEV_GCM
+        plev = coords.get(PLEV_GCM) if plev is None and has_lev else plev
+        lat = coords.get(LAT_GCM) if lat is None else lat
+        lon = coords.get(LON_GCM) if lon is None else lon
+    else:
+        has_lev = plev is not None
+    if len(shape) < (3 if has_lev else 2):
+        raise ValueError('expected an array (..., %slat, lon), got shape %s' % ('plev, ' if has_lev else '', shape))
+    nlat, nlon = shape[-2:]
+    nlev = shape[-3] if has_lev else 1
+    lev_idx, rows, cols, lon_out = None, (0, nlat), (0, nlon), None
+    if levels is not None:
+        if not has_lev or plev is None:
+            raise ValueError('levels need an array with a level axis and its plev coordinate')
+        if len(np.asarray(raw(plev)).reshape(-1)) != nlev:
+            raise ValueError('plev has %d values for %d levels' % (len(np.asarray(raw(plev)).reshape(-1)), nlev))
+        lev_idx = level_indices(plev, levels)
+    if box is not None:
+        if lat is None or lon is None:
+            raise ValueError('a box needs the lat and lon coordinates')
+        if np.shape(raw(lat)) != (nlat,) or np.shape(raw(lon)) != (nlon,):
+            raise ValueError('lat / lon do not match the last two axes %s' % ((nlat, nlon),))
+        lat0, nlat_sel, lon0, nlon_sel, lon_out = lonlat_box(lat, lon, box)
+        rows, cols = (lat0, nlat_sel), (lon0, nlon_sel)
+    item = _word_size(r.dtype)
+    lead = shape[:-3] if has_lev else shape[:-2]
+    nrec = int(np.prod(lead, dtype=np.int64))
+    nsel = nlev if lev_idx is None else len(lev_idx)
+    out_shape = lead + ((nsel,) if has_lev else ()) + (rows[1], cols[1])
+    if nrec < 1:
+        raise ValueError('empty array')
+    ctx = default_context()
+    if isinstance(r, DeviceArray):
+        d_in = r
+    else:
+        d_in = ctx.empty(shape, r.dtype)
+        _upload_words(ctx, d_in, r)
+    d_out = ctx.empty(out_shape, r.dtype)
+    _launch_select(ctx, item, nrec, nlev, nlat, nlon, d_in.ptr, lev_idx, rows, cols, nsel, 0, d_out.ptr)
+    if isinstance(r, DeviceArray):
+        return d_out
+    host = d_out.numpy()
+    if not labelled:
+        return host
+    if lev_idx is not None:
+        coords[PLEV_GCM] = np.asarray(raw(plev)).reshape(-1)[lev_idx]
+    if box is not None:
+        coords[LAT_GCM] = np.asarray(raw(lat))[rows[0]:rows[0] + rows[1]]
+        coords[LON_GCM] = lon_out
+    return ncio.Field(host, dims, coords, dict(getattr(field, 'attrs', {})), getattr(field, 'name', None))
+
+
+class _Cut:
+    """What a selection does to every OTHER variable of a file, on the host: the level indices along `plev`, the rows along
+    `lat`, the cyclic run of columns along `lon`; the longitude coordinate and its bounds take the +360 k shift."""
+
+    def __init__(self, ds, lev_idx=None, box=None):
+        self.lev_idx = None if lev_idx is None else np.asarray(lev_idx, dtype=np.int64)
+        self.rows = self.cols = self.shift = None
+        self.lon_names = ()
+        if box is not None:
+            for d in (LAT_GCM, LON_GCM):
+                if d not in ds:
+                    raise ValueError('a box needs the coordinate variable %s in the file' % d)
+            lat, lon = ds[LAT_GCM].values, ds[LON_GCM].values
+            self.lat0, self.nlat_sel, self.lon0, self.nlon_sel, lon_out = lonlat_box(lat, lon, box)
+            self.rows = slice(self.lat0, self.lat0 + self.nlat_sel)
+            self.cols = (self.lon0 + np.arange(self.nlon_sel)) % len(lon)
+            self.shift = np.round((lon_out.astype(np.float64) - np.asarray(lon, dtype=np.float64)[self.cols]) / 360.0) * 360.0
+            self.lon_names = (LON_GCM, str(ds[LON_GCM].attrs.get('bounds', LON_GCM + '_bnds')))
+
+    def touches(self, f):
+        return ((self.lev_idx is not None and PLEV_GCM in f.dims) or
+                (self.rows is not None and (LAT_GCM in f.dims or LON_GCM in f.dims)))
+
+    def field(self, name, f):
+        """The variable `f` of the input cut with the selection's indices."""
+        if not self.touches(f):
+            return ncio.Field(f.values, f.dims, f.coords, dict(f.attrs))
+        v = np.asarray(f.values)
+        for ax, d in enumerate(f.dims):
+            if d == PLEV_GCM and self.lev_idx is not None:
+                v = np.take(v, self.lev_idx, axis=ax)
+            elif d == LAT_GCM and self.rows is not None:
+                v = v[(slice(None),) * ax + (self.rows,)]
+            elif d == LON_GCM and self.cols is not None:
+                v = np.take(v, self.cols, axis=ax)
+                if name in self.lon_names and v.dtype.kind == 'f':
+                    sh = self.shift.reshape((-1,) + (1,) * (v.ndim - ax - 1))
+                    v = np.where(sh != 0, v + sh, v).astype(v.dtype)           # columns that do not move keep their bits
+        return ncio.Field(v, f.dims, {}, dict(f.attrs))
+
+
+def _grid_dims(dims, what):
+    """(number of leading dimensions, has a level axis) of a variable whose dimensions end in ([plev,] lat, lon)."""
+    dims = tuple(dims)
+    if len(dims) < 2 or dims[-2:] != (LAT_GCM, LON_GCM):
+        raise ValueError('%s: the dimensions must end in ([%s,] %s, %s), got %s' % (what, PLEV_GCM, LAT_GCM, LON_GCM, dims))
+    has_lev = len(dims) >= 3 and dims[-3] == PLEV_GCM
+    nlead = len(dims) - (3 if has_lev else 2)
+    if nlead < 1:
+        raise ValueError('%s: a leading (time) dimension is needed in front of ([%s,] %s, %s), got %s'
+                         % (what, PLEV_GCM, LAT_GCM, LON_GCM, dims))
+    return nlead, has_lev
+
+
+class _RawChunks:
+    """The records of one variable as raw file words through one device buffer of `nb` records: `load(r0, n)` reads records
+    r0 .. r0 + n - 1 (`RecordReader.read_record_raw`) and uploads them as they are; -> the device pointer."""
+
+    def __init__(self, ctx, reader, nb):
+        self.ctx, self.reader = ctx, reader
+        big = reader.file_dtype.newbyteorder('>')
+        self.host = np.empty((nb,) + reader.rec_shape, dtype=big)
+        self.dev = ctx.empty((nb,) + reader.rec_shape, big)
+
+    def load(self, r0, n):
+        for i in range(n):
+            self.reader.read_record_raw(r0 + i, out=self.host[i])
+        part = DeviceArray(self.ctx, (n,) + self.reader.rec_shape, self.host.dtype, ptr=self.dev.ptr, owner=self.dev)
+        _upload_words(self.ctx, part, self.host[:n])
+        return self.dev.ptr
+
+
+def select_file(inp, out, var_name, levels=None, box=None, max_records=None):
+    """`cdo sellevel,levels` and / or `cdo sellonlatbox,box` of one NetCDF-3 file (CFday_cut_subdomain.sh:28-30,
+    extract_climate_delta.sh:194-208, Emon_add_top_from_Amon.sh:45-52) -> `out`.
+    `var_name`, on (time, ..., [plev,] lat, lon) as named by settings, goes through the card in chunks of records
+    (`ncio.RecordReader`, what fits into 80 % of the free memory, at most `max_records`; the result does not depend on it)
+    AS THE RAW WORDS OF THE FILE: the output variable keeps its NetCDF type, every attribute, `_FillValue` and packing, and
+    its bytes are the input's.  Every other variable with the level, latitude or longitude dimension - the coordinates,
+    `lat_bnds`, `lon_bnds`, `plev_bnds` - is cut on the host with the same indices, `lon` and its bounds variable shifted by
+    the same 360 k (`lonlat_box`); everything else, the global attributes and the record dimension are carried over."""
+    ds, rd = _open_series(inp, var_name)
+    try:
+        nlead, has_lev = _grid_dims(rd.dims, var_name)
+        item = _word_size(rd.file_dtype)
+        lev_idx = None
+        if levels is not None:
+            if not has_lev or PLEV_GCM not in ds:
+                raise ValueError('%s: levels need the %s dimension and its coordinate variable' % (var_name, PLEV_GCM))
+            lev_idx = level_indices(ds[PLEV_GCM].values, levels)
+        cut = _Cut(ds, lev_idx, box)
+        nrec, rec_shape = rd.nrec, rd.rec_shape
+        nlat, nlon = rec_shape[-2:]
+        nlev = rec_shape[-3] if has_lev else 1
+        fold = int(np.prod(rec_shape[:nlead - 1], dtype=np.int64))          # leading dimensions behind the first one
+        rows = (cut.lat0, cut.nlat_sel) if box is not None else (0, nlat)
+        cols = (cut.lon0, cut.nlon_sel) if box is not None else (0, nlon)
+        nsel = nlev if lev_idx is None else len(lev_idx)
+        out_rec = rec_shape[:nlead - 1] + ((nsel,) if has_lev else ()) + (rows[1], cols[1])
+        big = rd.file_dtype.newbyteorder('>')
+        ctx = default_context()
+        per_rec = (int(np.prod(rec_shape, dtype=np.int64)) + int(np.prod(out_rec, dtype=np.int64))) * item
+        nb = _fit_records(ctx, nrec, per_rec, max_records)
+        chunks = _RawChunks(ctx, rd, nb)
+        d_out = ctx.empty((nb,) + out_rec, big)
+        result = np.empty((nrec,) + out_rec, dtype=big)
+        for r0 in range(0, nrec, nb):
+            n = min(nb, nrec - r0)
+            src = chunks.load(r0, n)
+            _launch_select(ctx, item, n * fold, nlev, nlat, nlon, src, lev_idx, rows, cols, nsel, 0, d_out.ptr)
+            result[r0:r0 + n] = DeviceArray(ctx, (n,) + out_rec, big, ptr=d_out.ptr, owner=d_out).numpy()
+    finally:
+        rd.close()
+    res = ncio.Dataset(attrs=dict(ds.attrs), record_dim=ds.record_dim)
+    for name, f in ds.variables.items():
+        res[name] = ncio.Field(result, rd.dims, {}, dict(rd.file_attrs)) if name == var_name else cut.field(name, f)
+    ncio.to_netcdf(res, out)
+    return out
+
+
+def merge_levels_files(path_a, path_b, out, var_name, levels_a=None, levels_b=None, max_records=None):
+    """Emon_add_top_from_Amon.sh:45-56 in one go - `cdo sellevel,levels_a a`, `cdo sellevel,levels_b b`, `cdo -O merge` -
+    without the two intermediate files: `var_name` of `out` holds the (selected, file order) levels of `path_a`, then those
+    of `path_b`, two `pgw_select_box` launches per chunk of records into one destination, raw file words as in
+    `select_file`.  levels_* = None: all levels of that file.
+    ValueError: the two variables are not on the same (time, ..., plev, lat, lon) dimensions and record shapes apart from the
+    number of levels, their time / lat / lon coordinates differ (the rule of `merge_hur_levels`: nothing is aligned), their
+    NetCDF types differ, a level is in both selections.  Metadata - global attributes, the variable's and the level
+    coordinate's attributes, every other variable - come from `path_a`; the level coordinate, and its bounds variable when
+    both files have it, are concatenated; other variables of `path_a` on the level dimension are left out.  The result
+    loads through `functions.load_delta`."""
+    ds_a, ra = _open_series(path_a, var_name)
+    try:
+        ds_b, rb = _open_series(path_b, var_name)
+    except Exception:
+        ra.close()
+        raise
+    try:
+        what = 'merge_levels_files'
+        for ds, rd, p in ((ds_a, ra, path_a), (ds_b, rb, path_b)):
+            nlead, has_lev = _grid_dims(rd.dims, '%s of %s' % (var_name, p))
+            if not has_lev or PLEV_GCM not in ds:
+                raise ValueError('%s of %s has no %s dimension with a coordinate variable' % (var_name, p, PLEV_GCM))
+        if ra.dims != rb.dims or ra.nrec != rb.nrec or ra.rec_shape[:-3] + ra.rec_shape[-2:] != rb.rec_shape[:-3] + rb.rec_shape[-2:]:
+            raise ValueError('%s: %s %s (%d records) of %s and %s %s (%d records) of %s do not match'
+                             % (what, ra.dims, ra.rec_shape, ra.nrec, path_a, rb.dims, rb.rec_shape, rb.nrec, path_b))
+        _same_coords(ds_a[var_name], ds_b[var_name], what)
+        if ra.file_dtype != rb.file_dtype:
+            raise ValueError('%s: the NetCDF types differ: %s in %s, %s in %s' % (what, ra.file_dtype, path_a, rb.file_dtype, path_b))
+        item = _word_size(ra.file_dtype)
+        plev_a, plev_b = np.asarray(ds_a[PLEV_GCM].values).reshape(-1), np.asarray(ds_b[PLEV_GCM].values).reshape(-1)
+        ia = np.arange(len(plev_a), dtype=np.int32) if levels_a is None else level_indices(plev_a, levels_a)
+        ib = np.arange(len(plev_b), dtype=np.int32) if levels_b is None else level_indices(plev_b, levels_b)
+        both = np.intersect1d(plev_a[ia].astype(np.float64), plev_b[ib].astype(np.float64))
+        if len(both):
+            raise ValueError('%s: levels %s are selected from both files' % (what, both.tolist()))
+        nlev_out = len(ia) + len(ib)
+        if nlev_out > MAX_LEVELS:
+            raise ValueError('%s: at most %d levels, got %d' % (what, MAX_LEVELS, nlev_out))
+        nrec, nlat, nlon = ra.nrec, ra.rec_shape[-2], ra.rec_shape[-1]
+        fold = int(np.prod(ra.rec_shape[:-3], dtype=np.int64))
+        out_rec = ra.rec_shape[:-3] + (nlev_out, nlat, nlon)
+        big = ra.file_dtype.newbyteorder('>')
+        ctx = default_context()
+        per_rec = sum(int(np.prod(s, dtype=np.int64)) for s in (ra.rec_shape, rb.rec_shape, out_rec)) * item
+        nb = _fit_records(ctx, nrec, per_rec, max_records)
+        ca, cb = _RawChunks(ctx, ra, nb), _RawChunks(ctx, rb, nb)
+        d_out = ctx.empty((nb,) + out_rec, big)
+        result = np.empty((nrec,) + out_rec, dtype=big)
+        for r0 in range(0, nrec, nb):
+            n = min(nb, nrec - r0)
+            src_a, src_b = ca.load(r0, n), cb.load(r0, n)
+            _launch_select(ctx, item, n * fold, len(plev_a), nlat, nlon, src_a, ia, (0, nlat), (0, nlon), nlev_out, 0, d_out.ptr)
+            _launch_select(ctx, item, n * fold, len(plev_b), nlat, nlon, src_b, ib, (0, nlat), (0, nlon), nlev_out, len(ia), d_out.ptr)
+            result[r0:r0 + n] = DeviceArray(ctx, (n,) + out_rec, big, ptr=d_out.ptr, owner=d_out).numpy()
+    finally:
+        ra.close(); rb.close()
+    bnds = str(ds_a[PLEV_GCM].attrs.get('bounds', PLEV_GCM + '_bnds'))
+    res = ncio.Dataset(attrs=dict(ds_a.attrs), record_dim=ds_a.record_dim)
+    for name, f in ds_a.variables.items():
+        if name == var_name:
+            res[name] = ncio.Field(result, ra.dims, {}, dict(ra.file_attrs))
+        elif name == PLEV_GCM or (name == bnds and name in ds_b and f.dims and f.dims[0] == PLEV_GCM and ds_b[name].dims == f.dims):
+            v = np.concatenate([np.asarray(f.values)[ia], np.asarray(ds_b[name].values)[ib].astype(f.values.dtype)])
+            res[name] = ncio.Field(v, f.dims, {}, dict(f.attrs))
+        elif PLEV_GCM not in f.dims:
+            res[name] = ncio.Field(f.values, f.dims, {}, dict(f.attrs))
+    if bnds not in res and 'bounds' in res[PLEV_GCM].attrs:
+        del res[PLEV_GCM].attrs['bounds']
+    ncio.to_netcdf(res, out)
+    return out
+
+
 # ------------------------------------------------------------------------------- climatologies and climate deltas
 CLIM_MODES = ('ymonmean', 'ydaymean')
 
@@ -493,10 +849,14 @@ def _encoded(values, raw_attrs):
     return values, attrs
 
 
-def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=None, out_dtype=None):
-    """extract_climate_delta.sh:194-219 without its `sellonlatbox`: `cdo -cat` of the files `inputs` (one path, or a list in
+def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=None, out_dtype=None, box=None):
+    """extract_climate_delta.sh:194-219: `cdo -cat` of the files `inputs` (one path, or a list in
     time order - CMIP series come in multi-year pieces), `-selyear` (years=(y0, y1)), `ymonmean` / `ydaymean` (mode) of
     `var_name` -> `out_path`.
+    box = (lon1, lon2, lat1, lat2): the `sellonlatbox,$box` in front of it (:194, :204; `lonlat_box`) - every uploaded chunk
+    of decoded records is cut on the device (`pgw_select_box`) before it is accumulated, the dimensions must end in
+    ([plev,] lat, lon), and the coordinates and bounds of the output are cut as `select_file` cuts them: the result is, bit
+    for bit, the climatology of the `select_file(box=box)` files.  None (default): no cut.
     The files must share the time units, the calendar and the record shape (ValueError).  Bin by bin (`calendar_bins`) the
     records are read in time order (`ncio.RecordReader`), uploaded in chunks of what fits into 80 % of the card's free
     memory, at most `max_records` (the results do not depend on it), and accumulated; records outside `years` are never
@@ -533,13 +893,20 @@ def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=
         if not len(keys):
             raise ValueError('no record lies within the years %s' % (years,))
         dt, odt = _clim_dtypes(r0.dtype, out_dtype)
-        rec_shape = r0.rec_shape
+        rec_shape = read_shape = r0.rec_shape
+        cut, inner_read = None, 0
+        if box is not None:                                       # records are read whole and cut on the device
+            _grid_dims(r0.dims, var_name)
+            cut = _Cut(ds0, None, box)
+            rec_shape = read_shape[:-2] + (cut.nlat_sel, cut.nlon_sel)
+            inner_read = int(np.prod(read_shape, dtype=np.int64))
         inner = int(np.prod(rec_shape, dtype=np.int64))
         recs = _records_of_bins(bins, len(keys))
         ctx = default_context()
-        nb = _fit_records(ctx, max(len(r) for r in recs), inner * dt.itemsize, max_records)
+        nb = _fit_records(ctx, max(len(r) for r in recs), (inner + inner_read) * dt.itemsize, max_records)
         acc = _BinMean(ctx, rec_shape, dt, odt, nb)
-        host = np.empty((nb,) + rec_shape, dtype=dt)
+        host = np.empty((nb,) + read_shape, dtype=dt)
+        d_read = ctx.empty((nb,) + read_shape, dt) if cut is not None else None      # the uncut records of a chunk
         d_mean = ctx.empty(rec_shape, odt)
         result = np.empty((len(keys),) + rec_shape, dtype=odt)
 
@@ -547,7 +914,13 @@ def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=
             for i, r in enumerate(part):
                 k, j = where[r]
                 host[i] = opened[k][1].read_record(j)
-            DeviceArray(ctx, (len(part),) + rec_shape, dt, ptr=d_chunk.ptr, owner=d_chunk).copy_from(host[:len(part)])
+            if cut is None:
+                DeviceArray(ctx, (len(part),) + rec_shape, dt, ptr=d_chunk.ptr, owner=d_chunk).copy_from(host[:len(part)])
+                return
+            DeviceArray(ctx, (len(part),) + read_shape, dt, ptr=d_read.ptr, owner=d_read).copy_from(host[:len(part)])
+            planes = len(part) * int(np.prod(read_shape[:-2], dtype=np.int64))
+            _launch_select(ctx, dt.itemsize, planes, 1, read_shape[-2], read_shape[-1], d_read.ptr, None,
+                           (cut.lat0, cut.nlat_sel), (cut.lon0, cut.nlon_sel), 1, 0, d_chunk.ptr)
 
         for k, part in enumerate(recs):
             acc.run(part, fill, d_mean)
@@ -558,7 +931,7 @@ def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=
             rd.close()
     result, vattrs = _encoded(result, ds0[var_name].attrs)
     out = ncio.Dataset(attrs=dict(ds0.attrs), record_dim=ds0.record_dim)
-    coords = {d: ds0[d].values for d in r0.dims[1:] if d in ds0}
+    coords = {d: ds0[d].values for d in r0.dims[1:] if d in ds0} if cut is None else {}
     coords[tdim] = t_out
     for name, f in ds0.variables.items():
         if name == var_name:
@@ -566,7 +939,7 @@ def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=
         elif name == tdim:
             out[name] = ncio.Field(t_out, (tdim,), {tdim: t_out}, {k: v for k, v in f.attrs.items() if k != 'bounds'})
         elif tdim not in f.dims:
-            out[name] = ncio.Field(f.values, f.dims, f.coords, dict(f.attrs))
+            out[name] = ncio.Field(f.values, f.dims, f.coords, dict(f.attrs)) if cut is None else cut.field(name, f)
     ncio.to_netcdf(out, out_path)
     return out_path
 
@@ -619,6 +992,30 @@ def delta_files(scen_path, hist_path, out_path, var_name):
     return out_path
 
 
+def _parse_floats(text, what, n=None):
+    if text is None:
+        return None
+    try:
+        vals = [float(t) for t in str(text).split(',')]
+    except ValueError:
+        raise ValueError('%s must be comma separated numbers, got %r' % (what, text)) from None
+    if n is not None and len(vals) != n:
+        raise ValueError('%s must be %d comma separated numbers, got %r' % (what, n, text))
+    return vals
+
+
+def _join_box_option(argv):
+    """`-b -73,37,-42,34`: argparse takes a value that starts with a minus sign and is not a plain number for an option;
+    the value is joined to its flag (`--box=-73,37,-42,34`), which argparse accepts."""
+    out, argv = [], list(argv)
+    while argv:
+        a = argv.pop(0)
+        if a in ('-b', '--box') and argv and argv[0][:1] == '-' and argv[0][1:2] in tuple('0123456789.'):
+            a = '--box=' + argv.pop(0)
+        out.append(a)
+    return out
+
+
 def _parse_years(text):
     if text is None:
         return None
@@ -632,8 +1029,10 @@ def _parse_years(text):
 def build_parser():
     p = argparse.ArgumentParser(prog='python -m pgw4era5_amd.step_01_extract_deltas',
                                 description='PGW for ERA5 step_01 on MI355X: CFday model levels to pressure levels, Emon hus to hur, '
-                                            'climatologies and climate deltas.')
+                                            'climatologies and climate deltas, level / lon-lat box selection and the '
+                                            'model-top merge.')
     sub = p.add_subparsers(dest='command', required=True)
+    box_help = 'LON1,LON2,LAT1,LAT2: cut to this longitude-latitude box (cdo sellonlatbox; may wrap across 0 deg)'
     a = sub.add_parser('interp_to_plev', help='Interpolate CFday output to pressure levels (CFday_interp_to_plev.py)')
     a.add_argument('-i', '--input', type=str, required=True,
                    help='NetCDF-3 input file with the variable, ap, b (lev) and ps; {} is replaced by the variable name')
@@ -657,16 +1056,33 @@ def build_parser():
     c.add_argument('-y', '--years', type=str, default=None, help='first and last year to use, e.g. 1985/2014 (cdo selyear)')
     c.add_argument('--max_records', type=int, default=None, help='at most this many time records per launch')
     c.add_argument('--out_dtype', type=str, default=None, choices=['float32', 'float64'])
+    c.add_argument('-b', '--box', type=str, default=None, help=box_help + ' in front of the climatology')
     d = sub.add_parser('delta', help='Scenario climatology minus historical climatology (cdo sub)')
     d.add_argument('scen_file', type=str, help='{} is replaced by the variable name (also in the other two paths)')
     d.add_argument('hist_file', type=str)
     d.add_argument('delta_file', type=str)
     d.add_argument('-v', '--var_names', type=str, required=True, help='comma separated variable names')
+    s = sub.add_parser('select', help='Select pressure levels and / or a lon-lat box of a file (cdo sellevel, sellonlatbox)')
+    s.add_argument('-i', '--input', type=str, required=True, help='NetCDF-3 input file; {} is replaced by the variable name')
+    s.add_argument('-o', '--output', type=str, required=True, help='output file; {} is replaced by the variable name')
+    s.add_argument('-v', '--var_names', type=str, required=True, help='comma separated variable names, e.g. ta,hur,ua,va')
+    s.add_argument('-l', '--levels', type=str, default=None, help='comma separated level values to keep, e.g. 100000,85000,50000')
+    s.add_argument('-b', '--box', type=str, default=None, help=box_help)
+    s.add_argument('--max_records', type=int, default=None, help='at most this many time records per launch')
+    m = sub.add_parser('merge_levels', help='Levels of FILE_A, then levels of FILE_B, as one variable (cdo sellevel, sellevel, '
+                                            'merge: Emon_add_top_from_Amon.sh)')
+    m.add_argument('file_a', type=str, help='{} is replaced by the variable name (also in the other two paths)')
+    m.add_argument('file_b', type=str)
+    m.add_argument('out_file', type=str)
+    m.add_argument('-v', '--var_names', type=str, required=True, help='comma separated variable names, e.g. ua,va,ta,zg,hur')
+    m.add_argument('--levels_a', type=str, default=None, help='comma separated level values to take from FILE_A (default: all)')
+    m.add_argument('--levels_b', type=str, default=None, help='comma separated level values to take from FILE_B (default: all)')
+    m.add_argument('--max_records', type=int, default=None, help='at most this many time records per launch')
     return p
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser().parse_args(_join_box_option(sys.argv[1:] if argv is None else argv))
     done = []
     if args.command == 'interp_to_plev':
         names = args.var_names.split(',')
@@ -686,14 +1102,36 @@ def main(argv=None):
         years = _parse_years(args.years)
         for name in names:
             done.append(climatology_files([i.replace('{}', name) for i in args.input], args.output.replace('{}', name), name,
-                                          args.mode, years=years, max_records=args.max_records, out_dtype=args.out_dtype))
-    else:
+                                          args.mode, years=years, max_records=args.max_records, out_dtype=args.out_dtype,
+                                          box=_parse_floats(args.box, 'box', 4)))
+    elif args.command == 'delta':
         names = args.var_names.split(',')
         paths = (args.scen_file, args.hist_file, args.delta_file)
         if len(names) > 1 and not all('{}' in p for p in paths):
             raise ValueError('several variables need {} in all three paths')
         for name in names:
             done.append(delta_files(*[p.replace('{}', name) for p in paths], name))
+    elif args.command == 'select':
+        names = args.var_names.split(',')
+        if len(names) > 1 and ('{}' not in args.input or '{}' not in args.output):
+            raise ValueError('several variables need {} in the input and the output path')
+        levels, box = _parse_floats(args.levels, 'levels'), _parse_floats(args.box, 'box', 4)
+        if levels is None and box is None:
+            raise ValueError('select needs --levels and / or --box')
+        for name in names:
+            done.append(select_file(args.input.replace('{}', name), args.output.replace('{}', name), name, levels=levels, box=box,
+                                    max_records=args.max_records))
+    elif args.command == 'merge_levels':
+        names = args.var_names.split(',')
+        paths = (args.file_a, args.file_b, args.out_file)
+        if len(names) > 1 and not all('{}' in p for p in paths):
+            raise ValueError('several variables need {} in all three paths')
+        for name in names:
+            done.append(merge_levels_files(*[p.replace('{}', name) for p in paths], name,
+                                           levels_a=_parse_floats(args.levels_a, 'levels_a'),
+                                           levels_b=_parse_floats(args.levels_b, 'levels_b'), max_records=args.max_records))
+    else:
+        raise ValueError('unknown command %r' % (args.command,))
     return done
 
 
