@@ -3184,9 +3184,10 @@ __global__ __launch_bounds__(BLOCK) void k_surface_update_lerp(int ntime, long l
     long long n = (long long)ntime * ncol;
     if (i >= n) return;
     long long t = i / ncol, c = i - t * ncol;
-    // REF and the instant IS a delta record (no time interpolation: the delta stays the file's float32, functions.py:282-283):
-    // numpy then takes `delta / 100`, the sum and the blend below in float32
-    const bool f32_delta = REF && !dsic.a;
+    // REF and the instant IS a record of a delta (no time interpolation: that delta stays the file's float32,
+    // functions.py:282-283; every delta file has its own time axis): numpy then takes `siconc / 100` and the sum onto the
+    // ice in float32, and in the blend every product in the dtype of ITS delta, the sum in float32 only if both are
+    const bool f32_delta = REF && !dsic.a, f32_ts = REF && !dts.a, f32_tos = REF && !dtos.a;
     auto ice_of = [&](long long k) -> double {
         double s0 = (double)sic[k], d0 = dsic.template get<REF>(k);
         double v = s0 + d0 / 100;                                     // step_03:105
@@ -3211,8 +3212,11 @@ __global__ __launch_bounds__(BLOCK) void k_surface_update_lerp(int ntime, long l
             if ((double)land[c] != (double)land[c]) fr = __builtin_nan("");
             omf = 1 - fr;
         }
-        comb = fr * ts + omf * tos;                                   // :1184
-        if (f32_delta) comb = (double)((float)fr * (float)ts + (float)omf * (float)tos);   // float32 products and sum
+        double p_ts = fr * ts, p_tos = omf * tos;                     // :1184, numpy's promotion operand by operand
+        if (f32_ts) p_ts = (double)((float)fr * (float)ts);           // float32 frac * float32 record
+        if (f32_tos) p_tos = (double)((float)omf * (float)tos);
+        comb = p_ts + p_tos;
+        if (f32_ts && f32_tos) comb = (double)((float)p_ts + (float)p_tos);
     }
     tskin_out[i] = (T)((double)tskin[i] + comb);                      // step_03:124
     if (tso_out) {
@@ -3231,7 +3235,8 @@ __global__ __launch_bounds__(BLOCK) void k_surface_update_lerp(int ntime, long l
 // delta_soilt (:139-143) as the float64 arrays the reference holds (np.ones in integrate_tos, functions.py:1180; float64
 // exp(-soil1 / 2.8)).  k_surface_update_lerp's expressions - its per-variable time axes, the sea-ice update the blend
 // sees, the float32 nodes of reference mode - without the sums onto the ERA fields; that kernel keeps its text (its
-// instantiations are what production runs), tests/test_step03_debug_hip.py holds the two together through T_SKIN / T_SO.
+// instantiations are what production runs), tests/test_step03_debug_hip.py and tests/test_surface_riders_hip.py hold the two
+// together through T_SKIN / T_SO.
 template <typename T, bool REF>
 __global__ __launch_bounds__(BLOCK) void k_surface_deltas(int ntime, long long ncol, SoilTable soil,
                                                           const T *__restrict__ sic, DeltaSrc<T> dsic, DeltaSrc<T> dtos,
@@ -3242,7 +3247,7 @@ __global__ __launch_bounds__(BLOCK) void k_surface_deltas(int ntime, long long n
     long long n = (long long)ntime * ncol;
     if (i >= n) return;
     long long t = i / ncol, c = i - t * ncol;
-    const bool f32_delta = REF && !dsic.a;                            // see k_surface_update_lerp
+    const bool f32_delta = REF && !dsic.a, f32_ts = REF && !dts.a, f32_tos = REF && !dtos.a;   // see k_surface_update_lerp
     auto ice_of = [&](long long k) -> double {
         double s0 = (double)sic[k], d0 = dsic.template get<REF>(k);
         double v = s0 + d0 / 100;                                     // step_03:105
@@ -3265,8 +3270,11 @@ __global__ __launch_bounds__(BLOCK) void k_surface_deltas(int ntime, long long n
             if ((double)land[c] != (double)land[c]) fr = __builtin_nan("");
             omf = 1 - fr;
         }
-        comb = fr * ts + omf * tos;                                   // :1184
-        if (f32_delta) comb = (double)((float)fr * (float)ts + (float)omf * (float)tos);   // float32 products and sum
+        double p_ts = fr * ts, p_tos = omf * tos;                     // :1184, numpy's promotion operand by operand
+        if (f32_ts) p_ts = (double)((float)fr * (float)ts);           // float32 frac * float32 record
+        if (f32_tos) p_tos = (double)((float)omf * (float)tos);
+        comb = p_ts + p_tos;
+        if (f32_ts && f32_tos) comb = (double)((float)p_ts + (float)p_tos);
     }
     comb_out[i] = comb;                                               // step_03:125
     if (dsoil_out) {

@@ -6,12 +6,15 @@ function-level entries bit for bit, and for its errors; then the command line on
 import datetime as dt
 import functools
 import os
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import pgw_oracle as O
-from oracle import pgw_oracle_refdtype as R
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from surface_edge_cases import oracle_surface_deltas                                 # noqa: E402
+from oracle import pgw_oracle as O                                                   # noqa: E402
+from oracle import pgw_oracle_refdtype as R                                          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -280,22 +283,8 @@ def test_errors_are_those_of_vert_interp_delta(gpu, what):
 
 
 # ================================================================== 5. surface deltas
-def oracle_surface_deltas(c, mode, clim):
-    """step_03:103-125, 139-143 by the oracle lines of the mode; `clim` is the annual-mean ts delta handed to both sides."""
-    era, deltas = c['era'], c['deltas']
-    if mode == 'f32_reference':
-        ld = lambda k: R.load_delta_values(deltas[k], c['delta_times'], c['target_dt'])
-        sic = np.array(era['FR_SEA_ICE'], copy=True)
-        with np.errstate(invalid='ignore'):
-            np.add(sic, ld('siconc') / 100, out=sic, casting='same_kind')          # step_03:105
-        sic = np.clip(sic, 0, 1)
-        comb = R.integrate_tos(ld('tos'), ld('ts'), np.asarray(era['FR_LAND'])[0], sic[0])
-    else:
-        e = widen(era)
-        ld = lambda k: O.load_delta_values(np.asarray(deltas[k], dtype=np.float64), c['delta_times'], c['target_dt'])
-        sic = O.sea_ice_update(e['FR_SEA_ICE'], ld('siconc'))
-        comb = O.integrate_tos(ld('tos'), ld('ts'), e['FR_LAND'][0], sic[0])
-    return comb, O.soil_temperature_delta(comb, clim, era['soil1'])
+# oracle_surface_deltas (step_03:103-125, 139-143 by the oracle lines of the mode) lives in tests/surface_edge_cases.py, shared
+# with tests/test_surface_riders_hip.py
 
 
 @pytest.mark.parametrize('instant', list(INSTANTS))
