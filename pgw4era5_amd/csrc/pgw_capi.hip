@@ -521,6 +521,17 @@ template <typename T> static inline PairSrc<T> pair_src(const void *b0, const vo
     return PairSrc<T>{delta_src<T>(b0, a0, x_hi, x_new), delta_src<T>(b1, a1, x_hi, x_new)};
 }
 
+// The riders' soil table (step_03:139-140): the layer count checked, w = exp(-depth / 2.8) in float64 on the host.
+// `caller` names the entry in the status text.  soil_depth may be NULL where no soil output is asked for (the callers check
+// that after the layer count): the weights then stay 0 and no kernel reads them.
+static int soil_table(pgw_ctx *ctx, const char *caller, int nsoil, const double *soil_depth, SoilTable *st) {
+    if (nsoil < 0 || nsoil > MAX_SOIL) return fail(ctx, PGW_ERR_ARG, "%s: %s", caller, "nsoil must be in [0, 16]");
+    memset(st, 0, sizeof(*st));
+    st->n = nsoil;
+    for (int s = 0; soil_depth && s < nsoil; ++s) st->w[s] = exp(-soil_depth[s] / 2.8);      // step_03:140
+    return PGW_OK;
+}
+
 extern "C" int pgw_pressure_levels(pgw_ctx *ctx, int dtype, int ntime, long long ncol,
                                    const void *ps, void *pa_hl, void *pa) {
     CHECK_COMMON(ctx, dtype, ntime, ncol);
@@ -1889,12 +1900,9 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     // ---- surface riders (step_03:103-146)
     if (a->FR_SEA_ICE && a->siconc_b && a->FR_SEA_ICE_out) {
         NEED(ctx, a->ts_b && a->tos_b && a->FR_LAND && a->T_SKIN && a->T_SKIN_out, "surface rider pointer is NULL");
-        NEED(ctx, a->nsoil >= 0 && a->nsoil <= MAX_SOIL, "nsoil must be in [0, 16]");
-        NEED(ctx, a->nsoil == 0 || (a->T_SO && a->T_SO_out && a->ts_clim && a->soil_depth), "soil pointers missing");
         SoilTable st;
-        memset(&st, 0, sizeof(st));
-        st.n = a->nsoil;
-        for (int s = 0; s < a->nsoil; ++s) st.w[s] = exp(-a->soil_depth[s] / 2.8);      // step_03:140
+        if ((rc = soil_table(ctx, __func__, a->nsoil, a->soil_depth, &st))) return rc;
+        NEED(ctx, a->nsoil == 0 || (a->T_SO && a->T_SO_out && a->ts_clim && a->soil_depth), "soil pointers missing");
         long long n = (long long)ntime * ncol;
         Prof pr(ctx, PGW_K_SURFACE);
         with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
@@ -1903,10 +1911,10 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
             const DeltaSrc<T> dsic = delta_src<T>(a->siconc_b, a->siconc_a, own ? a->siconc_x_hi : a->x_hi, own ? a->siconc_x_new : a->x_new);
             const DeltaSrc<T> dts = delta_src<T>(a->ts_b, a->ts_a, own ? a->ts_x_hi : a->x_hi, own ? a->ts_x_new : a->x_new);
             const DeltaSrc<T> dtos = delta_src<T>(a->tos_b, a->tos_a, own ? a->tos_x_hi : a->x_hi, own ? a->tos_x_new : a->x_new);
+            const RiderSrc<T> r{(const T *)a->FR_SEA_ICE, dsic, dtos, dts, (const T *)a->FR_LAND};
             hipLaunchKernelGGL((k_surface_update_lerp<T, decltype(ref_)::value>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream,
-                               ntime, ncol, st, (const T *)a->FR_SEA_ICE, dsic, dtos, dts, (const T *)a->FR_LAND, (const T *)a->ts_clim,
-                               (const T *)a->T_SKIN, (const T *)a->T_SO, (T *)a->FR_SEA_ICE_out, (T *)a->T_SKIN_out,
-                               (T *)a->T_SO_out);
+                               ntime, ncol, st, r, (const T *)a->ts_clim, (const T *)a->T_SKIN, (const T *)a->T_SO,
+                               (T *)a->FR_SEA_ICE_out, (T *)nullptr /* comb_out */, (T *)a->T_SKIN_out, (T *)a->T_SO_out);
         });
     }
 
@@ -2377,22 +2385,23 @@ extern "C" int pgw_surface_update(pgw_ctx *ctx, int dtype, int ntime, long long 
                                   const void *dts, const void *land, const void *ts_clim, const void *tskin,
                                   const void *tso, void *sic_out, void *dts_comb_out, void *tskin_out, void *tso_out) {
     CHECK_COMMON(ctx, dtype, ntime, ncol);
-    NEED(ctx, nsoil >= 0 && nsoil <= MAX_SOIL, "nsoil must be in [0, 16]");
+    SoilTable st;
+    int rc;
+    if ((rc = soil_table(ctx, __func__, nsoil, soil_depth, &st))) return rc;
     NEED(ctx, sic && dsic && dtos && dts && land, "null pointer");
     NEED(ctx, !tskin_out || tskin, "tskin required for tskin_out");
     NEED(ctx, !tso_out || (tso && ts_clim && soil_depth && nsoil > 0), "tso, ts_clim, soil_depth required for tso_out");
-    SoilTable st;
-    memset(&st, 0, sizeof(st));
-    st.n = nsoil;
-    for (int s = 0; s < nsoil; ++s) st.w[s] = exp(-soil_depth[s] / 2.8);      // step_03:140
     long long n = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_SURFACE);
         with_type(dtype, [&](auto t_) {
             using T = decltype(t_);
-            hipLaunchKernelGGL((k_surface_update<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, ntime, ncol, st,
-                               (const T *)sic, (const T *)dsic, (const T *)dtos, (const T *)dts, (const T *)land, (const T *)ts_clim,
-                               (const T *)tskin, (const T *)tso, (T *)sic_out, (T *)dts_comb_out, (T *)tskin_out, (T *)tso_out);
+            // the deltas at the instant, already interpolated: records with nothing after them
+            const RiderSrc<T> r{(const T *)sic, delta_src<T>(dsic, nullptr, 0.0, 0.0), delta_src<T>(dtos, nullptr, 0.0, 0.0),
+                                delta_src<T>(dts, nullptr, 0.0, 0.0), (const T *)land};
+            hipLaunchKernelGGL((k_surface_update_lerp<T, false>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, ntime, ncol, st,
+                               r, (const T *)ts_clim, (const T *)tskin, (const T *)tso, (T *)sic_out, (T *)dts_comb_out,
+                               (T *)tskin_out, (T *)tso_out);
         });
     }
     HIPCHK(ctx, hipGetLastError());
@@ -2410,24 +2419,23 @@ extern "C" int pgw_surface_deltas(pgw_ctx *ctx, int dtype, int ref_dtype, int nt
     CHECK_COMMON(ctx, dtype, ntime, ncol);
     const bool ref = ref_dtype != 0;
     NEED(ctx, !ref || dtype == PGW_F32, "ref_dtype = 1 is the float32-file mode: dtype must be PGW_F32");
-    NEED(ctx, nsoil >= 0 && nsoil <= MAX_SOIL, "nsoil must be in [0, 16]");
+    SoilTable st;
+    int rc;
+    if ((rc = soil_table(ctx, __func__, nsoil, soil_depth, &st))) return rc;
     NEED(ctx, sic && siconc_b && tos_b && ts_b && land && dts_comb, "null pointer");
     NEED(ctx, (siconc_x_hi == 0.0 || siconc_a) && (tos_x_hi == 0.0 || tos_a) && (ts_x_hi == 0.0 || ts_a),
          "record after the instant is NULL");
     NEED(ctx, !delta_soilt || (ts_clim && soil_depth && nsoil > 0), "ts_clim, soil_depth required for delta_soilt");
-    SoilTable st;
-    memset(&st, 0, sizeof(st));
-    st.n = nsoil;
-    for (int s = 0; s < nsoil; ++s) st.w[s] = exp(-soil_depth[s] / 2.8);      // step_03:140
     const long long n = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_SURFACE);
         with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
             using T = decltype(t_);
+            const RiderSrc<T> r{(const T *)sic, delta_src<T>(siconc_b, siconc_a, siconc_x_hi, siconc_x_new),
+                                delta_src<T>(tos_b, tos_a, tos_x_hi, tos_x_new), delta_src<T>(ts_b, ts_a, ts_x_hi, ts_x_new),
+                                (const T *)land};
             hipLaunchKernelGGL((k_surface_deltas<T, decltype(ref_)::value>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream,
-                               ntime, ncol, st, (const T *)sic, delta_src<T>(siconc_b, siconc_a, siconc_x_hi, siconc_x_new),
-                               delta_src<T>(tos_b, tos_a, tos_x_hi, tos_x_new), delta_src<T>(ts_b, ts_a, ts_x_hi, ts_x_new),
-                               (const T *)land, (const T *)ts_clim, dts_comb, delta_soilt);
+                               ntime, ncol, st, r, (const T *)ts_clim, dts_comb, delta_soilt);
         });
     }
     HIPCHK(ctx, hipGetLastError());

@@ -2774,50 +2774,71 @@ __global__ __launch_bounds__(BLOCK) void k_regrid(long long nfield, int nlat_s, 
 constexpr int MAX_SOIL = 16;
 struct SoilTable { double w[MAX_SOIL]; int n; };     // w = exp(-depth/2.8), computed on the host
 
-template <typename T>
-__global__ __launch_bounds__(BLOCK) void k_surface_update(int ntime, long long ncol, SoilTable soil,
-                                                          const T *__restrict__ sic, const T *__restrict__ dsic,
-                                                          const T *__restrict__ dtos, const T *__restrict__ dts,
-                                                          const T *__restrict__ land, const T *__restrict__ clim,
-                                                          const T *__restrict__ tskin, const T *__restrict__ tso,
-                                                          T *__restrict__ sic_out, T *__restrict__ comb_out,
-                                                          T *__restrict__ tskin_out, T *__restrict__ tso_out) {
-    long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    long long n = (long long)ntime * ncol;
-    if (i >= n) return;
-    long long t = i / ncol, c = i - t * ncol;
-    double ice = (double)sic[i] + (double)dsic[i] / 100;             // step_03:105
-    ice = fmin(fmax(ice, 0.0), 1.0);                                  // :106-107 (np.clip keeps NaN)
-    if ((double)sic[i] != (double)sic[i] || (double)dsic[i] != (double)dsic[i]) ice = __builtin_nan("");
-    if (sic_out) sic_out[i] = (T)ice;
-    double tos = (double)dtos[i], ts = (double)dts[i];
-    // land fraction / sea ice of time step 0 (step_03:121-122 .isel(time=0))
-    double lf = (double)land[c];
-    double ice0 = ice;
-    if (t != 0) {
-        double i0 = (double)sic[c] + (double)dsic[c] / 100;
-        i0 = fmin(fmax(i0, 0.0), 1.0);
-        if ((double)sic[c] != (double)sic[c] || (double)dsic[c] != (double)dsic[c]) i0 = __builtin_nan("");
-        ice0 = i0;
-    }
+// ---- rules every rider kernel follows: one statement each ------------------------------------------------------------
+// The sea-ice update (step_03:105-107) of one stored fraction `s0` and its delta `d0`.  f32_delta: reference mode and the
+// instant IS a record of the delta (no time interpolation: that delta stays the file's float32, functions.py:282-283) -
+// numpy then takes `siconc / 100` and the sum onto the ice in float32.  REF: what the blend sees is the float32 value
+// stored back into the file's array.
+template <typename T, bool REF>
+__device__ __forceinline__ double sea_ice_update(double s0, double d0, bool f32_delta) {
+    double v = s0 + d0 / 100;                                         // step_03:105
+    if (f32_delta) v = (double)((float)s0 + (float)d0 / 100.0f);
+    v = fmin(fmax(v, 0.0), 1.0);                                      // :106-107
+    if (s0 != s0 || d0 != d0) v = __builtin_nan("");                  // np.clip keeps NaN
+    return REF ? (double)(T)v : v;
+}
+
+// integrate_tos (functions.py:1173-1184): ts where sea ice or tos is missing, else the land+ice fraction of ts and the rest
+// of tos.  REF: `ice + land` and `1 - frac` are float32 operations on the file's float32 fractions (:1183-1184).  f32_ts /
+// f32_tos: that delta is a float32 record (see sea_ice_update) - numpy takes every product in the dtype of ITS delta, the
+// sum in float32 only if both are.
+template <bool REF>
+__device__ __forceinline__ double tos_ts_blend(double ice0, double lf, double tos, double ts, bool f32_ts, bool f32_tos) {
     double comb = ts;                                                 // functions.py:1180-1181
     if (ice0 == ice0 && tos == tos) {                                 // :1173
-        double fr = fmin(fmax(ice0 + lf, 0.0), 1.0);                  // :1183
-        if (lf != lf) fr = __builtin_nan("");                         // np.clip keeps NaN
-        comb = fr * ts + (1 - fr) * tos;                              // :1184
-    }
-    if (comb_out) comb_out[i] = (T)comb;
-    if (tskin_out) tskin_out[i] = (T)((double)tskin[i] + comb);       // step_03:124
-    if (tso_out) {
-        double cl = (double)clim[c];                                  // annual mean ts delta :134-136
-#pragma unroll
-        for (int s = 0; s < MAX_SOIL; ++s) {
-            if (s < soil.n) {
-                long long o = (t * soil.n + s) * ncol + c;
-                tso_out[o] = (T)((double)tso[o] + (cl + soil.w[s] * (comb - cl)));   // :139-144
-            }
+        double fr, omf;
+        if (REF) {
+            float f = fminf(fmaxf((float)ice0 + (float)lf, 0.0f), 1.0f);
+            if ((float)lf != (float)lf) f = __builtin_nanf("");
+            fr = (double)f; omf = (double)(1.0f - f);
+        } else {
+            fr = fmin(fmax(ice0 + lf, 0.0), 1.0);                     // :1183
+            if (lf != lf) fr = __builtin_nan("");                     // np.clip keeps NaN
+            omf = 1 - fr;
         }
+        double p_ts = fr * ts, p_tos = omf * tos;                     // :1184, numpy's promotion operand by operand
+        if (f32_ts) p_ts = (double)((float)fr * (float)ts);           // float32 frac * float32 record
+        if (f32_tos) p_tos = (double)((float)omf * (float)tos);
+        comb = p_ts + p_tos;
+        if (f32_ts && f32_tos) comb = (double)((float)p_ts + (float)p_tos);
     }
+    return comb;
+}
+
+// One point of the riders: the updated sea ice of element i = t * ncol + c and delta_ts_combined (step_03:118-125) there.
+// Every delta file has its own time axis, so each DeltaSrc has its own bracket and its own float32-record flag.
+template <typename T>
+struct RiderSrc { const T *sic; DeltaSrc<T> dsic, dtos, dts; const T *land; };
+struct RiderPoint { double ice, comb; };
+template <typename T, bool REF>
+__device__ __forceinline__ RiderPoint rider_point(const RiderSrc<T> &r, long long i, long long t, long long c) {
+    const bool f32_delta = REF && !r.dsic.a, f32_ts = REF && !r.dts.a, f32_tos = REF && !r.dtos.a;
+    auto ice_of = [&](long long k) { return sea_ice_update<T, REF>((double)r.sic[k], r.dsic.template get<REF>(k), f32_delta); };
+    RiderPoint p;
+    p.ice = ice_of(i);
+    const double ice0 = (t == 0) ? p.ice : ice_of(c);                 // .isel(time=0), :121-122
+    // tos and ts are read before land: the order of the loads decides which product the compiler names first in the blend's
+    // commutative sum, and so which NaN a NaN land fraction leaves there (+NaN from frac * ts, -NaN from (1 - frac) * tos).
+    // The sign of a NaN is no part of the contract (numpy promises none, the tests compare NaN positions): this order only
+    // keeps the bytes the kernels wrote before they shared this text
+    const double tos = r.dtos.template get<REF>(i), ts = r.dts.template get<REF>(i);
+    p.comb = tos_ts_blend<REF>(ice0, (double)r.land[c], tos, ts, f32_ts, f32_tos);
+    return p;
+}
+
+// delta_soilt of one layer (step_03:139-142) around `cl`, the annual mean ts delta (:134-136)
+__device__ __forceinline__ double soil_delta(const SoilTable &soil, int s, double cl, double comb) {
+    return cl + soil.w[s] * (comb - cl);
 }
 
 // replace_delta_sfc (functions.py:343-366) on many ascending-pressure columns: source_P is the
@@ -2858,14 +2879,7 @@ __global__ __launch_bounds__(BLOCK) void k_integrate_tos(long long n, const T *_
                                                          T *__restrict__ out) {
     long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    double o = (double)tos[i], s = (double)ts[i], ic = (double)ice[i];
-    double r = s;                                                   // :1180-1181
-    if (ic == ic && o == o) {                                       // :1173
-        double fr = fmin(fmax(ic + (double)land[i], 0.0), 1.0);     // :1183 (np.clip propagates NaN)
-        if ((double)land[i] != (double)land[i]) fr = __builtin_nan("");
-        r = fr * s + (1 - fr) * o;                                  // :1184
-    }
-    out[i] = (T)r;
+    out[i] = (T)tos_ts_blend<false>((double)ice[i], (double)land[i], (double)tos[i], (double)ts[i], false, false);
 }
 
 // integrate_tos in the reference's dtype flow: every operand in its own storage type, the blend (:1183-1184) in numpy's
@@ -3170,62 +3184,29 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
     }
 }
 
-// surface riders with the time lerp of the three 2-D deltas fused in (step_03:103-146)
-// REF: the sea-ice fraction the blend sees is the float32 value stored back into the file's array (step_03:105-107), and
-// `ice + land`, `1 - frac` are float32 operations on the file's float32 fractions (functions.py:1183-1184)
+// surface riders with the time lerp of the three 2-D deltas fused in (step_03:103-146): rider_point and the sums onto the
+// ERA fields, in the storage type.  Every output is optional (pgw_surface_update; pgw_step03_file writes all but comb_out).
 template <typename T, bool REF>
-__global__ __launch_bounds__(BLOCK) void k_surface_update_lerp(int ntime, long long ncol, SoilTable soil,
-                                                               const T *__restrict__ sic, DeltaSrc<T> dsic, DeltaSrc<T> dtos,
-                                                               DeltaSrc<T> dts, const T *__restrict__ land,
+__global__ __launch_bounds__(BLOCK) void k_surface_update_lerp(int ntime, long long ncol, SoilTable soil, RiderSrc<T> r,
                                                                const T *__restrict__ clim, const T *__restrict__ tskin,
                                                                const T *__restrict__ tso, T *__restrict__ sic_out,
-                                                               T *__restrict__ tskin_out, T *__restrict__ tso_out) {
+                                                               T *__restrict__ comb_out, T *__restrict__ tskin_out,
+                                                               T *__restrict__ tso_out) {
     long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
     long long n = (long long)ntime * ncol;
     if (i >= n) return;
     long long t = i / ncol, c = i - t * ncol;
-    // REF and the instant IS a record of a delta (no time interpolation: that delta stays the file's float32,
-    // functions.py:282-283; every delta file has its own time axis): numpy then takes `siconc / 100` and the sum onto the
-    // ice in float32, and in the blend every product in the dtype of ITS delta, the sum in float32 only if both are
-    const bool f32_delta = REF && !dsic.a, f32_ts = REF && !dts.a, f32_tos = REF && !dtos.a;
-    auto ice_of = [&](long long k) -> double {
-        double s0 = (double)sic[k], d0 = dsic.template get<REF>(k);
-        double v = s0 + d0 / 100;                                     // step_03:105
-        if (f32_delta) v = (double)((float)s0 + (float)d0 / 100.0f);
-        v = fmin(fmax(v, 0.0), 1.0);                                  // :106-107
-        if (s0 != s0 || d0 != d0) v = __builtin_nan("");              // np.clip keeps NaN
-        return REF ? (double)(T)v : v;
-    };
-    double ice = ice_of(i);
-    sic_out[i] = (T)ice;
-    double ice0 = (t == 0) ? ice : ice_of(c);                         // .isel(time=0), :121-122
-    double tos = dtos.template get<REF>(i), ts = dts.template get<REF>(i);
-    double comb = ts;                                                 // functions.py:1180-1181
-    if (ice0 == ice0 && tos == tos) {                                 // :1173
-        double fr, omf;
-        if (REF) {
-            float f = fminf(fmaxf((float)ice0 + (float)land[c], 0.0f), 1.0f);
-            if ((float)land[c] != (float)land[c]) f = __builtin_nanf("");
-            fr = (double)f; omf = (double)(1.0f - f);
-        } else {
-            fr = fmin(fmax(ice0 + (double)land[c], 0.0), 1.0);        // :1183
-            if ((double)land[c] != (double)land[c]) fr = __builtin_nan("");
-            omf = 1 - fr;
-        }
-        double p_ts = fr * ts, p_tos = omf * tos;                     // :1184, numpy's promotion operand by operand
-        if (f32_ts) p_ts = (double)((float)fr * (float)ts);           // float32 frac * float32 record
-        if (f32_tos) p_tos = (double)((float)omf * (float)tos);
-        comb = p_ts + p_tos;
-        if (f32_ts && f32_tos) comb = (double)((float)p_ts + (float)p_tos);
-    }
-    tskin_out[i] = (T)((double)tskin[i] + comb);                      // step_03:124
+    const RiderPoint p = rider_point<T, REF>(r, i, t, c);
+    if (sic_out) sic_out[i] = (T)p.ice;
+    if (comb_out) comb_out[i] = (T)p.comb;
+    if (tskin_out) tskin_out[i] = (T)((double)tskin[i] + p.comb);     // step_03:124
     if (tso_out) {
-        double cl = (double)clim[c];                                  // :134-136
+        double cl = (double)clim[c];                                  // annual mean ts delta :134-136
 #pragma unroll
         for (int s = 0; s < MAX_SOIL; ++s) {
             if (s < soil.n) {
                 long long o = (t * soil.n + s) * ncol + c;
-                tso_out[o] = (T)((double)tso[o] + (cl + soil.w[s] * (comb - cl)));   // :139-144
+                tso_out[o] = (T)((double)tso[o] + soil_delta(soil, s, cl, p.comb));   // :139-144
             }
         }
     }
@@ -3233,55 +3214,23 @@ __global__ __launch_bounds__(BLOCK) void k_surface_update_lerp(int ntime, long l
 
 // The two surface deltas themselves (step_03 --debug_mode interpolate_full): delta_ts_combined (step_03:118-125) and
 // delta_soilt (:139-143) as the float64 arrays the reference holds (np.ones in integrate_tos, functions.py:1180; float64
-// exp(-soil1 / 2.8)).  k_surface_update_lerp's expressions - its per-variable time axes, the sea-ice update the blend
-// sees, the float32 nodes of reference mode - without the sums onto the ERA fields; that kernel keeps its text (its
-// instantiations are what production runs), tests/test_step03_debug_hip.py and tests/test_surface_riders_hip.py hold the two
-// together through T_SKIN / T_SO.
+// exp(-soil1 / 2.8)): rider_point and soil_delta as k_surface_update_lerp calls them, without the sums onto the ERA fields
+// and the rounding to the storage type.
 template <typename T, bool REF>
-__global__ __launch_bounds__(BLOCK) void k_surface_deltas(int ntime, long long ncol, SoilTable soil,
-                                                          const T *__restrict__ sic, DeltaSrc<T> dsic, DeltaSrc<T> dtos,
-                                                          DeltaSrc<T> dts, const T *__restrict__ land,
+__global__ __launch_bounds__(BLOCK) void k_surface_deltas(int ntime, long long ncol, SoilTable soil, RiderSrc<T> r,
                                                           const T *__restrict__ clim, double *__restrict__ comb_out,
                                                           double *__restrict__ dsoil_out) {
     long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
     long long n = (long long)ntime * ncol;
     if (i >= n) return;
     long long t = i / ncol, c = i - t * ncol;
-    const bool f32_delta = REF && !dsic.a, f32_ts = REF && !dts.a, f32_tos = REF && !dtos.a;   // see k_surface_update_lerp
-    auto ice_of = [&](long long k) -> double {
-        double s0 = (double)sic[k], d0 = dsic.template get<REF>(k);
-        double v = s0 + d0 / 100;                                     // step_03:105
-        if (f32_delta) v = (double)((float)s0 + (float)d0 / 100.0f);
-        v = fmin(fmax(v, 0.0), 1.0);                                  // :106-107
-        if (s0 != s0 || d0 != d0) v = __builtin_nan("");              // np.clip keeps NaN
-        return REF ? (double)(T)v : v;
-    };
-    double ice0 = ice_of(c);                                          // .isel(time=0), :121-122
-    double tos = dtos.template get<REF>(i), ts = dts.template get<REF>(i);
-    double comb = ts;                                                 // functions.py:1180-1181
-    if (ice0 == ice0 && tos == tos) {                                 // :1173
-        double fr, omf;
-        if (REF) {
-            float f = fminf(fmaxf((float)ice0 + (float)land[c], 0.0f), 1.0f);
-            if ((float)land[c] != (float)land[c]) f = __builtin_nanf("");
-            fr = (double)f; omf = (double)(1.0f - f);
-        } else {
-            fr = fmin(fmax(ice0 + (double)land[c], 0.0), 1.0);        // :1183
-            if ((double)land[c] != (double)land[c]) fr = __builtin_nan("");
-            omf = 1 - fr;
-        }
-        double p_ts = fr * ts, p_tos = omf * tos;                     // :1184, numpy's promotion operand by operand
-        if (f32_ts) p_ts = (double)((float)fr * (float)ts);           // float32 frac * float32 record
-        if (f32_tos) p_tos = (double)((float)omf * (float)tos);
-        comb = p_ts + p_tos;
-        if (f32_ts && f32_tos) comb = (double)((float)p_ts + (float)p_tos);
-    }
+    const double comb = rider_point<T, REF>(r, i, t, c).comb;
     comb_out[i] = comb;                                               // step_03:125
     if (dsoil_out) {
-        double cl = (double)clim[c];                                  // :134-136
+        double cl = (double)clim[c];                                  // annual mean ts delta :134-136
 #pragma unroll
         for (int s = 0; s < MAX_SOIL; ++s) {
-            if (s < soil.n) dsoil_out[(t * soil.n + s) * ncol + c] = cl + soil.w[s] * (comb - cl);   // :139-142
+            if (s < soil.n) dsoil_out[(t * soil.n + s) * ncol + c] = soil_delta(soil, s, cl, comb);   // :139-142
         }
     }
 }

@@ -1,5 +1,5 @@
 """GPU tests of the surface riders (step_03:103-146, functions.py:1145-1186) at their masks, clips and mixed time axes:
-`pgw_surface_update` (k_surface_update), `pgw_surface_deltas` (k_surface_deltas), the production kernel inside
+`pgw_surface_update` (k_surface_update_lerp), `pgw_surface_deltas` (k_surface_deltas), the production kernel inside
 `pgw_step03_file` (k_surface_update_lerp) and `F.integrate_tos` (k_integrate_tos, k_integrate_tos_mixed), all on the edge
 inputs of tests/surface_edge_cases.py (checked on the CPU by tests/test_surface_riders_host.py).
 
@@ -117,7 +117,7 @@ def check_update(got, want, dtype, what=''):
 @pytest.mark.parametrize('ncol', E.NCOLS)
 @pytest.mark.parametrize('dtype', STORAGE)
 def test_surface_update_vs_oracle(gpu, dtype, ncol, ntime):
-    """k_surface_update on the edge table, 1 / 64 / 257 / 300 columns, one and three time steps, 1, 4 and 16 soil layers,
+    """k_surface_update_lerp on the edge table, 1 / 64 / 257 / 300 columns, one and three time steps, 1, 4 and 16 soil layers,
     against O.sea_ice_update, O.integrate_tos (land and the updated ice of time step 0 at every step, step_03:121-122),
     tskin + comb and tso + O.soil_temperature_delta in float64 on the float64-cast inputs."""
     s3, dbg, ctx = gpu
@@ -325,6 +325,40 @@ def test_surface_deltas_mixed_time_axes(gpu, mode, on_record):
 
 
 # ================================================================== 4. production tied to the debug kernel
+@pytest.mark.parametrize('nsoil', [1, 16])
+@pytest.mark.parametrize('dtype', STORAGE)
+def test_surface_update_is_the_debug_deltas_bit_for_bit(gpu, dtype, nsoil):
+    """pgw_surface_update and pgw_surface_deltas on the same exact records (x_hi = 0, no record after the instant), float64
+    and float32 non-reference storage, three time steps, 257 and 300 columns, 1 and 16 soil layers: dts_comb_out is the
+    float64 delta_ts_combined rounded to the storage type, tskin_out and tso_out are float64(era) + the float64 delta
+    rounded once - the soil weights come from the same host exp on both sides, so tso is held bit for bit too."""
+    from pgw4era5_amd import _lib
+    from pgw4era5_amd.device import dtype_tag
+    s3, dbg, ctx = gpu
+    T = np.dtype(dtype)
+    for ncol in (257, 300):
+        inp = E.build(ncol, dtype, nsoil=nsoil, ntime=3)
+        got = surface_update(ctx, inp)
+        d = {k: ctx.to_device(np.ascontiguousarray(getattr(inp, k)), T) for k in ('sic', 'dsic', 'dtos', 'dts', 'land', 'clim')}
+        ts, st = ctx.empty((3, ncol), np.float64), ctx.empty((3, nsoil, ncol), np.float64)
+        soil = np.ascontiguousarray(inp.soil, dtype=np.float64)
+        args = []
+        for k in ('dsic', 'dtos', 'dts'):
+            args += [d[k].ptr, None, 0.0, 0.0]
+        try:
+            ctx._check(ctx.lib.pgw_surface_deltas(ctx.handle, dtype_tag(T), 0, 3, ncol, nsoil, soil.ctypes.data_as(_lib._dp), d['sic'].ptr, *args, d['land'].ptr, d['clim'].ptr, ts.ptr, st.ptr))
+            dts_comb, delta_soilt = ts.numpy(), st.numpy()
+        finally:
+            for v in list(d.values()) + [ts, st]:
+                v.free()
+        what = 'ncol %d ' % ncol
+        np.testing.assert_array_equal(got['comb'], dts_comb.astype(T), err_msg=what + 'comb')
+        np.testing.assert_array_equal(got['tskin'], (E.f64(inp.tskin) + dts_comb).astype(T), err_msg=what + 'tskin')
+        np.testing.assert_array_equal(got['tso'], (E.f64(inp.tso) + delta_soilt).astype(T), err_msg=what + 'tso')
+        np.testing.assert_array_equal(np.isnan(dts_comb), inp.nan_comb)
+        np.testing.assert_array_equal(np.isnan(delta_soilt), inp.nan_soil)
+
+
 AXES = dict(shared=(None, LERP), shared_record=(None, RECORD), siconc_on_record=(('siconc',), LERP), ts_on_record=(('ts',), LERP))
 
 
@@ -375,7 +409,7 @@ def test_production_riders_are_the_debug_deltas_bit_for_bit(gpu, mode, axes):
     np.testing.assert_array_equal(np.isnan(prod['T_SKIN']).reshape(1, 300), inp.nan_comb)
     if mode == 'f64':
         # settings.i_reinterp = 1: the one-call path runs the same kernel; the host-composed path interpolates the three
-        # deltas first (DeltaSet.lerp2d: k_time_lerp, or a copy of the record) and calls k_surface_update on them - the
+        # deltas first (DeltaSet.lerp2d: k_time_lerp, or a copy of the record) and calls pgw_surface_update on them - the
         # same float64 expressions in the same order, so the same bits
         again = s3.pgw_for_era5_arrays(c['era'], c['deltas'], c['delta_times'], c['plev'], target, True, i_reinterp=True)
         ds = (s3.DeltaSet(ctx, c['deltas'], times.get('ta'), c['plev'], T, times_by_var=times) if isinstance(times, dict) else
