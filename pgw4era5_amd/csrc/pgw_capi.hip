@@ -1042,9 +1042,13 @@ extern "C" int pgw_delta_fields(pgw_ctx *ctx, int dtype, int ref_dtype, int ntim
             const DeltaSrc<T> ph = delta_src<T>(pshist_b, pshist_a, x_hi, x_new);
             const PairSrc<T> dwd = pair_src<T>(ua_b, ua_a, va_b, va_a, x_hi, x_new);
             with_offsets(o32, [&](auto o_) { with_int<2>(x_hi != 0.0, [&](auto lerp_) {
+                // k_delta_quad<.., DELTAS = true>: blocks of 128, the quad kernel's dynamic LDS; no ERA fields, no e / QV outputs, no FusedFirst
                 hipLaunchKernelGGL((k_delta_fields<T, decltype(o_), decltype(lerp_)::value != 0, decltype(ref_)::value>),
-                                   dim3(nblocks(total, FIELDS_TPB)), dim3(FIELDS_TPB), 0, ctx->stream, ctx->plev_tab, lv, ntime, ncol,
-                                   (const T *)ps, dth, ds, ph, dwd, ignore_top ? 0 : 1, dta, dhur, dua, dva, ctx->n_pure, ctx->d_status);
+                                   dim3(nblocks(total, 128)), dim3(128), (size_t)(5 * nlev + 2) * sizeof(double), ctx->stream,
+                                   ctx->plev_tab, lv, ntime, ncol, (const T *)nullptr, (const T *)nullptr, (const T *)nullptr,
+                                   (const T *)nullptr, (const T *)ps, dth, ds, ph, dwd, ignore_top ? 0 : 1, dta, (double *)nullptr,
+                                   dhur, dua, dva, (double *)nullptr, 0, ctx->n_pure, ctx->d_status, 0.0,
+                                   (const FusedFirst<T> *)nullptr);
             }); });
         });
     }

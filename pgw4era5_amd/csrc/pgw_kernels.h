@@ -2063,8 +2063,9 @@ struct FusedFirst {
     DevStatus *st_era, *st_pass;
 };
 
-template <typename T, typename TO, int U, int TPB, typename O, bool LERP, bool REF, bool FUSE>
-__global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) void k_delta_quad(PlevTable pt, Levels lv, int ntime, long long ncol,
+// DELTAS (k_delta_fields below): the same walk, but the four deltas themselves are the output.
+template <typename T, typename TO, int U, int TPB, typename O, bool LERP, bool REF, bool FUSE, bool DELTAS = false>
+__global__ __launch_bounds__(TPB, (sizeof(T) == 4 || DELTAS ? QUAD_MINW_F32 : QUAD_MINW)) void k_delta_quad(PlevTable pt, Levels lv, int ntime, long long ncol,
                                                        const T *__restrict__ fT, const T *__restrict__ fQ,
                                                        const T *__restrict__ fU, const T *__restrict__ fV,
                                                        const T *__restrict__ PS,
@@ -2080,6 +2081,7 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
     // (instead of e, which only the levels below p_ref and k_finalize_ps_hus need) and the finalize kernel skips them.
     // n_pure_lv: number of leading pure-pressure levels (n_pure is 0 when the QV shortcut is off); their pressure akm[l]
     // is the same in every column, so ln(akm[l]) is taken once per block instead of once per column and level
+    static_assert(!(DELTAS && FUSE), "the deltas-only instantiation has no ERA state to scan");
     extern __shared__ double lds_quad[];            // akm[N] | bkm[N] | ln(akm)[N] (first n_pure_lv entries) | ak[N+1] | bk[N+1]
     __shared__ double s_lnpref;                     // pgw_log(p_ref)
     __shared__ double s_mint[TPB / 64], s_mins[TPB / 64];
@@ -2176,7 +2178,7 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
         // the six more live registers it spills) and its time is its bytes.
         double px1 = 0.0;
         SharedDivisor by_Dp(1.0, 1.0);
-        constexpr bool HOIST_DP = (sizeof(T) == 4);
+        constexpr bool HOIST_DP = (sizeof(T) == 4) || DELTAS;     // DELTAS holds no prefetched rows: room for every storage type
         auto plain_bracket = [&](int i1, int ih) { if (HOIST_DP) { px1 = s_lnp[i1]; by_Dp = SharedDivisor(s_lnp[ih] - px1); } };
         auto fetch2 = [&](int i1) {
             if (ci2 == i1) return;
@@ -2232,13 +2234,13 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             O o = base + (O)((N - 1 - u) > 0 ? (N - 1 - u) : 0) * row;
-            nT[u] = QLD(fT, o); nQ[u] = QLD(fQ, o); nU[u] = QLD(fU, o); nV[u] = QLD(fV, o);
+            if constexpr (!DELTAS) { nT[u] = QLD(fT, o); nQ[u] = QLD(fQ, o); nU[u] = QLD(fU, o); nV[u] = QLD(fV, o); }
         }
         for (int l0 = N - 1; l0 >= 0; l0 -= U) {
             T cT[U], cQ[U], cU[U], cV[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) { cT[u] = nT[u]; cQ[u] = nQ[u]; cU[u] = nU[u]; cV[u] = nV[u]; }
-            if (l0 - U >= 0) {
+            for (int u = 0; u < U; ++u) if constexpr (!DELTAS) { cT[u] = nT[u]; cQ[u] = nQ[u]; cU[u] = nU[u]; cV[u] = nV[u]; }
+            if (!DELTAS && l0 - U >= 0) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     O o = base + (O)((l0 - U - u) > 0 ? (l0 - U - u) : 0) * row;
@@ -2313,27 +2315,31 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
                         }
                     }
                     const O o = obase + (O)l * orow;
-                    QST(oU, o, (TO)((double)cU[u] + dc));                                  // step_03:170-173
-                    QST(oV, o, (TO)((double)cV[u] + dd));
-                    double rh_era;                                                 // step_03:91-94
-                    if (REF) rh_era = q_to_rh_f32((float)cQ[u], pa, (float)cT[u]);
-                    else rh_era = q_to_rh((double)cQ[u], pa, (double)cT[u]);
-                    double ta_pgw = (double)cT[u] + da;
-                    double hur_pgw = rh_era + db;
-                    QST2(oT, o, (TO)ta_pgw);
-                    double e_pgw = rh_to_e(hur_pgw, ta_pgw);                       // functions.py:123
-                    if (l < n_pure) QST(oQ, o, (TO)e_to_q_ns(e_pgw, pa));          // pa == akm[l] for every finite ps
-                    else QST2(oE, o, (TO)e_pgw);
-                    if (oHur) st_off(oHur, o, (TO)hur_pgw);
-                    if (FUSE && below_pref) {                                      // layer l of both scans, as in scan_columns
-                        double rtv[2];
-                        if (REF) rtv[0] = rd_tv_f32((double)cT[u], (double)cQ[u]);
-                        else rtv[0] = CON_RD * ((double)cT[u] * (1 + 0.61 * (double)cQ[u]));   // functions.py:144
-                        const double tp = (double)(TO)ta_pgw, ep = (double)(TO)e_pgw;          // what the loop kernel reads back
-                        const double q = SharedDivisor(pa - (1 - CON_MW_MD) * ep).divide(CON_MW_MD * ep);   // e_to_q, ps_of(ps, 0) == ps
-                        rtv[1] = CON_RD * (tp * (1 + 0.61 * q));
-                        geo_mono_layer<REF>(geo, rtv, s_ak[l] + ps * s_bk[l], p_ref, s_lnpref, s_logt);
-                        below_pref = !__all(geo.p_lo < p_ref && geo.have);      // scan_columns' stop, level by level
+                    if constexpr (DELTAS) {                                        // functions.py:472-473: float64 rows
+                        QST(oT, o, (TO)da); QST(oHur, o, (TO)db); QST(oU, o, (TO)dc); QST(oV, o, (TO)dd);
+                    } else {
+                        QST(oU, o, (TO)((double)cU[u] + dc));                                  // step_03:170-173
+                        QST(oV, o, (TO)((double)cV[u] + dd));
+                        double rh_era;                                                 // step_03:91-94
+                        if (REF) rh_era = q_to_rh_f32((float)cQ[u], pa, (float)cT[u]);
+                        else rh_era = q_to_rh((double)cQ[u], pa, (double)cT[u]);
+                        double ta_pgw = (double)cT[u] + da;
+                        double hur_pgw = rh_era + db;
+                        QST2(oT, o, (TO)ta_pgw);
+                        double e_pgw = rh_to_e(hur_pgw, ta_pgw);                       // functions.py:123
+                        if (l < n_pure) QST(oQ, o, (TO)e_to_q_ns(e_pgw, pa));          // pa == akm[l] for every finite ps
+                        else QST2(oE, o, (TO)e_pgw);
+                        if (oHur) st_off(oHur, o, (TO)hur_pgw);
+                        if (FUSE && below_pref) {                                      // layer l of both scans, as in scan_columns
+                            double rtv[2];
+                            if (REF) rtv[0] = rd_tv_f32((double)cT[u], (double)cQ[u]);
+                            else rtv[0] = CON_RD * ((double)cT[u] * (1 + 0.61 * (double)cQ[u]));   // functions.py:144
+                            const double tp = (double)(TO)ta_pgw, ep = (double)(TO)e_pgw;          // what the loop kernel reads back
+                            const double q = SharedDivisor(pa - (1 - CON_MW_MD) * ep).divide(CON_MW_MD * ep);   // e_to_q, ps_of(ps, 0) == ps
+                            rtv[1] = CON_RD * (tp * (1 + 0.61 * q));
+                            geo_mono_layer<REF>(geo, rtv, s_ak[l] + ps * s_bk[l], p_ref, s_lnpref, s_logt);
+                            below_pref = !__all(geo.p_lo < p_ref && geo.have);      // scan_columns' stop, level by level
+                        }
                     }
                 }
             }
@@ -2366,197 +2372,16 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 ? QUAD_MINW_F32 : QUAD_MINW)) 
 
 // -------------------------------------------------------------------------------------
 // k_delta_fields: the four deltas k_delta_quad adds, as arrays (step_03 --debug_mode interpolate_full, step_03:350-361:
-// the reference writes what load_delta_interp returned, functions.py:306-340).  da, db, dc, dd of k_delta_quad with the
-// same expressions in the same order - time lerp of the records (lerp_pair), surface insertion for ta / hur, one ln p
-// per level for both source axes, the two bracket scans from the surface up, y_hi - y_lo in the delta's dtype when the
-// instant is a float32 record (REF && !LERP) - so era + delta in numpy gives production's bits.  What the quad kernel
-// does around them is gone: no ERA field is read, no humidity chain, no loop scans.  Inputs: the surface pressure the
-// levels stand on (PS of the file; the converged ps_pgw under i_reinterp, step_03:212-216, 336-343) and the record
-// gathers; outputs: four streaming float64 rows per level (xr.zeros_like(targ_P), functions.py:472-473: float64 on
-// float32 files too).  The surface rule is sfc_level on pt.p (uniform index: scalar loads), the source minimum
-// source_min.  With no prefetched rows to hold, the level loop is not chunked and the plain-axis bracket's reciprocal
-// is hoisted for both storage types (SharedDivisor: the same quotient bits as the quad's per-level form).
-// One column per thread, whole waves; level tables, ln(plev) and the log table in LDS.
+// the reference writes what load_delta_interp returned, functions.py:306-340).  It is k_delta_quad<.., DELTAS = true>:
+// the quad kernel's own body with everything around the delta walk compiled out - no ERA field is read (fT, fQ, fU, fV
+// unused), no humidity chain, no loop scans - so era + delta in numpy gives production's bits.  Inputs: the surface
+// pressure the levels stand on (PS of the file; the converged ps_pgw under i_reinterp, step_03:212-216, 336-343) and the
+// record gathers; outputs: four streaming float64 rows per level in oT, oHur, oU, oV (xr.zeros_like(targ_P),
+// functions.py:472-473: float64 on float32 files too; oE, oQ unused).  With no prefetched rows to hold, the level loop is
+// not chunked (U = 1), four waves fit for every storage type and the plain-axis bracket's reciprocal is hoisted for all.
 // -------------------------------------------------------------------------------------
-#define FIELDS_TPB 128
 template <typename T, typename O, bool LERP, bool REF>
-__global__ __launch_bounds__(FIELDS_TPB) void k_delta_fields(PlevTable pt, Levels lv, int ntime, long long ncol,
-                                                             const T *__restrict__ PS,
-                                                             PairSrc<T> dth, PairSrc<T> dsfc, DeltaSrc<T> psh, PairSrc<T> dw,
-                                                             int check_top, double *__restrict__ oTa, double *__restrict__ oHur,
-                                                             double *__restrict__ oUa, double *__restrict__ oVa, int n_pure_lv,
-                                                             DevStatus *st) {
-    constexpr int TPB = FIELDS_TPB;
-    __shared__ double s_lev[LEVTAB_DOUBLES];        // akm | bkm | table of pgw_log_tab (stage_levels; the half-level slots stay unused)
-    __shared__ double s_lnpa[MAX_NLEV];             // ln(akm) of the first n_pure_lv levels (see k_delta_quad)
-    __shared__ double s_mint[TPB / 64], s_mins[TPB / 64];
-    __shared__ int s_nan[TPB / 64];
-    __shared__ double s_lnp[MAX_PLEV];
-    const int S = pt.n;
-    const LevTab lt = stage_levels<false, true>(lv, s_lev, TPB);
-    const double *s_akm = lt.akm, *s_bkm = lt.bkm, *s_logt = lt.logtab;
-    stage_plev(pt.lnp, s_lnp, TPB);
-    for (int i = threadIdx.x; i < n_pure_lv; i += TPB) s_lnpa[i] = pgw_log_tab(s_akm[i], s_logt);
-    __syncthreads();
-    long long flat = (long long)blockIdx.x * TPB + threadIdx.x;
-    double min_t = __builtin_inf(), min_s = __builtin_inf();
-    int nanflag = 0;
-    const double x_hi = dth.a.x_hi, x_new = dth.a.x_new;     // one instant for every record of the file (see k_delta_quad)
-    const SharedDivisor by_x_hi(x_hi);                      // unused when the instant is a record
-    const DeltaSrc<T> sTa{dth.a.b, dth.a.a, x_hi, x_new}, sHur{dth.b.b, dth.b.a, x_hi, x_new};
-    const DeltaSrc<T> sUa{dw.a.b, dw.a.a, x_hi, x_new}, sVa{dw.b.b, dw.b.a, x_hi, x_new};
-    if (flat < (long long)ntime * ncol) {
-        const int N = lv.nlev;
-        long long t = flat / ncol, c = flat - t * ncol;
-        // byte offsets (type O, see ld_off): delta records (ntime, S, ncol) of T, outputs (ntime, N, ncol) of double
-        const O row = (O)((unsigned long long)ncol * sizeof(T));
-        const O dbase = (O)((unsigned long long)(t * S * ncol + c) * sizeof(T));
-        const O orow = (O)((unsigned long long)ncol * sizeof(double));
-        const O obase = (O)((unsigned long long)(t * N * ncol + c) * sizeof(double));
-        const double ps = (double)PS[flat];
-        const bool ps_finite = __builtin_fabs(ps) <= 1.7976931348623157e308;   // false for NaN, +-inf
-        // ---- surface insertion for ta / hur (replace_delta_sfc, functions.py:343-366)
-        const double pshv = psh.template get<REF>(flat), sfa = dsfc.a.template get<REF>(flat), sfb = dsfc.b.template get<REF>(flat);
-        const SfcLevel sl = sfc_level(pt, pt.p, pshv, st, flat);
-        const int ksfc = sl.ksfc;
-        const bool fill = sl.fill;
-        const double lnps = pgw_log_tab(pshv, s_logt);
-        if (check_top) source_min<true>(S, pt.p, ksfc, pshv, min_s, nanflag);
-        auto sx1 = [&](int i) -> double { const double v = s_lnp[i]; return (i == ksfc) ? lnps : v; };
-        auto is_sfc = [&](int i) -> bool { return ksfc >= 0 && (i == ksfc || (fill && i > ksfc)); };
-        // register caches: source levels (ci, ci+1) of each pair
-        int ci1 = -2, ci2 = -2;
-        double a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;       // ta, hur
-        double c_lo = 0, c_hi = 0, d_lo = 0, d_hi = 0;       // ua, va
-        // all loads of one bracket change go out before the first use (see k_delta_quad)
-        auto tl = [&](const DeltaSrc<T> &sv, T rb, T ra) -> double { return sv.template lerp_pair<REF>(LERP, rb, ra, by_x_hi); };
-        auto off_of = [&](int i) -> O { return dbase + (O)(S - 1 - i) * row; };
-        auto fetch1 = [&](int i1) {
-            if (ci1 == i1) return;
-            const int ih = (i1 + 1 < S) ? i1 + 1 : i1;
-            const O oh = off_of(ih);
-            const bool seq = (ci1 - 1 == i1);
-            const O o = off_of(i1);
-            T lb0 = ld_off(sTa.b, o), lb1 = ld_off(sHur.b, o), la0 = 0, la1 = 0, hb0 = 0, hb1 = 0, ha0 = 0, ha1 = 0;
-            if (LERP) { la0 = ld_off(sTa.a, o); la1 = ld_off(sHur.a, o); }
-            if (!seq) {
-                hb0 = ld_off(sTa.b, oh); hb1 = ld_off(sHur.b, oh);
-                if (LERP) { ha0 = ld_off(sTa.a, oh); ha1 = ld_off(sHur.a, oh); }
-            }
-            if (seq) { a_hi = a_lo; b_hi = b_lo; }
-            else { a_hi = is_sfc(ih) ? sfa : tl(sTa, hb0, ha0); b_hi = is_sfc(ih) ? sfb : tl(sHur, hb1, ha1); }
-            a_lo = is_sfc(i1) ? sfa : tl(sTa, lb0, la0);
-            b_lo = is_sfc(i1) ? sfb : tl(sHur, lb1, la1);
-            ci1 = i1;
-        };
-        // plain-axis bracket (ci2, ci2 + 1): its lower abscissa and the reciprocal of its ln-pressure interval
-        double px1 = 0.0;
-        SharedDivisor by_Dp(1.0, 1.0);
-        auto plain_bracket = [&](int i1, int ih) { px1 = s_lnp[i1]; by_Dp = SharedDivisor(s_lnp[ih] - px1); };
-        auto fetch2 = [&](int i1) {
-            if (ci2 == i1) return;
-            const int ih = (i1 + 1 < S) ? i1 + 1 : i1;
-            const O oh = off_of(ih);
-            const bool seq = (ci2 - 1 == i1);
-            plain_bracket(i1, ih);
-            const O o = off_of(i1);
-            T lb0 = ld_off(sUa.b, o), lb1 = ld_off(sVa.b, o), la0 = 0, la1 = 0, hb0 = 0, hb1 = 0, ha0 = 0, ha1 = 0;
-            if (LERP) { la0 = ld_off(sUa.a, o); la1 = ld_off(sVa.a, o); }
-            if (!seq) {
-                hb0 = ld_off(sUa.b, oh); hb1 = ld_off(sVa.b, oh);
-                if (LERP) { ha0 = ld_off(sUa.a, oh); ha1 = ld_off(sVa.a, oh); }
-            }
-            if (seq) { c_hi = c_lo; d_hi = d_lo; }
-            else { c_hi = tl(sUa, hb0, ha0); d_hi = tl(sVa, hb1, ha1); }
-            c_lo = tl(sUa, lb0, la0);
-            d_lo = tl(sVa, lb1, la1);
-            ci2 = i1;
-        };
-        // both axes step down to the same bracket: the records of all four variables in one batch
-        auto fetch12 = [&](int i1) {
-            if (!(ci1 - 1 == i1 && ci2 - 1 == i1)) { fetch2(i1); fetch1(i1); return; }
-            const O o = off_of(i1);
-            T b0 = ld_off(sTa.b, o), b1 = ld_off(sHur.b, o), b2 = ld_off(sUa.b, o), b3 = ld_off(sVa.b, o);
-            T a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-            if (LERP) { a0 = ld_off(sTa.a, o); a1 = ld_off(sHur.a, o); a2 = ld_off(sUa.a, o); a3 = ld_off(sVa.a, o); }
-            plain_bracket(i1, i1 + 1);
-            a_hi = a_lo; b_hi = b_lo; c_hi = c_lo; d_hi = d_lo;
-            a_lo = is_sfc(i1) ? sfa : tl(sTa, b0, a0);
-            b_lo = is_sfc(i1) ? sfb : tl(sHur, b1, a1);
-            c_lo = tl(sUa, b2, a2);
-            d_lo = tl(sVa, b3, a3);
-            ci1 = ci2 = i1;
-        };
-        // y_hi - y_lo of the column interpolation (functions.py:575-578) in the delta's dtype (see k_delta_quad)
-        auto ydiff = [](double hi, double lo) -> double {
-            return (REF && !LERP) ? (double)((float)hi - (float)lo) : hi - lo; };
-        // from the surface up: targets descend, both scans step down under the reference's rule (`src == x or src > x`)
-        int j1 = S, j2 = S;
-        double xprev = __builtin_inf();
-        for (int l = N - 1; l >= 0; --l) {
-            const double pa = s_akm[l] + ps * s_bkm[l];                            // step_03:87-88
-            if (check_top) { if (pa != pa) nanflag |= 1; else min_t = fmin(min_t, pa); }
-            double x;                                                              // functions.py:471
-            if (l < n_pure_lv) x = ps_finite ? s_lnpa[l] : pa;                     // pa == akm[l]; NaN for a non-finite ps
-            else x = pgw_log_tab(pa, s_logt);
-            if (!(x <= xprev)) { j1 = S; j2 = S; }
-            while (j2 > 0) { double xs = s_lnp[j2 - 1]; if (!(xs == x || xs > x)) break; --j2; }
-            xprev = x;                                       // NaN stays: the next level restarts the scans
-            // ua, va on the plain plev axis
-            int p1, p2;
-            if (j2 >= S) { p1 = p2 = S - 1; }                                      // above range, constant :558-560
-            else {
-                const double xs = s_lnp[j2];
-                if (xs == x) { p1 = p2 = j2; }                                     // exact                 :540-543
-                else if (j2 == 0) { p1 = p2 = 0; }                                 // below range, constant :534-536
-                else { p1 = j2 - 1; p2 = j2; }                                     // bracket               :545-548
-            }
-            const bool same_axis = (ksfc < 0 || j2 < ksfc);   // ta / hur stand at the same bracket (see k_delta_quad)
-            if (same_axis) fetch12(p1); else fetch2(p1);
-            double dc = c_lo, dd = d_lo;
-            double dxp = 0.0;
-            if (p1 != p2) {                                                        // :575-578
-                dxp = x - px1;
-                dc = c_lo + by_Dp.divide(dxp * ydiff(c_hi, c_lo));
-                dd = d_lo + by_Dp.divide(dxp * ydiff(d_hi, d_lo));
-            }
-            // ta, hur on the axis modified by the surface insertion (level ksfc moved to ps_hist, :362-365)
-            double da, db;
-            if (same_axis) {
-                da = a_lo; db = b_lo;
-                if (p1 != p2) {
-                    da = a_lo + by_Dp.divide(dxp * ydiff(a_hi, a_lo));
-                    db = b_lo + by_Dp.divide(dxp * ydiff(b_hi, b_lo));
-                }
-            } else {
-                while (j1 > 0) { double xs = sx1(j1 - 1); if (!(xs == x || xs > x)) break; --j1; }
-                int i1, i2;
-                if (j1 >= S) { i1 = i2 = S - 1; }
-                else {
-                    const double xs = sx1(j1);
-                    if (xs == x) { i1 = i2 = j1; }
-                    else if (j1 == 0) { i1 = i2 = 0; }
-                    else { i1 = j1 - 1; i2 = j1; }
-                }
-                fetch1(i1);
-                da = a_lo; db = b_lo;
-                if (i1 != i2) {
-                    const double x1 = sx1(i1), x2 = sx1(i2);
-                    const double dx = x - x1;
-                    const SharedDivisor by_Dx(x2 - x1);
-                    da = a_lo + by_Dx.divide(dx * ydiff(a_hi, a_lo));
-                    db = b_lo + by_Dx.divide(dx * ydiff(b_hi, b_lo));
-                }
-            }
-            const O o = obase + (O)l * orow;
-            st_off_nt(oTa, o, da);
-            st_off_nt(oHur, o, db);
-            st_off_nt(oUa, o, dc);
-            st_off_nt(oVa, o, dd);
-        }
-    }
-    if (check_top) top_pressure_report<TPB / 64>(min_t, min_s, nanflag, s_mint, s_mins, s_nan, st);
-}
+constexpr auto k_delta_fields = k_delta_quad<T, double, 1, 128, O, LERP, REF, false, true>;
 
 // =====================================================================================
 // a10  bilinear regridding (lat then lon)                      functions.py:817-893

@@ -128,22 +128,32 @@ def test_delta_fields_vs_oracle(gpu, mode, grid, instant):
 @pytest.mark.parametrize('mode', MODES)
 def test_era_plus_delta_is_production_bit_for_bit(gpu, mode, grid, instant):
     """era + delta in numpy float64 (float32 files: float64(field) + delta; fast mode: that sum cast to float32) equals the T, U, V
-    the per-file path returns, on the tie columns of the surface rule too.  dhur has no ERA-state output to be added to
-    (RELHUM of the ERA state is not an output): it is compared with the oracle, at test 1's tolerance."""
+    the per-file path returns, on the tie columns of the surface rule too - with 32- and 64-bit byte offsets on both sides and,
+    for float64 files, with and without the loop's first scans in the production kernel (fused_first), so every production
+    instantiation of the delta walk is held to the fields kernel's.  dhur has no ERA-state output to be added to (RELHUM of
+    the ERA state is not an output): it is compared with the oracle, at test 1's tolerance."""
     s3, dbg, ctx = gpu
     c = make(grid, 21, 19, np.dtype(DTYPE[mode]).name, instant)
     deltas = tie_deltas(c)
-    prod = s3.pgw_for_era5_arrays(c['era'], deltas, c['delta_times'], c['plev'], c['target_dt'], True,
-                                  ref_dtype=dict(f64=None, f32_fast=False, f32_reference=True)[mode])
-    got = device_fields(gpu, c, deltas, mode)
-    for var, name in (('ta', 'T'), ('ua', 'U'), ('va', 'V')):
-        total = np.asarray(c['era'][name], dtype=np.float64) + got[var]
-        if mode == 'f32_fast':
-            total = total.astype(np.float32)
-        assert prod[name].dtype == total.dtype
-        np.testing.assert_array_equal(total, prod[name], err_msg=name)
     want = oracle_fields(c, deltas, mode)
-    np.testing.assert_allclose(got['hur'], want['hur'], rtol=1e-9, atol=1e-9, err_msg='hur')
+    for off64 in (0, 1):
+        got = device_fields(gpu, c, deltas, mode, opts=dict(force_off64=off64))
+        for fused in ((0, 1) if mode == 'f64' else (None,)):
+            opts = dict(force_off64=off64) if fused is None else dict(force_off64=off64, fused_first=fused)
+            old = {k: ctx.set_option(k, v) for k, v in opts.items()}
+            try:
+                prod = s3.pgw_for_era5_arrays(c['era'], deltas, c['delta_times'], c['plev'], c['target_dt'], True,
+                                              ref_dtype=dict(f64=None, f32_fast=False, f32_reference=True)[mode])
+            finally:
+                for k, v in old.items():
+                    ctx.set_option(k, v)
+            for var, name in (('ta', 'T'), ('ua', 'U'), ('va', 'V')):
+                total = np.asarray(c['era'][name], dtype=np.float64) + got[var]
+                if mode == 'f32_fast':
+                    total = total.astype(np.float32)
+                assert prod[name].dtype == total.dtype
+                np.testing.assert_array_equal(total, prod[name], err_msg='%s off64 %d fused_first %s' % (name, off64, fused))
+        np.testing.assert_allclose(got['hur'], want['hur'], rtol=1e-9, atol=1e-9, err_msg='hur off64 %d' % off64)
 
 
 # ================================================================== 3. bit for bit the composed entries
