@@ -731,6 +731,36 @@ int pgw_select_box(pgw_ctx *ctx, int elem_bytes, int nrec, int nlev_src, int nla
  * PGW_K_CLIM_READ - what the card gives this access pattern (tools/clim_time.py); no reference counterpart. */
 int pgw_test_read_records(pgw_ctx *ctx, int dtype, int nrec, long long inner, const void *x);
 
+/* c1 hydrostatic check: geopotential on a list of pressure levels.  No reference counterpart as a function: it is
+ * integ_geopot (functions.py:128-189) evaluated at p_ref = plev[i] for every i in one walk of each column, on the vertical
+ * grid of pgw_set_levels (pa_hl = ak + PS * bk, step_03_apply_to_era.py:64-66), and for two states the loop's
+ * phi_ref_error (step_03_apply_to_era.py:289, 298) on every level instead of one.
+ *  plev (nplev <= 64, HOST, any order): finite and > 1e-4, the guard value of functions.py:135 (else PGW_ERR_ARG).
+ *  FIS, PS_a, PS_b (ntime, ncol) of dtype_2d; T_a, QV_a (ntime, nlev, ncol) of dtype_a; T_b, QV_b of dtype_b.
+ *  PS_b = T_b = QV_b = NULL: out = phi_a.  Otherwise out = phi_b - phi_a, and with zg_before != NULL
+ *    out = (phi_b - phi_a) - g * zg_delta, zg_delta = the records zg_before / zg_after (ntime, nplev, ncol) of dtype_zg,
+ *    in the order of plev, interpolated like load_delta (functions.py:288-292; x_hi == 0: zg_before itself, :282-283).
+ *  out (ntime, nplev, ncol) float64, rows in the order of plev.  float64 arithmetic on the stored values whatever the
+ *  storage types; the float32 roundings of the reference's dtype flow are not reproduced.
+ *  Value at p: k* = half level with the smallest non-negative p_hl - p (ties: lowest index, functions.py:160-163), phi =
+ *  phi_hl[k*] - Rd Tv[k* - 1] (ln p - ln p_hl[k*]) (:174-179); p equal to a half-level pressure gives phi_hl[k*] bit for
+ *  bit.  NaN where no half level has p_hl >= p (the reference raises there, :162-165) or k* = 0 (:176).
+ *  nan_count (nplev, HOST, may be NULL): NaN elements of each output row, over all times and columns.
+ *  form (two states): 0 = both states in one walk, 1 = state a's walk, then state b's; the same bits.  One launch in
+ *  every form, timed under PGW_K_INTEG_GEOPOT. */
+int pgw_geopot_on_plev(pgw_ctx *ctx, int dtype_2d, int dtype_a, int dtype_b, int ntime, int nplev, long long ncol,
+                       const double *plev, const void *FIS, const void *PS_a, const void *T_a, const void *QV_a,
+                       const void *PS_b, const void *T_b, const void *QV_b, int dtype_zg, const void *zg_before,
+                       const void *zg_after, double x_hi, double x_new, double g, int form, double *out,
+                       long long *nan_count);
+
+/* c2 per-row statistics of x (nrow, ncol) float64 on the device, NaN skipped - what step_03_apply_to_era.py:308 does for
+ * one level (`np.abs(phi_ref_error).max()`, skipna) for the table of the hydrostatic check: count, sum, sum of squares
+ * and max |x| of every row into the HOST arrays (nrow).  A row without a finite element gives 0, 0, 0, 0.  Partial sums
+ * are combined in an order that depends on the shape alone: two calls give the same bits.  Not timed by the profiler. */
+int pgw_level_stats(pgw_ctx *ctx, int nrow, long long ncol, const double *x, long long *count, double *sum, double *sumsq,
+                    double *maxabs);
+
 #ifdef __cplusplus
 }
 #endif

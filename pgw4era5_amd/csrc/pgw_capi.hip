@@ -858,6 +858,109 @@ extern "C" int pgw_field_sub(pgw_ctx *ctx, int dtype, long long n, const void *a
     return PGW_OK;
 }
 
+// ------------------------------------------------------------------ hydrostatic check: geopotential on pressure levels
+// The level list in descending pressure with the permutation back to the caller's order (stable: equal levels keep the
+// caller's order), logarithms from the device table like plev_table's.
+static int geo_targets(pgw_ctx *ctx, int nplev, const double *plev, GeoTargets *gt) {
+    memset(gt, 0, sizeof(*gt));
+    gt->n = nplev;
+    for (int i = 0; i < nplev; ++i) {
+        if (!(plev[i] > 0.0001 && plev[i] <= 1.7976931348623157e308))             // :135 guard value; NaN fails too
+            return fail(ctx, PGW_ERR_ARG, "pgw_geopot_on_plev: plev[%d] = %g must be finite and greater than 1e-4", i, plev[i]);
+        gt->row[i] = i;
+    }
+    std::stable_sort(gt->row, gt->row + nplev, [&](int a, int b) { return plev[a] > plev[b]; });
+    for (int i = 0; i < nplev; ++i) gt->p[i] = plev[gt->row[i]];
+    double *d_in = ctx->d_small, *d_out = ctx->d_small + MAX_PLEV;
+    HIPCHK(ctx, hipMemcpyAsync(d_in, gt->p, sizeof(double) * nplev, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_log_table, dim3(1), dim3(64), 0, ctx->stream, nplev, d_in, d_out);
+    HIPCHK(ctx, hipMemcpyAsync(gt->lnp, d_out, sizeof(double) * nplev, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PGW_OK;
+}
+
+extern "C" int pgw_geopot_on_plev(pgw_ctx *ctx, int dtype_2d, int dtype_a, int dtype_b, int ntime, int nplev, long long ncol,
+                                  const double *plev, const void *FIS, const void *PS_a, const void *T_a, const void *QV_a,
+                                  const void *PS_b, const void *T_b, const void *QV_b, int dtype_zg, const void *zg_before,
+                                  const void *zg_after, double x_hi, double x_new, double g, int form, double *out,
+                                  long long *nan_count) {
+    CHECK_COMMON(ctx, dtype_2d, ntime, ncol);
+    NEED(ctx, ctx->nlev > 0, "pgw_set_levels has not been called");
+    NEED(ctx, TAG_OK(dtype_a), "dtype_a must be PGW_F32 or PGW_F64");
+    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV && plev, "nplev must be in [1, 64]");
+    NEED(ctx, FIS && PS_a && T_a && QV_a && out, "null pointer");
+    const bool two = PS_b != nullptr;
+    NEED(ctx, two == (T_b != nullptr) && two == (QV_b != nullptr), "PS_b, T_b and QV_b must be given together");
+    NEED(ctx, !two || TAG_OK(dtype_b), "dtype_b must be PGW_F32 or PGW_F64");
+    NEED(ctx, !zg_before || two, "a zg record needs two states");
+    NEED(ctx, !zg_before || TAG_OK(dtype_zg), "dtype_zg must be PGW_F32 or PGW_F64");
+    NEED(ctx, !zg_before || x_hi == 0.0 || zg_after, "zg_after is needed unless x_hi is 0");
+    NEED(ctx, form == 0 || form == 1, "form must be 0 (one walk) or 1 (two walks)");
+    for (const void *p : {FIS, PS_a, T_a, QV_a, PS_b, T_b, QV_b, zg_before, zg_after})
+        NEED(ctx, p != (const void *)out, "out must not be one of the inputs");
+    GeoTargets gt;
+    int rc = geo_targets(ctx, nplev, plev, &gt);
+    if (rc) return rc;
+    unsigned long long *d_cnt = (unsigned long long *)(ctx->d_small + 2 * MAX_PLEV);
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * MAX_PLEV, ctx->stream));
+    ZgDelta zg = {zg_before, (zg_before && x_hi != 0.0) ? zg_after : nullptr, dtype_zg == PGW_F32 ? 1 : 0, x_hi, x_new, g};
+    const Levels lv = levels_of(ctx);
+    const unsigned int nb = nblocks((long long)ntime * ncol, BLOCK);
+    {
+        Prof pr(ctx, PGW_K_INTEG_GEOPOT);
+        with_type(dtype_2d, [&](auto t2_) { with_type(dtype_a, [&](auto ta_) {
+            using T2 = decltype(t2_); using TLA = decltype(ta_);
+            if (!two) {
+                hipLaunchKernelGGL((k_geopot_plev<T2, TLA, TLA, 1, false>), dim3(nb), dim3(BLOCK), 0, ctx->stream, gt, lv, ntime, ncol,
+                                   (const T2 *)FIS, (const T2 *)PS_a, (const TLA *)T_a, (const TLA *)QV_a, (const T2 *)nullptr,
+                                   (const TLA *)nullptr, (const TLA *)nullptr, zg, out, d_cnt);
+                return;
+            }
+            with_type(dtype_b, [&](auto tb_) { with_int<2>(form, [&](auto f_) {
+                using TLB = decltype(tb_);
+                hipLaunchKernelGGL((k_geopot_plev<T2, TLA, TLB, 2, decltype(f_)::value == 0>), dim3(nb), dim3(BLOCK), 0, ctx->stream, gt,
+                                   lv, ntime, ncol, (const T2 *)FIS, (const T2 *)PS_a, (const TLA *)T_a, (const TLA *)QV_a,
+                                   (const T2 *)PS_b, (const TLB *)T_b, (const TLB *)QV_b, zg, out, d_cnt);
+            }); });
+        }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (nan_count) {
+        unsigned long long h[MAX_PLEV];
+        HIPCHK(ctx, hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < nplev; ++i) nan_count[i] = (long long)h[i];            // the kernel counts by output row
+    }
+    return PGW_OK;
+}
+
+extern "C" int pgw_level_stats(pgw_ctx *ctx, int nrow, long long ncol, const double *x, long long *count, double *sum,
+                               double *sumsq, double *maxabs) {
+    NEED(ctx, nrow >= 1 && nrow <= 65535 && ncol >= 1, "nrow must be in [1, 65535], ncol positive");
+    NEED(ctx, x && count && sum && sumsq && maxabs, "null pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    unsigned int nbx = nblocks(ncol, BLOCK * 8);                  // a function of the shape alone
+    if (nbx > 64) nbx = 64;
+    void *part = nullptr;
+    const size_t bytes = sizeof(double) * 4 * nbx * (size_t)nrow;
+    int rc = ws_get(ctx, 7, bytes, &part);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_level_stats, dim3(nbx, nrow), dim3(BLOCK), 0, ctx->stream, ncol, x, (double *)part);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<double> h((size_t)4 * nbx * nrow);
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), part, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int r = 0; r < nrow; ++r) {
+        double c = 0.0, s = 0.0, q = 0.0, m = 0.0;
+        for (unsigned int b = 0; b < nbx; ++b) {                  // the blocks of a row in the order of their index
+            const double *p = h.data() + ((size_t)r * nbx + b) * 4;
+            c += p[0]; s += p[1]; q += p[2]; m = p[3] > m ? p[3] : m;
+        }
+        count[r] = (long long)c; sum[r] = s; sumsq[r] = q; maxabs[r] = m;
+    }
+    return PGW_OK;
+}
+
 // ------------------------------------------------------------------ step_01: level list, lon-lat box, model-top merge
 extern "C" int pgw_select_box(pgw_ctx *ctx, int elem_bytes, int nrec, int nlev_src, int nlat_src, int nlon_src, const void *src,
                               int nlev_sel, const int *lev_index, int lat0, int nlat_sel, int lon0, int nlon_sel, int nlev_dst,

@@ -3432,6 +3432,262 @@ __global__ void k_log_table(int n, const double *in, double *out) {
     if (i < n) out[i] = pgw_log_tab(in[i], s_tab);
 }
 
+// =====================================================================================
+// c1  hydrostatic check: geopotential on a list of pressure levels       functions.py:128-189, once per level
+// phi(p) = integ_geopot(ak + PS * bk, FIS, T, QV, level1, p_ref = p) for every p of a level list, in ONE walk of the
+// column from the surface up; for two states (ERA5 and PGW: own PS, T, QV; shared FIS and coefficients) the difference
+// phi_b - phi_a, and with a zg record pair phi_error = (phi_b - phi_a) - g * zg_delta (step_03:298 on every level).
+// float64 arithmetic on the stored values (the REF = false forms), every logarithm from pgw_log_tab - half levels and
+// targets alike (GeoTargets::lnp is made by k_log_table), so a target that equals a half-level pressure has a zero
+// logarithm difference and gets phi_hl[k*] bit for bit (p == p_hl[N]: FIS).
+//
+// Rule.  k* = the half level with the smallest non-negative fix_p(p_hl) - p, ties to the lowest index (:160-163); the
+// value is phi_hl[k*] - Rd Tv[k* - 1] (ln p - ln p_hl[k*]) (:174-179).  NaN, and the column counted for that level,
+// where no half level has p_hl >= p (the reference raises, :162-165) and where k* = 0 (level 0 has no layer above it:
+// the reference's KeyError, :176; cannot happen for ak[0] = 0, because the host refuses p <= 1e-4).
+// A wave whose columns all have ascending half-level pressures in every state (ps >= Levels::ps_mono_min; false for
+// NaN) walks once: the targets are held in descending pressure, a column's position j in that list only moves forward,
+// and layer l (between half levels l + 1 and l) emits every target with p_hl[l] < p <= p_hl[l + 1] - for which k* = l + 1 -
+// from the running phi, exactly geo_layer's capture and geo_finish's expression.  Any other wave takes the general form:
+// per target one full scan with geo_layer's k* tracking (dmin, `<=` for the ties), S scans in all.  Both forms do the
+// same operations on the same values for an ascending column: same bits.
+//
+// Two states meet in the output row itself: a state that reaches target j first stores its own value there, the other
+// one reads it back and stores the result (same thread, same address: program order).  MEET walks both states level by
+// level in one loop (162 VGPRs, 3 waves per SIMD); the two-walk form walks state a, then state b, in the same launch (116
+// VGPRs, 4 waves) and is what functions.GEOPOT_PLEV_FORM selects: the only form that beat two one-state launches plus a
+// subtraction for float64 and for float32 level arrays.  DESIGN.md section 4 has the times.
+// =====================================================================================
+struct GeoTargets {
+    double p[MAX_PLEV];      // descending pressure
+    double lnp[MAX_PLEV];    // pgw_log_tab of them
+    int row[MAX_PLEV];       // output row of each: the caller's order
+    int n;
+};
+struct ZgDelta {             // bracketing zg records (time, S, ncol) in the caller's level order; b == nullptr: none
+    const void *b, *a;       // a == nullptr: the instant is record b
+    int f32;                 // storage type of both
+    double x_hi, x_new, g;
+    __device__ __forceinline__ double gdz(long long off) const {
+        if (f32) return DeltaSrc<float>{(const float *)b, (const float *)a, x_hi, x_new}.get(off) * g;
+        return DeltaSrc<double>{(const double *)b, (const double *)a, x_hi, x_new}.get(off) * g;
+    }
+};
+constexpr int GEOPLEV_U = 4;
+enum { GEO_PLAIN = 0, GEO_COMBINE = 1, GEO_MEET = 2 };
+
+// One target's value leaves the walk.  PLAIN: stored.  COMBINE: the row holds state a's value, this is state b's.
+// MEET: `other_done` says whether the other state has been here.
+template <int MODE>
+__device__ __forceinline__ void geo_emit(double val, int s, bool other_done, long long idx, int row, bool live, const ZgDelta &zg,
+                                         double *out, unsigned int *s_cnt) {
+    if (!live) return;
+    if (MODE == GEO_PLAIN || (MODE == GEO_MEET && !other_done)) {
+        out[idx] = val;
+        if (MODE == GEO_PLAIN && s_cnt && val != val) atomicAdd(&s_cnt[row], 1u);      // s_cnt == nullptr: a value that waits
+        return;
+    }
+    const double prev = out[idx];
+    double r = (MODE == GEO_COMBINE || s == 1) ? val - prev : prev - val;          // phi_b - phi_a
+    if (zg.b) r = r - zg.gdz(idx);                                                 // step_03:298
+    out[idx] = r;
+    if (r != r) atomicAdd(&s_cnt[row], 1u);
+}
+
+// The walk of NSW states of one column (ascending half-level pressures) through the descending targets
+template <int NSW, int MODE, typename TLA, typename TLB>
+__device__ __forceinline__ void geo_walk(const LevTab &lt, int N, int S, long long ncol, const double *s_p, const double *s_lnp,
+                                         const int *s_row, const double *s_lnhl, const TLA *__restrict__ ta0, const TLA *__restrict__ q0,
+                                         const TLB *__restrict__ ta1, const TLB *__restrict__ q1, const double (&ps)[NSW], double z,
+                                         long long obase, bool live, const ZgDelta &zg, double *out, unsigned int *s_cnt) {
+    constexpr int U = GEOPLEV_U;
+    double phi[NSW], p_lo[NSW], lnp_lo[NSW];
+    double pn[NSW];                            // the target at j: read again only after an emit (s_p[S] = -inf ends the list)
+    int j[NSW];
+    const double nan = __builtin_nan("");
+    auto emit = [&](int s, double val) {
+        const int row = s_row[j[s]];
+        geo_emit<MODE>(val, s, NSW == 2 && j[NSW - 1 - s] > j[s], obase + (long long)row * ncol, row, live, zg, out, s_cnt);
+        j[s] += 1;
+        pn[s] = s_p[j[s]];
+    };
+    {
+        const double akN = lt.ak[N], bkN = lt.bk[N];
+#pragma unroll
+        for (int s = 0; s < NSW; ++s) {
+            phi[s] = z;
+            p_lo[s] = fix_p(akN + ps[s] * bkN);
+            lnp_lo[s] = pgw_log_tab(p_lo[s], lt.logtab);
+            j[s] = 0;
+            pn[s] = s_p[0];
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NSW; ++s)
+        while (pn[s] > p_lo[s]) emit(s, nan);                                      // below the surface half level
+    double tn[U][NSW], qn[U][NSW];
+    auto request = [&](int l0) {                                                   // rows l0, l0 - 1, ... (clamped at 0)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long lu = (l0 - u) > 0 ? (l0 - u) : 0;
+            tn[u][0] = (double)__builtin_nontemporal_load(ta0 + lu * ncol);
+            qn[u][0] = (double)__builtin_nontemporal_load(q0 + lu * ncol);
+            if constexpr (NSW == 2) {
+                tn[u][1] = (double)__builtin_nontemporal_load(ta1 + lu * ncol);
+                qn[u][1] = (double)__builtin_nontemporal_load(q1 + lu * ncol);
+            }
+        }
+    };
+    request(N - 1);
+    for (int l = N - 1; l >= 0; l -= U) {
+        double t[U][NSW], q[U][NSW];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int s = 0; s < NSW; ++s) { t[u][s] = tn[u][s]; q[u][s] = qn[u][s]; }
+        if (l - U >= 0) request(l - U);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int lc = l - u;
+            if (lc >= 0) {
+                const double a = lt.ak[lc], b = lt.bk[lc];
+                const bool pure = b == 0.0;                                        // the same pressure in every column: ak
+                const double lna = s_lnhl[lc];
+#pragma unroll
+                for (int s = 0; s < NSW; ++s) {
+                    const double rtv = CON_RD * (t[u][s] * (1 + 0.61 * q[u][s]));  // :144, :150
+                    const double p_hi = fix_p(a + ps[s] * b);                      // :135
+                    const double lnp_hi = pure ? lna : pgw_log_tab(p_hi, lt.logtab);
+                    while (pn[s] > p_hi) emit(s, phi[s] - rtv * (s_lnp[j[s]] - lnp_lo[s]));    // k* = lc + 1, :174-179
+                    phi[s] = phi[s] + rtv * (lnp_lo[s] - lnp_hi);                  // :149-152
+                    p_lo[s] = p_hi; lnp_lo[s] = lnp_hi;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NSW; ++s)
+        while (j[s] < S) emit(s, nan);                                             // k* = 0
+}
+
+// One target, one state, any column: geo_layer's scan and geo_finish's expression with the target's tabulated logarithm
+template <typename TL>
+__device__ __forceinline__ double geo_general(const LevTab &lt, int N, long long ncol, const TL *__restrict__ ta, const TL *__restrict__ hus,
+                                              double ps, double z, double p, double lnp) {
+    GeoAcc acc;
+    geo_init(acc, z, lt.ak[N] + ps * lt.bk[N], lt.logtab);
+    for (int l = N - 1; l >= 0; --l) {
+        const double t = (double)ta[(long long)l * ncol], q = (double)hus[(long long)l * ncol];
+        geo_layer<false, true>(acc, l, CON_RD * (t * (1 + 0.61 * q)), lt.ak[l] + ps * lt.bk[l], p, lt.logtab);
+    }
+    const double d = acc.p_lo - p;                                                 // candidate k = 0
+    if (d >= 0 && d <= acc.dmin) acc.kstar = 0;
+    if (acc.kstar <= 0) return __builtin_nan("");
+    return acc.phi_s - acc.rtv_s * (lnp - acc.lnp_s);
+}
+
+// T2: storage type of PS (both states) and FIS; TLA / TLB: of the level arrays of state a / b.  NS = 1: out = phi_a;
+// NS = 2: phi_b - phi_a, minus g * zg_delta when zg.b is set.  out (ntime, S, ncol) float64 in the caller's level order;
+// nan_count[row] += NaN columns of that row (integer adds: the same total in any order).
+template <typename T2, typename TLA, typename TLB, int NS, bool MEET>
+__global__ __launch_bounds__(BLOCK) void k_geopot_plev(GeoTargets gt, Levels lv, int ntime, long long ncol,
+                                                       const T2 *__restrict__ FIS, const T2 *__restrict__ PS_a,
+                                                       const TLA *__restrict__ T_a, const TLA *__restrict__ QV_a,
+                                                       const T2 *__restrict__ PS_b, const TLB *__restrict__ T_b,
+                                                       const TLB *__restrict__ QV_b, ZgDelta zg, double *out,
+                                                       unsigned long long *__restrict__ nan_count) {
+    __shared__ double s_lev[LEVTAB_DOUBLES];
+    __shared__ double s_p[MAX_PLEV + 1], s_lnp[MAX_PLEV + 1];
+    __shared__ int s_row[MAX_PLEV + 1];
+    __shared__ unsigned int s_cnt[MAX_PLEV];
+    __shared__ double s_lnhl[MAX_NLEV + 1];    // ln fix_p(ak[l]): the logarithm of a pure-pressure half level (bk[l] = 0), once per block
+    const int S = gt.n, N = lv.nlev;
+    for (int i = threadIdx.x; i <= MAX_PLEV; i += BLOCK) {
+        const bool in = i < S;                 // behind the list: a pressure no half level lies below
+        s_p[i] = in ? gt.p[i] : -__builtin_inf(); s_lnp[i] = in ? gt.lnp[i] : 0.0; s_row[i] = in ? gt.row[i] : 0;
+        if (i < MAX_PLEV) s_cnt[i] = 0u;
+    }
+    LevTab lt = stage_levels<true, false>(lv, s_lev, BLOCK);                      // synchronises
+    for (int i = threadIdx.x; i <= N; i += BLOCK) s_lnhl[i] = pgw_log_tab(fix_p(lt.ak[i]), lt.logtab);
+    __syncthreads();
+    const long long ntot = (long long)ntime * ncol;
+    long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = g < ntot;
+    if (!live) g = ntot - 1;                  // idle lanes of the last block shadow its last column and store nothing
+    const long long t = g / ncol, c = g - t * ncol;
+    const long long lbase = t * N * ncol + c, obase = t * S * ncol + c;
+    const double z = (double)FIS[g];
+    double ps[NS];
+    ps[0] = (double)PS_a[g];
+    if constexpr (NS == 2) ps[1] = (double)PS_b[g];
+    constexpr double DBL_MAX_ = 1.7976931348623157e308;           // an infinite PS ascends nowhere (inf * 0 on the pure-pressure levels)
+    bool mono = ps[0] >= lv.ps_mono_min && ps[0] <= DBL_MAX_;
+    if constexpr (NS == 2) mono = mono && ps[1] >= lv.ps_mono_min && ps[1] <= DBL_MAX_;
+    if (__all(mono)) {
+        if constexpr (NS == 1) {
+            geo_walk<1, GEO_PLAIN, TLA, TLA>(lt, N, S, ncol, s_p, s_lnp, s_row, s_lnhl, T_a + lbase, QV_a + lbase, nullptr, nullptr, ps, z,
+                                             obase, live, zg, out, s_cnt);
+        } else if constexpr (MEET) {
+            geo_walk<2, GEO_MEET, TLA, TLB>(lt, N, S, ncol, s_p, s_lnp, s_row, s_lnhl, T_a + lbase, QV_a + lbase, T_b + lbase, QV_b + lbase,
+                                            ps, z, obase, live, zg, out, s_cnt);
+        } else {
+            const double pa[1] = {ps[0]}, pb[1] = {ps[1]};
+            geo_walk<1, GEO_PLAIN, TLA, TLA>(lt, N, S, ncol, s_p, s_lnp, s_row, s_lnhl, T_a + lbase, QV_a + lbase, nullptr, nullptr, pa, z,
+                                             obase, live, zg, out, nullptr);
+            geo_walk<1, GEO_COMBINE, TLB, TLB>(lt, N, S, ncol, s_p, s_lnp, s_row, s_lnhl, T_b + lbase, QV_b + lbase, nullptr, nullptr, pb, z,
+                                               obase, live, zg, out, s_cnt);
+        }
+    } else {
+        for (int j = 0; j < S; ++j) {
+            const int row = s_row[j];
+            const long long idx = obase + (long long)row * ncol;
+            double r = geo_general<TLA>(lt, N, ncol, T_a + lbase, QV_a + lbase, ps[0], z, s_p[j], s_lnp[j]);
+            if constexpr (NS == 2) {
+                r = geo_general<TLB>(lt, N, ncol, T_b + lbase, QV_b + lbase, ps[1], z, s_p[j], s_lnp[j]) - r;
+                if (zg.b) r = r - zg.gdz(idx);
+            }
+            if (live) {
+                out[idx] = r;
+                if (r != r) atomicAdd(&s_cnt[row], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < S; i += BLOCK)
+        if (s_cnt[i]) atomicAdd(&nan_count[i], (unsigned long long)s_cnt[i]);
+}
+
+// =====================================================================================
+// c2  per-row statistics of a (nrow, ncol) float64 array, NaN skipped: count, sum, sum of squares, max |x|
+// Block (bx, row) takes the columns bx * BLOCK + tid, + gridDim.x * BLOCK, ... in that order, the block folds its 256
+// partials with a fixed tree, and writes part[(row * gridDim.x + bx) * 4 ..]; the host entry adds the blocks of a row in
+// the order of bx.  The grid depends on the shape alone: two calls give the same bits.
+// =====================================================================================
+__global__ __launch_bounds__(BLOCK) void k_level_stats(long long ncol, const double *__restrict__ x, double *__restrict__ part) {
+    __shared__ double s_red[4][BLOCK];
+    const double *r = x + (long long)blockIdx.y * ncol;
+    double cnt = 0.0, sum = 0.0, sq = 0.0, mx = 0.0;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < ncol; i += (long long)gridDim.x * BLOCK) {
+        const double v = r[i];
+        if (v == v) { cnt += 1.0; sum += v; sq += v * v; mx = fmax(mx, fabs(v)); }
+    }
+    s_red[0][threadIdx.x] = cnt; s_red[1][threadIdx.x] = sum; s_red[2][threadIdx.x] = sq; s_red[3][threadIdx.x] = mx;
+    __syncthreads();
+    for (int h = BLOCK / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            s_red[0][threadIdx.x] += s_red[0][threadIdx.x + h];
+            s_red[1][threadIdx.x] += s_red[1][threadIdx.x + h];
+            s_red[2][threadIdx.x] += s_red[2][threadIdx.x + h];
+            s_red[3][threadIdx.x] = fmax(s_red[3][threadIdx.x], s_red[3][threadIdx.x + h]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double *o = part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 4;
+        o[0] = s_red[0][0]; o[1] = s_red[1][0]; o[2] = s_red[2][0]; o[3] = s_red[3][0];
+    }
+}
+
 
 // =====================================================================================
 // a10b  bilinear regridding from curvilinear / rotated source grids       functions.py:797-810

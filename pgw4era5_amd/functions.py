@@ -436,6 +436,115 @@ def adjust_ps_loop(ak, bk, PS, FIS, T, QV, ta_pgw, hur_pgw, dzg_pref, akm=None, 
     return res
 
 
+# ------------------------------------------------------------------------------- hydrostatic check
+# How two states meet in `pgw_geopot_on_plev`: 0 = both in one walk of the column, 1 = one walk each in the same launch.
+# The same bits.  1 is the form that beat the composed calls for float64 AND float32 level arrays.
+GEOPOT_PLEV_FORM = 1
+
+
+def check_plev(plev):
+    """The level list of the hydrostatic check as a float64 vector: 1 to 64 finite pressures above 1e-4 Pa, the guard value
+    of reference functions.py:135 (ValueError otherwise, before anything reaches the device)."""
+    p = np.ascontiguousarray(raw(plev), dtype=np.float64)
+    if p.ndim != 1 or not 1 <= p.size <= 64:
+        raise ValueError('plev must be a vector of 1 to 64 levels, got shape %s' % (p.shape,))
+    if not np.all(np.isfinite(p)):
+        raise ValueError('plev must be finite')
+    if not np.all(p > 0.0001):
+        raise ValueError('plev must be greater than 1e-4 Pa')
+    return p
+
+
+def _geopot_plev(states, zgs, ak, bk, plev, dzg, counts, form):
+    p = check_plev(plev)
+    ak_, bk_ = np.asarray(raw(ak), dtype=np.float64), np.asarray(raw(bk), dtype=np.float64)
+    if ak_.ndim != 1 or ak_.shape != bk_.shape or ak_.size < 2:
+        raise ValueError('ak and bk must be vectors of one length (nlev + 1)')
+    s3 = tuple(raw(zgs).shape)
+    if len(s3) != 3:
+        raise ValueError('zgs must be (time, lat, lon), got shape %s' % (s3,))
+    nlev = ak_.size - 1
+    for i, (ps, ta, hus) in enumerate(states):
+        st = shape4(ta)
+        lab = 'state %s' % 'ab'[i]
+        if shape4(hus) != st:
+            raise ValueError('%s: ta %s and hus %s differ in shape' % (lab, st, shape4(hus)))
+        if (st[0], st[2], st[3]) != s3 or tuple(raw(ps).shape) != s3:
+            raise ValueError('%s: ps %s / ta %s do not lie on the grid %s of zgs' % (lab, tuple(raw(ps).shape), st, s3))
+        if st[1] != nlev:
+            raise ValueError('%s: %d levels, but ak and bk describe %d' % (lab, st[1], nlev))
+    zg = None
+    if dzg is not None:
+        zb, za, x_hi, x_new = dzg if isinstance(dzg, tuple) else (dzg, None, 0.0, 0.0)
+        sz = (s3[0], p.size, s3[1], s3[2])
+        if shape4(zb) != sz or (za is not None and shape4(za) != sz):
+            raise ValueError('dzg must be (time, plev, lat, lon) = %s' % (sz,))
+        if za is None and float(x_hi) != 0.0:
+            raise ValueError('dzg: the record after the instant is needed unless x_hi is 0')
+        zg = (zb, za, float(x_hi), float(x_new))
+    if form not in (None, 0, 1):
+        raise ValueError('form must be 0 or 1')
+    # nothing has touched the device up to here
+    ctx = default_context()
+    ctx.set_levels(ak_, bk_)
+    dt2 = common_dtype(zgs, *[s[0] for s in states])
+    d_z = dev(ctx, zgs, dt2, s3)
+    d_states, tags = [], []
+    for ps, ta, hus in states:
+        dtl = common_dtype(ta, hus)
+        d_states.append((dev(ctx, ps, dt2, s3), dev(ctx, ta, dtl), dev(ctx, hus, dtl)))
+        tags.append(dtype_tag(dtl))
+    if len(states) == 1:
+        d_states.append((None, None, None))
+        tags.append(0)
+    tz, d_zb, d_za, x_hi, x_new = 0, None, None, 0.0, 0.0
+    if zg is not None:
+        dtz = common_dtype(zg[0], zg[1])
+        tz, d_zb, d_za, x_hi, x_new = dtype_tag(dtz), dev(ctx, zg[0], dtz), dev(ctx, zg[1], dtz), zg[2], zg[3]
+    out = ctx.empty((s3[0], p.size, s3[1], s3[2]), F64)
+    nan = (C.c_longlong * p.size)()
+    (pa, ta_a, qa), (pb, ta_b, qb) = d_states
+    ctx._check(ctx.lib.pgw_geopot_on_plev(
+        ctx.handle, dtype_tag(dt2), tags[0], tags[1], s3[0], p.size, s3[1] * s3[2], p.ctypes.data_as(_dp), d_z.ptr,
+        pa.ptr, ta_a.ptr, qa.ptr, ptr(pb), ptr(ta_b), ptr(qb), tz, ptr(d_zb), ptr(d_za), x_hi, x_new, CON_G,
+        int(GEOPOT_PLEV_FORM if form is None else form), out.ptr, nan))
+    res = out if isinstance(raw(states[0][1]), DeviceArray) else out.numpy()
+    return (res, np.array(nan[:], dtype=np.int64)) if counts else res
+
+
+def geopot_on_plev(ps, zgs, ta, hus, ak, bk, plev, counts=False):
+    """Geopotential of one state on every pressure of `plev`: reference functions.py:128-189 (`integ_geopot`) with
+    pa_hl = ak + ps * bk evaluated at p_ref = plev[i] for all i in one walk of the columns.  ps, zgs (time, lat, lon);
+    ta, hus (time, N, lat, lon); returns (time, plev, lat, lon) float64 in the order of `plev` - a DeviceArray for
+    DeviceArray input, an ndarray otherwise.  NaN where the level lies below the column's surface half level (the reference
+    raises there, :162-165).  float64 arithmetic on the stored values; `counts=True` also returns the NaN count per level.
+    ValueError for inconsistent shapes or level counts and for a `plev` that is not finite and above 1e-4 Pa."""
+    return _geopot_plev([(ps, ta, hus)], zgs, ak, bk, plev, None, counts, None)
+
+
+def geopot_change_on_plev(ps_a, ta_a, hus_a, ps_b, ta_b, hus_b, zgs, ak, bk, plev, dzg=None, counts=False, form=None):
+    """phi_b - phi_a of two states that share zgs and the coefficients (`geopot_on_plev` of each, one launch), the loop's
+    `phi_ref_pgw - phi_ref_era` (reference step_03_apply_to_era.py:289) on every level of `plev`.  With `dzg` - the zg delta
+    (time, plev, lat, lon) in the order of `plev`, or `(record_before, record_after, x_hi, x_new)` for the time
+    interpolation of `load_delta` (functions.py:288-292) - the result is phi_error = (phi_b - phi_a) - g * dzg (step_03:298).
+    NaN where either state is NaN.  The level arrays of each state keep their own dtype; the surface fields share one."""
+    return _geopot_plev([(ps_a, ta_a, hus_a), (ps_b, ta_b, hus_b)], zgs, ak, bk, plev, dzg, counts, form)
+
+
+def level_stats(x):
+    """Per row of x (nrow, ncol) float64, NaN skipped: dict(count, sum, sumsq, maxabs) as host vectors (`pgw_level_stats`);
+    two calls give the same bits."""
+    r = raw(x)
+    if len(r.shape) != 2 or r.shape[0] < 1 or r.shape[1] < 1:
+        raise ValueError('level_stats takes a non-empty (nrow, ncol) array, got shape %s' % (tuple(r.shape),))
+    ctx = default_context()
+    d = dev(ctx, x, F64)
+    n = r.shape[0]
+    cnt, s, q, m = (C.c_longlong * n)(), (C.c_double * n)(), (C.c_double * n)(), (C.c_double * n)()
+    ctx._check(ctx.lib.pgw_level_stats(ctx.handle, n, r.shape[1], d.ptr, cnt, s, q, m))
+    return dict(count=np.array(cnt[:], dtype=np.int64), sum=np.array(s[:]), sumsq=np.array(q[:]), maxabs=np.array(m[:]))
+
+
 # ------------------------------------------------------------------------------- regridding
 def regrid_tables(src_lat, src_lon, targ_lat, targ_lon):
     """Index/weight tables for the separable lat-then-lon linear interpolation of
