@@ -423,7 +423,9 @@ int pgw_step03_file(pgw_ctx *ctx, pgw_file_args *args);
  *    latitude axis: -1 = south-pole row, nlat_s = north-pole row, else physical row index
  *    (already un-flipped); lat_dx = x_new - x_lo, lat_Dx = x_hi - x_lo; lat_oob != 0 -> NaN.
  *  lon_lo/lon_hi (nlon_t): physical source column (periodic copies folded); lon_dx, lon_Dx, lon_oob.
- *  pole rows use the NaN-skipping zonal mean of physical row `south_row` / `north_row`. */
+ *  pole rows use the NaN-skipping zonal mean of physical row `south_row` / `north_row`.  Tables whose non-oob lat_lo /
+ *  lat_hi entries name the south-pole row (-1) while south_row < 0, or the north-pole row (nlat_s) while north_row < 0, are
+ *  rejected with PGW_ERR_ARG before anything is uploaded or launched. */
 int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s,
                         int nlat_t, int nlon_t, const void *src,
                         const int *lat_lo, const int *lat_hi, const double *lat_dx, const double *lat_Dx,

@@ -2346,6 +2346,12 @@ extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, in
     NEED(ctx, south_row < nlat_s && north_row < nlat_s, "bad pole row");
     for (int j = 0; j < nlat_t; ++j)
         NEED(ctx, lat_oob[j] || (lat_lo[j] >= -1 && lat_lo[j] <= nlat_s && lat_hi[j] >= -1 && lat_hi[j] <= nlat_s), "lat index out of range");
+    // a pole row is only there when its zonal mean is taken: k_zonal_mean_rows leaves the pole value of a negative row unwritten
+    for (int j = 0; j < nlat_t; ++j) {
+        if (lat_oob[j]) continue;
+        NEED(ctx, south_row >= 0 || (lat_lo[j] != -1 && lat_hi[j] != -1), "south-pole row in the tables but south_row < 0");
+        NEED(ctx, north_row >= 0 || (lat_lo[j] != nlat_s && lat_hi[j] != nlat_s), "north-pole row in the tables but north_row < 0");
+    }
     for (int i = 0; i < nlon_t; ++i)
         NEED(ctx, lon_oob[i] || (lon_lo[i] >= 0 && lon_lo[i] < nlon_s && lon_hi[i] >= 0 && lon_hi[i] < nlon_s), "lon index out of range");
     // tables -> device workspace slot 3

@@ -2476,7 +2476,9 @@ __global__ __launch_bounds__(BLOCK) void k_regrid(long long nfield, int nlat_s, 
     const bool lo_pole = jl < 0 || jl >= nlat_s, hi_pole = jh < 0 || jh >= nlat_s;
     const long long row_lo = (long long)(lo_pole ? 0 : jl) * nlon_s, row_hi = (long long)(hi_pole ? 0 : jh) * nlon_s;
     const int lo_which = jl < 0 ? 0 : 1, hi_which = jh < 0 ? 0 : 1;
-    // the grid spacings divide every plane's differences: reciprocals once per thread (SharedDivisor)
+    // the grid spacings divide every plane's differences: reciprocals once per thread (SharedDivisor).  lDx == 0 (the
+    // reference's pole row beside a source row at -90 itself): the reciprocal and with it every quotient is NaN, where the
+    // reference has slope = +-inf or NaN times x_new - x_lo = 0: NaN too (tests/test_regrid_edges_hip.py, `pole in source`)
     const SharedDivisor by_lDx(lDx);
     struct DivW { SharedDivisor d[W]; };
     const DivW by_o = [&]() { if constexpr (W == 1) return DivW{{SharedDivisor(oDx[0])}}; else return DivW{{SharedDivisor(oDx[0]), SharedDivisor(oDx[1])}}; }();
