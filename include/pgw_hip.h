@@ -705,6 +705,37 @@ int pgw_hur_merge_levels(pgw_ctx *ctx, int dtype_amon, int ntime, int nplev, int
 int pgw_clim_accumulate(pgw_ctx *ctx, int dtype_in, int dtype_out, int nrec, long long inner, const void *x, int first,
                         int last, double *sum, int *cnt, void *mean);
 
+/* p1 T_CL of a COSMO extpar file + the time mean of the ts delta            postproc_cosmo/extpar_adapt.py:20-32
+ *   delta_ts_clim = delta_ts.mean(dim=['time'])            - xarray on a float array: np.nanmean(values, axis=0)
+ *   ext_file['T_CL'][:] += delta_ts_clim.values.squeeze()  - numpy's in-place add on netCDF4's masked array
+ * x (nrec, n): device array of dtype_x (X), the records in time order, NaN = missing; base, out (n) of dtype_base (B).
+ * Per cell i:
+ *  1. x'[r] = isnan(x[r][i]) ? +0.0 : x[r][i];  tot = +0.0, then tot = (X)(tot + x'[r]) for r = 0 .. nrec - 1 in record
+ *     order, in X (numpy's sum over the leading axis, which starts from the identity +0.0);  cnt = number of non-NaN
+ *     records.  A NaN record ADDS +0.0.  Only a cell whose records are all -0.0 shows either: it sums to +0.0, with or
+ *     without a NaN record, as numpy's does.
+ *  2. mean = (X)((double)tot / (double)cnt); cnt == 0 gives NaN (0 / 0).
+ *  3. base[i] equal to one of the mask values: out[i] = base[i] bit for bit (a NaN payload too).  mask_values (HOST,
+ *     nmask in 0..2): the variable's `_FillValue` and / or `missing_value`, or NetCDF's default fill value when it has
+ *     neither - the caller's choice; each is rounded to B and compared with ==, a NaN mask value masks NaN cells.
+ *  4. otherwise out[i] = (B)(base[i] + mean), the addition in the promoted type of B and X: float32 + float32 is one
+ *     float32 addition, float32 + float64 one float64 addition rounded once, float64 + either a float64 addition.  A NaN
+ *     mean gives NaN, as the reference writes it.
+ * A grid of one cell (n == 1) is summed in another order, as numpy does it: the records then lie contiguous and numpy's
+ * reduction adds them pairwise (fewer than 8 one after the other; up to 128 in eight partial sums r[j] += x'[8 k + j]
+ * combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), the n % 8 last ones added to that; more are halved at
+ * n2 = n / 2 - (n / 2) % 8); tot = 0.0 + that sum.  From two cells on it is step 1.
+ * All four (dtype_base, dtype_x) pairs.  base = out = NULL: the mean alone.  out may be base (in place).  mean (n) of
+ * dtype_x, may be NULL: the result of step 2.  n_masked, n_new_nan (HOST, may be NULL): the masked cells, and the
+ * unmasked cells whose base was not NaN and whose result is.  The entry synchronises.
+ * A lane takes 16 bytes of a record when n and every address allow it (PGW_OPT_FORCE_VEC1: one cell); byte offsets into x
+ * are 32-bit while it is smaller than 4 GiB (PGW_OPT_FORCE_OFF64: 64-bit); the same bits in every form.  Not timed by the
+ * launch profiler.  PGW_ERR_ARG, and nothing launched, for: an unknown dtype, nrec < 1, n < 1, x == NULL, base without
+ * out or out without base, nmask outside 0..2. */
+int pgw_time_mean_add(pgw_ctx *ctx, int dtype_base, int dtype_x, int nrec, long long n, const void *base, int nmask,
+                      const double *mask_values, const void *x, void *out, void *mean, long long *n_masked,
+                      long long *n_new_nan);
+
 /* s5 `cdo sub` of two climatology files                  step_01_extract_deltas/extract_climate_delta.sh:244-249
  * out[i] = (dtype)((double)a[i] - (double)b[i]) on n elements; NaN (missing) in either operand gives NaN. */
 int pgw_field_sub(pgw_ctx *ctx, int dtype, long long n, const void *a, const void *b, void *out);

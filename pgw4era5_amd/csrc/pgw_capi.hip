@@ -840,6 +840,39 @@ extern "C" int pgw_test_read_records(pgw_ctx *ctx, int dtype, int nrec, long lon
     return PGW_OK;
 }
 
+// postproc_cosmo/extpar_adapt.py:20-32: out = base + time mean of x where base is not a mask value (k_time_mean_add)
+extern "C" int pgw_time_mean_add(pgw_ctx *ctx, int dtype_base, int dtype_x, int nrec, long long n, const void *base, int nmask,
+                                 const double *mask_values, const void *x, void *out, void *mean, long long *n_masked,
+                                 long long *n_new_nan) {
+    NEED(ctx, TAG_OK(dtype_base), "dtype_base must be PGW_F32 or PGW_F64");
+    CHECK_COMMON(ctx, dtype_x, nrec, n);
+    NEED(ctx, x, "null pointer");
+    NEED(ctx, (base != nullptr) == (out != nullptr), "base and out must be given together");
+    NEED(ctx, nmask >= 0 && nmask <= 2 && (nmask == 0 || mask_values), "nmask must be in [0, 2]");
+    MeanAddMask mk = {nmask, {0.0, 0.0}};
+    for (int k = 0; k < nmask; ++k) mk.v[k] = dtype_base == PGW_F32 ? (double)(float)mask_values[k] : mask_values[k];
+    const ClimForm f = clim_form(ctx, dtype_x, nrec, n, {x, base, out, mean});
+    unsigned long long *d_cnt = (unsigned long long *)ctx->d_small, h_cnt[2] = {0, 0};
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, sizeof(h_cnt), ctx->stream));
+    if (n == 1) with_type(dtype_base, [&](auto b_) { with_type(dtype_x, [&](auto x_) {     // one cell: numpy's pairwise order
+        using TB = decltype(b_); using TX = decltype(x_);
+        hipLaunchKernelGGL((k_time_mean_add_one<TX, TB>), dim3(1), dim3(64), 0, ctx->stream, nrec, (const TB *)base, mk,
+                           (const TX *)x, (TB *)out, (TX *)mean, d_cnt);
+    }); });
+    else with_type(dtype_base, [&](auto b_) { with_type_vec(dtype_x, f.vec, [&](auto x_, auto v_) { with_offsets(f.o32, [&](auto o_) {
+        using TB = decltype(b_); using TX = decltype(x_); using O = decltype(o_);
+        constexpr int V = decltype(v_)::value;
+        hipLaunchKernelGGL((k_time_mean_add<TX, TB, V, O>), dim3(nblocks(n / V, BLOCK)), dim3(BLOCK), 0, ctx->stream, nrec, n,
+                           (const TB *)base, mk, (const TX *)x, (TB *)out, (TX *)mean, d_cnt);
+    }); }); });
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_masked) *n_masked = (long long)h_cnt[0];
+    if (n_new_nan) *n_new_nan = (long long)h_cnt[1];
+    return PGW_OK;
+}
+
 extern "C" int pgw_field_sub(pgw_ctx *ctx, int dtype, long long n, const void *a, const void *b, void *out) {
     NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
     NEED(ctx, n >= 1 && a && b && out, "bad argument");

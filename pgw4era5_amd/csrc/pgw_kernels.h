@@ -1056,6 +1056,28 @@ __device__ __forceinline__ void clim_ld(const T *__restrict__ base, O byte_off, 
         for (int v = 0; v < V; ++v) out[v] = t[v];
     }
 }
+// The record walk of the kernels over x (nrec, inner): the V cells from cell i on, record after record in time order, each
+// record handed to `take` as it comes; the loads of CLIM_UNROLL records are issued before the first of them is taken.
+template <typename TI, int V, typename O, typename F>
+__device__ __forceinline__ void clim_walk(int nrec, long long inner, const TI *__restrict__ x, long long i, F &&take) {
+    const O rowb = (O)((unsigned long long)inner * sizeof(TI));
+    O off = (O)((unsigned long long)i * sizeof(TI));
+    int r = 0;
+    for (; r + CLIM_UNROLL <= nrec; r += CLIM_UNROLL) {
+        TI b[CLIM_UNROLL][V];
+#pragma unroll
+        for (int u = 0; u < CLIM_UNROLL; ++u) clim_ld<TI, V, O>(x, off + (O)u * rowb, b[u]);
+        off += (O)CLIM_UNROLL * rowb;
+#pragma unroll
+        for (int u = 0; u < CLIM_UNROLL; ++u) take(b[u]);
+    }
+    for (; r < nrec; ++r) {
+        TI b[V];
+        clim_ld<TI, V, O>(x, off, b);
+        off += rowb;
+        take(b);
+    }
+}
 template <typename TI, typename TO, int V, typename O>
 __global__ __launch_bounds__(BLOCK) void k_clim_accumulate(int nrec, long long inner, const TI *__restrict__ x, int first,
                                                            int last, double *__restrict__ sum, int *__restrict__ cnt,
@@ -1073,28 +1095,11 @@ __global__ __launch_bounds__(BLOCK) void k_clim_accumulate(int nrec, long long i
         loadv16<double, V>(sum + i, s);
         c = *reinterpret_cast<const Pack<int, V> *>(cnt + i);
     }
-    const O rowb = (O)((unsigned long long)inner * sizeof(TI));
-    O off = (O)((unsigned long long)i * sizeof(TI));
-    auto add = [&](const TI (&b)[V]) {
+    clim_walk<TI, V, O>(nrec, inner, x, i, [&](const TI (&b)[V]) {
 #pragma unroll
         for (int v = 0; v < V; ++v)
             if (b[v] == b[v]) { s[v] += (double)b[v]; c.v[v] += 1; }
-    };
-    int r = 0;
-    for (; r + CLIM_UNROLL <= nrec; r += CLIM_UNROLL) {
-        TI b[CLIM_UNROLL][V];
-#pragma unroll
-        for (int u = 0; u < CLIM_UNROLL; ++u) clim_ld<TI, V, O>(x, off + (O)u * rowb, b[u]);
-        off += (O)CLIM_UNROLL * rowb;
-#pragma unroll
-        for (int u = 0; u < CLIM_UNROLL; ++u) add(b[u]);
-    }
-    for (; r < nrec; ++r) {
-        TI b[V];
-        clim_ld<TI, V, O>(x, off, b);
-        off += rowb;
-        add(b);
-    }
+    });
     if (last) {
         double m[V];
 #pragma unroll
@@ -1112,33 +1117,157 @@ template <typename TI, int V, typename O>
 __global__ __launch_bounds__(BLOCK) void k_clim_read(int nrec, long long inner, const TI *__restrict__ x, TI *__restrict__ sink) {
     const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (g >= inner / V) return;
-    const O rowb = (O)((unsigned long long)inner * sizeof(TI));
-    O off = (O)((unsigned long long)(g * V) * sizeof(TI));
     TI keep[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) keep[v] = 0;
-    auto take = [&](const TI (&b)[V]) {
+    clim_walk<TI, V, O>(nrec, inner, x, g * V, [&](const TI (&b)[V]) {
 #pragma unroll
         for (int v = 0; v < V; ++v) keep[v] = b[v] > keep[v] ? b[v] : keep[v];
-    };
-    int r = 0;
-    for (; r + CLIM_UNROLL <= nrec; r += CLIM_UNROLL) {
-        TI b[CLIM_UNROLL][V];
-#pragma unroll
-        for (int u = 0; u < CLIM_UNROLL; ++u) clim_ld<TI, V, O>(x, off + (O)u * rowb, b[u]);
-        off += (O)CLIM_UNROLL * rowb;
-#pragma unroll
-        for (int u = 0; u < CLIM_UNROLL; ++u) take(b[u]);
-    }
-    for (; r < nrec; ++r) {
-        TI b[V];
-        clim_ld<TI, V, O>(x, off, b);
-        off += rowb;
-        take(b);
-    }
+    });
     if (sink) {
 #pragma unroll
         for (int v = 0; v < V; ++v) sink[g * V + v] = keep[v];
+    }
+}
+
+// =====================================================================================
+// p1  T_CL of a COSMO extpar file + time mean of the ts delta                     postproc_cosmo/extpar_adapt.py:20-32
+//   delta_ts_clim = delta_ts.mean(dim=['time'])           xarray on a float array: np.nanmean(values, axis=0)
+//   ext_file['T_CL'][:] += delta_ts_clim.values.squeeze() numpy's in-place add on netCDF4's masked array
+// x (nrec, n) of TX: the records in time order, NaN = missing; base, out (n) of TB.  Per cell i:
+//   1. x'[r] = isnan(x[r][i]) ? +0.0 : x[r][i];  tot = +0.0, then tot = (TX)(tot + x'[r]) for r = 0 .. nrec - 1 in record
+//      order, IN TX;  cnt = number of non-NaN records.  A NaN record ADDS +0.0, and the sum starts from +0.0 (the identity
+//      numpy's add.reduce starts from): 0.0 + v is v for every v but -0.0, so only a cell whose records are all -0.0 shows
+//      it - its sum is +0.0, with or without a NaN record, as numpy's is.
+//   2. mean = (TX)((double)tot / (double)cnt);  cnt == 0: 0 / 0 = NaN.
+//   3. base[i] equal to a mask value (`mk`, already rounded to TB; a NaN mask value masks NaN cells): out[i] = base[i], bit
+//      for bit.
+//   4. otherwise out[i] = (TB)(base[i] + mean) with the addition in the promoted type of TB and TX; a NaN mean gives NaN.
+// base == nullptr: the mean alone (out is not touched); mean == nullptr: it is not stored.  out may be base: a thread reads
+// its cells before it writes them.  counts[0] += masked cells, counts[1] += unmasked cells whose base was not NaN and whose
+// result is: summed over the wave, then lanes 0 and 1 add the two sums with one atomic instruction.
+// The walk over the records is k_clim_accumulate's (clim_walk): one thread per V cells, one access of V * sizeof(TX) <= 16
+// bytes per record and lane, byte offsets of type O into x.
+// A grid of ONE cell (n == 1) is another sum in numpy: the records then lie contiguous, numpy's reduction runs along them and
+// adds pairwise.  k_time_mean_add_one takes that case with numpy's order (np_pairwise_sum below); from two cells on numpy
+// adds record after record, which is step 1.
+// =====================================================================================
+struct MeanAddMask { int n; double v[2]; };
+// steps 3 and 4 for one cell: base value b, mean m -> the cell of out; the two counts are advanced
+template <typename TX, typename TB>
+__device__ __forceinline__ TB mean_add_cell(TB b, TX m, const MeanAddMask &mk, unsigned int &n_masked, unsigned int &n_new_nan) {
+    using P = promo_t<TB, TX>;
+    bool masked = false;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const TB mv = (TB)mk.v[k];
+        if (k < mk.n) masked = masked || (mv != mv ? b != b : b == mv);
+    }
+    const TB r = (TB)((P)b + (P)m);
+    n_masked += masked ? 1u : 0u;
+    n_new_nan += (!masked && b == b && r != r) ? 1u : 0u;
+    return masked ? b : r;                                     // a select moves the masked cell's bits, NaN payloads included
+}
+template <typename TX, typename TB, int V, typename O>
+__global__ __launch_bounds__(BLOCK) void k_time_mean_add(int nrec, long long n, const TB *base, MeanAddMask mk,
+                                                         const TX *__restrict__ x, TB *out, TX *__restrict__ mean,
+                                                         unsigned long long *__restrict__ counts) {
+    static_assert(V * sizeof(TX) <= 16, "one access per record and lane");
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    unsigned int n_masked = 0, n_new_nan = 0;
+    if (g < n / V) {                                           // V | n; no early return: the wave sums below need every lane
+        const long long i = g * V;
+        TX tot[V];
+        int cnt[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) { tot[v] = (TX)0.0; cnt[v] = 0; }
+        clim_walk<TX, V, O>(nrec, n, x, i, [&](const TX (&b)[V]) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const bool there = b[v] == b[v];
+                tot[v] = tot[v] + (there ? b[v] : (TX)0.0);
+                cnt[v] += there ? 1 : 0;
+            }
+        });
+        TX m[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) m[v] = (TX)((double)tot[v] / (double)cnt[v]);
+        if (mean) storev_typed<TX, V>(mean + i, m);
+        if (base) {
+            TB b[V], o[V];
+            loadv_typed<TB, V>(base + i, b);
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = mean_add_cell<TX, TB>(b[v], m[v], mk, n_masked, n_new_nan);
+            storev_typed<TB, V>(out + i, o);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        n_masked += __shfl_xor(n_masked, off, 64);
+        n_new_nan += __shfl_xor(n_new_nan, off, 64);
+    }
+    const unsigned int lane = threadIdx.x & 63u;
+    const unsigned int mine = lane == 0 ? n_masked : n_new_nan;
+    if (lane < 2 && mine) atomicAdd(counts + lane, (unsigned long long)mine);
+}
+
+// numpy's pairwise_sum (numpy/core/src/umath/loops_utils.h.src) on x'[0 .. n): fewer than 8 elements are added one after the
+// other from 0.0; up to 128 go into eight partial sums r[j] += x'[8 k + j], combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) +
+// (r6 + r7)), the n % 8 last ones added to that; more are split at n2 = n / 2 - (n / 2) % 8 and the halves' sums added.  The
+// recursion is written with an explicit stack (depth <= log2 n).
+template <typename T>
+__device__ T np_block_sum(const T *__restrict__ x, long long n) {          // n <= 128
+    auto at = [&](long long r) { const T v = x[r]; return v == v ? v : (T)0.0; };
+    if (n < 8) {
+        T res = (T)0.0;
+        for (long long i = 0; i < n; ++i) res = res + at(i);
+        return res;
+    }
+    T r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = at(j);
+    long long i = 8;
+    for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + at(i + j);
+    }
+    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res = res + at(i);
+    return res;
+}
+template <typename T>
+__device__ T np_pairwise_sum(const T *__restrict__ x, long long n) {
+    struct Frame { long long start, len; int stage; };
+    Frame st[40];
+    T val[40];
+    int sp = 0, nv = 0;
+    st[sp++] = Frame{0, n, 0};
+    while (sp > 0) {
+        Frame &f = st[sp - 1];
+        if (f.len <= 128) { val[nv++] = np_block_sum<T>(x + f.start, f.len); --sp; continue; }
+        long long n2 = f.len / 2;
+        n2 -= n2 % 8;
+        if (f.stage == 0) { f.stage = 1; st[sp++] = Frame{f.start, n2, 0}; }
+        else if (f.stage == 1) { f.stage = 2; st[sp++] = Frame{f.start + n2, f.len - n2, 0}; }
+        else { const T right = val[--nv], left = val[--nv]; val[nv++] = left + right; --sp; }
+    }
+    return val[0];
+}
+// k_time_mean_add for a grid of one cell, one thread: tot = 0.0 + pairwise_sum(x'), then steps 2 - 4 as they are.
+template <typename TX, typename TB>
+__global__ void k_time_mean_add_one(int nrec, const TB *base, MeanAddMask mk, const TX *__restrict__ x, TB *out,
+                                    TX *__restrict__ mean, unsigned long long *__restrict__ counts) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int cnt = 0;
+    for (int r = 0; r < nrec; ++r) cnt += x[r] == x[r] ? 1 : 0;
+    const TX tot = (TX)0.0 + np_pairwise_sum<TX>(x, nrec);
+    const TX m = (TX)((double)tot / (double)cnt);
+    if (mean) mean[0] = m;
+    if (base) {
+        unsigned int n_masked = 0, n_new_nan = 0;
+        out[0] = mean_add_cell<TX, TB>(base[0], m, mk, n_masked, n_new_nan);
+        counts[0] = n_masked;
+        counts[1] = n_new_nan;
     }
 }
 

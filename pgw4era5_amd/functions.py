@@ -545,6 +545,82 @@ def level_stats(x):
     return dict(count=np.array(cnt[:], dtype=np.int64), sum=np.array(s[:]), sumsq=np.array(q[:]), maxabs=np.array(m[:]))
 
 
+# ------------------------------------------------------------------------------- postproc_cosmo
+def _mean_add_plan(base, x, mask_values, out):
+    """Shapes and dtypes of one `pgw_time_mean_add` call, checked before the device is touched: x is (nrec,) + S, base is S
+    or S behind leading axes of length 1 (`T_CL(time=1, rlat, rlon)` meeting the squeezed mean of the reference).
+    -> (nrec, n, S, mask vector)."""
+    sx = tuple(raw(x).shape)
+    if len(sx) < 1 or sx[0] < 1:
+        raise ValueError('x must be (nrec, ...) with at least one record, got shape %s' % (sx,))
+    S = sx[1:]
+    n = int(np.prod(S, dtype=np.int64))
+    if n < 1:
+        raise ValueError('x has no cells: shape %s' % (sx,))
+    mask = np.ascontiguousarray(mask_values, dtype=np.float64).reshape(-1)
+    if mask.size > 2:
+        raise ValueError('at most two mask values (_FillValue, missing_value), got %d' % mask.size)
+    if base is not None:
+        sb = tuple(raw(base).shape)
+        lead = len(sb) - len(S)
+        if lead < 0 or sb[lead:] != S or any(k != 1 for k in sb[:lead]):
+            raise ValueError('base of shape %s does not take the mean of x %s: it must be %s, or that behind axes of length 1'
+                             % (sb, sx, S))
+        if out is not None and not (isinstance(out, DeviceArray) and isinstance(raw(base), DeviceArray)
+                                    and out.shape == sb and out.dtype == raw(base).dtype):
+            raise ValueError('out must be a DeviceArray of the shape and dtype of a DeviceArray base')
+    elif out is not None or mask.size:
+        raise ValueError('out and mask_values need a base')
+    return sx[0], n, S, mask
+
+
+def _time_mean_add(base, x, mask_values=(), out=None, want_mean=False):
+    """One `pgw_time_mean_add` call -> (out, mean, n_masked, n_new_nan) as DeviceArrays / ints (out, mean: None when not
+    asked for)."""
+    nrec, n, S, mask = _mean_add_plan(base, x, mask_values, out)
+    ctx = default_context()
+    d_x = dev_own(ctx, x, (nrec, n))
+    d_b = dev_own(ctx, base)
+    if d_b is not None and out is None:
+        out = ctx.empty(d_b.shape, d_b.dtype)
+    d_m = ctx.empty(S, d_x.dtype) if (want_mean or d_b is None) else None
+    n_masked, n_new_nan = C.c_longlong(0), C.c_longlong(0)
+    ctx._check(ctx.lib.pgw_time_mean_add(ctx.handle, dtype_tag(d_x.dtype if d_b is None else d_b.dtype), dtype_tag(d_x.dtype),
+                                         nrec, n, ptr(d_b), mask.size, mask.ctypes.data_as(_dp) if mask.size else None,
+                                         d_x.ptr, ptr(out), ptr(d_m), C.byref(n_masked), C.byref(n_new_nan)))
+    return out, d_m, n_masked.value, n_new_nan.value
+
+
+def time_mean(x):
+    """Mean over the leading axis of x (nrec, ...), NaN records left out: `delta_ts.mean(dim=['time'])` of the reference's
+    postproc_cosmo/extpar_adapt.py:29, which xarray evaluates as `np.nanmean(values, axis=0)` - a sum in x's dtype in record
+    order with NaN replaced by +0.0, divided by the count; NaN where every record is NaN.  The result has x's dtype and
+    kind (ndarray, DeviceArray, or a labelled array without the leading dimension)."""
+    mean = _time_mean_add(None, x)[1]
+    if isinstance(x, DeviceArray):
+        return mean
+    host = mean.numpy()
+    if is_labelled(x) and hasattr(x, 'like'):
+        return x.like(host, tuple(x.dims)[1:])
+    return host
+
+
+def time_mean_add(base, x, mask_values=(), counts=False, out=None):
+    """base + time_mean(x) where base is not a mask value: `ext_file['T_CL'][:] += delta_ts_clim.values.squeeze()` of the
+    reference's postproc_cosmo/extpar_adapt.py:32 (numpy's in-place add on netCDF4's masked array).  x (nrec,) + S; base S,
+    or S behind leading axes of length 1; the result has base's shape, dtype and kind.  The addition runs in the promoted
+    type of the two and is rounded once to base's dtype.  mask_values: up to two values (`_FillValue`, `missing_value`);
+    cells of base equal to one of them (NaN cells for a NaN value) keep their bits.  counts=True: (out, dict(n_masked,
+    n_new_nan, mean)) - the masked cells, the unmasked ones that were not NaN and are now, and the mean that was added
+    (shape S, x's dtype, the kind of out), all from the one launch.  out: for a DeviceArray base, the DeviceArray that
+    takes the result (base itself: in place).  ValueError for shapes that do not fit, before the device is touched."""
+    res, mean, n_masked, n_new_nan = _time_mean_add(base, x, mask_values, out, want_mean=counts)
+    res = out_like(res, base)
+    if not counts:
+        return res
+    return res, dict(n_masked=n_masked, n_new_nan=n_new_nan, mean=mean if isinstance(res, DeviceArray) else mean.numpy())
+
+
 # ------------------------------------------------------------------------------- regridding
 def regrid_tables(src_lat, src_lon, targ_lat, targ_lon):
     """Index/weight tables for the separable lat-then-lon linear interpolation of

@@ -812,6 +812,72 @@ def to_netcdf(ds, path, threads=None, skip=()):
         os.close(fd)
 
 
+# ------------------------------------------------------------------------------ one variable of an existing file
+# postproc_cosmo/extpar_adapt.py opens the extpar file in append mode and assigns to one variable; here the variable's byte
+# ranges come from the header and nothing else of the file is read or written.
+def _variable_ranges(fd, name):
+    """-> (header entry of `name`, [(file offset, byte count)] of its data in C order): one range for a fixed-size variable,
+    one per record for a record variable.  KeyError when the file has no such variable."""
+    import os
+    hdr = _parse_header(fd, os.fstat(fd).st_size)
+    for v in hdr['vars']:
+        if v['name'] == name:
+            if v['record']:
+                return v, [(v['begin'] + r * hdr['recsize'], v['nbytes']) for r in range(hdr['numrecs'])]
+            return v, [(v['begin'], v['nbytes'])]
+    raise KeyError(name)
+
+
+def _file_dtype(v):
+    return v['dtype'].newbyteorder('>') if v['dtype'].itemsize > 1 else v['dtype']
+
+
+def read_variable_raw(path, name):
+    """One variable as the file holds it: (array of the variable's shape in the file's big-endian dtype - '>f4', '>i2', ...;
+    no byte swap and no decoding -, its dimension names, its attributes as stored).  Nothing else of the file is read."""
+    import os
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        v, ranges = _variable_ranges(fd, name)
+        buf = np.empty(sum(n for _, n in ranges), dtype=np.uint8)
+        pos = 0
+        for off, n in ranges:
+            if n:
+                _pread_into(fd, buf[pos:pos + n], off)
+            pos += n
+    finally:
+        os.close(fd)
+    return buf.view(_file_dtype(v)).reshape(v['shape']), v['dims'], dict(v['attrs'])
+
+
+def update_variable(path, name, values):
+    """Overwrite the data of the existing variable `name` of a NetCDF-3 file with `values`: `os.pwrite` at the offsets the
+    header gives (fixed-size and record variables), in the file's byte order - big-endian values go out as they are, native
+    ones are swapped in one pass.  `values` must have the variable's shape and its type (kind and size; either byte order).
+    Every other byte of the file stays as it was; the file is neither rewritten nor resized.  KeyError for an unknown
+    variable, ValueError for a shape or dtype that differs; nothing is written then."""
+    import os
+    values = np.asarray(values)
+    fd = os.open(path, os.O_RDWR)
+    try:
+        v, ranges = _variable_ranges(fd, name)
+        if (values.dtype.kind, values.dtype.itemsize) != (v['dtype'].kind, v['dtype'].itemsize):
+            raise ValueError('variable %s is stored as %s, got values of dtype %s' % (name, v['dtype'], values.dtype))
+        if tuple(values.shape) != tuple(v['shape']):
+            raise ValueError('variable %s has shape %s, got values of shape %s' % (name, tuple(v['shape']), tuple(values.shape)))
+        flat = np.ascontiguousarray(values).astype(_file_dtype(v), copy=False).reshape(-1).view(np.uint8)
+        pos = 0
+        for off, n in ranges:
+            mv = memoryview(flat[pos:pos + n])
+            pos += n
+            while len(mv):
+                done = os.pwrite(fd, mv, off)
+                off += done
+                mv = mv[done:]
+    finally:
+        os.close(fd)
+
+
 # ------------------------------------------------------------------------------ band-wise I/O (latency mode)
 # One ERA5 file over several ranks in latitude bands (SURVEY.md section 8e, row 2): every rank reads and writes only its
 # rows of the fields.  In the classic layout a variable (..., lat, lon) is C-ordered, so rows [j0, j1) of one (time, level)

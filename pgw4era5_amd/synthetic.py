@@ -215,6 +215,54 @@ def make_rotated_delta(nrlat=24, nrlon=48, nplev=3, ntime=2, seed=0, dtype=np.fl
     return ds
 
 
+def make_extpar(path, nrlat=7, nrlon=9, dtype=np.float32, time_axis=False, fill='_FillValue', masked_share=0.15, seed=0,
+                **grid):
+    """A small COSMO extpar file on a rotated-pole grid, as postproc_cosmo.extpar_adapt meets it: `rlat`, `rlon`, 2-D `lat` /
+    `lon` over (rlat, rlon), the scalar `char rotated_pole`, and the fields HSURF, T_CL (deep soil temperature climatology)
+    and FR_LAND - T_CL lies between two other variables in the file.  dtype: float32 or float64 for T_CL; time_axis: T_CL
+    is (time = 1, rlat, rlon) like in files written by newer extpar versions, else (rlat, rlon).  fill: which attribute(s)
+    name the value of the cells without soil (water points) - '_FillValue', 'missing_value', 'both' (two different values)
+    or None (no attribute: NetCDF's default fill value 9.969209968386869e36 stands in those cells); masked_share of the
+    cells hold it.  Returns dict(path, T_CL (the values written), masked (bool, shape of T_CL), mask_values (floats))."""
+    from . import ncio
+    if fill not in ('_FillValue', 'missing_value', 'both', None):
+        raise ValueError("fill must be '_FillValue', 'missing_value', 'both' or None")
+    rng = np.random.default_rng(seed)
+    dt = np.dtype(dtype)
+    rlat, rlon, lat, lon = rotated_pole_grid(nrlat, nrlon, **grid)
+    hsurf = 1500.0 * _smooth2d(rng, nrlat, nrlon) ** 2
+    t_cl = (284.0 - 0.0065 * hsurf - 0.4 * (lat - 45.0) + 0.5 * rng.standard_normal((nrlat, nrlon))).astype(dt)
+    values = {'_FillValue': [-1.0e20], 'missing_value': [-999.0], 'both': [-1.0e20, -999.0], None: [9.969209968386869e36]}[fill]
+    values = [float(dt.type(v)) for v in values]
+    masked = rng.random((nrlat, nrlon)) < masked_share
+    which = rng.integers(0, len(values), (nrlat, nrlon))
+    for k, v in enumerate(values):
+        t_cl[masked & (which == k)] = v
+    attrs = dict(standard_name='soil_temperature', long_name='CRU near surface temperature climatology', units='K',
+                 grid_mapping='rotated_pole')
+    if fill in ('_FillValue', 'both'):
+        attrs['_FillValue'] = dt.type(values[0])
+    if fill in ('missing_value', 'both'):
+        attrs['missing_value'] = dt.type(values[-1])
+    F = ncio.Field
+    ds = ncio.Dataset(attrs=dict(title='synthetic external parameters', source='pgw4era5_amd.synthetic'))
+    hdims = ('rlat', 'rlon')
+    if time_axis:
+        ds['time'] = F(np.array([0.0]), ('time',), attrs=dict(units='seconds since 2000-01-01 00:00:00'))
+    ds['rlat'] = F(rlat, ('rlat',), attrs=dict(units='degrees', standard_name='grid_latitude'))
+    ds['rlon'] = F(rlon, ('rlon',), attrs=dict(units='degrees', standard_name='grid_longitude'))
+    ds['lat'] = F(lat, hdims, attrs=dict(units='degrees_north', standard_name='latitude'))
+    ds['lon'] = F(lon, hdims, attrs=dict(units='degrees_east', standard_name='longitude'))
+    ds['rotated_pole'] = F(np.array(b'', dtype='S1'), (), attrs=dict(grid_mapping_name='rotated_latitude_longitude'))
+    ds['HSURF'] = F(hsurf.astype(np.float32), hdims, attrs=dict(units='m', grid_mapping='rotated_pole'))
+    if time_axis:
+        t_cl, masked = t_cl[None], masked[None]
+    ds['T_CL'] = F(t_cl, (('time',) if time_axis else ()) + hdims, attrs=attrs)
+    ds['FR_LAND'] = F((~masked).reshape(nrlat, nrlon).astype(np.float32), hdims, attrs=dict(units='1', grid_mapping='rotated_pole'))
+    ncio.to_netcdf(ds, path)
+    return dict(path=path, T_CL=t_cl.copy(), masked=masked, mask_values=values)
+
+
 def make_ocean_grid_case(nj=40, ni=60, ntime=12, seed=0, land_patches=3):
     """An ocean-model-like delta for step_02's NaN-ignoring interpolation (tos / siconc): curvilinear grid with 2-D
     `latitude` / `longitude` coordinates (a regular grid sheared and stretched so that rows are not parallels, longitudes
