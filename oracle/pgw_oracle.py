@@ -546,10 +546,12 @@ def adjust_ps_loop(ak, bk, akm, bkm, PS, FIS, T, QV, ta_pgw, hur_pgw, dzg_pref,
 
 
 def adjust_ps_loop_local_pref(ak, bk, akm, bkm, PS, FIS, T, QV, ta_pgw, hur_pgw, dzg, plev,
-                              adj_factor=ADJ_FACTOR, thresh=THRESH_PHI_REF_MAX_ERROR, max_n_iter=MAX_N_ITER):
+                              adj_factor=ADJ_FACTOR, thresh=THRESH_PHI_REF_MAX_ERROR, max_n_iter=MAX_N_ITER, trace=None):
     """The loop with p_ref_inp = None (step_03:219-253): the reference pressure is chosen per
     column and per pass as the first plev (file order) below 95 % of both surface pressures, never
-    lower in altitude than in the previous pass.  dzg (time, plev, lat, lon) [m] in file order."""
+    lower in altitude than in the previous pass.  dzg (time, plev, lat, lon) [m] in file order.
+    trace: a list that receives, per pass, dict(p_ref, idx, ps_pgw) and `cand` = the level index before min(p, p_ref_last)
+    (-1: none); a pass that finds no level for some column is recorded (with NaN / -1 there) before it raises."""
     PS = np.asarray(PS, dtype=np.float64)
     plev = np.asarray(plev, dtype=np.float64)
     level1 = np.arange(1, len(ak) + 1)
@@ -573,10 +575,13 @@ def adjust_ps_loop_local_pref(ak, bk, akm, bkm, PS, FIS, T, QV, ta_pgw, hur_pgw,
             ok = (p_min_era > plev[k]) & (p_min_pgw > plev[k])
             new = np.where(ok, plev[k], new)
             idx = np.where(ok, k, idx)
+        cand = idx
         if p_ref is not None:                                        # min(p, p_ref_last), :598
             lower = p_ref < new
             new = np.where(lower, p_ref, new)
             idx = np.where(lower, idx_last, idx)
+        if trace is not None:
+            trace.append(dict(p_ref=new.copy(), idx=idx.copy(), cand=cand.copy(), ps_pgw=ps_pgw.copy()))
         if np.any(np.isnan(new)):                                    # :245-251
             raise ValueError('No reference pressure level above the required local minimum pressure level '
                              'could not be found everywhere.')
@@ -685,14 +690,15 @@ def _zonal_mean(row):
 # whole-file restatement on arrays                                   step_03:44-381
 # ----------------------------------------------------------------------------------------
 def pgw_for_era5_arrays_reinterp(era, deltas, delta_times, plev, target_dt,
-                                 ignore_top_pressure_error=False, p_ref=P_REF_INP):
+                                 ignore_top_pressure_error=False, p_ref=P_REF_INP, adj_factor=ADJ_FACTOR):
     """pgw_for_era5 with i_reinterp = 1 (step_03:202-216, 330-343) and fixed p_ref; p_ref=None (p_ref_inp = None, the local
     reference level of :219-253): the general restatement of pgw_oracle_refdtype on float64 copies of the inputs."""
     if p_ref is None:
         from . import pgw_oracle_refdtype as R
         f = lambda v: np.asarray(v, dtype=np.float64) if isinstance(v, np.ndarray) and v.dtype.kind == 'f' else v
         return R.pgw_for_era5_arrays_reinterp({k: f(v) for k, v in era.items()}, {k: f(v) for k, v in deltas.items()},
-                                              delta_times, plev, target_dt, ignore_top_pressure_error, p_ref=None)
+                                              delta_times, plev, target_dt, ignore_top_pressure_error, p_ref=None,
+                                              adj_factor=adj_factor)
     ak, bk = era['ak'], era['bk']
     akm, bkm = era.get('akm'), era.get('bkm')
     if akm is None:
@@ -725,7 +731,7 @@ def pgw_for_era5_arrays_reinterp(era, deltas, delta_times, plev, target_dt,
         ta_pgw, hur_pgw = reinterp('ta', pa_pgw), reinterp('hur', pa_pgw)
         hus_pgw = relative_to_specific_humidity(hur_pgw, pa_pgw, ta_pgw)
         err = (integ_geopot(pa_hl_pgw, FIS, ta_pgw, hus_pgw, level1, p_ref) - phi_ref_era) - dzg * CON_G
-        adj_ps = - ADJ_FACTOR * ps_pgw / (CON_RD * ta_pgw[:, -1]) * err
+        adj_ps = - adj_factor * ps_pgw / (CON_RD * ta_pgw[:, -1]) * err
         err_max = np.nanmax(np.abs(err))
         hist.append(float(err_max))
         it += 1

@@ -298,12 +298,51 @@ def adjust_ps_loop(ak, bk, akm, bkm, PS, FIS, T, QV, ta_pgw, hur_pgw, dzg_pref,
                 phi_ref_era=phi_ref_era, phi_ref_pgw=phi_ref_pgw)
 
 
+def adjust_ps_loop_local_pref(ak, bk, akm, bkm, PS, FIS, T, QV, ta_pgw, hur_pgw, dzg, plev, adj_factor=O.ADJ_FACTOR,
+                              thresh=O.THRESH_PHI_REF_MAX_ERROR, max_n_iter=O.MAX_N_ITER):
+    """adjust_ps_loop with p_ref_inp = None (step_03:219-253, i_reinterp = 0): the reference level of every column is chosen
+    in every pass (local_p_ref below) from the float64 half-level pressures of both states (float32 PS / ps_pgw times the
+    float64 bk), and the zg delta - dzg (time, plev, lat, lon) in file order, float64 when it was interpolated in time - is
+    taken at that level (:292-295).  The dtype flow of delta_ps / ps_pgw / phi_hl is adjust_ps_loop's."""
+    PS, FIS, T, QV = _a(PS), _a(FIS), _a(T), _a(QV)
+    ta_pgw, hur_pgw, dzg = _a(ta_pgw), _a(hur_pgw), _a(dzg)
+    plev = np.asarray(plev, dtype=np.float64)
+    level1 = np.arange(1, len(ak) + 1)
+    pa_hl_era, _ = hybrid_pressure(ak, bk, PS, akm, bkm)
+    delta_ps = np.zeros_like(PS)                                        # :182
+    adj_ps = np.zeros_like(PS)                                          # :184
+    phi_ref_max_error = np.inf
+    it = 1
+    hist = []
+    p_ref, idx = None, None
+    n_lowest = ta_pgw.shape[1] - 1
+    while phi_ref_max_error > thresh:
+        np.add(delta_ps, adj_ps, out=delta_ps, casting='same_kind')     # :192
+        ps_pgw = PS + delta_ps                                          # :193
+        pa_hl_pgw, pa_pgw = hybrid_pressure(ak, bk, ps_pgw, akm, bkm)   # :196-199
+        p_ref, idx = local_p_ref(pa_hl_era, pa_hl_pgw, plev, p_ref, idx)             # :219-253
+        hus_pgw = relative_to_specific_humidity(hur_pgw, pa_pgw, ta_pgw)             # :262-266
+        phi_ref_pgw = integ_geopot(pa_hl_pgw, FIS, ta_pgw, hus_pgw, level1, p_ref)   # :269-276
+        phi_ref_era = integ_geopot(pa_hl_era, FIS, T, QV, level1, p_ref)             # :280-287
+        climate_delta_phi_ref = np.take_along_axis(dzg * CON_G, idx[:, None], axis=1)[:, 0]   # :292-295
+        phi_ref_error = (phi_ref_pgw - phi_ref_era) - climate_delta_phi_ref          # :289, :298
+        adj_ps = - adj_factor * ps_pgw / (CON_RD * ta_pgw[:, n_lowest]) * phi_ref_error   # :301-304
+        a = np.abs(phi_ref_error)
+        phi_ref_max_error = np.nanmax(a) if not np.all(np.isnan(a)) else np.nan       # :308
+        hist.append(float(phi_ref_max_error))
+        it += 1
+        if it > max_n_iter:                                             # :313-319
+            raise ValueError('ERROR! Pressure adjustment did not converge')
+    return dict(ps_pgw=ps_pgw, hus_pgw=hus_pgw, delta_ps=delta_ps, n_iter=it - 1, max_err=hist, p_ref=p_ref)
+
+
 # ----------------------------------------------------------------------------------------
 # whole file                                                              step_03:44-381
 # ----------------------------------------------------------------------------------------
 def pgw_for_era5_arrays(era, deltas, delta_times, plev, target_dt, ignore_top_pressure_error=False,
-                        p_ref=O.P_REF_INP):
-    """pgw_oracle.pgw_for_era5_arrays with the reference's dtype flow (i_reinterp = 0, fixed p_ref).
+                        p_ref=O.P_REF_INP, adj_factor=O.ADJ_FACTOR):
+    """pgw_oracle.pgw_for_era5_arrays with the reference's dtype flow (i_reinterp = 0; p_ref fixed, or None for
+    p_ref_inp = None, step_03:219-253).
     Outputs carry the dtypes the reference writes: PS, T_SKIN, T_SO, FR_SEA_ICE in the file dtype (in-place
     updates / float32 sums), T, QV, U, V float64 whenever a float64 operand took part (era + delta, step_03:170-173)."""
     ak, bk = _a(era['ak']), _a(era['bk'])
@@ -343,11 +382,16 @@ def pgw_for_era5_arrays(era, deltas, delta_times, plev, target_dt, ignore_top_pr
         dsfc, psh = (ld(var + 's'), ld('ps_hist')) if var in ('ta', 'hur') else (None, None)
         pgw[var] = era_fields[var] + vert_interp_delta(d, plev, pa_era, dsfc, psh, ignore_top_pressure_error)
     plev = np.asarray(plev, dtype=np.float64)
-    kref = np.nonzero(plev == p_ref)[0]
-    if len(kref) != 1:
-        raise KeyError(p_ref)
-    dzg = ld('zg')[:, kref[0]]                                            # :292-295
-    res = adjust_ps_loop(ak, bk, akm, bkm, PS, _a(era['FIS']), T, QV, pgw['ta'], pgw['hur'], dzg, p_ref=p_ref)
+    if p_ref is None:                                                    # p_ref_inp = None, :219-253
+        res = adjust_ps_loop_local_pref(ak, bk, akm, bkm, PS, _a(era['FIS']), T, QV, pgw['ta'], pgw['hur'], ld('zg'), plev,
+                                        adj_factor=adj_factor)
+    else:
+        kref = np.nonzero(plev == p_ref)[0]
+        if len(kref) != 1:
+            raise KeyError(p_ref)
+        dzg = ld('zg')[:, kref[0]]                                        # :292-295
+        res = adjust_ps_loop(ak, bk, akm, bkm, PS, _a(era['FIS']), T, QV, pgw['ta'], pgw['hur'], dzg, p_ref=p_ref,
+                             adj_factor=adj_factor)
     out.update(PS=res['ps_pgw'], T=pgw['ta'], QV=res['hus_pgw'], U=pgw['ua'], V=pgw['va'],
                n_iter=res['n_iter'], max_err=res['max_err'], RELHUM_pgw=pgw['hur'])
     return out
