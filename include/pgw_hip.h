@@ -414,6 +414,53 @@ typedef struct pgw_file_args {
  * The two give the same bits, pass counts, histories and error reports. */
 int pgw_step03_file(pgw_ctx *ctx, pgw_file_args *args);
 
+/* The record bracketing of load_delta (functions.py:224-283) on integer seconds since 1970-01-01 - host arithmetic only,
+ * no HIP call.  times_s[n]: the stamps of one delta file; target_s: the instant of the ERA5 file.
+ *  - the LAST stamp that is a Feb 29 is dropped (:224-230): *dropped = its index, -1 when there is none;
+ *  - every kept stamp is re-yeared to the target's year (:235-238): first second of (year, the stamp's month) + the stamp's
+ *    offset within its month, so a remaining Feb 29 rolls into March in a non-leap year;
+ *  - *ind_before = the last kept stamp <= target, *ind_after = the first kept stamp >= target (:242-243, :262-263), both as
+ *    indices into the KEPT stamps (record index = i + (dropped >= 0 && i >= dropped)); when there is no stamp at or before
+ *    the target the last kept stamp re-yeared to year - 1 stands in (:253-258), when there is none at or after it the first
+ *    one re-yeared to year + 1 (:273-278);
+ *  - *x_hi = (double)(after - before), *x_new = (double)(target - before) in nanoseconds, the int64 differences cast as
+ *    Python's float(int) rounds them; both 0.0 when *ind_before == *ind_after (:282-283).
+ * PGW_ERR_ARG: a NULL pointer, n < 1, or no stamp kept. */
+int pgw_delta_bracket(const long long *times_s, int n, long long target_s, int *ind_before, int *ind_after, double *x_hi,
+                      double *x_new, int *dropped);
+
+/* What pgw_step03_file needs for a file, split into what stays from file to file and what the instant decides.  A plain
+ * struct the caller owns and fills (the library keeps no copy and allocates nothing for it): ERA5 and output pointers, shapes,
+ * tables and loop controls in `args`; for every delta variable whose record array is resident on the device, where its records
+ * lie and which time axis brackets them.  pgw_step03_file_at then costs the host one call per file. */
+#define PGW_PLAN_MAX_AXES 8
+enum pgw_plan_var_id {
+    PGW_PV_TA = 0, PGW_PV_HUR, PGW_PV_UA, PGW_PV_VA, PGW_PV_TAS, PGW_PV_HURS, PGW_PV_PS_HIST,   /* the quad group: ta's axis */
+    PGW_PV_ZG, PGW_PV_SICONC, PGW_PV_TS, PGW_PV_TOS,                                           /* bracketed on their own */
+    PGW_PV_COUNT
+};
+typedef struct pgw_plan_var {
+    const void *base;          /* device, record 0 of the resident array [nrec, ...]; NULL: the template's pointers stay */
+    long long rec_bytes;       /* bytes from one record to the next */
+    long long ref_offset;      /* zg with a fixed p_ref: bytes from a record's start to its plev == p_ref slab; else 0 */
+    int axis;                  /* index into axis_times */
+    int _pad;
+} pgw_plan_var;
+typedef struct pgw_file_plan {
+    pgw_file_args args;        /* template: every field that does not depend on the instant (per_var_time must be 1) */
+    int n_axes, _pad;
+    const long long *axis_times[PGW_PLAN_MAX_AXES];   /* host, seconds since 1970-01-01, one entry per distinct time axis */
+    int axis_len[PGW_PLAN_MAX_AXES];
+    pgw_plan_var var[PGW_PV_COUNT];
+} pgw_file_plan;
+
+/* pgw_step03_file for the instant `target_s`: *filled = plan->args; every axis bracketed once (pgw_delta_bracket); the `_b` /
+ * `_a` record pointers of every variable with a base; x_hi / x_new from ta's axis (the whole quad group must share it);
+ * zg_x_*, siconc_x_*, ts_x_*, tos_x_* from each variable's own; zg into zg3_b / zg3_a when args.local_p_ref, else zg_b / zg_a
+ * at ref_offset; then pgw_step03_file(ctx, filled).  *filled carries the results (n_iter, max_err_hist, levels_touched,
+ * passes_launched) and shows what the call was made with. */
+int pgw_step03_file_at(pgw_ctx *ctx, const pgw_file_plan *plan, long long target_s, pgw_file_args *filled);
+
 /* ---------------------------------------------------------------- step_02 regridding - */
 /* a10 regrid_lat_lon, xarray branch (functions.py:774-789, 817-893): separable linear
  * interpolation, latitude first then longitude, on tables the host derives from the

@@ -126,6 +126,26 @@ class FileArgs(C.Structure):
 
 
 SIGNATURES['pgw_step03_file'] = (_i, [_vp, C.POINTER(FileArgs)])
+
+# enum pgw_plan_var_id: the delta variables of a file plan, in the order of pgw_file_plan.var
+PLAN_MAX_AXES = 8
+PLAN_VARS = ('ta', 'hur', 'ua', 'va', 'tas', 'hurs', 'ps_hist', 'zg', 'siconc', 'ts', 'tos')
+PLAN_QUAD_GROUP = 7                      # the first seven are interpolated together, on ta's axis
+
+
+class PlanVar(C.Structure):
+    """`pgw_plan_var` of include/pgw_hip.h."""
+    _fields_ = [('base', C.c_void_p), ('rec_bytes', C.c_longlong), ('ref_offset', C.c_longlong), ('axis', C.c_int), ('_pad', C.c_int)]
+
+
+class FilePlan(C.Structure):
+    """`pgw_file_plan` of include/pgw_hip.h (pgw_step03_file_at)."""
+    _fields_ = [('args', FileArgs), ('n_axes', C.c_int), ('_pad', C.c_int), ('axis_times', C.POINTER(C.c_longlong) * PLAN_MAX_AXES),
+                ('axis_len', C.c_int * PLAN_MAX_AXES), ('var', PlanVar * len(PLAN_VARS))]
+
+
+SIGNATURES['pgw_delta_bracket'] = (_i, [C.POINTER(_ll), _i, _ll, _ip, _ip, _dp, _dp, _ip])
+SIGNATURES['pgw_step03_file_at'] = (_i, [_vp, C.POINTER(FilePlan), _ll, C.POINTER(FileArgs)])
 REDUCE_MAX_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)      # pgw_reduce_max_fn
 SIGNATURES['pgw_set_reduce_hook'] = (_i, [_vp, REDUCE_MAX_FN, _vp])
 SIGNATURES['pgw_test_log'] = (_i, [_vp, _ll, _vp, _vp])

@@ -2005,6 +2005,116 @@ extern "C" int pgw_step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     return (rc != PGW_OK && ctx->reduce_fn) ? band_fail(ctx, rc, a ? a->max_n_iter : 1) : rc;
 }
 
+// ------------------------------------------------------------------ record bracketing on the host (functions.py:224-283)
+// Civil dates of the proleptic Gregorian calendar from days since 1970-01-01 and back (the usual era-of-400-years pair);
+// floor semantics before 1970 like numpy's datetime64 casts.
+static long long floor_div(long long a, long long b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0))); }
+
+static long long days_from_civil(long long y, int m, int d) {
+    y -= m <= 2;
+    const long long era = floor_div(y, 400);
+    const long long yoe = y - era * 400;
+    const long long doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
+    const long long doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+    return era * 146097 + doe - 719468;
+}
+
+static void civil_from_days(long long z, long long *y, int *m, int *d) {
+    z += 719468;
+    const long long era = floor_div(z, 146097);
+    const long long doe = z - era * 146097;
+    const long long yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
+    const long long doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
+    const long long mp = (5 * doy + 2) / 153;
+    *d = (int)(doy - (153 * mp + 2) / 5 + 1);
+    *m = (int)(mp < 10 ? mp + 3 : mp - 9);
+    *y = yoe + era * 400 + (*m <= 2);
+}
+
+// `dt64_to_dt(t).replace(year=year)` as the array form states it: first second of (year, month of t) + offset of t in its month
+static long long reyear(long long t, long long year) {
+    long long y; int m, d;
+    civil_from_days(floor_div(t, 86400), &y, &m, &d);
+    return days_from_civil(year, m, 1) * 86400 + (t - days_from_civil(y, m, 1) * 86400);
+}
+
+extern "C" int pgw_delta_bracket(const long long *times_s, int n, long long target_s, int *ind_before, int *ind_after,
+                                 double *x_hi, double *x_new, int *dropped) {
+    if (!times_s || !ind_before || !ind_after || !x_hi || !x_new || !dropped || n < 1) return PGW_ERR_ARG;
+    int leap = -1;                                                  // :224-230: the LAST Feb 29 found is dropped
+    for (int i = 0; i < n; ++i) {
+        long long y; int m, d;
+        civil_from_days(floor_div(times_s[i], 86400), &y, &m, &d);
+        if (m == 2 && d == 29) leap = i;
+    }
+    const int nk = n - (leap >= 0);
+    if (nk < 1) return PGW_ERR_ARG;
+    long long year; int tm, td;
+    civil_from_days(floor_div(target_s, 86400), &year, &tm, &td);
+    int ib = -1, ia = -1, k = 0;
+    long long tb = 0, ta = 0, first = 0, last = 0;
+    for (int i = 0; i < n; ++i) {
+        if (i == leap) continue;
+        const long long ty = reyear(times_s[i], year);              // :235-238
+        if (k == 0) first = ty;
+        last = ty;
+        if (ty <= target_s) { ib = k; tb = ty; }                    // :242-243: the last one at or before
+        if (ty >= target_s && ia < 0) { ia = k; ta = ty; }          // :262-263: the first one at or after
+        ++k;
+    }
+    if (ib < 0) { ib = nk - 1; tb = reyear(last, year - 1); }       // :253-258
+    if (ia < 0) { ia = 0; ta = reyear(first, year + 1); }           // :273-278
+    *ind_before = ib; *ind_after = ia; *dropped = leap;
+    if (ib == ia) { *x_hi = 0.0; *x_new = 0.0; }                    // :282-283
+    else {
+        *x_hi = (double)((ta - tb) * 1000000000LL);
+        *x_new = (double)((target_s - tb) * 1000000000LL);
+    }
+    return PGW_OK;
+}
+
+// ------------------------------------------------------------------ whole file from a plan
+extern "C" int pgw_step03_file_at(pgw_ctx *ctx, const pgw_file_plan *plan, long long target_s, pgw_file_args *filled) {
+    if (!ctx) return PGW_ERR_ARG;
+    NEED(ctx, plan != nullptr && filled != nullptr, "null plan or args");
+    NEED(ctx, plan->n_axes >= 1 && plan->n_axes <= PGW_PLAN_MAX_AXES, "bad number of time axes");
+    NEED(ctx, plan->args.per_var_time != 0, "the plan's template must have per_var_time = 1");
+    struct { int ib, ia; double x_hi, x_new; } br[PGW_PLAN_MAX_AXES];
+    for (int i = 0; i < plan->n_axes; ++i) {
+        int ib, ia, drop;
+        NEED(ctx, pgw_delta_bracket(plan->axis_times[i], plan->axis_len[i], target_s, &ib, &ia, &br[i].x_hi, &br[i].x_new,
+                                    &drop) == PGW_OK, "time axis without a usable stamp");
+        br[i].ib = ib + (drop >= 0 && ib >= drop);                  // kept index -> record
+        br[i].ia = ia + (drop >= 0 && ia >= drop);
+    }
+    *filled = plan->args;
+    pgw_file_args *a = filled;
+    const void **slot_b[PGW_PV_COUNT] = {&a->ta_b, &a->hur_b, &a->ua_b, &a->va_b, &a->tas_b, &a->hurs_b, &a->pshist_b,
+                                         a->local_p_ref ? &a->zg3_b : &a->zg_b, &a->siconc_b, &a->ts_b, &a->tos_b};
+    const void **slot_a[PGW_PV_COUNT] = {&a->ta_a, &a->hur_a, &a->ua_a, &a->va_a, &a->tas_a, &a->hurs_a, &a->pshist_a,
+                                         a->local_p_ref ? &a->zg3_a : &a->zg_a, &a->siconc_a, &a->ts_a, &a->tos_a};
+    double *own_hi[PGW_PV_COUNT] = {}, *own_new[PGW_PV_COUNT] = {};  // abscissae of the variables bracketed on their own
+    own_hi[PGW_PV_ZG] = &a->zg_x_hi;         own_new[PGW_PV_ZG] = &a->zg_x_new;
+    own_hi[PGW_PV_SICONC] = &a->siconc_x_hi; own_new[PGW_PV_SICONC] = &a->siconc_x_new;
+    own_hi[PGW_PV_TS] = &a->ts_x_hi;         own_new[PGW_PV_TS] = &a->ts_x_new;
+    own_hi[PGW_PV_TOS] = &a->tos_x_hi;       own_new[PGW_PV_TOS] = &a->tos_x_new;
+    const pgw_plan_var *ta = &plan->var[PGW_PV_TA];
+    NEED(ctx, ta->base != nullptr, "the plan has no ta records");
+    for (int v = 0; v < PGW_PV_COUNT; ++v) {
+        const pgw_plan_var *pv = &plan->var[v];
+        if (!pv->base) continue;
+        NEED(ctx, pv->axis >= 0 && pv->axis < plan->n_axes, "variable on an axis the plan does not have");
+        NEED(ctx, v > PGW_PV_PS_HIST || pv->axis == ta->axis, "the quad group must share ta's time axis");
+        const char *base = (const char *)pv->base + (a->local_p_ref ? 0 : pv->ref_offset);
+        *slot_b[v] = base + (long long)br[pv->axis].ib * pv->rec_bytes;
+        *slot_a[v] = base + (long long)br[pv->axis].ia * pv->rec_bytes;
+        if (own_hi[v]) { *own_hi[v] = br[pv->axis].x_hi; *own_new[v] = br[pv->axis].x_new; }
+    }
+    a->x_hi = br[ta->axis].x_hi;
+    a->x_new = br[ta->axis].x_new;
+    return pgw_step03_file(ctx, a);
+}
+
 static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     NEED(ctx, a != nullptr, "null args");
     const int dtype = a->dtype, ntime = a->ntime;

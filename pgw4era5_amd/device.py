@@ -6,6 +6,7 @@ device buffer.  Arrays stay in HBM between calls (288 GB per MI355X: a whole 0.2
 its PGW state and all twelve months of every delta fit many times over), host<->device copies
 happen only at the edges (`Context.to_device`, `DeviceArray.numpy`).
 """
+import collections
 import ctypes as C
 import os
 
@@ -357,7 +358,9 @@ class Context:
         self.device = int(device) % n.value
         self._live = 0
         self._levels_key = None
-        self._reduce_cb = None                  # keeps the ctypes callback of set_reduce_hook alive
+        self._file_plans = collections.OrderedDict()    # step_03's file plans of this context, least recently used first
+        self._last_file_args = None             # the pgw_file_args of the last file call (tests compare the two host paths)
+        self._reduce_cb = None                 # keeps the ctypes callback of set_reduce_hook alive
         self._side = {}
         self._reduce_exc = None
 

@@ -67,6 +67,13 @@ function_dtype_flow = 'common'
 # reference's either way.
 f32_out_dtype = 'float64'
 
+# The host side of a file call.  True: process_file_device keeps, per context, a plan of everything that stays the same from file
+# to file (pointers, shapes, tables, loop controls) and the library brackets the delta records for the instant itself
+# (pgw_step03_file_at): one C call per file.  False: the argument struct is put together in Python for every file, as it is
+# anyway whenever the plan does not cover the call (delta records not all resident, a member of the ta group on another time
+# axis, keep_hur, an instant with a sub-second part).  `PGW_FILE_PLAN=0` / `=1` overrides.  No influence on any result.
+file_plan = True
+
 # Placement of the level arrays (T, QV, U, V in and out, the vapour-pressure workspace) in the card's memory.  'spread': the
 # context draws them so that half lie in one stretch of physical memory and half in another (device.SpreadPool; the quad
 # kernel runs 12 % faster than with all of them in one stretch, which is what consecutive hipMallocs give; DESIGN.md section

@@ -312,10 +312,32 @@ def process_file_device(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure
     come back as float64 arrays like the reference's `era + delta`.  i_reinterp: settings.i_reinterp = 1 (step_03:202-216,
     330-343: ta / hur and their deltas re-interpolated onto the current levels in every pass, ua / va after convergence) - the
     same call with `pgw_file_args.i_reinterp` set, every combination with the reference level and the storage modes.
-    Returns (dict of DeviceArrays, info)."""
-    lib, h = ctx.lib, ctx.handle
+    Returns (dict of DeviceArrays, info).
+
+    Host side: with settings.file_plan (default) and reused `out` buffers, everything but the instant comes from a plan kept on
+    the context and the library brackets the delta records itself (`pgw_step03_file_at`, _process_file_planned); otherwise, and
+    wherever the plan does not cover the call, the argument struct is put together here for every file (_file_args)."""
     if p_ref is None:
         p_ref = S.p_ref_inp
+    ref = ref_dtype_mode(deltas.dtype, ref_dtype)
+    if out is not None and not keep_hur and _file_plan_on():
+        done = _process_file_planned(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p_ref, out, ref, i_reinterp)
+        if done is not None:
+            return done
+    a, _held, out = _file_args(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p_ref, out, keep_hur, ref, i_reinterp)
+    ctx._last_file_args = a
+    ctx._check(ctx.lib.pgw_step03_file(ctx.handle, C.byref(a)))
+    return out, _file_info(a)
+
+
+def _file_info(a):
+    return dict(n_iter=a.n_iter, max_err=a.max_err_hist[:min(a.n_iter, 32)],
+                levels_touched=int(a.levels_touched), passes_launched=int(a.passes_launched))
+
+
+def _file_args(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p_ref, out, keep_hur, ref, i_reinterp):
+    """The `pgw_file_args` of one file put together on the host: every delta variable bracketed on its own time axis, output
+    buffers drawn into `out` where they are missing.  Returns (args, what the args point into, out)."""
     local_p_ref = (p_ref is None) or (p_ref == 'local')          # settings.p_ref_inp = None, step_03:219-253
     dt = deltas.dtype
     ctx.set_levels(coeffs['ak'], coeffs['bk'], coeffs.get('akm'), coeffs.get('bkm'))
@@ -326,7 +348,6 @@ def process_file_device(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure
         # the file the reference fails in vert_interp_delta -> interp_logp_4d (functions.py:457-459)
         raise ValueError('Time dimension of input files is inconsistent!')
     out = {} if out is None else out
-    ref = ref_dtype_mode(dt, ref_dtype)
     dt4 = np.dtype('float64') if ref else dt                        # era (float32) + delta (float64), step_03:170-173
 
     def buf(name, shape, dtype=dt):
@@ -368,9 +389,10 @@ def process_file_device(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure
         held += [b_, a_]
         setattr(a, name + '_b', b_.ptr)
         setattr(a, name + '_a', a_.ptr)
-    soil = None
+    held += [zb, za, plev]
     if 'FR_SEA_ICE' in era and 'siconc' in deltas:                  # surface riders, step_03:103-146
         soil = np.ascontiguousarray(coeffs['soil1'], dtype=np.float64)
+        held.append(soil)
         a.nsoil = len(soil)
         a.soil_depth = soil.ctypes.data_as(_dp)
         for k in ('T_SKIN', 'T_SO', 'FR_LAND', 'FR_SEA_ICE'):
@@ -391,10 +413,129 @@ def process_file_device(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure
         setattr(a, k + '_out', buf(k, T.shape, dt4).ptr)
     if keep_hur:
         a.hur_pgw_out = buf('_hur_pgw', T.shape, dt4).ptr
-    ctx._check(lib.pgw_step03_file(h, C.byref(a)))
-    info = dict(n_iter=a.n_iter, max_err=[a.max_err_hist[i] for i in range(min(a.n_iter, 32))],
-                levels_touched=int(a.levels_touched), passes_launched=int(a.passes_launched))
-    return out, info
+    return a, held, out
+
+
+# ----------------------------------------------------------------------------------------
+# the file call from a plan: what stays from file to file is put together once per context
+# ----------------------------------------------------------------------------------------
+_ERA_NAMES = ('PS', 'FIS', 'T', 'QV', 'U', 'V', 'T_SKIN', 'T_SO', 'FR_LAND', 'FR_SEA_ICE')
+_OUT_NAMES = ('PS', 'T', 'QV', 'U', 'V', 'T_SKIN', 'T_SO', 'FR_SEA_ICE')
+_EPOCH = _dt.datetime(1970, 1, 1)
+FILE_PLANS_KEPT = 8
+
+
+def _file_plan_on():
+    env = os.environ.get('PGW_FILE_PLAN')
+    return bool(S.file_plan) if env is None else env != '0'
+
+
+def _whole_seconds(t):
+    """Seconds since 1970-01-01 of an instant without a sub-second part and without a time zone, else None."""
+    if type(t) is _dt.datetime:
+        if t.tzinfo is not None or t.microsecond:
+            return None
+        d = t - _EPOCH
+        return d.days * 86400 + d.seconds
+    try:
+        t64 = np.datetime64(t)
+        s = t64.astype('datetime64[s]')
+        if np.isnat(s) or s != t64:
+            return None
+        return int(s.astype(np.int64))
+    except (TypeError, ValueError):
+        return None
+
+
+def _array_key(arrays, names):
+    return tuple([None if v is None else (v.ptr, v.shape, v.dtype) for v in map(arrays.get, names)])
+
+
+class _FilePlan:
+    """A `pgw_file_plan` and what it points into: the record arrays (through the DeltaSet), plev, soil1, the time axes."""
+
+    def __init__(self, plan, deltas, held):
+        self.plan, self.deltas, self.held = plan, deltas, held      # plan None: these arguments take the host-built struct
+        self.ref = None if plan is None else C.byref(plan)
+
+
+def _make_file_plan(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p_ref, out, ref, i_reinterp):
+    """The plan of this call, or None where the plan does not cover it: delta records not all resident, a member of the ta
+    group on another time axis (it needs the pgw_time_lerp pre-pass of DeltaSet.pair_on_axis_of), anything _file_args
+    refuses.  The template is the struct _file_args builds for this instant: the two host paths cannot drift apart."""
+    riders = 'FR_SEA_ICE' in era and 'siconc' in deltas
+    used = _lib.PLAN_VARS if riders else _lib.PLAN_VARS[:_lib.PLAN_QUAD_GROUP + 1]
+    if any(var not in deltas.dev for var in used):
+        return None
+    if not all(deltas.same_axis(var) for var in _lib.PLAN_VARS[:_lib.PLAN_QUAD_GROUP]):
+        return None
+    if era['T'].shape[0] != 1:
+        return None
+    local_p_ref = (p_ref is None) or (p_ref == 'local')
+    zg = deltas.dev['zg']
+    if local_p_ref:
+        if len(deltas.plev_zg) != len(deltas.plev) or np.any(deltas.plev_zg != deltas.plev):
+            return None
+        ref_offset = 0
+    else:
+        kref = np.nonzero(deltas.plev_zg == p_ref)[0]
+        if len(kref) != 1:
+            return None
+        ref_offset = int(kref[0]) * (zg.nbytes // (zg.shape[0] * zg.shape[1]))
+    a, held, _ = _file_args(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p_ref, out, False, ref, i_reinterp)
+    plan = _lib.FilePlan()
+    plan.args = a
+    axes = {}
+    for i, var in enumerate(used):                                  # `used` is a prefix of PLAN_VARS: i is the pgw_plan_var_id
+        arr, ax = deltas.dev[var], deltas._axis_of[var]
+        if ax not in axes:
+            if len(axes) == _lib.PLAN_MAX_AXES:
+                return None
+            t = np.ascontiguousarray(deltas._axes[ax].astype('datetime64[s]').astype(np.int64))
+            held.append(t)
+            plan.axis_times[len(axes)] = t.ctypes.data_as(C.POINTER(C.c_longlong))
+            plan.axis_len[len(axes)] = len(t)
+            axes[ax] = len(axes)
+        pv = plan.var[i]
+        pv.base, pv.rec_bytes, pv.axis = arr.ptr, arr.nbytes // arr.shape[0], axes[ax]
+        pv.ref_offset = ref_offset if var == 'zg' else 0
+    plan.n_axes = len(axes)
+    return _FilePlan(plan, deltas, held)
+
+
+def _process_file_planned(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p_ref, out, ref, i_reinterp):
+    """process_file_device through the context's plan for these arguments: one C call.  None where the plan does not cover the
+    call.  The key holds every value the template was built from (tests change `settings` between calls); the plans live on
+    the Context, a few of them, least recently used dropped first (the command-line pipeline rotates a few buffer sets)."""
+    target_s = _whole_seconds(target_dt)
+    if target_s is None:
+        return None
+    soil1 = coeffs.get('soil1')
+
+    def key_now():
+        return (id(deltas), deltas.dtype, _array_key(era, _ERA_NAMES), _array_key(out, _OUT_NAMES), p_ref, ref, bool(i_reinterp),
+                bool(ignore_top_pressure_error), S.max_n_iter, S.adj_factor, S.thresh_phi_ref_max_error,
+                None if soil1 is None else np.asarray(soil1, dtype=np.float64).tobytes())
+
+    plans = ctx._file_plans
+    key = key_now()
+    ent = plans.get(key)
+    if ent is None or ent.deltas is not deltas:
+        ent = (_make_file_plan(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p_ref, out, ref, i_reinterp)
+               or _FilePlan(None, deltas, None))
+        plans.pop(key, None)
+        plans[key_now()] = ent                                      # the output buffers may have been drawn just now
+        while len(plans) > FILE_PLANS_KEPT:
+            plans.popitem(last=False)
+    else:
+        plans.move_to_end(key)
+    if ent.plan is None:
+        return None
+    ctx.set_levels(coeffs['ak'], coeffs['bk'], coeffs.get('akm'), coeffs.get('bkm'))
+    a = _lib.FileArgs()
+    ctx._last_file_args = a
+    ctx._check(ctx.lib.pgw_step03_file_at(ctx.handle, ent.ref, target_s, C.byref(a)))
+    return out, _file_info(a)
 
 
 def process_file_device_reinterp(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error=False,
