@@ -481,6 +481,21 @@ int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, i
                         const int *lon_oob,
                         int south_row, int north_row, void *out);
 
+/* a10 with point-wise targets (functions.py:812-893 where `targ_lat` / `targ_lon` are 2-D over shared dimensions, or 1-D
+ * over one shared dimension: `.interp({lat: targ_lat})` then `.interp({lon: targ_lon})` is xarray's point-wise
+ * interpolation): every target g has its own latitude and its own longitude bracket.  Same arithmetic, same order and
+ * the same pole values as pgw_regrid_bilinear - a mesh handed over as points gives the same bits.
+ *  src (nfield, nlat_s, nlon_s) DEVICE; out (nfield, ntarg) DEVICE; the nine tables HOST, length ntarg, uploaded here:
+ *  lat_lo / lat_hi / lat_dx / lat_Dx and lon_lo / lon_hi / lon_dx / lon_Dx as above, per target; oob != 0 (lat_oob | lon_oob)
+ *  -> NaN, the target's other entries are not read.  A NaN dx (NaN target coordinate) or a NaN corner gives NaN.
+ *  PGW_ERR_ARG before anything is uploaded or launched for: nfield < 1, ntarg < 1, a source grid below 2 x 2, a null
+ *  pointer, a non-oob lat index outside [-1, nlat_s] or lon index outside [0, nlon_s), a pole row named while south_row /
+ *  north_row < 0.  One target per lane.  Timed under PGW_K_REGRID. */
+int pgw_regrid_points(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, long long ntarg, const void *src,
+                      const int *lat_lo, const int *lat_hi, const double *lat_dx, const double *lat_Dx,
+                      const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
+                      const int *oob, int south_row, int north_row, void *out);
+
 /* regrid_lat_lon, xESMF branch (functions.py:797-810, settings.py:117-129): what `xe.Regridder(ds_in, ds_era5, "bilinear",
  * periodic=periodic_lon)` (:799-800) asks ESMF for and `regridder(ds_in[var_name])` (:802) applies, for source grids with
  * 2-D coordinates (rotated-pole, curvilinear).  Bilinear on the unit sphere in 3-D Cartesian space, cell edges being chords;

@@ -182,6 +182,8 @@ SIGNATURES['pgw_surface_deltas'] = (_i, [_vp, _i, _i, _i, _ll, _i, _dp, _vp, _vp
 # regrid_lat_lon's xESMF branch: locate once per grid pair, apply per variable
 SIGNATURES['pgw_bilinear_locate'] = (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_ll)])
 SIGNATURES['pgw_regrid_sparse'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _vp, _vp, _i, _vp])
+# regrid_lat_lon's default branch onto point-wise targets (2-D lat / lon): host tables of length ntarg
+SIGNATURES['pgw_regrid_points'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _ip, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _i, _i, _vp])
 # hydrostatic check (check_geopot.py): integ_geopot on a level list, per-level statistics
 SIGNATURES['pgw_geopot_on_plev'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _dp] + [_vp] * 7 + [_i, _vp, _vp, _d, _d, _d, _i, _vp,
                                          C.POINTER(_ll)])

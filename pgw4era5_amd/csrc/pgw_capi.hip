@@ -2553,6 +2553,67 @@ extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, in
     return PGW_OK;
 }
 
+// regrid_lat_lon, xarray branch with point-wise targets (functions.py:812-893 with 2-D targ_lat / targ_lon)
+extern "C" int pgw_regrid_points(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, long long ntarg, const void *src,
+                                 const int *lat_lo, const int *lat_hi, const double *lat_dx, const double *lat_Dx, const int *lon_lo,
+                                 const int *lon_hi, const double *lon_dx, const double *lon_Dx, const int *oob, int south_row,
+                                 int north_row, void *out) {
+    NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
+    NEED(ctx, nfield >= 1 && ntarg >= 1 && ntarg < (1ll << 29), "nfield >= 1 and ntarg in [1, 2^29)");
+    NEED(ctx, nlat_s >= 2 && nlon_s >= 2 && (long long)nlat_s * nlon_s < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
+    NEED(ctx, src && out && lat_lo && lat_hi && lat_dx && lat_Dx && lon_lo && lon_hi && lon_dx && lon_Dx && oob, "null pointer");
+    NEED(ctx, ((uintptr_t)src % elem_size(dtype)) == 0 && ((uintptr_t)out % elem_size(dtype)) == 0, "pointers must be element-aligned");
+    NEED(ctx, south_row < nlat_s && north_row < nlat_s, "bad pole row");
+    for (long long g = 0; g < ntarg; ++g) {
+        if (oob[g]) continue;
+        NEED(ctx, lat_lo[g] >= -1 && lat_lo[g] <= nlat_s && lat_hi[g] >= -1 && lat_hi[g] <= nlat_s, "lat index out of range");
+        NEED(ctx, lon_lo[g] >= 0 && lon_lo[g] < nlon_s && lon_hi[g] >= 0 && lon_hi[g] < nlon_s, "lon index out of range");
+        // a pole row is only there when its zonal mean is taken (pgw_regrid_bilinear)
+        NEED(ctx, south_row >= 0 || (lat_lo[g] != -1 && lat_hi[g] != -1), "south-pole row in the tables but south_row < 0");
+        NEED(ctx, north_row >= 0 || (lat_lo[g] != nlat_s && lat_hi[g] != nlat_s), "north-pole row in the tables but north_row < 0");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // tables -> device workspace slot 3: [4 double tables][pole][5 int tables]
+    const size_t n = (size_t)ntarg;
+    const size_t td = sizeof(double) * 4 * n, tp = sizeof(double) * 2 * (size_t)nfield, ti = sizeof(int) * 5 * n;
+    void *tab = nullptr;
+    int rc = ws_get(ctx, 3, td + tp + ti + 64, &tab);
+    if (rc) return rc;
+    std::vector<char> h(td + ti);
+    double *hd = (double *)h.data();
+    memcpy(hd, lat_dx, 8 * n); memcpy(hd + n, lat_Dx, 8 * n); memcpy(hd + 2 * n, lon_dx, 8 * n); memcpy(hd + 3 * n, lon_Dx, 8 * n);
+    int *hi = (int *)(h.data() + td);
+    memcpy(hi, lat_lo, 4 * n); memcpy(hi + n, lat_hi, 4 * n); memcpy(hi + 2 * n, lon_lo, 4 * n); memcpy(hi + 3 * n, lon_hi, 4 * n);
+    memcpy(hi + 4 * n, oob, 4 * n);
+    double *dd = (double *)tab;
+    double *dpole = dd + 4 * n;
+    int *di = (int *)(dpole + 2 * nfield);
+    HIPCHK(ctx, hipMemcpyAsync(dd, hd, td, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(di, hi, ti, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    PointTables tb;
+    tb.lat_dx = dd; tb.lat_Dx = dd + n; tb.lon_dx = dd + 2 * n; tb.lon_Dx = dd + 3 * n;
+    tb.lat_lo = di; tb.lat_hi = di + n; tb.lon_lo = di + 2 * n; tb.lon_hi = di + 3 * n; tb.oob = di + 4 * n;
+    const unsigned int bx = nblocks(ntarg, BLOCK);            // one target per thread (k_regrid_points)
+    // z-slices: enough blocks to fill 256 CUs several times over even for few targets
+    long long want = (8192 + (long long)bx - 1) / bx;
+    unsigned int gz = (unsigned int)(want < 1 ? 1 : (want > nfield ? nfield : want));
+    if (gz > 65535u) gz = 65535u;
+    {
+        Prof pr(ctx, PGW_K_REGRID);
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            if (south_row >= 0 || north_row >= 0)
+                hipLaunchKernelGGL((k_zonal_mean_rows<T>), dim3(nblocks(nfield * 2 * 64, BLOCK)), dim3(BLOCK), 0, ctx->stream, nfield,
+                                   nlat_s, nlon_s, (const T *)src, south_row, north_row, dpole);
+            hipLaunchKernelGGL((k_regrid_points<T>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s, ntarg, gz,
+                               (const T *)src, tb, dpole, (T *)out);
+        });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
 // regrid_lat_lon, xESMF branch (functions.py:797-810): locate once per grid pair ...
 extern "C" int pgw_bilinear_locate(pgw_ctx *ctx, long long ntarg, const double *P, int ny, int nx, int periodic, const double *X,
                                    int nb, const int *bucket_start, const int *bucket_cells, int *idx, double *w,

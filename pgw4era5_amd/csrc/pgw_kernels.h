@@ -2724,6 +2724,74 @@ __global__ __launch_bounds__(BLOCK) void k_regrid(long long nfield, int nlat_s, 
     }
 }
 
+// a10, point-wise targets: `ds_gcm.interp({lat: targ_lat}).interp({lon: targ_lon})` (functions.py:859, :892) with 2-D
+// targ_lat / targ_lon over shared dimensions (a rotated-pole extpar file, an unstructured cell list) is xarray's point-wise
+// interpolation - every target g has its own latitude bracket as well as its own longitude bracket.  Per target and plane,
+// the arithmetic of k_regrid (same order, same scale-free quotients: the same bits where the target is a mesh):
+//   ya = (v[hi_row, lon_lo] - v[lo_row, lon_lo]) / lat_Dx * lat_dx + v[lo_row, lon_lo]      lat pass at the lower column
+//   yb = the same at lon_hi;   out = (yb - ya) / lon_Dx * lon_dx + ya                        lon pass
+// row -1 / nlat_s is the pole value of k_zonal_mean_rows; oob gives NaN.  A thread owns ONE flat target, keeps its four
+// corners, the two dx and the two reciprocals in registers and walks the planes of its z-slice (blockIdx.y) with streaming
+// stores; the next plane's four gathers are issued before this plane's store.  A corner is kept as one int: >= 0 an
+// element of the plane, -1 / -2 the south / north pole value.  A target that is oob or past the end reads element 0 and
+// is not used.  Two things the first version had were measured and removed (same bits in every form):
+// staging the bounding box of a block's entries in LDS never beat gathering - neighbouring targets gather from the same few
+// cache lines of a source plane that stays in L2, and the staging added a barrier per plane; and with it gone, 2 / 4 targets
+// per lane (16-byte stores, 114 / 162 VGPRs) were slower than this form (52-56 VGPRs, 8 waves): the gathers, not the
+// stores, bound the kernel.
+struct PointTables {
+    const int *lat_lo, *lat_hi, *lon_lo, *lon_hi, *oob;
+    const double *lat_dx, *lat_Dx, *lon_dx, *lon_Dx;
+};
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_regrid_points(long long nfield, int nlat_s, int nlon_s, long long ntarg, unsigned int gz,
+                                                         const T *__restrict__ src, PointTables tb, const double *__restrict__ pole,
+                                                         T *__restrict__ out) {
+    const long long g0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    const bool active = g0 < ntarg;
+    const long long g = active ? g0 : ntarg - 1;
+    const bool oob = tb.oob[g] != 0;
+    const bool live = active && !oob;
+    const int jl = tb.lat_lo[g], jh = tb.lat_hi[g], il = tb.lon_lo[g], ih = tb.lon_hi[g];
+    const double ldx = tb.lat_dx[g], odx = tb.lon_dx[g];
+    // reciprocals once per target (SharedDivisor); a Dx of 0 gives NaN like k_regrid's
+    const SharedDivisor by_lDx(tb.lat_Dx[g]), by_oDx(tb.lon_Dx[g]);
+    int c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int row = k < 2 ? jl : jh;
+        int code = row * nlon_s + ((k & 1) ? ih : il);
+        if (row < 0) code = -1;
+        if (row >= nlat_s) code = -2;
+        c[k] = live ? code : 0;
+    }
+    const long long plane_s = (long long)nlat_s * nlon_s;
+    const long long per = (nfield + gz - 1) / gz;
+    const long long f0 = (long long)blockIdx.y * per, f1 = f0 + per < nfield ? f0 + per : nfield;
+    auto gather = [&](long long f, T (&v)[4]) {
+        const T *sp = src + f * plane_s;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = sp[c[k] >= 0 ? c[k] : 0];
+    };
+    T cur[4], nxt[4];
+    if (f0 < f1) gather(f0, cur);
+    for (long long f = f0; f < f1; ++f) {
+        if (f + 1 < f1) gather(f + 1, nxt);                   // the next plane's loads fly during this plane's store
+        double v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = c[k] >= 0 ? (double)cur[k] : pole[f * 2 + (-1 - c[k])];
+        const double ya = by_lDx.divide(v[2] - v[0]) * ldx + v[0];                // lat pass at the lower lon  :859
+        const double yb = by_lDx.divide(v[3] - v[1]) * ldx + v[1];                // lat pass at the upper lon
+        const double r = oob ? __builtin_nan("") : by_oDx.divide(yb - ya) * odx + ya;   // lon pass  :892
+        if (active) __builtin_nontemporal_store((T)r, out + f * ntarg + g0);      // streaming: the output must not push the source planes out of L2
+        if (f + 1 < f1) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
+        }
+    }
+}
+
 // =====================================================================================
 // a9  surface riders               step_03_apply_to_era.py:103-146, functions.py:1145-1186
 // =====================================================================================

@@ -707,6 +707,37 @@ def regrid_field(field, src_lat, src_lon, targ_lat, targ_lon):
     return out_like(out, field)
 
 
+def regrid_points(field, src_lat, src_lon, targ_lat, targ_lon):
+    """Bilinear (lat, then lon) regridding of field (..., nlat_s, nlon_s) onto point-wise targets on the GPU: `targ_lat` and
+    `targ_lon` have one common shape of any rank >= 1 (2-D coordinates of a rotated-pole grid, a list of cells), target g
+    lies at (targ_lat[g], targ_lon[g]) - what xarray's `.interp({lat: targ_lat}).interp({lon: targ_lon})` computes for
+    coordinates over shared dimensions (reference functions.py:812-893).  Degrees.  Returns (...,) + the targets' shape;
+    dtype and array kind as `regrid_field`, whose bits a mesh handed over as points reproduces."""
+    ctx = default_context()
+    targ_lat, targ_lon = np.asarray(targ_lat, dtype=np.float64), np.asarray(targ_lon, dtype=np.float64)
+    if targ_lat.ndim < 1 or targ_lat.shape != targ_lon.shape:
+        raise ValueError('point-wise targets need lat and lon of one common shape (rank >= 1); got %s and %s'
+                         % (targ_lat.shape, targ_lon.shape))
+    tb = regrid_tables(src_lat, src_lon, targ_lat.ravel(), targ_lon.ravel())      # the extent errors, before any launch
+    shp = raw(field).shape
+    ops = OperandPlan(ctx, 'regrid_points', field=field)
+    if len(shp) < 2 or shp[-2] != len(src_lat) or shp[-1] != len(src_lon):
+        raise ValueError('field shape does not match the source coordinates')
+    nlat_s, nlon_s = shp[-2], shp[-1]
+    nfield = int(np.prod(shp[:-2], dtype=np.int64)) if len(shp) > 2 else 1
+    d_src = ops.dev('field')
+    out = ctx.empty(tuple(shp[:-2]) + targ_lat.shape, ops.result)
+    c = {k: np.ascontiguousarray(v) for k, v in tb.items() if isinstance(v, np.ndarray)}
+    oob = np.ascontiguousarray(c['lat_oob'] | c['lon_oob'], dtype=np.int32)
+    ctx._check(ctx.lib.pgw_regrid_points(
+        ctx.handle, ops.tag('field'), nfield, nlat_s, nlon_s, targ_lat.size, d_src.ptr,
+        c['lat_lo'].ctypes.data_as(_ip), c['lat_hi'].ctypes.data_as(_ip), c['lat_dx'].ctypes.data_as(_dp),
+        c['lat_Dx'].ctypes.data_as(_dp), c['lon_lo'].ctypes.data_as(_ip), c['lon_hi'].ctypes.data_as(_ip),
+        c['lon_dx'].ctypes.data_as(_dp), c['lon_Dx'].ctypes.data_as(_dp), oob.ctypes.data_as(_ip),
+        tb['south_row'], tb['north_row'], out.ptr))
+    return out_like(out, field)
+
+
 # ------------------------------------------------------------------------------- regridding, 2-D source coordinates
 def unit_vectors(lat_deg, lon_deg):
     """(..., 3) unit vectors (cos lat cos lon, cos lat sin lon, sin lat) of points in degrees, float64: the only
@@ -985,16 +1016,30 @@ def _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name):
 
 def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
     """Bilinear regridding onto the ERA5 grid of `ds_era5` (reference functions.py:748-898).  i_use_xesmf = 0: the xarray
-    branch, every lat/lon variable of `ds_gcm` through the separable kernel (1-D coordinates).  i_use_xesmf = 1: the xESMF
+    branch, every lat/lon variable of `ds_gcm` (1-D source coordinates) through the separable kernel when the target's lat
+    and lon are 1-D axes of their own (a mesh), through `regrid_points` when they lie over the same dimensions (2-D
+    coordinates of a rotated-pole file, one `cell` dimension): the result then lies on the target's dimensions and lat / lon
+    are written as variables over them, like the xESMF branch does; any other combination is a ValueError.  i_use_xesmf = 1: the xESMF
     branch (:797-810) for source grids with 2-D coordinates (rotated-pole, curvilinear; 1-D ones are meshed), `var_name`
     through the cell-locate and sparse-apply kernels.  Returns a new Dataset on the target grid."""
     from . import ncio
     if i_use_xesmf:
         return _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name)
-    targ_lon = np.asarray(ds_era5[LON_ERA].values, dtype=np.float64)
-    targ_lat = np.asarray(ds_era5[LAT_ERA].values, dtype=np.float64)
+    t_lat, t_lon = ds_era5[LAT_ERA], ds_era5[LON_ERA]
+    targ_lon = np.asarray(t_lon.values, dtype=np.float64)
+    targ_lat = np.asarray(t_lat.values, dtype=np.float64)
     src_lon = np.asarray(ds_gcm[LON_GCM].values, dtype=np.float64)
     src_lat = np.asarray(ds_gcm[LAT_GCM].values, dtype=np.float64)
+    # 1-D lat over its own dimension and 1-D lon over its own: a mesh.  lat and lon over the same dimensions (2-D coordinates
+    # of a rotated-pole grid, one `cell` dimension): xarray interpolates point by point.
+    if targ_lat.ndim == 1 and targ_lon.ndim == 1 and tuple(t_lat.dims) != tuple(t_lon.dims):
+        points, tdims = False, (LAT_GCM, LON_GCM)
+    elif targ_lat.ndim >= 1 and tuple(t_lat.dims) == tuple(t_lon.dims) and targ_lat.shape == targ_lon.shape:
+        points, tdims = True, tuple(t_lat.dims)
+    else:
+        raise ValueError('target %s %s over %s and %s %s over %s are neither two 1-D axes of a mesh nor point-wise coordinates '
+                         'over the same dimensions' % (LAT_ERA, targ_lat.shape, tuple(t_lat.dims), LON_ERA, targ_lon.shape,
+                                                       tuple(t_lon.dims)))
     out = ncio.Dataset(attrs=ds_gcm.attrs)
     for name, f in ds_gcm.variables.items():
         if name in (LAT_GCM, LON_GCM):
@@ -1003,15 +1048,22 @@ def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
             lead = [d for d in f.dims if d not in (LAT_GCM, LON_GCM)]
             g = f.transpose(*(lead + [LAT_GCM, LON_GCM]))
             vals = g.values if g.values.dtype in (np.float32, np.float64) else g.values.astype(np.float64)
-            res = regrid_field(vals, src_lat, src_lon, targ_lat, targ_lon)
             coords = {d: f.coords[d] for d in lead if d in f.coords}
-            coords[LAT_GCM] = targ_lat
-            coords[LON_GCM] = targ_lon
-            out[name] = ncio.Field(res, tuple(lead) + (LAT_GCM, LON_GCM), coords, f.attrs, name)
+            if points:
+                res = regrid_points(vals, src_lat, src_lon, targ_lat, targ_lon)
+            else:
+                res = regrid_field(vals, src_lat, src_lon, targ_lat, targ_lon)
+                coords[LAT_GCM] = targ_lat
+                coords[LON_GCM] = targ_lon
+            out[name] = ncio.Field(res, tuple(lead) + tdims, coords, f.attrs, name)
         elif LAT_GCM not in f.dims and LON_GCM not in f.dims:
             out[name] = f
-    out[LAT_GCM] = ncio.Field(targ_lat, (LAT_GCM,), {LAT_GCM: targ_lat}, ds_gcm[LAT_GCM].attrs, LAT_GCM)
-    out[LON_GCM] = ncio.Field(targ_lon, (LON_GCM,), {LON_GCM: targ_lon}, ds_gcm[LON_GCM].attrs, LON_GCM)
+    if points:                                                  # laid out like the xESMF branch's 2-D target
+        out[LAT_GCM] = ncio.Field(targ_lat, tdims, {}, ds_gcm[LAT_GCM].attrs, LAT_GCM)
+        out[LON_GCM] = ncio.Field(targ_lon, tdims, {}, ds_gcm[LON_GCM].attrs, LON_GCM)
+    else:
+        out[LAT_GCM] = ncio.Field(targ_lat, (LAT_GCM,), {LAT_GCM: targ_lat}, ds_gcm[LAT_GCM].attrs, LAT_GCM)
+        out[LON_GCM] = ncio.Field(targ_lon, (LON_GCM,), {LON_GCM: targ_lon}, ds_gcm[LON_GCM].attrs, LON_GCM)
     return out
 
 

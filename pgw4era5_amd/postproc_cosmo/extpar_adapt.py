@@ -3,8 +3,8 @@ COSMO-specific: perturb the deep soil temperature climatology T_CL of an extpar 
 
 Program and command line of the reference's postproc_cosmo/extpar_adapt.py (:13-63): positional extpar_file_path,
 -d/--delta_input_dir.  The delta directory holds `ts_delta.nc` on the grid of the extpar file, e.g. from
-`step_02_preproc_deltas regridding -e EXTPAR -v ts` with settings.i_use_xesmf_regridding = 1 (an extpar file on a rotated
-grid has 2-D lat / lon).
+`step_02_preproc_deltas regridding -e EXTPAR -v ts` under default settings (an extpar file on a rotated grid has 2-D lat /
+lon: a regular-grid delta is interpolated onto them point by point, functions.regrid_points).
 
     delta_ts      = load_delta(delta_inp_path, 'ts', None)           # every record                       :20
     delta_ts_clim = delta_ts.mean(dim=['time'])                      # np.nanmean over the records        :29

@@ -4,7 +4,8 @@ step_02: regrid GCM climate deltas (and HIST climatologies) to the ERA5 grid on 
 Command line of the reference's step_02_preproc_deltas.py (:27-87): positional
 {smoothing,regridding}, -i, -o, -e, -v.  For every variable both `{var}_historical.nc` and
 `{var}_delta.nc` are processed (:116-119).  `regridding` runs the bilinear lat-then-lon kernel
-(functions.regrid_lat_lon), or with settings.i_use_xesmf_regridding = 1 the cell-locate / sparse-apply kernels for source
+(functions.regrid_lat_lon; onto a target file with 2-D lat / lon over shared dimensions, such as an extpar file, its
+point-wise form), or with settings.i_use_xesmf_regridding = 1 the cell-locate / sparse-apply kernels for source
 grids with 2-D coordinates; `smoothing` runs the annual-cycle filter for daily deltas
 (functions.filter_data, reference functions.py:603-740); tos / siconc on the ocean grid go through the
 NaN-ignoring Gaussian-kernel interpolation (functions.nan_ignoring_interp, reference functions.py:900-1060).
