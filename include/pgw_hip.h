@@ -221,6 +221,8 @@ int pgw_interp_logp_4d(pgw_ctx *ctx, int dtype, int ntime, int nsrc, int ntarg, 
                        int extrapolate, int logp_in, void *out);
 
 /* ---------------------------------------------------------------- deltas ------------- */
+#define PGW_MAX_PLEV 128       /* levels of the plev axis of ta / hur / ua / va deltas */
+#define PGW_MAX_PLEV_ZG 64     /* levels of zg's plev axis (pgw_file_args.nplev_zg, pgw_geopot_on_plev) */
 /* a7 the arithmetic of load_delta's time interpolation (functions.py:288-292 -> scipy
  * interp1d linear): out = (v_after - v_before)/x_hi * x_new + v_before, flat over n. */
 int pgw_time_lerp(pgw_ctx *ctx, int dtype, long long n, const void *v_before, const void *v_after,
@@ -230,6 +232,9 @@ int pgw_time_lerp(pgw_ctx *ctx, int dtype, long long n, const void *v_before, co
  * (+ replace_delta_sfc :343-366, + the time lerp of load_delta, + `era + delta` of
  * step_03_apply_to_era.py:170-173) fused per column.
  *  plev (nplev, host): the delta file's plev coordinate in FILE order; it is reversed like :383-384.
+ *    2 <= nplev <= 128 (PGW_MAX_PLEV), here and in every entry below that takes the plev axis of a delta (the reference's
+ *    step_01 writes 99 levels).  An axis of up to 64 levels runs the kernels built for a 64-entry table, a longer one their
+ *    128-entry instantiations: same arithmetic, the table is a by-value kernel argument either way.
  *  delta_b / delta_a (nplev, ncol) per time: the two bracketing records (delta_a NULL, or
  *    x_hi == 0 -> delta_b is used as is, functions.py:282-283); same for the optional
  *    surface pairs dsfc_*, pshist_* (ntime, ncol) (NULL -> no surface insertion).
@@ -249,7 +254,7 @@ int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int nplev, int nle
  * :330-343):  out = interp_logp_4d(era_field, pa_era, pa_pgw, extrapolate='constant') + load_delta_interp(var, pa_pgw)
  * as ONE kernel: pa_era = akm + ps_era*bkm (source axis of the first term) and pa_pgw = akm + ps_pgw*bkm (target of
  * both) are rebuilt in registers from the two surface-pressure fields (ntime, ncol) and pgw_set_levels, the delta
- * arguments are those of pgw_vert_interp_delta.  era_field, out: (ntime, nlev, ncol). */
+ * arguments are those of pgw_vert_interp_delta (nplev up to 128).  era_field, out: (ntime, nlev, ncol). */
 int pgw_reinterp_field(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const double *plev,
                        const void *delta_b, const void *delta_a, double x_hi, double x_new, const void *dsfc_b,
                        const void *dsfc_a, const void *pshist_b, const void *pshist_a, const void *era_field,
@@ -259,7 +264,7 @@ int pgw_reinterp_field(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long 
  * or ua + va (:330-343; dsfc_b = NULL) - in one kernel: one target logarithm per level, one source logarithm per level of
  * the ERA column and one bracket search per axis serve both.  delta_b / delta_a / dsfc_b / dsfc_a / era_field / out are
  * arrays of two device pointers (dsfc_b, dsfc_a, delta_a may be NULL as in pgw_reinterp_field); results are the bits of
- * two pgw_reinterp_field calls. */
+ * two pgw_reinterp_field calls.  nplev up to 128. */
 int pgw_reinterp_pair(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const double *plev,
                       const void *const *delta_b, const void *const *delta_a, double x_hi, double x_new,
                       const void *const *dsfc_b, const void *const *dsfc_a, const void *pshist_b, const void *pshist_a,
@@ -270,7 +275,7 @@ int pgw_reinterp_pair(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long n
  * interp_logp_4d(T / RELHUM of the ERA state, pa_era, pa_pgw, 'constant') + load_delta_interp(ta / hur, pa_pgw) (:202-216,
  * pgw_reinterp_pair, which also leaves e = hur_pgw / 100 * e_sat(ta_pgw) in a workspace); then the pass of pgw_adjust_ps_step
  * on them: adj_ps and the global max |phi error| (:262-308).  Same bits as pgw_update_ps + pgw_reinterp_pair +
- * pgw_adjust_ps_step(apply_adj = 0).  ps_pgw (ntime, ncol), ta_pgw, hur_pgw (ntime, nlev, ncol) are outputs. */
+ * pgw_adjust_ps_step(apply_adj = 0).  ps_pgw (ntime, ncol), ta_pgw, hur_pgw (ntime, nlev, ncol) are outputs.  nplev up to 128. */
 int pgw_reinterp_pass(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const double *plev,
                       const void *const *delta_b, const void *const *delta_a, double x_hi, double x_new,
                       const void *const *dsfc_b, const void *const *dsfc_a, const void *pshist_b, const void *pshist_a,
@@ -279,7 +284,7 @@ int pgw_reinterp_pass(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long n
                       int ignore_top, void *ps_pgw, void *ta_pgw, void *hur_pgw, double *max_abs_err);
 
 /* replace_delta_sfc(source_P, ps_hist, delta, delta_sfc)  functions.py:343-366, on many columns:
- * plev_asc (nplev, host, ascending); delta (ntime, nplev, ncol) in ascending order;
+ * plev_asc (nplev, host, ascending; 1 <= nplev <= 128); delta (ntime, nplev, ncol) in ascending order;
  * delta_sfc, ps_hist (ntime, ncol); outputs out_P, out_delta (ntime, nplev, ncol). */
 int pgw_replace_delta_sfc(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol,
                           const double *plev_asc, const void *delta, const void *delta_sfc,
@@ -354,7 +359,7 @@ int pgw_last_qv_from_pass(pgw_ctx *ctx, unsigned long long *skipped);
  * Results are identical to calling the function-level entry points in the reference's order. */
 typedef struct pgw_file_args {
     /* shapes */
-    int dtype, ntime, nlev, nplev, nsoil, ignore_top, max_n_iter;
+    int dtype, ntime, nlev, nplev, nsoil, ignore_top, max_n_iter;      /* 2 <= nplev <= 128 (PGW_MAX_PLEV) */
     int local_p_ref;      /* != 0: p_ref_inp = None, reference pressure chosen per column and pass (step_03:219-253) */
     int ref_dtype;        /* != 0 (dtype must be PGW_F32): reference-dtype mode - the float32 roundings numpy's promotion
                              puts into the reference on float32 ERA5 files are reproduced (phi_hl stored float32 per level,
@@ -373,7 +378,8 @@ typedef struct pgw_file_args {
     /* delta records (device) */
     const void *ta_b, *ta_a, *hur_b, *hur_a, *ua_b, *ua_a, *va_b, *va_a;   /* (ntime,nplev,ncol) */
     const void *zg_b, *zg_a;                                /* (ntime,ncol): zg delta at plev == p_ref */
-    const void *zg3_b, *zg3_a;                              /* (ntime,nplev,ncol): full zg records (local_p_ref) */
+    const void *zg3_b, *zg3_a;                              /* full zg records (local_p_ref): (ntime,nplev,ncol), or
+                                                               (ntime,nplev_zg,ncol) when nplev_zg != 0 */
     const void *tas_b, *tas_a, *hurs_b, *hurs_a, *pshist_b, *pshist_a;     /* (ntime,ncol)       */
     const void *siconc_b, *siconc_a, *ts_b, *ts_a, *tos_b, *tos_a, *ts_clim;
     double x_hi, x_new;                                     /* time-lerp abscissae (pgw_time_lerp) */
@@ -402,6 +408,14 @@ typedef struct pgw_file_args {
      * (the multi-pass loop kernel needs iterate-independent T_pgw / e); no latitude-band sharding. */
     int i_reinterp;
     double zg_x_hi, zg_x_new, siconc_x_hi, siconc_x_new, ts_x_hi, ts_x_new, tos_x_hi, tos_x_new;
+    /* local_p_ref != 0 with zg on a plev axis of its own (the reference takes the candidates for the reference level from
+     * zg's plev, step_03:219-222, and selects the zg delta on it, :292-295; in the CFday workflow ta / hur / ua / va stand
+     * on 99 levels and zg on Emon / Amon's).  nplev_zg == 0: zg shares `plev` (then nplev <= 64).  Otherwise plev_zg
+     * (host, nplev_zg, file order) is the axis of zg3_b / zg3_a and of the level search, in every form of the loop
+     * (multi-pass, one launch per pass, i_reinterp).  1 <= nplev_zg <= 64 (PGW_MAX_PLEV_ZG): the loop kernel carries this
+     * table by value and sits on its register budget; a zg file has 19 to 34 levels.  Ignored with a fixed p_ref. */
+    int nplev_zg, _pad1;
+    const double *plev_zg;
 } pgw_file_args;
 
 /* Who produces the loop's state (fixed p_ref, multi-pass loop).  With PGW_OPT_FUSED_FIRST = 1 the delta kernel, walking each
@@ -544,7 +558,7 @@ int pgw_surface_update(pgw_ctx *ctx, int dtype, int ntime, long long ncol, int n
  * The four deltas of load_delta_interp (functions.py:306-340) on the model-level pressures akm + ps*bkm (tables of
  * the last set_levels call), one kernel: the values the whole-file entry adds to T, RELHUM, U, V, with its
  * expressions (time interpolation of the records, surface insertion for ta / hur from tas / hurs / ps_hist, the column
- * interpolation in ln p), so `era + delta` in numpy reproduces its outputs bit for bit.  Records (ntime, nplev, ncol) /
+ * interpolation in ln p), so `era + delta` in numpy reproduces its outputs bit for bit.  Records (ntime, nplev, ncol; 2 <= nplev <= 128) /
  * (ntime, ncol) in `dtype`, `*_a` unused when x_hi == 0 (the instant is a record); ps in `dtype`: PS of the file, or the
  * converged ps_pgw under settings.i_reinterp = 1 (step_03:212-216, 336-343).  ref_dtype = 1 (dtype PGW_F32 only): the
  * reference's dtype flow on float32 files.  Outputs (ntime, nlev, ncol) are float64 for every dtype
@@ -689,7 +703,7 @@ int pgw_interp_logp_4d_mixed(pgw_ctx *ctx, int dt_var, int dt_p, int ntime, int 
 
 /* vert_interp_delta, functions.py:369-431 (+ :343-366): delta_sfc stored in the delta's dtype, ps_hist inserted into the
  * float64 source pressures, then as interp_logp_4d with 'constant'; `add_to` (may be NULL) is added in float64.
- * delta (ntime, nplev, ncol) in file order; delta_sfc, ps_hist (ntime, ncol), both or neither; targ_P (ntime, nlev_t, ncol)
+ * delta (ntime, nplev, ncol) in file order, 2 <= nplev <= 128; delta_sfc, ps_hist (ntime, ncol), both or neither; targ_P (ntime, nlev_t, ncol)
  * float64 (dt_targ = PGW_F64); out float64.  No time interpolation and no hybrid-level targets in this entry. */
 int pgw_vert_interp_delta_mixed(pgw_ctx *ctx, int dt_delta, int dt_sfc, int dt_pshist, int dt_targ, int dt_add,
                                 int ntime, int nplev, int nlev_t, long long ncol, const double *plev,

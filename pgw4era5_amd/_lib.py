@@ -30,6 +30,27 @@ KERNEL_IDS = dict(pressure=0, q_to_rh=1, rh_to_q=2, integ_geopot=3, interp_logp=
 # enum pgw_option (include/pgw_hip.h)
 OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7, mixed_vec=8, sparse_direct=9, qv_from_pass=10)
 
+# PGW_MAX_PLEV / PGW_MAX_PLEV_ZG (include/pgw_hip.h): levels of the plev axis of a delta, and of zg's own axis when the
+# reference level is chosen per column (p_ref_inp = None)
+MAX_PLEV = 128
+MAX_PLEV_ZG = 64
+
+
+def check_nplev(nplev, lowest=2, what='nplev'):
+    """The library's own argument check on the length of a delta's plev axis, made before anything is copied or
+    launched: ValueError with the library's text."""
+    if not lowest <= int(nplev) <= MAX_PLEV:
+        raise ValueError('%s must be in [%d, %d] (got %d): the plev table of a delta is a kernel argument of at most %d levels'
+                         % (what, lowest, MAX_PLEV, int(nplev), MAX_PLEV))
+
+
+def check_nplev_zg(nplev_zg):
+    """The same for zg's plev axis under p_ref_inp = None (pgw_file_args.nplev_zg)."""
+    if not 1 <= int(nplev_zg) <= MAX_PLEV_ZG:
+        raise ValueError('the plev axis of zg must have 1 to %d levels when the reference level is chosen per column '
+                         '(p_ref_inp = None); got %d' % (MAX_PLEV_ZG, int(nplev_zg)))
+
+
 PGW_OK = 0
 PGW_ERR_HIP = 1
 PGW_ERR_ARG = 2
@@ -122,7 +143,10 @@ class FileArgs(C.Structure):
         [('n_iter', C.c_int), ('passes_launched', C.c_int), ('levels_touched', C.c_ulonglong),
          ('max_err_hist', C.c_double * 32), ('per_var_time', C.c_int), ('i_reinterp', C.c_int)] +
         [(n, C.c_double) for n in ('zg_x_hi', 'zg_x_new', 'siconc_x_hi', 'siconc_x_new', 'ts_x_hi', 'ts_x_new',
-                                   'tos_x_hi', 'tos_x_new')])
+                                   'tos_x_hi', 'tos_x_new')] +
+        # local_p_ref with zg on a plev axis of its own (0 / NULL: zg shares `plev`); the host table as an address, so
+        # that two structs filled for one DeltaSet compare equal field by field
+        [('nplev_zg', C.c_int), ('_pad1', C.c_int), ('plev_zg', C.c_void_p)])
 
 
 SIGNATURES['pgw_step03_file'] = (_i, [_vp, C.POINTER(FileArgs)])

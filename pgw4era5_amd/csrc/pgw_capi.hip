@@ -43,8 +43,10 @@ struct pgw_ctx {
     double ps_mono_min = 0.0;
     int n_pure = 0;                    // leading full levels with bkm == 0 (pure-pressure levels)
     // plev table cache for vert_interp_delta
+    // (the narrow table for an axis of up to MAX_PLEV levels, else the wide one: with_plev)
     std::vector<double> plev_key;
     PlevTable plev_tab;
+    PlevTableWide plev_tab_wide;
     double *d_small = nullptr;         // small scratch (tables), 64 KiB
     // named workspaces grown on demand
     void *ws[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1067,10 +1069,52 @@ extern "C" int pgw_time_lerp(pgw_ctx *ctx, int dtype, long long n, const void *v
 }
 
 // ------------------------------------------------------------------ vert_interp_delta
+// The first MAX_PLEV entries of a table as a narrow one (all of it when n <= MAX_PLEV; the unused entries of both are 0)
+static PlevTable narrow_table(const PlevTableWide &w) {
+    PlevTable t;
+    memset(&t, 0, sizeof(t));
+    memcpy(t.p, w.p, sizeof(t.p));
+    memcpy(t.lnp, w.lnp, sizeof(t.lnp));
+    t.pmax = w.pmax; t.pmin = w.pmin; t.n = w.n;
+    return t;
+}
+
+// f(table) with the table type the axis needs: PlevTable for up to MAX_PLEV levels - the instantiations every such
+// caller has always launched - and PlevTableWide above.  The callers have checked n <= MAX_PLEV_WIDE.
+template <typename F>
+static void with_plev(const PlevTableWide &w, F &&f) {
+    if (w.n > MAX_PLEV) f(w);
+    else f(narrow_table(w));
+}
+template <typename F>
+static void with_plev(pgw_ctx *ctx, F &&f) {
+    if (ctx->plev_tab_wide.n > MAX_PLEV) f(ctx->plev_tab_wide);
+    else f(ctx->plev_tab);
+}
+// the error texts take the limit from the header's constant, which is the kernels'
+#define PGW_STR2(x) #x
+#define PGW_STR(x) PGW_STR2(x)
+#define PLEV_RANGE_2 "nplev must be in [2, " PGW_STR(PGW_MAX_PLEV) "]"
+#define PLEV_RANGE_1 "nplev must be in [1, " PGW_STR(PGW_MAX_PLEV) "]"
+static_assert(MAX_PLEV_WIDE == PGW_MAX_PLEV && MAX_PLEV == PGW_MAX_PLEV_ZG, "include/pgw_hip.h names the kernels' limits");
+
+// The plev axis of zg for the local reference level of a file: its own (nplev_zg, plev_zg) when given, else the deltas'.
+// Its table stays narrow (LocalPRef, k_local_p_ref).
+struct ZgAxis { int n; const double *plev; };
+static int zg_axis(pgw_ctx *ctx, const pgw_file_args *a, ZgAxis *z) {
+    NEED(ctx, a->nplev_zg >= 0 && a->nplev_zg <= MAX_PLEV, "nplev_zg must be in [1, " PGW_STR(PGW_MAX_PLEV_ZG) "], or 0 when zg shares plev");
+    NEED(ctx, a->nplev_zg == 0 || a->plev_zg != nullptr, "plev_zg is NULL");
+    z->n = a->nplev_zg ? a->nplev_zg : a->nplev;
+    z->plev = a->nplev_zg ? a->plev_zg : a->plev;
+    NEED(ctx, z->n <= MAX_PLEV, "local_p_ref: zg's plev axis must have at most " PGW_STR(PGW_MAX_PLEV_ZG) " levels (give nplev_zg / plev_zg when nplev is larger)");
+    return PGW_OK;
+}
+
 static int plev_table(pgw_ctx *ctx, int nplev, const double *plev) {
     if ((int)ctx->plev_key.size() == nplev && memcmp(ctx->plev_key.data(), plev, sizeof(double) * nplev) == 0)
         return PGW_OK;
-    PlevTable &t = ctx->plev_tab;
+    ctx->plev_key.clear();
+    PlevTableWide &t = ctx->plev_tab_wide;
     memset(&t, 0, sizeof(t));
     t.n = nplev;
     t.pmax = -INFINITY; t.pmin = INFINITY;
@@ -1083,11 +1127,14 @@ static int plev_table(pgw_ctx *ctx, int nplev, const double *plev) {
     }
     if (anynan) return fail(ctx, PGW_ERR_ARG, "vert_interp_delta: NaN in plev");
     // ln(plev) with the device log so that table and per-column logs are from one implementation
-    double *d_in = ctx->d_small, *d_out = ctx->d_small + MAX_PLEV;
+    static_assert(2 * MAX_PLEV_WIDE * sizeof(double) <= SMALL_BYTES, "d_small holds the table and its logarithms");
+    double *d_in = ctx->d_small, *d_out = ctx->d_small + MAX_PLEV_WIDE;
     HIPCHK(ctx, hipMemcpyAsync(d_in, t.p, sizeof(double) * nplev, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_log_table, dim3(1), dim3(64), 0, ctx->stream, nplev, d_in, d_out);
+    // one entry per thread, blocks of 64: a second block for the levels past the 64th
+    hipLaunchKernelGGL(k_log_table, dim3(nblocks(nplev, 64)), dim3(64), 0, ctx->stream, nplev, d_in, d_out);
     HIPCHK(ctx, hipMemcpyAsync(t.lnp, d_out, sizeof(double) * nplev, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->plev_tab = narrow_table(t);
     ctx->plev_key.assign(plev, plev + nplev);
     return PGW_OK;
 }
@@ -1113,7 +1160,7 @@ extern "C" int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int npl
                                      const void *pshist_a, const void *targ_P, const void *ps, int ignore_top,
                                      const void *add_to, void *out) {
     CHECK_COMMON(ctx, dtype, ntime, ncol);
-    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV_WIDE, PLEV_RANGE_2);
     NEED(ctx, plev && delta_b && out, "null pointer");
     NEED(ctx, targ_P || ps, "need targ_P or ps");
     NEED(ctx, (dsfc_b == nullptr) == (pshist_b == nullptr), "delta_sfc and ps_hist must be given together");
@@ -1131,13 +1178,13 @@ extern "C" int pgw_vert_interp_delta(pgw_ctx *ctx, int dtype, int ntime, int npl
     long long total = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        with_type(dtype, [&](auto t_) { with_int<2>(dsfc_b != nullptr, [&](auto sfc_) {
-            using T = decltype(t_);
-            hipLaunchKernelGGL((k_vert_interp_delta<T, T, T, decltype(sfc_)::value != 0>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0,
-                               ctx->stream, ctx->plev_tab, lv, ntime, nlev_t, ncol, delta_src<T>(delta_b, delta_a, x_hi, x_new),
+        with_type(dtype, [&](auto t_) { with_int<2>(dsfc_b != nullptr, [&](auto sfc_) { with_plev(ctx, [&](const auto &pt) {
+            using T = decltype(t_); using PT = std::decay_t<decltype(pt)>;
+            hipLaunchKernelGGL((k_vert_interp_delta<T, T, T, decltype(sfc_)::value != 0, T, T, T, PT>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0,
+                               ctx->stream, pt, lv, ntime, nlev_t, ncol, delta_src<T>(delta_b, delta_a, x_hi, x_new),
                                delta_src<T>(dsfc_b, dsfc_a, x_hi, x_new), delta_src<T>(pshist_b, pshist_a, x_hi, x_new),
                                (const T *)targ_P, (const T *)ps, ignore_top ? 0 : 1, (const T *)add_to, (T *)out, ctx->d_status);
-        }); });
+        }); }); });
     }
     HIPCHK(ctx, hipGetLastError());
     rc = status_check(ctx);
@@ -1156,7 +1203,7 @@ extern "C" int pgw_delta_fields(pgw_ctx *ctx, int dtype, int ref_dtype, int ntim
     const bool ref = ref_dtype != 0;
     NEED(ctx, !ref || dtype == PGW_F32, "ref_dtype = 1 is the float32-file mode: dtype must be PGW_F32");
     NEED(ctx, ctx->nlev > 0 && nlev == ctx->nlev, "nlev must match pgw_set_levels");
-    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV_WIDE, PLEV_RANGE_2);
     NEED(ctx, plev && ps && ta_b && hur_b && ua_b && va_b && tas_b && hurs_b && pshist_b, "null pointer");
     NEED(ctx, x_hi == 0.0 || (ta_a && hur_a && ua_a && va_a && tas_a && hurs_a && pshist_a), "record after the instant is NULL");
     NEED(ctx, dta && dhur && dua && dva, "output pointer is NULL");
@@ -1177,15 +1224,15 @@ extern "C" int pgw_delta_fields(pgw_ctx *ctx, int dtype, int ref_dtype, int ntim
             const PairSrc<T> ds = pair_src<T>(tas_b, tas_a, hurs_b, hurs_a, x_hi, x_new);
             const DeltaSrc<T> ph = delta_src<T>(pshist_b, pshist_a, x_hi, x_new);
             const PairSrc<T> dwd = pair_src<T>(ua_b, ua_a, va_b, va_a, x_hi, x_new);
-            with_offsets(o32, [&](auto o_) { with_int<2>(x_hi != 0.0, [&](auto lerp_) {
+            with_offsets(o32, [&](auto o_) { with_int<2>(x_hi != 0.0, [&](auto lerp_) { with_plev(ctx, [&](const auto &pt) {
                 // k_delta_quad<.., DELTAS = true>: blocks of 128, the quad kernel's dynamic LDS; no ERA fields, no e / QV outputs, no FusedFirst
-                hipLaunchKernelGGL((k_delta_fields<T, decltype(o_), decltype(lerp_)::value != 0, decltype(ref_)::value>),
+                hipLaunchKernelGGL((k_delta_fields<T, decltype(o_), decltype(lerp_)::value != 0, decltype(ref_)::value, std::decay_t<decltype(pt)>>),
                                    dim3(nblocks(total, 128)), dim3(128), (size_t)(5 * nlev + 2) * sizeof(double), ctx->stream,
-                                   ctx->plev_tab, lv, ntime, ncol, (const T *)nullptr, (const T *)nullptr, (const T *)nullptr,
+                                   pt, lv, ntime, ncol, (const T *)nullptr, (const T *)nullptr, (const T *)nullptr,
                                    (const T *)nullptr, (const T *)ps, dth, ds, ph, dwd, ignore_top ? 0 : 1, dta, (double *)nullptr,
                                    dhur, dua, dva, (double *)nullptr, 0, ctx->n_pure, ctx->d_status, 0.0,
                                    (const FusedFirst<T> *)nullptr);
-            }); });
+            }); }); });
         });
     }
     HIPCHK(ctx, hipGetLastError());
@@ -1198,7 +1245,7 @@ extern "C" int pgw_reinterp_field(pgw_ctx *ctx, int dtype, int ntime, int nplev,
                                   const void *dsfc_a, const void *pshist_b, const void *pshist_a, const void *era_field,
                                   const void *ps_era, const void *ps_pgw, int ignore_top, void *out) {
     CHECK_COMMON(ctx, dtype, ntime, ncol);
-    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV_WIDE, PLEV_RANGE_2);
     NEED(ctx, plev && delta_b && era_field && ps_era && ps_pgw && out, "null pointer");
     NEED(ctx, (dsfc_b == nullptr) == (pshist_b == nullptr), "delta_sfc and ps_hist must be given together");
     NEED(ctx, ctx->nlev > 0, "pgw_set_levels has not been called");
@@ -1209,14 +1256,14 @@ extern "C" int pgw_reinterp_field(pgw_ctx *ctx, int dtype, int ntime, int nplev,
     const long long total = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        with_type(dtype, [&](auto t_) { with_int<2>(dsfc_b != nullptr, [&](auto sfc_) {
+        with_type(dtype, [&](auto t_) { with_int<2>(dsfc_b != nullptr, [&](auto sfc_) { with_plev(ctx, [&](const auto &pt) {
             using T = decltype(t_);
-            hipLaunchKernelGGL((k_reinterp_field<T, decltype(sfc_)::value != 0>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0,
-                               ctx->stream, ctx->plev_tab, lv, ntime, ncol, delta_src<T>(delta_b, delta_a, x_hi, x_new),
+            hipLaunchKernelGGL((k_reinterp_field<T, decltype(sfc_)::value != 0, std::decay_t<decltype(pt)>>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0,
+                               ctx->stream, pt, lv, ntime, ncol, delta_src<T>(delta_b, delta_a, x_hi, x_new),
                                delta_src<T>(dsfc_b, dsfc_a, x_hi, x_new), delta_src<T>(pshist_b, pshist_a, x_hi, x_new),
                                (const T *)era_field, (const T *)ps_era, (const T *)ps_pgw, ignore_top ? 0 : 1, (T *)out,
                                ctx->d_status);
-        }); });
+        }); }); });
     }
     HIPCHK(ctx, hipGetLastError());
     if ((rc = status_check(ctx))) return rc;
@@ -1231,16 +1278,16 @@ static void launch_reinterp_pair(pgw_ctx *ctx, const Levels &lv, int ntime, int 
                                  const DeltaSrc<T> &p, const T *ps_era, const T *ps_pgw, bool sfc, int check_top) {
     // 32-bit byte offsets when every array (fields: nlev levels, delta records: nplev levels) is smaller than 4 GiB
     const unsigned long long big = (unsigned long long)ntime * (lv.nlev > nplev ? lv.nlev : nplev) * ncol * sizeof(TO);
-    with_offsets(big < (1ull << 32) && !ctx->opt[PGW_OPT_FORCE_OFF64], [&](auto o_) {
+    with_offsets(big < (1ull << 32) && !ctx->opt[PGW_OPT_FORCE_OFF64], [&](auto o_) { with_plev(ctx, [&](const auto &pt) {
         auto launch = [&](auto sfc_, auto evap_) {
-            hipLaunchKernelGGL((k_reinterp_pair<T, decltype(sfc_)::value, decltype(o_), decltype(evap_)::value, TE0, TE1, TO, REF>),
+            hipLaunchKernelGGL((k_reinterp_pair<T, decltype(sfc_)::value, decltype(o_), decltype(evap_)::value, TE0, TE1, TO, REF, std::decay_t<decltype(pt)>>),
                                dim3(nblocks((long long)ntime * ncol, BLOCK)), dim3(BLOCK), 2 * lv.nlev * sizeof(double), ctx->stream,
-                               ctx->plev_tab, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top, ctx->d_status);
+                               pt, lv, ntime, ncol, rv, p, ps_era, ps_pgw, check_top, ctx->d_status);
         };
         if (rv.evap) return launch(std::true_type(), std::true_type());
         if constexpr (!REF) { if (sfc) return launch(std::true_type(), std::false_type()); }
         launch(std::false_type(), std::false_type());
-    });
+    }); });
 }
 
 extern "C" int pgw_reinterp_pair(pgw_ctx *ctx, int dtype, int ntime, int nplev, long long ncol, const double *plev,
@@ -1249,7 +1296,7 @@ extern "C" int pgw_reinterp_pair(pgw_ctx *ctx, int dtype, int ntime, int nplev, 
                                  const void *pshist_a, const void *const *era_field, const void *ps_era, const void *ps_pgw,
                                  int ignore_top, void *const *out) {
     CHECK_COMMON(ctx, dtype, ntime, ncol);
-    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV_WIDE, PLEV_RANGE_2);
     NEED(ctx, plev && delta_b && era_field && ps_era && ps_pgw && out, "null pointer");
     NEED(ctx, delta_b[0] && delta_b[1] && era_field[0] && era_field[1] && out[0] && out[1], "null pointer");
     NEED(ctx, (dsfc_b == nullptr) == (pshist_b == nullptr), "delta_sfc and ps_hist must be given together");
@@ -1284,8 +1331,8 @@ extern "C" int pgw_reinterp_pair(pgw_ctx *ctx, int dtype, int ntime, int nplev, 
 }
 
 // pressure levels that are ascending as given (no reversal, no logarithms): p, n and the extrema
-static PlevTable ascending_plev_table(int nplev, const double *plev_asc) {
-    PlevTable t;
+static PlevTableWide ascending_plev_table(int nplev, const double *plev_asc) {
+    PlevTableWide t;
     memset(&t, 0, sizeof(t));
     t.n = nplev; t.pmax = -INFINITY; t.pmin = INFINITY;
     for (int i = 0; i < nplev; ++i) {
@@ -1300,19 +1347,19 @@ extern "C" int pgw_replace_delta_sfc(pgw_ctx *ctx, int dtype, int ntime, int npl
                                      const double *plev_asc, const void *delta, const void *delta_sfc,
                                      const void *ps_hist, void *out_P, void *out_delta) {
     CHECK_COMMON(ctx, dtype, ntime, ncol);
-    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV, "nplev must be in [1, 64]");
+    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV_WIDE, PLEV_RANGE_1);
     NEED(ctx, plev_asc && delta && delta_sfc && ps_hist && out_P && out_delta, "null pointer");
-    const PlevTable t = ascending_plev_table(nplev, plev_asc);
+    const PlevTableWide tw = ascending_plev_table(nplev, plev_asc);
     int rc = status_reset(ctx);
     if (rc) return rc;
     long long total = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        with_type(dtype, [&](auto t_) {
+        with_type(dtype, [&](auto t_) { with_plev(tw, [&](const auto &pt) {
             using T = decltype(t_);
-            hipLaunchKernelGGL((k_replace_delta_sfc<T>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, t, ntime, ncol,
+            hipLaunchKernelGGL((k_replace_delta_sfc<T, T, T, T, std::decay_t<decltype(pt)>>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, pt, ntime, ncol,
                                (const T *)delta, (const T *)delta_sfc, (const T *)ps_hist, (T *)out_P, (T *)out_delta, ctx->d_status);
-        });
+        }); });
     }
     HIPCHK(ctx, hipGetLastError());
     return status_check(ctx);
@@ -1415,7 +1462,7 @@ extern "C" int pgw_reinterp_pass(pgw_ctx *ctx, int dtype, int ntime, int nplev, 
                                  double *adj_ps, double p_ref, double adj_factor, int ignore_top, void *ps_pgw,
                                  void *ta_pgw, void *hur_pgw, double *max_abs_err) {
     CHECK_COMMON(ctx, dtype, ntime, ncol);
-    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV_WIDE, PLEV_RANGE_2);
     NEED(ctx, ctx->nlev > 0, "pgw_set_levels has not been called");
     NEED(ctx, plev && delta_b && dsfc_b && pshist_b && T_era && RELHUM_era && PS && FIS && phi_ref_era && dphi_clim && delta_ps &&
          adj_ps && ps_pgw && ta_pgw && hur_pgw, "null pointer");
@@ -1898,7 +1945,9 @@ static int run_reinterp_file(pgw_ctx *ctx, pgw_file_args *a, int check_top) {
     const int full_column = ctx->opt[PGW_OPT_FULL_COLUMN];
     const double zx_hi = a->per_var_time ? a->zg_x_hi : a->x_hi, zx_new = a->per_var_time ? a->zg_x_new : a->x_new;
     if (local) NEED(ctx, a->zg3_b != nullptr, "local_p_ref needs the full zg records (zg3_b / zg3_a)");
-    const PlevTable ptf = file_order_table(local ? S : 0, a->plev);
+    ZgAxis zax = {0, nullptr};
+    if (local && (rc = zg_axis(ctx, a, &zax))) return rc;
+    const PlevTable ptf = file_order_table(zax.n, zax.plev);
     if ((rc = status_reset(ctx))) return rc;
     // ---- ERA state: RELHUM (step_03:87-94)
     {
@@ -2121,7 +2170,7 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     const long long ncol = a->ncol;
     CHECK_COMMON(ctx, dtype, ntime, ncol);
     NEED(ctx, ctx->nlev > 0 && a->nlev == ctx->nlev, "nlev must match pgw_set_levels");
-    NEED(ctx, a->nplev >= 2 && a->nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, a->nplev >= 2 && a->nplev <= MAX_PLEV_WIDE, PLEV_RANGE_2);
     NEED(ctx, a->PS && a->FIS && a->T && a->QV && a->U && a->V, "ERA5 field pointer is NULL");
     NEED(ctx, a->plev && a->ta_b && a->hur_b && a->ua_b && a->va_b && (a->zg_b || a->local_p_ref) && a->tas_b && a->hurs_b &&
          a->pshist_b, "delta record pointer is NULL");
@@ -2134,6 +2183,8 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     NEED(ctx, !ref || ctx->opt[PGW_OPT_QUAD], "ref_dtype = 1 needs the quad kernel (PGW_OPT_QUAD = 1)");
     const int N = a->nlev;
     int rc;
+    ZgAxis zax = {0, nullptr};                            // local_p_ref: checked before anything is launched
+    if (a->local_p_ref && (rc = zg_axis(ctx, a, &zax))) return rc;
     int qv_done = 0;          // leading levels whose final QV the quad kernel has already written
     // PGW_OPT_FUSED_FIRST: the quad kernel runs the first two scans of the multi-pass loop with a fixed p_ref.  float64
     // storage only: the float32 instantiations of the quad kernel lose more than the loop kernel gains
@@ -2219,14 +2270,14 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
                     const PairSrc<T> dwd = pair_src<T>(a->ua_b, a->ua_a, a->va_b, a->va_a, a->x_hi, a->x_new);
                     // O: arrays below 4 GiB (a 0.25 deg L137 field is 1.1 GB): 32-bit byte offsets from uniform bases
                     // LERP: the instant lies between two records (false: it is a record); FUSE: fused_first
-                    auto launch = [&](auto o_, auto lerp_, auto fuse_) {
-                        hipLaunchKernelGGL((k_delta_quad<T, TL, QUAD_U, QUAD_TPB, decltype(o_), decltype(lerp_)::value != 0, decltype(ref_)::value, decltype(fuse_)::value>),
-                                           dim3(nblocks((long long)ntime * ncol, QUAD_TPB)), dim3(QUAD_TPB), qlds, ctx->stream, ctx->plev_tab,
+                    auto launch = [&](auto o_, auto lerp_, auto fuse_) { with_plev(ctx, [&](const auto &pt) {
+                        hipLaunchKernelGGL((k_delta_quad<T, TL, QUAD_U, QUAD_TPB, decltype(o_), decltype(lerp_)::value != 0, decltype(ref_)::value, decltype(fuse_)::value, false, std::decay_t<decltype(pt)>>),
+                                           dim3(nblocks((long long)ntime * ncol, QUAD_TPB)), dim3(QUAD_TPB), qlds, ctx->stream, pt,
                                            lv, ntime, ncol, (const T *)a->T, (const T *)a->QV, (const T *)a->U, (const T *)a->V,
                                            (const T *)a->PS, dth, ds, ph, dwd, check_top, (TL *)a->T_out, (TL *)evap,
                                            (TL *)a->hur_pgw_out, (TL *)a->U_out, (TL *)a->V_out, (TL *)a->QV_out, qv_done, ctx->n_pure,
                                            ctx->d_status, a->p_ref, d_ff);
-                    };
+                    }); };
                     const bool o32 = !ctx->opt[PGW_OPT_FORCE_OFF64] &&
                                      (unsigned long long)ntime * (N > S ? N : S) * ncol * sizeof(TL) < (1ull << 32);
                     with_offsets(o32, [&](auto o_) { with_int<2>(a->x_hi != 0.0, [&](auto lerp_) {
@@ -2244,26 +2295,26 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
             const unsigned int grid = nblocks((long long)ntime * ncol, 128);
             {
                 Prof pr(ctx, PGW_K_THERMO_DELTA);
-                with_type(dtype, [&](auto t_) {
+                with_type(dtype, [&](auto t_) { with_plev(ctx, [&](const auto &pt) {
                     using T = decltype(t_);
-                    hipLaunchKernelGGL((k_delta_pair<T, 1, true, 2, 128>), dim3(grid), dim3(128), lds, ctx->stream, ctx->plev_tab, lv, ntime,
+                    hipLaunchKernelGGL((k_delta_pair<T, 1, true, 2, 128, std::decay_t<decltype(pt)>>), dim3(grid), dim3(128), lds, ctx->stream, pt, lv, ntime,
                                        ncol, (const T *)a->T, (const T *)a->QV, (const T *)a->PS,
                                        pair_src<T>(a->ta_b, a->ta_a, a->hur_b, a->hur_a, a->x_hi, a->x_new),
                                        pair_src<T>(a->tas_b, a->tas_a, a->hurs_b, a->hurs_a, a->x_hi, a->x_new),
                                        delta_src<T>(a->pshist_b, a->pshist_a, a->x_hi, a->x_new), check_top, (T *)a->T_out, (T *)evap,
                                        (T *)a->hur_pgw_out, ctx->d_status);
-                });
+                }); });
             }
             {
                 Prof pr(ctx, PGW_K_WIND_DELTA);
-                with_type(dtype, [&](auto t_) {
+                with_type(dtype, [&](auto t_) { with_plev(ctx, [&](const auto &pt) {
                     using T = decltype(t_);
-                    hipLaunchKernelGGL((k_delta_pair<T, 1, false, PAIR_U, 128>), dim3(grid), dim3(128), lds, ctx->stream, ctx->plev_tab, lv,
+                    hipLaunchKernelGGL((k_delta_pair<T, 1, false, PAIR_U, 128, std::decay_t<decltype(pt)>>), dim3(grid), dim3(128), lds, ctx->stream, pt, lv,
                                        ntime, ncol, (const T *)a->U, (const T *)a->V, (const T *)a->PS,
                                        pair_src<T>(a->ua_b, a->ua_a, a->va_b, a->va_a, a->x_hi, a->x_new),
                                        pair_src<T>(nullptr, nullptr, nullptr, nullptr, 0.0, 0.0), delta_src<T>(nullptr, nullptr, 0.0, 0.0),
                                        check_top, (T *)a->U_out, (T *)a->V_out, (T *)nullptr, ctx->d_status);
-                });
+                }); });
             }
             HIPCHK(ctx, hipGetLastError());
         }
@@ -2286,7 +2337,7 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     la.p_ref = a->p_ref; la.adj_factor = a->adj_factor; la.thresh = a->thresh; la.max_n_iter = a->max_n_iter;
     la.ps_pgw = a->PS_out; la.hus_pgw = a->QV_out;
     la.n_iter = &a->n_iter; la.max_err_hist = a->max_err_hist; la.hist_len = 32;
-    if (a->local_p_ref) { la.local_nplev = a->nplev; la.plev_file = a->plev; }
+    if (a->local_p_ref) { la.local_nplev = zax.n; la.plev_file = zax.plev; }
     la.status_armed = !check_top && !a->local_p_ref;
     la.qv_done_levels = qv_done; la.ref = ref; la.fused_first = fused_first;
     la.qv_from_pass = ctx->opt[PGW_OPT_QUAD] != 0;
@@ -2869,7 +2920,7 @@ extern "C" int pgw_vert_interp_delta_mixed(pgw_ctx *ctx, int dt_delta, int dt_sf
          "dtype tags must be PGW_F32 or PGW_F64");
     NEED(ctx, dt_targ == PGW_F64, "pgw_vert_interp_delta_mixed: float32 target pressures (a float32 logarithm) are not instantiated");
     NEED(ctx, ntime >= 1 && ncol >= 1 && nlev_t >= 1, "ntime, nlev_t and ncol must be positive");
-    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV, "nplev must be in [2, 64]");
+    NEED(ctx, nplev >= 2 && nplev <= MAX_PLEV_WIDE, PLEV_RANGE_2);
     NEED(ctx, plev && delta && targ_P && out, "null pointer");
     NEED(ctx, (delta_sfc == nullptr) == (ps_hist == nullptr), "delta_sfc and ps_hist must be given together");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2884,26 +2935,26 @@ extern "C" int pgw_vert_interp_delta_mixed(pgw_ctx *ctx, int dt_delta, int dt_sf
     if (!delta_sfc) { dt_sfc = dt_delta; dt_pshist = PGW_F64; }
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        with_type(dt_delta, [&](auto d_) { with_type(dt_add, [&](auto a_) {
-            using TD = decltype(d_); using TA = decltype(a_);
+        with_type(dt_delta, [&](auto d_) { with_type(dt_add, [&](auto a_) { with_plev(ctx, [&](const auto &pt) {
+            using TD = decltype(d_); using TA = decltype(a_); using PT = std::decay_t<decltype(pt)>;
             const DeltaSrc<TD> d = delta_src<TD>(delta, nullptr, 0.0, 0.0);           // the records of the instant itself
             if (!delta_sfc) {
                 const DeltaSrc<TD> s = delta_src<TD>(nullptr, nullptr, 0.0, 0.0);
                 const DeltaSrc<double> p = delta_src<double>(nullptr, nullptr, 0.0, 0.0);
-                hipLaunchKernelGGL((k_vert_interp_delta<TD, double, double, false, TA, TD, double>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
-                                   0, ctx->stream, ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const double *)targ_P,
+                hipLaunchKernelGGL((k_vert_interp_delta<TD, double, double, false, TA, TD, double, PT>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
+                                   0, ctx->stream, pt, lv, ntime, nlev_t, ncol, d, s, p, (const double *)targ_P,
                                    (const double *)nullptr, ignore_top ? 0 : 1, (const TA *)add_to, out, ctx->d_status);
             } else {
                 with_type(dt_sfc, [&](auto s_) { with_type(dt_pshist, [&](auto h_) {
                     using TS = decltype(s_); using TH = decltype(h_);
                     const DeltaSrc<TS> s = delta_src<TS>(delta_sfc, nullptr, 0.0, 0.0);
                     const DeltaSrc<TH> p = delta_src<TH>(ps_hist, nullptr, 0.0, 0.0);
-                    hipLaunchKernelGGL((k_vert_interp_delta<TD, double, double, true, TA, TS, TH>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
-                                       0, ctx->stream, ctx->plev_tab, lv, ntime, nlev_t, ncol, d, s, p, (const double *)targ_P,
+                    hipLaunchKernelGGL((k_vert_interp_delta<TD, double, double, true, TA, TS, TH, PT>), dim3(nblocks(total, BLOCK)), dim3(BLOCK),
+                                       0, ctx->stream, pt, lv, ntime, nlev_t, ncol, d, s, p, (const double *)targ_P,
                                        (const double *)nullptr, ignore_top ? 0 : 1, (const TA *)add_to, out, ctx->d_status);
                 }); });
             }
-        }); });
+        }); }); });
     }
     HIPCHK(ctx, hipGetLastError());
     rc = status_check(ctx);
@@ -2916,21 +2967,21 @@ extern "C" int pgw_replace_delta_sfc_mixed(pgw_ctx *ctx, int dt_delta, int dt_sf
                                            const void *ps_hist, double *out_P, void *out_delta) {
     NEED(ctx, TAG_OK(dt_delta) && TAG_OK(dt_sfc) && TAG_OK(dt_pshist), "dtype tags must be PGW_F32 or PGW_F64");
     NEED(ctx, ntime >= 1 && ncol >= 1, "ntime and ncol must be positive");
-    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV, "nplev must be in [1, 64]");
+    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV_WIDE, PLEV_RANGE_1);
     NEED(ctx, plev_asc && delta && delta_sfc && ps_hist && out_P && out_delta, "null pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const PlevTable t = ascending_plev_table(nplev, plev_asc);
+    const PlevTableWide tw = ascending_plev_table(nplev, plev_asc);
     int rc = status_reset(ctx);
     if (rc) return rc;
     const long long total = (long long)ntime * ncol;
     {
         Prof pr(ctx, PGW_K_VERT_INTERP_DELTA);
-        with_type(dt_delta, [&](auto d_) { with_type(dt_sfc, [&](auto s_) { with_type(dt_pshist, [&](auto h_) {
+        with_type(dt_delta, [&](auto d_) { with_type(dt_sfc, [&](auto s_) { with_type(dt_pshist, [&](auto h_) { with_plev(tw, [&](const auto &pt) {
             using TD = decltype(d_); using TS = decltype(s_); using TH = decltype(h_);
-            hipLaunchKernelGGL((k_replace_delta_sfc<TD, TS, TH, double>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, t,
+            hipLaunchKernelGGL((k_replace_delta_sfc<TD, TS, TH, double, std::decay_t<decltype(pt)>>), dim3(nblocks(total, BLOCK)), dim3(BLOCK), 0, ctx->stream, pt,
                                ntime, ncol, (const TD *)delta, (const TS *)delta_sfc, (const TH *)ps_hist, out_P, (TD *)out_delta,
                                ctx->d_status);
-        }); }); });
+        }); }); }); });
     }
     HIPCHK(ctx, hipGetLastError());
     return status_check(ctx);

@@ -1380,13 +1380,29 @@ __global__ __launch_bounds__(BLOCK) void k_time_lerp(long long n, const TB *__re
 // ps_hist, so nothing is staged: ln(plev) is a scalar table, delta values are gathered from
 // the two bracketing records as the scan advances (each source level is read ~once).
 // =====================================================================================
+// The table's capacity is a compile-time property of every kernel that takes one (template parameter PT, last in each
+// list, default the narrow table): the tuned kernels read it with scalar loads and stage `lnp` into an LDS array of CAP
+// entries, so a kernel built for 64 entries is the same code whatever else exists.  The host picks the wide
+// instantiation only for an axis of more than MAX_PLEV levels (pgw_capi.hip: with_plev).
+//   MAX_PLEV       narrow table: zg's axis (k_local_p_ref, LocalPRef, pgw_geopot_on_plev) and every delta axis that fits
+//   MAX_PLEV_WIDE  the cap of a delta axis (ta / hur / ua / va; the reference's step_01 writes 99 levels).  2 x 128 doubles
+//                  are 2 KB of the 4 KB of kernel arguments HIP allows; a longer axis needs a table in device memory.
 constexpr int MAX_PLEV = 64;
-struct PlevTable {
-    double p[MAX_PLEV];      // ascending-index order (file order reversed, :383-384)
-    double lnp[MAX_PLEV];
+constexpr int MAX_PLEV_WIDE = 128;
+template <int CAP_>
+struct PlevTableT {
+    static constexpr int CAP = CAP_;
+    double p[CAP_];          // ascending-index order (file order reversed, :383-384)
+    double lnp[CAP_];
     double pmax, pmin;
     int n;
 };
+using PlevTable = PlevTableT<MAX_PLEV>;
+using PlevTableWide = PlevTableT<MAX_PLEV_WIDE>;
+// every by-value argument of a kernel together must stay below HIP's 4 KB: asserted where a kernel takes a table
+constexpr size_t KERNARG_LIMIT = 4096;
+// upper bound of the argument block of a kernel with parameters A...: every argument padded to 8 bytes
+template <typename... A> constexpr size_t kernarg_bytes() { return (0 + ... + ((sizeof(A) + 7) & ~(size_t)7)); }
 
 template <typename T>
 struct DeltaSrc {
@@ -1447,9 +1463,10 @@ __device__ __forceinline__ void top_pressure_report(double min_t, double min_s, 
 }
 
 // One table of the by-value PlevTable (p or lnp) into LDS, for lanes that index it with their own (divergent) scan
-// position.  The caller synchronises afterwards.
-__device__ __forceinline__ void stage_plev(const double (&tab)[MAX_PLEV], double *lds, int nthreads) {
-    for (int i = threadIdx.x; i < MAX_PLEV; i += nthreads) lds[i] = tab[i];
+// position.  The caller synchronises afterwards.  All CAP entries of the table are copied: `lds` holds CAP doubles.
+template <int CAP>
+__device__ __forceinline__ void stage_plev(const double (&tab)[CAP], double *lds, int nthreads) {
+    for (int i = threadIdx.x; i < CAP; i += nthreads) lds[i] = tab[i];
 }
 
 // replace_delta_sfc (functions.py:356-365) for one column: the source level `ksfc` that moves to ps_hist (-1: none) and
@@ -1463,8 +1480,8 @@ __device__ __forceinline__ void stage_plev(const double (&tab)[MAX_PLEV], double
 // tests/test_surface_rule_edges.py holds the three texts together: ps_hist on a level, one ulp beside it, above all levels,
 // on min(plev) and NaN, and NaN deltas below the ground, through every kernel that carries the rule.
 struct SfcLevel { int ksfc; bool fill; };
-template <typename P>
-__device__ __forceinline__ SfcLevel sfc_level(const PlevTable &pt, const P &p, double pshv, DevStatus *st, long long col) {
+template <typename PT, typename P>
+__device__ __forceinline__ SfcLevel sfc_level(const PT &pt, const P &p, double pshv, DevStatus *st, long long col) {
     const int S = pt.n;
     SfcLevel r{-1, false};
     bool bad = false;
@@ -1509,8 +1526,8 @@ struct DeltaColumn {
     double y_lo = 0.0, y_hi = 0.0;
 
     // surface insertion from (sfc, psh) of column `flat`, and with check_top the column's source minimum
-    template <typename TS, typename TH, typename P>
-    __device__ __forceinline__ void insert_sfc(const PlevTable &pt, const P &s_p, const DeltaSrc<TS> &sfc, const DeltaSrc<TH> &psh,
+    template <typename PT, typename TS, typename TH, typename P>
+    __device__ __forceinline__ void insert_sfc(const PT &pt, const P &s_p, const DeltaSrc<TS> &sfc, const DeltaSrc<TH> &psh,
                                                long long flat, const double *logtab, int check_top, double &min_s,
                                                int &nanflag, DevStatus *st) {
         double pshv = 0.0;
@@ -1560,17 +1577,19 @@ struct DeltaColumn {
 // TO = double is the reference's dtype flow: the surface delta is stored in the delta's dtype (np.vectorize keeps it,
 // functions.py:343-366), ps_hist enters the float64 source pressures, `src_y[i2] - src_y[i1]` is a float32 subtraction
 // (numba, :575-578) and everything else float64.
-template <typename TD, typename TP, typename TO, bool HAS_SFC, typename TA = TO, typename TS = TD, typename TH = TP>
-__global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PlevTable pt, Levels lv, int ntime, int N, long long ncol,
+template <typename TD, typename TP, typename TO, bool HAS_SFC, typename TA = TO, typename TS = TD, typename TH = TP, typename PT = PlevTable>
+__global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PT pt, Levels lv, int ntime, int N, long long ncol,
                                                              DeltaSrc<TD> dsrc, DeltaSrc<TS> sfc, DeltaSrc<TH> psh,
                                                              const TP *__restrict__ trgP, const TP *__restrict__ ps,
                                                              int check_top, const TA *__restrict__ add_to,
                                                              TO *__restrict__ out, DevStatus *st) {
     constexpr bool DY32 = sizeof(TD) == 4 && sizeof(TO) == 8;
+    static_assert(kernarg_bytes<PT, Levels, int, int, long long, DeltaSrc<TD>, DeltaSrc<TS>, DeltaSrc<TH>, void *, void *, int, void *,
+                                void *, void *>() <= KERNARG_LIMIT, "kernel arguments");
     __shared__ double s_mint[BLOCK / 64], s_mins[BLOCK / 64];
     __shared__ int s_nan[BLOCK / 64];
     // plev / ln(plev) staged in LDS: lanes index them with their own (divergent) scan position
-    __shared__ double s_p[MAX_PLEV], s_lnp[MAX_PLEV];
+    __shared__ double s_p[PT::CAP], s_lnp[PT::CAP];
     __shared__ double s_lev[LEVTAB_DOUBLES];
     // the delta kernels take every logarithm from pgw_log_tab - like k_log_table, which makes ln(plev): the exact-hit test
     // `src_x == targ_x` (functions.py:540) compares values of ONE implementation
@@ -1639,15 +1658,17 @@ __global__ __launch_bounds__(BLOCK) void k_vert_interp_delta(PlevTable pt, Level
 // three-value window (level j-1, j and the raw value of j+1 in flight): the two pressure sets differ by the loop's
 // surface-pressure increment, so the bracket of target level l lies next to source level l.  Selection rule and lerp
 // arithmetic are interp_extrap_1d's (functions.py:527-578, 'constant'); all logarithms from pgw_log_tab.
-template <typename T, bool HAS_SFC>
-__global__ __launch_bounds__(BLOCK) void k_reinterp_field(PlevTable pt, Levels lv, int ntime, long long ncol,
+template <typename T, bool HAS_SFC, typename PT = PlevTable>
+__global__ __launch_bounds__(BLOCK) void k_reinterp_field(PT pt, Levels lv, int ntime, long long ncol,
                                                           DeltaSrc<T> dsrc, DeltaSrc<T> sfc, DeltaSrc<T> psh,
                                                           const T *__restrict__ era_field, const T *__restrict__ ps_era,
                                                           const T *__restrict__ ps_pgw, int check_top,
                                                           T *__restrict__ out, DevStatus *st) {
+    static_assert(kernarg_bytes<PT, Levels, int, long long, DeltaSrc<T>, DeltaSrc<T>, DeltaSrc<T>, void *, void *, void *, int, void *,
+                                void *>() <= KERNARG_LIMIT, "kernel arguments");
     __shared__ double s_mint[BLOCK / 64], s_mins[BLOCK / 64];
     __shared__ int s_nan[BLOCK / 64];
-    __shared__ double s_p[MAX_PLEV], s_lnp[MAX_PLEV];
+    __shared__ double s_p[PT::CAP], s_lnp[PT::CAP];
     __shared__ double s_lev[LEVTAB_DOUBLES];
     LevTab lt = stage_levels<false, true>(lv, s_lev, BLOCK);
     const int N = lv.nlev;
@@ -1747,15 +1768,17 @@ constexpr int RING = 8, RING_LEAD = 4;
 // the time interpolation in float32 (DeltaSrc::get<REF>), numba's `src_y[i2] - src_y[i1]` of interp_extrap_1d in the dtype
 // of the source (float32 for an ERA field of the file, float64 for RELHUM; for the deltas float32 only when the instant is
 // a record, functions.py:282-283, 575-578), everything else float64.
-template <typename T, bool HAS_SFC, typename O, bool EVAP = false, typename TE0 = T, typename TE1 = T, typename TO = T, bool REF = false>
-__global__ __launch_bounds__(BLOCK, (EVAP ? RP_MINW_EVAP : RP_MINW)) void k_reinterp_pair(PlevTable pt, Levels lv, int ntime, long long ncol,
+template <typename T, bool HAS_SFC, typename O, bool EVAP = false, typename TE0 = T, typename TE1 = T, typename TO = T, bool REF = false, typename PT = PlevTable>
+__global__ __launch_bounds__(BLOCK, (EVAP ? RP_MINW_EVAP : RP_MINW)) void k_reinterp_pair(PT pt, Levels lv, int ntime, long long ncol,
                                                             ReinterpPair<T, TE0, TE1, TO> rv,
                                                             DeltaSrc<T> psh, const T *__restrict__ ps_era,
                                                             const T *__restrict__ ps_pgw, int check_top, DevStatus *st) {
+    static_assert(kernarg_bytes<PT, Levels, int, long long, ReinterpPair<T, TE0, TE1, TO>, DeltaSrc<T>, void *, void *, int, void *>() <=
+                  KERNARG_LIMIT, "kernel arguments");
     extern __shared__ double lds_rp[];               // akm[N] | bkm[N]
     __shared__ double s_mint[BLOCK / 64], s_mins[BLOCK / 64];
     __shared__ int s_nan[BLOCK / 64];
-    __shared__ double s_p[MAX_PLEV], s_lnp[MAX_PLEV];
+    __shared__ double s_p[PT::CAP], s_lnp[PT::CAP];
     __shared__ double s_logt[2 * LOG_TABLE_N];
     // slot RING: see era_at.  Not for float64 fields without `e` (RP_SPARE): that instantiation runs 4 blocks per CU, and the
     // ninth slot (2 x 2 KB) would cost it one of them.
@@ -1976,17 +1999,19 @@ struct PairSrc {       // the two variables of a pair
 // measured 25 % slower: 2.44 vs 1.85 ms).
 // THERMO: 4 waves/SIMD (VGPR <= 128) with 2-level chunks measured 6 % faster than 3 waves with 4-level
 // chunks (fp64-VALU/latency bound); the wind pair is HBM bound and prefers the deeper prefetch.
-template <typename T, int V, bool THERMO, int U, int TPB>
-__global__ __launch_bounds__(TPB, THERMO ? 4 : 1) void k_delta_pair(PlevTable pt, Levels lv, int ntime, long long ncol,
+template <typename T, int V, bool THERMO, int U, int TPB, typename PT = PlevTable>
+__global__ __launch_bounds__(TPB, THERMO ? 4 : 1) void k_delta_pair(PT pt, Levels lv, int ntime, long long ncol,
                                                     const T *__restrict__ fa, const T *__restrict__ fb,
                                                     const T *__restrict__ PS,
                                                     PairSrc<T> d3, PairSrc<T> dsfc, DeltaSrc<T> psh,
                                                     int check_top, T *__restrict__ out_a, T *__restrict__ out_b,
                                                     T *__restrict__ out_hur, DevStatus *st) {
+    static_assert(kernarg_bytes<PT, Levels, int, long long, void *, void *, void *, PairSrc<T>, PairSrc<T>, DeltaSrc<T>, int, void *,
+                                void *, void *, void *>() <= KERNARG_LIMIT, "kernel arguments");
     extern __shared__ double lds_pair[];            // akm[N] | bkm[N]
     __shared__ double s_mint[TPB / 64], s_mins[TPB / 64];
     __shared__ int s_nan[TPB / 64];
-    __shared__ double s_lnp[MAX_PLEV];
+    __shared__ double s_lnp[PT::CAP];
     __shared__ double s_logt[2 * LOG_TABLE_N];
     const int S = pt.n;
     double *s_akm = lds_pair, *s_bkm = s_akm + lv.nlev;
@@ -2193,8 +2218,8 @@ struct FusedFirst {
 };
 
 // DELTAS (k_delta_fields below): the same walk, but the four deltas themselves are the output.
-template <typename T, typename TO, int U, int TPB, typename O, bool LERP, bool REF, bool FUSE, bool DELTAS = false>
-__global__ __launch_bounds__(TPB, (sizeof(T) == 4 || DELTAS ? QUAD_MINW_F32 : QUAD_MINW)) void k_delta_quad(PlevTable pt, Levels lv, int ntime, long long ncol,
+template <typename T, typename TO, int U, int TPB, typename O, bool LERP, bool REF, bool FUSE, bool DELTAS = false, typename PT = PlevTable>
+__global__ __launch_bounds__(TPB, (sizeof(T) == 4 || DELTAS ? QUAD_MINW_F32 : QUAD_MINW)) void k_delta_quad(PT pt, Levels lv, int ntime, long long ncol,
                                                        const T *__restrict__ fT, const T *__restrict__ fQ,
                                                        const T *__restrict__ fU, const T *__restrict__ fV,
                                                        const T *__restrict__ PS,
@@ -2211,11 +2236,15 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 || DELTAS ? QUAD_MINW_F32 : QU
     // n_pure_lv: number of leading pure-pressure levels (n_pure is 0 when the QV shortcut is off); their pressure akm[l]
     // is the same in every column, so ln(akm[l]) is taken once per block instead of once per column and level
     static_assert(!(DELTAS && FUSE), "the deltas-only instantiation has no ERA state to scan");
+    // the widest argument block of the library: a table beside four record pairs (2.5 KB with the 128-entry table)
+    static_assert(kernarg_bytes<PT, Levels, int, long long, void *, void *, void *, void *, void *, PairSrc<T>, PairSrc<T>, DeltaSrc<T>,
+                                PairSrc<T>, int, void *, void *, void *, void *, void *, void *, int, int, void *, double, void *>() <=
+                  KERNARG_LIMIT, "kernel arguments");
     extern __shared__ double lds_quad[];            // akm[N] | bkm[N] | ln(akm)[N] (first n_pure_lv entries) | ak[N+1] | bk[N+1]
     __shared__ double s_lnpref;                     // pgw_log(p_ref)
     __shared__ double s_mint[TPB / 64], s_mins[TPB / 64];
     __shared__ int s_nan[TPB / 64];
-    __shared__ double s_lnp[MAX_PLEV];
+    __shared__ double s_lnp[PT::CAP];
     __shared__ double s_logt[2 * LOG_TABLE_N];      // table of pgw_log_tab: every logarithm of the delta kernels (see k_vert_interp_delta)
     const int S = pt.n;
     double *s_akm = lds_quad, *s_bkm = lds_quad + lv.nlev, *s_lnpa = lds_quad + 2 * lv.nlev;
@@ -2509,8 +2538,8 @@ __global__ __launch_bounds__(TPB, (sizeof(T) == 4 || DELTAS ? QUAD_MINW_F32 : QU
 // functions.py:472-473: float64 on float32 files too; oE, oQ unused).  With no prefetched rows to hold, the level loop is
 // not chunked (U = 1), four waves fit for every storage type and the plain-axis bracket's reciprocal is hoisted for all.
 // -------------------------------------------------------------------------------------
-template <typename T, typename O, bool LERP, bool REF>
-constexpr auto k_delta_fields = k_delta_quad<T, double, 1, 128, O, LERP, REF, false, true>;
+template <typename T, typename O, bool LERP, bool REF, typename PT = PlevTable>
+constexpr auto k_delta_fields = k_delta_quad<T, double, 1, 128, O, LERP, REF, false, true, PT>;
 
 // =====================================================================================
 // a10  bilinear regridding (lat then lon)                      functions.py:817-893
@@ -2870,12 +2899,13 @@ __device__ __forceinline__ double soil_delta(const SoilTable &soil, int s, doubl
 // T: the delta (and its output column); TS / TH: delta_sfc and ps_hist; TP: the pressure output.  The surface delta is
 // stored in the delta's dtype and ps_hist in the pressures' (np.vectorize allocates its outputs from the first call's
 // dtypes: float64 pressures, the delta's own type).
-template <typename T, typename TS = T, typename TH = T, typename TP = T>
-__global__ __launch_bounds__(BLOCK) void k_replace_delta_sfc(PlevTable pt, int ntime, long long ncol,
+template <typename T, typename TS = T, typename TH = T, typename TP = T, typename PT = PlevTable>
+__global__ __launch_bounds__(BLOCK) void k_replace_delta_sfc(PT pt, int ntime, long long ncol,
                                                              const T *__restrict__ delta, const TS *__restrict__ dsfc,
                                                              const TH *__restrict__ pshist, TP *__restrict__ outP,
                                                              T *__restrict__ outD, DevStatus *st) {
-    __shared__ double s_p[MAX_PLEV];
+    static_assert(kernarg_bytes<PT, int, long long, void *, void *, void *, void *, void *, void *>() <= KERNARG_LIMIT, "kernel arguments");
+    __shared__ double s_p[PT::CAP];
     const int S = pt.n;
     stage_plev(pt.p, s_p, BLOCK);
     __syncthreads();
@@ -3017,7 +3047,13 @@ template <typename TL, bool REF> constexpr bool QV_FROM_PASS = sizeof(TL) == 8;
 // when the level changed, it depends on nothing else) and g * dzg at it (:292-295).  `zg` then holds the full
 // (nplev, ncol) records, `pt.p` the plev coordinate in file order, `p_ref_col` / `p_idx_col` the per-column memory that a
 // continuation launch resumes from.  One column per lane (V = 1).
+// The table is zg's plev axis, which is not the axis of ta / hur / ua / va when zg comes from another file (CFday: 99
+// levels against Emon / Amon's 19 to 34).  It stays the narrow table: the loop kernel sits on its register budget
+// (MULTI_MINW) and a zg file has no more levels than that.
 struct LocalPRef { PlevTable pt; double akN, bkN; double *p_ref_col; int *p_idx_col; };
+static_assert(kernarg_bytes<LocalPRef, Levels, int, long long, void *, void *, void *, void *, void *, void *, DeltaSrc<double>, void *,
+                            void *, void *, void *, void *, double, double, int, int, void *, void *, void *, void *, void *, int,
+                            void *>() <= KERNARG_LIMIT, "k_ps_loop_multi: kernel arguments");
 
 template <typename T, typename TL, int V, int U, bool REF, bool LOCAL, bool FLAGGED = false>
 __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, int ntime, long long ncol,

@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from ._lib import _dp, _ip
+from ._lib import _dp, _ip, check_nplev
 from .constants import CON_G, CON_RD, CON_MW_MD   # noqa: F401  (re-exported like the reference)
 from .device import DeviceArray, default_context, dtype_tag, ptr
 from .operands import (F64, aligned, check_extrapolate, common_dtype, dev, dev_own, fit, float_dtype, is_labelled, out_like,
@@ -323,6 +323,7 @@ def replace_delta_sfc(source_P, ps_hist, delta, delta_sfc):
         len(source_P)                                       # flow and in the cast below in the other: each keeps its own
     P = np.ascontiguousarray(source_P, dtype=F64)           # read on the host; float64 in both flows
     S = len(P)
+    check_nplev(S, 1, 'len(source_P)')
     d_d, d_s, d_p = ops.dev('delta', (1, S, 1)), ops.dev('delta_sfc', (1, 1)), ops.dev('ps_hist', (1, 1))
     oP, oD = (ctx.empty((1, S, 1), dt) for dt in ops.result)
     tail = (1, S, 1, P.ctypes.data_as(_dp), d_d.ptr, d_s.ptr, d_p.ptr, oP.ptr, oD.ptr)
@@ -356,6 +357,7 @@ def vert_interp_delta(delta, target_P, delta_sfc=None, ps_hist=None, ignore_top_
     if (delta_sfc is None) != (ps_hist is None):
         raise ValueError('delta_sfc and ps_hist must be given together')
     nt, S, ncol, N, s3 = sd[0], sd[1], sd[2] * sd[3], st[1], (sd[0], sd[2], sd[3])
+    check_nplev(S)                                          # 2 to 128 levels, before anything reaches the device
     # the common dtype is decided on the caller's add_to: `fit` keeps an operand's dtype, so the fitted one decides the same
     ops = OperandPlan(ctx, 'vert_interp_delta', delta=delta, target_P=target_P, delta_sfc=delta_sfc, ps_hist=ps_hist,
                       add_to=None if add_to is None else fit(add_to, st, 'add_to'))

@@ -360,12 +360,22 @@ def _file_args(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p
     a = _lib.FileArgs()
     a.per_var_time = 1                                              # every delta file is bracketed on its own time axis
     a.i_reinterp = 1 if i_reinterp else 0
+    _lib.check_nplev(len(plev))                                     # before anything is copied or launched
+    plev_zg = deltas.plev_zg
+    if not (isinstance(plev_zg, np.ndarray) and plev_zg.dtype == np.float64 and plev_zg.flags.c_contiguous):
+        plev_zg = deltas.plev_zg = np.ascontiguousarray(plev_zg, dtype=np.float64)       # once: the DeltaSet keeps the table
+    if local_p_ref:
+        _lib.check_nplev_zg(len(plev_zg))
     zb, za, a.zg_x_hi, a.zg_x_new = deltas.pair('zg', target_dt, buf)
     if local_p_ref:
-        if len(deltas.plev_zg) != len(plev) or np.any(deltas.plev_zg != plev):
-            raise NotImplementedError('p_ref_inp = None with a zg delta on other pressure levels than ta / hur / ua / va')
+        # the candidates for the reference level are zg's plev (step_03:219-222) and the zg delta is selected on that
+        # axis (:292-295): it need not be the axis of ta / hur / ua / va (CFday: 99 levels against Emon / Amon's)
+        if zb.shape[-3] != len(plev_zg):
+            raise ValueError('the zg delta has %d levels, its plev axis %d' % (zb.shape[-3], len(plev_zg)))
         a.local_p_ref = 1
         a.zg3_b, a.zg3_a = zb.ptr, za.ptr
+        a.nplev_zg = len(plev_zg)
+        a.plev_zg = plev_zg.ctypes.data
     else:
         kref = np.nonzero(deltas.plev_zg == p_ref)[0]               # .sel(plev=p_ref), step_03:294
         if len(kref) != 1:
@@ -389,7 +399,7 @@ def _file_args(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_error, p
         held += [b_, a_]
         setattr(a, name + '_b', b_.ptr)
         setattr(a, name + '_a', a_.ptr)
-    held += [zb, za, plev]
+    held += [zb, za, plev, plev_zg]
     if 'FR_SEA_ICE' in era and 'siconc' in deltas:                  # surface riders, step_03:103-146
         soil = np.ascontiguousarray(coeffs['soil1'], dtype=np.float64)
         held.append(soil)
@@ -474,9 +484,7 @@ def _make_file_plan(ctx, era, coeffs, deltas, target_dt, ignore_top_pressure_err
     local_p_ref = (p_ref is None) or (p_ref == 'local')
     zg = deltas.dev['zg']
     if local_p_ref:
-        if len(deltas.plev_zg) != len(deltas.plev) or np.any(deltas.plev_zg != deltas.plev):
-            return None
-        ref_offset = 0
+        ref_offset = 0                                              # the full records, on zg's own plev axis (args.plev_zg)
     else:
         kref = np.nonzero(deltas.plev_zg == p_ref)[0]
         if len(kref) != 1:
@@ -663,8 +671,13 @@ def _band_of(arrays, j0, j1):
 
 
 def pgw_for_era5_arrays(era, deltas, delta_times, plev, target_dt, ignore_top_pressure_error=False,
-                        p_ref=None, dtype=None, i_reinterp=False, ref_dtype=None, band=None, reduce_max=None, resident=None):
+                        p_ref=None, dtype=None, i_reinterp=False, ref_dtype=None, band=None, reduce_max=None, resident=None,
+                        plev_zg=None):
     """Whole-file path on in-memory host arrays (upload, compute on the GPU, download).
+
+    plev (file order, 2 to 128 levels) is the axis of ta / hur / ua / va; plev_zg, when given, the axis of deltas['zg']
+    (zg_delta.nc may come from another table: CFday ta beside Emon / Amon zg).  A fixed p_ref must be one of its levels;
+    with p_ref = None / 'local' its levels (at most 64) are the candidates for the per-column reference level.
 
     band = (rank, world): this process handles latitude band `rank` of `world` of the file (parallel.band_rows) and
     returns that band's rows; `reduce_max` (parallel.band_max_hook) makes the loop's stopping test global, so the bands
@@ -682,17 +695,20 @@ def pgw_for_era5_arrays(era, deltas, delta_times, plev, target_dt, ignore_top_pr
         ctx.set_reduce_hook(reduce_max)
         try:
             return pgw_for_era5_arrays(era, deltas, delta_times, plev, target_dt, ignore_top_pressure_error, p_ref, dtype,
-                                       i_reinterp, ref_dtype, resident=resident)
+                                       i_reinterp, ref_dtype, resident=resident, plev_zg=plev_zg)
         finally:
             ctx.set_reduce_hook(None)
     if dtype is None:
         dtype = np.asarray(era['T']).dtype
     dtype = np.dtype(dtype)
     try:
+        _lib.check_nplev(len(plev))
         if isinstance(delta_times, dict):                 # one time axis per delta file, like the reference's load_delta
             ds = DeltaSet(ctx, deltas, delta_times.get('ta'), plev, dtype, times_by_var=delta_times, resident=resident)
         else:
             ds = DeltaSet(ctx, deltas, delta_times, plev, dtype, resident=resident)
+        if plev_zg is not None:
+            ds.plev_zg = np.ascontiguousarray(plev_zg, dtype=np.float64)
         e = _upload_era(ctx, era, dtype)
         coeffs = dict(ak=era['ak'], bk=era['bk'], akm=era.get('akm'), bkm=era.get('bkm'), soil1=era['soil1'])
         if os.environ.get('PGW_TEST_FAIL_SETUP') == os.environ.get('RANK', '0') and ctx.has_reduce_hook():

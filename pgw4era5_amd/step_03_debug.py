@@ -117,6 +117,7 @@ def delta_fields_device(ctx, ps, deltas, target_dt, nlev, ref, ignore_top_pressu
             scratch[name] = ctx.empty(shape, dtype)
         return scratch[name]
 
+    _lib.check_nplev(len(deltas.plev))
     _, _, x_hi, x_new, _ = deltas.bracket(target_dt, 'ta')
     rec = []
     for var in ('ta', 'hur', 'ua', 'va', 'tas', 'hurs', 'ps_hist'):
