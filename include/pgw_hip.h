@@ -646,11 +646,21 @@ int pgw_test_log(pgw_ctx *ctx, long long n, const double *in, double *out);
 /* same for the table-driven logarithm of the hybrid-level loops (pgw_device.h pgw_log_tab: 128-entry table, r = fma(z, 1/c, -1),
  * degree-7 polynomial; generated by tools/gen_log_table.py) */
 int pgw_test_log_table(pgw_ctx *ctx, long long n, const double *in, double *out);
+/* same for pgw_log_f3 (pgw_log with three-address FMA Horner steps: the same bits) and pgw_log_dd (the fdlibm kernel carried
+ * in double-double pairs: the logarithm whose last bit reaches a float64 result of integ_geopot in the reference's dtype flow) */
+int pgw_test_log_f3(pgw_ctx *ctx, long long n, const double *in, double *out);
+int pgw_test_log_dd(pgw_ctx *ctx, long long n, const double *in, double *out);
 
 /* diagnostic: out[i] = pgw_exp(in[i]) (pgw_device.h: the device library's exp arithmetic written with explicit FMAs, the
  * exponential of every e_sat evaluation), ref[i] = exp(in[i]) of the device library; device fp64 arrays.  Tests require
  * out == ref bit for bit and <= 1 ulp from numpy. */
 int pgw_test_exp(pgw_ctx *ctx, long long n, const double *in, double *out, double *ref);
+/* diagnostic: out[i] = pgw_exp_finite(in[i]) (pgw_exp without the two range selects, with a guard on the remainder for huge
+ * arguments); device fp64 arrays.  Tests require the bits of pgw_exp for every finite argument and NaN, and NaN at +-inf. */
+int pgw_test_exp_finite(pgw_ctx *ctx, long long n, const double *in, double *out);
+/* diagnostic: out[i] = pgw_exp_reduced(in[i]) (the same without that guard: the exponential of the float64 e_sat fast path and
+ * of the Magnus formula of step_01, for |x| <= 1000); device fp64 arrays.  Tests require the bits of pgw_exp on that range. */
+int pgw_test_exp_reduced(pgw_ctx *ctx, long long n, const double *in, double *out);
 
 /* diagnostic: RELHUM of a float32 ERA state as numpy's promotion evaluates functions.py:58-116 on float32 files
  * (reference-dtype mode, step_03_apply_to_era.py:91-94): out = the form the quad kernel uses (the one phase a temperature

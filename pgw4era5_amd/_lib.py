@@ -174,7 +174,11 @@ REDUCE_MAX_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
 SIGNATURES['pgw_set_reduce_hook'] = (_i, [_vp, REDUCE_MAX_FN, _vp])
 SIGNATURES['pgw_test_log'] = (_i, [_vp, _ll, _vp, _vp])
 SIGNATURES['pgw_test_log_table'] = (_i, [_vp, _ll, _vp, _vp])
+SIGNATURES['pgw_test_log_f3'] = (_i, [_vp, _ll, _vp, _vp])
+SIGNATURES['pgw_test_log_dd'] = (_i, [_vp, _ll, _vp, _vp])
 SIGNATURES['pgw_test_exp'] = (_i, [_vp, _ll, _vp, _vp, _vp])
+SIGNATURES['pgw_test_exp_finite'] = (_i, [_vp, _ll, _vp, _vp])
+SIGNATURES['pgw_test_exp_reduced'] = (_i, [_vp, _ll, _vp, _vp])
 SIGNATURES['pgw_test_shared_div'] = (_i, [_vp, _ll, _vp, _vp, _vp])
 SIGNATURES['pgw_test_rh_f32'] = (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 SIGNATURES['pgw_byteswap'] = (_i, [_vp, _i, _ll, _vp, _vp])

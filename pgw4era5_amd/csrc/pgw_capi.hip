@@ -2527,6 +2527,34 @@ extern "C" int pgw_test_log_table(pgw_ctx *ctx, long long n, const double *in, d
     return PGW_OK;
 }
 
+extern "C" int pgw_test_log_f3(pgw_ctx *ctx, long long n, const double *in, double *out) {
+    NEED(ctx, n >= 1 && in && out, "bad argument");
+    hipLaunchKernelGGL(k_test_log, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, n, in, out, 2);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_test_log_dd(pgw_ctx *ctx, long long n, const double *in, double *out) {
+    NEED(ctx, n >= 1 && in && out, "bad argument");
+    hipLaunchKernelGGL(k_test_log, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, n, in, out, 3);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_test_exp_finite(pgw_ctx *ctx, long long n, const double *in, double *out) {
+    NEED(ctx, n >= 1 && in && out, "bad argument");
+    hipLaunchKernelGGL(k_test_exp_finite, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, n, in, out, 0);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_test_exp_reduced(pgw_ctx *ctx, long long n, const double *in, double *out) {
+    NEED(ctx, n >= 1 && in && out, "bad argument");
+    hipLaunchKernelGGL(k_test_exp_finite, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, n, in, out, 1);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
 // ------------------------------------------------------------------ regridding
 extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, int nlat_t,
                                    int nlon_t, const void *src, const int *lat_lo, const int *lat_hi,

@@ -185,7 +185,9 @@ __device__ __forceinline__ double div_ns(double n, double d) { return SharedDivi
 // quotient formed by v_rcp_f64 + two Newton steps + one residual correction; everything else
 // (0, negative, denormal, inf, NaN) goes to the ocml log.  One implementation serves table
 // entries and per-column values, so `src_x == targ_x` comparisons (functions.py:540) are
-// consistent.
+// consistent.  Against the exact logarithm (tests/test_device_math_hip.py::test_log_true_error_is_at_most_one_ulp,
+// 111 000 arguments from bit patterns: every interval end of the table below in 12 binades, the arguments whose logarithm
+// lies just under a power of two, the neighbourhood of 1): at most 0.758 ulp; the test requires <= 1.
 // keeps a rarely taken block a real (wave-uniform) branch: volatile asm cannot be speculated, so
 // the compiler does not if-convert the block into "compute both sides and select"
 __device__ __forceinline__ double no_speculate(double x) {
@@ -250,8 +252,12 @@ __device__ __forceinline__ double pgw_log(double x) { return pgw_log_impl<false>
 __device__ __forceinline__ double pgw_log_f3(double x) { return pgw_log_impl<true>(x); }    // same bits
 
 // The fdlibm kernel again, with the quotient s = f / (2 + f) and the final sum k ln2 + f - f^2/2 + s (f^2/2 + R) carried as
-// double-double pairs (error-free two-sums, FMA residuals): the result is the correctly rounded logarithm for all but ~3 in
-// 10^4 arguments (checked against a long-double logarithm), where pgw_log is up to one ulp off for 1-2 % of them.  About twice the
+// double-double pairs (error-free two-sums, FMA residuals): at most 0.513 ulp from the exact logarithm on every argument tried
+// (the test requires <= 0.55), and the correctly rounded double for all but 2.3 in 10^4 of the pressures of the path (uniform in
+// 1e-4 .. 1.1e5 Pa; required: <= 1 in 10^3) - elsewhere the share differs: 0.5 in 10^4 over all magnitudes, 8.5 in 10^4 on the
+// interval ends of the table below, 15 in 10^4 where ln x lies just under a power of two
+// (tests/test_device_math_hip.py::test_log_dd_true_error_and_share_correctly_rounded, exact reference).  pgw_log is not the
+// correctly rounded double for 1.1 % of those pressures and 2.9 % of the interval ends.  About twice the
 // instructions: for the few logarithms whose last bit reaches a float64 RESULT - the final expression of integ_geopot
 // (functions.py:174-179) in the reference's dtype flow, which is compared with numpy's bit for bit - not for level loops.
 __device__ __forceinline__ void two_sum(double a, double b, double &s, double &e) {
@@ -302,7 +308,20 @@ __device__ __forceinline__ double pgw_log_dd(double x) {
 //     log x = (k ln2_hi + logc) + r + [r^2 (A0 + A1 r + ... + A5 r^5) + k ln2_lo]     (truncation r^8/8 < 1e-20)
 // with the leading sum split exactly into hi + lo.  ~25 instructions and one 16-B LDS read.  The two intervals next to
 // z = 1 with k = 0 (results near zero, where the table's absolute accuracy is not a relative one) and everything
-// outside the positive normal range go to pgw_log.  tests/...::test_device_log_accuracy: <= 1 ulp of numpy's log.
+// outside the positive normal range go to pgw_log.
+// Accuracy: NOT within 1 ulp of the exact logarithm.  w = fma(k, ln2_hi, logc) is rounded once and that rounding is not
+// compensated (lo compensates only h = w + r); where the result lies one binade below w - ln x just under 1/2, 1, 2, 4, 8:
+// x just under sqrt(e), e, e^2, e^4, e^8 = 2981 Pa - half an ulp of w is a whole ulp of the result.  Bound: 0.5 (final
+// rounding) + 1.0 (w) + 0.25 (logc's 2.2e-19 against the smallest result ulp 2^-60) + 0.05 (the rest) = 1.8 ulp; the result
+// cannot lie two binades below a rounded w (for k = 0, w = logc is exact; otherwise |w| >= ln 1.375 = 0.318 and |r| < 0.004).
+// Measured maximum: 1.489 ulp at x = 1.6487212707001178 (the double below sqrt(e); 1.334 at x = 1.6484375); above 1 ulp only
+// under sqrt(e) among 111 000 arguments; up to a quarter of the results (25 % of the pressures of the path, 0.2 % over all
+// magnitudes) are not the correctly rounded double.  1e-16
+// relative: harmless to the physics, and the distance to numpy's log (itself up to 0.52 ulp off) stays <= 1 ulp
+// (tests/test_hip_parity.py::test_device_log_accuracy).  Established by an exact restatement of the function in
+// tests/device_math_cases.py, held to the exact logarithm and the 1.8 ulp on the CPU (tests/test_device_math_host.py, which
+// also checks the table's two bounds quoted above) and equal to this function bit for bit on the GPU
+// (tests/test_device_math_hip.py::test_log_tab_is_its_restatement_bit_for_bit).
 // The table lives in LDS (stage_log_table): lanes index it with their own interval.
 __device__ const double LOG_TABLE_DEV[2 * LOG_TABLE_N] = {
 #define PGW_LOG_TABLE_BODY
@@ -344,11 +363,19 @@ __device__ __forceinline__ double pgw_log_tab(double x, const double *tab) {
 // Same operations and constants, hence the same bits as exp() (tests/...::test_device_exp_is_library_exp); the point
 // is code generation: for most of the inlined library instances in the delta kernels the compiler forms each Horner
 // step as v_mov_b64 (copy of the coefficient) + v_fmac, two instructions, where one three-address v_fma_f64 does.
-template <bool RANGE>
+template <bool RANGE, bool GUARD = false>
 __device__ __forceinline__ double pgw_exp_impl(double x) {
     const double n = __builtin_rint(x * 0x1.71547652b82fep+0);
     double r = __builtin_fma(-0x1.62e42fefa39efp-1, n, x);
     r = __builtin_fma(-0x1.abc9e3b39803fp-56, n, r);
+    if (GUARD) {
+        // beyond |x| ~ 2^50 the product x log2(e) is not exact to a unit, n is off by many and r is not a reduced remainder:
+        // the polynomial's value, and with it the sign of the saturated ldexp, would be arbitrary (-0 / -inf were measured
+        // from |x| = 1.4e17).  The result is decided by n alone from |x| = 1076 on, so r = x - x there: 0 for a finite x
+        // (p = 1 exactly), NaN for +-inf; a NaN x compares false and keeps its NaN r.  Same bits for every |x| <= 2000.
+        const double z = x - x;
+        r = (__builtin_fabs(x) > 2000.0) ? z : r;
+    }
     double p = fma3(0x1.ade156a5dcb37p-26, r, 0x1.28af3fca7ab0cp-22);
     p = fma3(r, p, 0x1.71dee623fde64p-19);
     p = fma3(r, p, 0x1.a01997c89e6b0p-16);
@@ -368,9 +395,19 @@ __device__ __forceinline__ double pgw_exp_impl(double x) {
     return v;
 }
 __device__ __forceinline__ double pgw_exp(double x) { return pgw_exp_impl<true>(x); }
-// without the library's two range selects: the same bits for every finite x (v_ldexp_f64 saturates to 0 / inf by itself,
-// the conversion of n saturates too) and for NaN; only x = +-inf gives NaN instead of inf / 0.  For arguments of known range.
-__device__ __forceinline__ double pgw_exp_finite(double x) { return pgw_exp_impl<false>(x); }
+// Three forms of one arithmetic.  pgw_exp: the library's, with its two range selects (six instructions).
+// pgw_exp_reduced: neither selects nor guard, for callers that use the value only where |x| <= 1000 and replace it elsewhere -
+// the same bits as pgw_exp there (tests/test_device_math_hip.py::test_exp_reduced_is_exp_on_its_range); beyond |x| ~ 2^50 the
+// sign of the saturated result is arbitrary.  It is what the kernels call: e_sat's one unconditional exponential (esat_mixed,
+// |x| < 130 wherever the value is kept; tests/...::test_esat_fast_path_is_the_literal_expression goes through every temperature
+// at which it is replaced, the zero divisors with |x| up to 5.6e19 included) and the Magnus formula of step_01 (|x| < 700).
+// pgw_exp_finite: no selects but the guard on r above (four instructions), the same bits as pgw_exp for EVERY finite x and for
+// NaN - v_ldexp_f64 saturates to 0 / inf by itself, the conversion of n saturates too, and r is a reduced remainder or zero, so
+// the polynomial is positive and finite; only x = +-inf gives NaN instead of inf / 0
+// (tests/...::test_exp_finite_is_exp_for_every_finite_argument).  No kernel calls it at present - the guard in the delta
+// kernels cost 0.15 % of a file for a value esat_mixed throws away; it is the form for an argument that is finite but not bounded.
+__device__ __forceinline__ double pgw_exp_finite(double x) { return pgw_exp_impl<false, true>(x); }
+__device__ __forceinline__ double pgw_exp_reduced(double x) { return pgw_exp_impl<false, false>(x); }
 
 // ---- humidity thermodynamics (functions.py:58-125), operation order as written there ----
 __device__ __forceinline__ double esat_water(double ta) {   // :74-89 water
@@ -381,8 +418,11 @@ __device__ __forceinline__ double esat_ice(double ta) {     // :74-89 ice (a4 = 
 }
 // :91-105.  alpha = 1 (T>=T0), 0 (T<=Ti), ((T-Ti)/(T0-Ti))^2 in between, NaN for NaN T.
 // alpha*e_w + (1-alpha)*e_i is evaluated in full only in the mixed range; for alpha in {0,1}
-// the dropped term is exactly 0*finite = 0 for every finite T (e_w, e_i are finite for all
-// T > 32.19 K), so the value is unchanged.
+// the dropped term is exactly 0*finite = 0, so the value is unchanged: e_w and e_i are finite for
+// 32.19 K < T <= 1e300 (tests/test_device_math_hip.py::test_esat_fast_path_is_the_literal_expression: the
+// reference's expression bit for bit at every limit below, +-inf and NaN included).  Not for finite T
+// between 7.96e306 and 1.03e307: there a3 (T - T0) overflows, the literal expression is 0 * inf = NaN
+// and this one is finite.  Known; no branch is spent on it.
 // One unconditional division + exp evaluates the phase every temperature needs (water for
 // T >= T0, ice otherwise; the coefficients are selected, not the results), and only lanes in the
 // mixed range take a real branch (no_speculate) for the second one.
@@ -411,14 +451,19 @@ __device__ __forceinline__ double esat_mixed(double ta) {
     const double a3 = warm ? 17.502 : 22.587;
     const double a4 = warm ? 32.19 : -0.7;
     // e_w if warm else e_i (NaN for NaN ta); |argument| < 130 for every T the value is used for: no range selects
-    double e1 = 611.21 * pgw_exp_finite(div_ns(a3 * (ta - T0), ta - a4));
+    double e1 = 611.21 * pgw_exp_reduced(div_ns(a3 * (ta - T0), ta - a4));
     // ONE divergent region per call (every branch costs scalar instructions and issue slots the few resident waves of the
     // delta kernels cannot hide): e1 is the answer for T >= T0 and for 40 K < T <= Ti
     if (__builtin_expect(!(warm || (ta <= Ti && ta > 40.0)), 0)) e1 = esat_special(no_speculate(ta), e1);
     return e1;
 }
+// div_ns followed by the division's own last instruction, v_div_fixup: the sign of a zero quotient (div_ns turns a -0
+// numerator into +0) and the IEEE results for zero and infinite operands come back, finite non-zero quotients pass through
+// unchanged.  For q -> RH, whose value for q = -0.0 numpy gives as -0.0
+// (tests/test_device_math_hip.py::test_specific_to_relative_humidity_is_the_numpy_expression).
+__device__ __forceinline__ double div_ns_fixup(double n, double d) { return __builtin_amdgcn_div_fixup(div_ns(n, d), d, n); }
 __device__ __forceinline__ double q_to_e(double hus, double pa) {          // :58-64
-    return div_ns(hus * pa, CON_MW_MD + 0.378 * hus);
+    return div_ns_fixup(hus * pa, CON_MW_MD + 0.378 * hus);
 }
 __device__ __forceinline__ double e_to_q(double vapp, double pa) {         // :66-72
     return CON_MW_MD * vapp / (pa - (1 - CON_MW_MD) * vapp);
@@ -428,7 +473,7 @@ __device__ __forceinline__ double e_to_q_ns(double vapp, double pa) {
     return div_ns(CON_MW_MD * vapp, pa - (1 - CON_MW_MD) * vapp);
 }
 __device__ __forceinline__ double q_to_rh(double hus, double pa, double ta) {   // :107-116
-    return div_ns(q_to_e(hus, pa), esat_mixed(ta)) * 100;
+    return div_ns_fixup(q_to_e(hus, pa), esat_mixed(ta)) * 100;
 }
 // ---- reference-dtype mode: RELHUM of a float32 ERA state as numpy's promotion evaluates functions.py:58-116 ----
 // e_sat of a float32 temperature is float32 throughout (alpha = full_like(ta): :95-98; a1*np.exp(a3*(ta-T0)/(ta-a4)):
@@ -489,7 +534,8 @@ __device__ __forceinline__ float esat_mixed_f32(float ta) {
     return e1;
 }
 // hus float32, pa float64 (ak/bk are float64): hus*pa is float64, the denominator CON_MW_MD + 0.378*hus float32 (:63).
-// The two float64 quotients through div_ns like q_to_e / q_to_rh above (divisors of known range: 0.622 + 0.378 q, e_sat).
+// The two float64 quotients through div_ns (divisors of known range: 0.622 + 0.378 q, e_sat; without the v_div_fixup that
+// q_to_e / q_to_rh above add).
 __device__ __forceinline__ double q_to_rh_f32_literal(float hus, double pa, float ta);
 __device__ __forceinline__ double q_to_rh_f32(float hus, double pa, float ta) {
 #ifdef PGW_ESAT_F32_LITERAL

@@ -995,7 +995,7 @@ __global__ __launch_bounds__(BLOCK) void k_magnus_rh(long long n, int nplev, lon
             r = (double)(1.0f / e);
         } else {
             const double a = 17.67 * (tk - 273.15) / (tk - 29.65);
-            const double e = (a > -700.0 && a < 700.0) ? pgw_exp_finite(a) : pgw_exp(a);
+            const double e = (a > -700.0 && a < 700.0) ? pgw_exp_reduced(a) : pgw_exp(a);
             r = 1.0 / e;
         }
         SIG_ST(0.263 * p * q * r, rh + i);
@@ -3620,13 +3620,16 @@ __global__ __launch_bounds__(BLOCK) void k_byteswap(long long n16, long long n, 
     }
 }
 
-// pgw_log / pgw_log_tab over an array (diagnostic entry pgw_test_log; tests compare them with numpy's log)
-__global__ void k_test_log(long long n, const double *__restrict__ in, double *__restrict__ out, int table) {
+// the device logarithms over an array (diagnostic entries pgw_test_log, pgw_test_log_table, pgw_test_log_f3, pgw_test_log_dd;
+// tests compare them with the exact logarithm): which = 0 pgw_log, 1 pgw_log_tab, 2 pgw_log_f3, 3 pgw_log_dd
+__global__ void k_test_log(long long n, const double *__restrict__ in, double *__restrict__ out, int which) {
     __shared__ double s_tab[2 * LOG_TABLE_N];
     stage_log_table(s_tab, blockDim.x);
     __syncthreads();
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = table ? pgw_log_tab(in[i], s_tab) : pgw_log(in[i]);
+    if (i >= n) return;
+    const double x = in[i];
+    out[i] = which == 1 ? pgw_log_tab(x, s_tab) : which == 2 ? pgw_log_f3(x) : which == 3 ? pgw_log_dd(x) : pgw_log(x);
 }
 
 // pgw_exp and the device library's exp over an array (diagnostic entry pgw_test_exp): out[i] = pgw_exp(in[i]),
@@ -3634,6 +3637,13 @@ __global__ void k_test_log(long long n, const double *__restrict__ in, double *_
 __global__ void k_test_exp(long long n, const double *__restrict__ in, double *__restrict__ out, double *__restrict__ ref) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { out[i] = pgw_exp(in[i]); ref[i] = exp(in[i]); }
+}
+
+// pgw_exp_finite / pgw_exp_reduced over an array (diagnostic entries pgw_test_exp_finite, pgw_test_exp_reduced; tests compare
+// them with pgw_exp)
+__global__ void k_test_exp_finite(long long n, const double *__restrict__ in, double *__restrict__ out, int reduced) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = reduced ? pgw_exp_reduced(in[i]) : pgw_exp_finite(in[i]);
 }
 
 // RELHUM of a float32 ERA state in reference-dtype mode (diagnostic entry pgw_test_rh_f32): the fast form the quad kernel
