@@ -614,6 +614,24 @@ int pgw_gauss_interp(pgw_ctx *ctx, long long ntarg, const double *tx, const doub
 int pgw_planar_metres(pgw_ctx *ctx, long long n, const double *lat, const double *lon, double *lat_m, double *lon_m,
                       double *lon_off);
 
+/* Target side of that interpolation for POINT-WISE targets (2-D lat / lon of a rotated-pole file, a cell list;
+ * functions.py:998-1023 without the mesh).  pgw_ocean_targets: lat, lon [deg] of n targets -> planar metres tx, ty; a longitude
+ * above 180 is folded by -360; the lengths are evaluated on (|lat|, |lon|) and multiplied by sign(lat), sign(lon), as the
+ * mesh path does for the distinct values of its axes (same device code as pgw_planar_metres: same bits).  `land` (n, may be
+ * NULL): a target with land > 0.7 (:1032; a NaN fraction is not) or a NaN coordinate is inactive, tx = ty = NaN.
+ * pgw_gauss_interp_points: pgw_gauss_interp for targets in any order (NaN coordinates = inactive); the library orders them
+ * by the cell of the source grid they fall into (key, counting sort, scatter - all on the device, workspace of the context)
+ * and walks blocks of 256 sorted targets; out (nfield, ntarg) in the CALLER's order, every element written, inactive targets
+ * NaN.  Bit for bit what pgw_gauss_interp gives for the same (tx, ty), whatever the order.  A target outside the cell grid
+ * is treated like one in the ring of cells around it (it can be within one radius of a border cell's points); ntarg < 2^31
+ * and 16 * (ncx + 2) * (ncy + 2) < 2^31.  The walk is timed under PGW_K_GAUSS_INTERP; key and order are not profiled
+ * separately (pgw_timer_start / _stop around the call gives the sum).  Device pointers. */
+int pgw_ocean_targets(pgw_ctx *ctx, long long n, const double *lat, const double *lon, const double *land, double *tx,
+                      double *ty);
+int pgw_gauss_interp_points(pgw_ctx *ctx, long long ntarg, const double *tx, const double *ty, int ncx, int ncy,
+                            double x0, double y0, double cell, const int *cell_start, long long nsrc, const double *sx,
+                            const double *sy, const double *sval, int nfield, double radius, double sharpness, double *out);
+
 /* Placement of the level arrays in HBM (no counterpart in the reference: numpy arrays live wherever malloc put them).
  * On an MI355X the rate a column kernel gets depends on WHERE hipMalloc put its arrays relative to each other: an array
  * written while an array of the same stretch of physical memory is read runs at 5.0-5.4 TB/s, arrays of different stretches

@@ -188,6 +188,9 @@ SIGNATURES['pgw_narrow_f64_f32'] = (_i, [_vp, _ll, _vp, _vp, _i])
 SIGNATURES['pgw_harmonic_smooth'] = (_i, [_vp, _i, _i, _ll, _dp, _dp, _vp, _vp])
 SIGNATURES['pgw_gauss_interp'] = (_i, [_vp, _ll, _vp, _vp, _i, _i, _d, _d, _d, _vp, _ll, _vp, _vp, _vp, _i, _d, _d, _vp])
 SIGNATURES['pgw_planar_metres'] = (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp])
+# tos / siconc onto point-wise targets: planar-metre target coordinates, then the interpolation with the targets in any order
+SIGNATURES['pgw_ocean_targets'] = (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp])
+SIGNATURES['pgw_gauss_interp_points'] = SIGNATURES['pgw_gauss_interp']
 SIGNATURES['pgw_interp_hybrid_to_plev'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _vp, _vp, _dp, _dp, _dp, _i, _i, _i, _vp])
 SIGNATURES['pgw_magnus_rh'] = (_i, [_vp, _i, _i, _i, _ll, _vp, _dp, _vp, _vp])
 # settings.function_dtype_flow = 'reference': one dtype tag per operand

@@ -49,8 +49,9 @@ struct pgw_ctx {
     PlevTableWide plev_tab_wide;
     double *d_small = nullptr;         // small scratch (tables), 64 KiB
     // named workspaces grown on demand
-    void *ws[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t ws_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // (0 .. 7 may be adopted from the host layer, pgw_ws_adopt; 8: keys, order and histogram of pgw_gauss_interp_points)
+    void *ws[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t ws_bytes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // profiler
     bool prof_on = false;
     std::vector<ProfRec> prof_pending;
@@ -302,7 +303,7 @@ extern "C" int pgw_ctx_destroy(pgw_ctx *ctx) {
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     for (auto &r : ctx->prof_pending) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     for (auto &e : ctx->event_pool) hipEventDestroy(e);
-    for (int i = 0; i < 8; ++i) if (ctx->ws[i]) hipFree(ctx->ws[i]);
+    for (int i = 0; i < 9; ++i) if (ctx->ws[i]) hipFree(ctx->ws[i]);
     if (ctx->d_levels) hipFree(ctx->d_levels);
     if (ctx->d_small) hipFree(ctx->d_small);
     if (ctx->d_status) hipFree(ctx->d_status);
@@ -2429,6 +2430,52 @@ extern "C" int pgw_planar_metres(pgw_ctx *ctx, long long n, const double *lat, c
     if (n == 0) return PGW_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(k_planar_metres, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, lat, lon, lat_m, lon_m, lon_off);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_ocean_targets(pgw_ctx *ctx, long long n, const double *lat, const double *lon, const double *land, double *tx,
+                                 double *ty) {
+    NEED(ctx, n >= 0 && (n == 0 || (lat && lon && tx && ty)), "bad argument");
+    if (n == 0) return PGW_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_ocean_targets, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, lat, lon, land, tx, ty);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_gauss_interp_points(pgw_ctx *ctx, long long ntarg, const double *tx, const double *ty, int ncx, int ncy,
+                                       double x0, double y0, double cell, const int *cell_start, long long nsrc, const double *sx,
+                                       const double *sy, const double *sval, int nfield, double radius, double sharpness,
+                                       double *out) {
+    NEED(ctx, ntarg >= 1 && nsrc >= 0 && tx && ty && cell_start && out, "bad argument");
+    NEED(ctx, nsrc == 0 || (sx && sy && sval), "null source pointer");
+    NEED(ctx, ncx >= 1 && ncy >= 1 && cell > 0.0 && radius > 0.0, "bad cell grid");
+    NEED(ctx, cell >= radius, "cells must be at least one kernel radius wide (3 x 3 block search)");
+    NEED(ctx, nfield >= 1 && nfield <= GAUSS_MAX_FIELDS, "nfield must be in [1, 16]");
+    NEED(ctx, ntarg < (1ll << 31), "ntarg must be below 2^31 (the order of the targets is kept in 32-bit indices)");
+    // keys: the cells and a ring around them, GAUSS_SUB x GAUSS_SUB parts of each, and one for the inactive targets
+    const long long nkey = ((long long)ncx + 2) * ((long long)ncy + 2) * (GAUSS_SUB * GAUSS_SUB) + 1;
+    NEED(ctx, nkey < (1ll << 31), "16 * (ncx + 2) * (ncy + 2) must be below 2^31");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // workspace: n_active (and padding) | key [ntarg] | order [ntarg] | count -> start [nkey]
+    void *wsp = nullptr;
+    int rc = ws_get(ctx, 8, sizeof(int) * (4 + 2 * (size_t)ntarg + (size_t)nkey), &wsp);
+    if (rc) return rc;
+    int *n_active = (int *)wsp, *key = n_active + 4, *order = key + ntarg, *count = order + ntarg;
+    const double r2 = radius * radius, f2 = (sharpness * sharpness) / (radius * radius);     // vtkGaussianKernel: F2 = (Sharpness / Radius)^2
+    const double inv_h = 1.0 / cell;
+    const unsigned int nb = nblocks(ntarg, BLOCK);
+    HIPCHK(ctx, hipMemsetAsync(count, 0, sizeof(int) * (size_t)nkey, ctx->stream));
+    hipLaunchKernelGGL(k_gauss_keys, dim3(nb), dim3(BLOCK), 0, ctx->stream, (int)ntarg, tx, ty, ncx, ncy, x0, y0, inv_h, key, count);
+    hipLaunchKernelGGL(k_gauss_scan, dim3(1), dim3(SCAN_BLOCK), 0, ctx->stream, (int)nkey, count, n_active);
+    hipLaunchKernelGGL(k_gauss_scatter, dim3(nb), dim3(BLOCK), 0, ctx->stream, (int)ntarg, key, count, order);
+    HIPCHK(ctx, hipGetLastError());
+    {
+        Prof pr(ctx, PGW_K_GAUSS_INTERP);
+        hipLaunchKernelGGL((k_gauss_points<GAUSS_MAX_FIELDS>), dim3(nb), dim3(BLOCK), 0, ctx->stream, (int)ntarg, order, n_active, tx, ty,
+                           ncx, ncy, x0, y0, inv_h, cell_start, sx, sy, sval, nfield, r2, f2, out);
+    }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
 }

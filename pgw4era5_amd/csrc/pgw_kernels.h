@@ -3373,29 +3373,23 @@ constexpr int GAUSS_MAX_FIELDS = 16;
 // filled with such targets): a block's box of cells stays small, and so does the set of points a wave accepts for some of
 // its lanes only (a wave runs the weight arithmetic of a point when ANY lane has it within the radius).
 constexpr int GAUSS_CHUNK = 256;
+// The source walk of one block, shared by k_gauss_interp and k_gauss_points: (cx, cy) is the thread's own cell (used when
+// `active`), the block's box of cells is formed from the active threads' cells, and sw / swv / hit / has_hit come back as the
+// thread's sums.  Called by every thread of the block (it synchronises).
 template <int NM>
-__global__ __launch_bounds__(BLOCK) void k_gauss_interp(long long ntarg, const double *__restrict__ tx, const double *__restrict__ ty,
-                                                        int ncx, int ncy, double x0, double y0, double inv_h,
-                                                        const int *__restrict__ cell_start, const double *__restrict__ sx,
-                                                        const double *__restrict__ sy, const double *__restrict__ sval /* [nsrc][nm] */,
-                                                        int nm, double r2, double f2, double *__restrict__ out /* [nm][ntarg] */) {
+__device__ __forceinline__ void gauss_walk(bool active, double x, double y, int cx, int cy, int ncx, int ncy,
+                                           const int *__restrict__ cell_start, const double *__restrict__ sx,
+                                           const double *__restrict__ sy, const double *__restrict__ sval /* [nsrc][nm] */, int nm,
+                                           double r2, double f2, double (&sw)[NM], double (&swv)[NM], double (&hit)[NM],
+                                           bool (&has_hit)[NM]) {
     __shared__ double s_x[GAUSS_CHUNK], s_y[GAUSS_CHUNK];
     __shared__ double s_v[GAUSS_CHUNK * NM];
     __shared__ int s_box[4];                                    // cx_min, cx_max, cy_min, cy_max of the block's active targets
     __shared__ int s_nan[GAUSS_CHUNK];                          // the point has a NaN month (rare: the common path tests nothing)
-    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    double x = __builtin_nan(""), y = __builtin_nan("");
-    if (i < ntarg) { x = tx[i]; y = ty[i]; }
-    const bool active = (x == x) && (y == y);
     if (threadIdx.x == 0) { s_box[0] = 0x7fffffff; s_box[1] = -0x7fffffff; s_box[2] = 0x7fffffff; s_box[3] = -0x7fffffff; }
     __syncthreads();
-    if (active) {
-        const int cx = (int)floor((x - x0) * inv_h), cy = (int)floor((y - y0) * inv_h);
-        atomicMin(&s_box[0], cx); atomicMax(&s_box[1], cx); atomicMin(&s_box[2], cy); atomicMax(&s_box[3], cy);
-    }
+    if (active) { atomicMin(&s_box[0], cx); atomicMax(&s_box[1], cx); atomicMin(&s_box[2], cy); atomicMax(&s_box[3], cy); }
     __syncthreads();
-    double sw[NM], swv[NM], hit[NM];
-    bool has_hit[NM];
 #pragma unroll
     for (int m = 0; m < NM; ++m) { sw[m] = 0.0; swv[m] = 0.0; hit[m] = 0.0; has_hit[m] = false; }
     const double tol = 256.0 * 2.220446049250313e-16;           // vtkMathUtilities::FuzzyCompare(d2, 0.0, eps * 256)
@@ -3448,17 +3442,153 @@ __global__ __launch_bounds__(BLOCK) void k_gauss_interp(long long ntarg, const d
             }
         }
     }
-    if (i < ntarg) {
+}
+
+// null_value (:1041) where nothing was in reach, the coincident point's value, else the quotient of the two sums
+template <int NM>
+__device__ __forceinline__ void gauss_store(long long ntarg, long long i, int nm, const double (&sw)[NM], const double (&swv)[NM],
+                                            const double (&hit)[NM], const bool (&has_hit)[NM], double *__restrict__ out) {
 #pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            if (m < nm) {
-                double r = __builtin_nan("");                    // null_value (:1041)
-                if (has_hit[m]) r = hit[m];
-                else if (sw[m] > 0.0) r = swv[m] / sw[m];
-                out[(long long)m * ntarg + i] = r;
-            }
+    for (int m = 0; m < NM; ++m) {
+        if (m < nm) {
+            double r = __builtin_nan("");
+            if (has_hit[m]) r = hit[m];
+            else if (sw[m] > 0.0) r = swv[m] / sw[m];
+            out[(long long)m * ntarg + i] = r;
         }
     }
+}
+
+template <int NM>
+__global__ __launch_bounds__(BLOCK) void k_gauss_interp(long long ntarg, const double *__restrict__ tx, const double *__restrict__ ty,
+                                                        int ncx, int ncy, double x0, double y0, double inv_h,
+                                                        const int *__restrict__ cell_start, const double *__restrict__ sx,
+                                                        const double *__restrict__ sy, const double *__restrict__ sval /* [nsrc][nm] */,
+                                                        int nm, double r2, double f2, double *__restrict__ out /* [nm][ntarg] */) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    double x = __builtin_nan(""), y = __builtin_nan("");
+    if (i < ntarg) { x = tx[i]; y = ty[i]; }
+    const bool active = (x == x) && (y == y);
+    int cx = 0, cy = 0;
+    if (active) { cx = (int)floor((x - x0) * inv_h); cy = (int)floor((y - y0) * inv_h); }
+    double sw[NM], swv[NM], hit[NM];
+    bool has_hit[NM];
+    gauss_walk<NM>(active, x, y, cx, cy, ncx, ncy, cell_start, sx, sy, sval, nm, r2, f2, sw, swv, hit, has_hit);
+    if (i < ntarg) gauss_store<NM>(ntarg, i, nm, sw, swv, hit, has_hit, out);
+}
+
+// -------------------------------------------------------------------------------------
+// The same interpolation for targets in ANY order (point-wise targets: 2-D lat / lon of a rotated-pole file, a cell list).
+// The targets are put into the order of the source's cells on the device, so that a block of 256 consecutive sorted
+// positions has a small box of cells to stage, and every result is written to the target's own index:
+//   k_gauss_keys     key of the target's cell + histogram of the keys.  The cell index is the walk's floor((x - x0) * inv_h),
+//                    clamped in double to [-1, ncx] x [-1, ncy] before the conversion: a target outside the grid can still be
+//                    within one radius of a border cell's points; one far away (1e18) lands in the same ring of outside
+//                    cells, stages the border cells and accepts nothing.  Cell rows alternate their direction (a snake), so
+//                    that the block that runs from the end of one row into the next has neighbouring cells, not a box as
+//                    long as the row.  Inside a cell the key goes on with the target's place in GAUSS_SUB x GAUSS_SUB parts of
+//                    the cell: a wave runs the weight arithmetic of a point when ANY of its lanes has it within the radius,
+//                    so the 64 targets of a wave should lie close together, not anywhere in a cell one radius wide.
+//                    Inactive targets (NaN coordinate) get the key behind all cells.
+//   k_gauss_scan     exclusive scan of the histogram by one block; n_active = start of the last key.
+//   k_gauss_scatter  order[atomicAdd(&start[key], 1)] = i.  The order inside one cell is whatever the atomics give: per thread
+//                    the accepted points arrive in the order (ix, iy, p) whatever the block stages, so a target's sums do not
+//                    depend on its position.
+//   k_gauss_points   the walk on i = order[pos]; positions from n_active on write NaN and walk nothing.
+// -------------------------------------------------------------------------------------
+__device__ __forceinline__ int gauss_cell(double v, double v0, double inv_h, int nc) {
+    double c = floor((v - v0) * inv_h);
+    c = c < -1.0 ? -1.0 : c;
+    c = c > (double)nc ? (double)nc : c;
+    return (int)c;
+}
+
+// which of the GAUSS_SUB parts of its cell (index c, not clamped) along one axis the coordinate lies in
+constexpr int GAUSS_SUB = 4;
+__device__ __forceinline__ int gauss_sub(double v, double v0, double inv_h, int c) {
+    double f = ((v - v0) * inv_h - (double)c) * GAUSS_SUB;
+    f = f > 0.0 ? f : 0.0;                                       // (a clamped cell: the coordinate lies outside it)
+    f = f < (double)(GAUSS_SUB - 1) ? f : (double)(GAUSS_SUB - 1);
+    return (int)f;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_gauss_keys(int ntarg, const double *__restrict__ tx, const double *__restrict__ ty, int ncx,
+                                                      int ncy, double x0, double y0, double inv_h, int *__restrict__ key,
+                                                      int *__restrict__ count /* [(ncx + 2) * (ncy + 2) * GAUSS_SUB^2 + 1], zero */) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= ntarg) return;
+    const double x = tx[i], y = ty[i];
+    int k = (ncx + 2) * (ncy + 2) * (GAUSS_SUB * GAUSS_SUB);
+    if (x == x && y == y) {
+        const int cx = gauss_cell(x, x0, inv_h, ncx), cy = gauss_cell(y, y0, inv_h, ncy);
+        const int row = cx + 1, col = (row & 1) ? ncy - cy : cy + 1;
+        k = (row * (ncy + 2) + col) * (GAUSS_SUB * GAUSS_SUB) + gauss_sub(x, x0, inv_h, cx) * GAUSS_SUB + gauss_sub(y, y0, inv_h, cy);
+    }
+    key[i] = k;
+    atomicAdd(&count[k], 1);
+}
+
+constexpr int SCAN_BLOCK = 1024;
+__global__ __launch_bounds__(SCAN_BLOCK) void k_gauss_scan(int nkey, int *__restrict__ count /* in: counts, out: starts */,
+                                                           int *__restrict__ n_active) {
+    __shared__ int s_sum[SCAN_BLOCK];
+    const int per = (nkey + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    const int lo = threadIdx.x * per < nkey ? threadIdx.x * per : nkey;
+    const int hi = lo + per < nkey ? lo + per : nkey;
+    int sum = 0;
+    for (int k = lo; k < hi; ++k) sum += count[k];
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < SCAN_BLOCK; d <<= 1) {                   // inclusive scan of the per-thread sums
+        const int v = threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0;
+        __syncthreads();
+        s_sum[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = s_sum[threadIdx.x] - sum;
+    for (int k = lo; k < hi; ++k) {
+        const int c = count[k];
+        count[k] = run;
+        if (k == nkey - 1) *n_active = run;                      // the last key is the inactive targets'
+        run += c;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_gauss_scatter(int ntarg, const int *__restrict__ key, int *__restrict__ start,
+                                                         int *__restrict__ order) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= ntarg) return;
+    order[atomicAdd(&start[key[i]], 1)] = (int)i;
+}
+
+template <int NM>
+__global__ __launch_bounds__(BLOCK) void k_gauss_points(int ntarg, const int *__restrict__ order, const int *__restrict__ n_active,
+                                                        const double *__restrict__ tx, const double *__restrict__ ty,
+                                                        int ncx, int ncy, double x0, double y0, double inv_h,
+                                                        const int *__restrict__ cell_start, const double *__restrict__ sx,
+                                                        const double *__restrict__ sy, const double *__restrict__ sval /* [nsrc][nm] */,
+                                                        int nm, double r2, double f2, double *__restrict__ out /* [nm][ntarg] */) {
+    const long long pos = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    const int na = *n_active;
+    const int i = pos < ntarg ? order[pos] : -1;
+    if ((long long)blockIdx.x * BLOCK >= na) {                             // a block of inactive targets only (uniform over the block)
+        if (i >= 0) {
+#pragma unroll
+            for (int m = 0; m < NM; ++m) if (m < nm) out[(long long)m * ntarg + i] = __builtin_nan("");
+        }
+        return;
+    }
+    const bool active = pos < na;
+    double x = __builtin_nan(""), y = __builtin_nan("");
+    int cx = 0, cy = 0;
+    if (active) {
+        x = tx[i]; y = ty[i];
+        cx = gauss_cell(x, x0, inv_h, ncx); cy = gauss_cell(y, y0, inv_h, ncy);
+    }
+    double sw[NM], swv[NM], hit[NM];
+    bool has_hit[NM];
+    gauss_walk<NM>(active, x, y, cx, cy, ncx, ncy, cell_start, sx, sy, sval, nm, r2, f2, sw, swv, hit, has_hit);
+    if (i >= 0) gauss_store<NM>(ntarg, i, nm, sw, swv, hit, has_hit, out);
 }
 
 // float64 -> float32 (round to nearest even, the conversion numpy's astype does), two elements per lane, optionally byte-reversed
@@ -3509,36 +3639,67 @@ __device__ __forceinline__ void symmetric(double U, double a1, double &L, double
     L = omega - (1 - s.c) * F * sin_alpha * (sigma + s.c * sin_s * (cos_2sm + s.c * cos_s * (-1 + 2 * cos_2sm * cos_2sm)));
     len = arc(sigma, cos_2sm, s.a, s.b);
 }
+// lat, lon [deg] (lon folded to (-180, 180]) -> lat_m, lon_m, lon_off; quarter = meridian_arc(90)
+struct Planar { double lat_m, lon_m, lon_off; };
+__device__ __forceinline__ Planar planar(double la, double lo) {
+    const double quarter = meridian_arc(90.0);
+    const double arc_m = meridian_arc(la);
+    const double over_pole = 2.0 * (quarter - arc_m);
+    const double sgn_la = (la > 0) - (la < 0), sgn_lo = (lo > 0) - (lo < 0);
+    const double dl = fabs(lo), U = fabs(reduced_latitude(la)), Ls = dl * (PI / 180.0);
+    double a_lo = 0.0, a_hi = 0.5 * PI, L, len;
+    for (int it = 0; it < 70; ++it) {
+        const double mid = 0.5 * (a_lo + a_hi);
+        symmetric(U, mid, L, len);
+        if (L > Ls) a_lo = mid; else a_hi = mid;
+    }
+    symmetric(U, 0.5 * (a_lo + a_hi), L, len);
+    double s = len;
+    if (U < 1e-15 && Ls <= (1.0 - F) * PI) s = A * Ls;                    // the equator itself
+    if (dl >= 180.0) s = over_pole;
+    if (fabs(la) >= 90.0) s = 0.0;
+    if (dl == 0.0) s = 0.0;
+    if (la != la || lo != lo) s = __builtin_nan("");
+    Planar p;
+    p.lat_m = arc_m * sgn_la;
+    p.lon_m = s * sgn_lo;
+    p.lon_off = over_pole;
+    return p;
+}
 }  // namespace geo
 
-// lat, lon [deg] (lon folded to (-180, 180] by the caller) -> lat_m, lon_m, lon_off; quarter = meridian_arc(90)
 __global__ __launch_bounds__(BLOCK) void k_planar_metres(long long n, const double *__restrict__ lat, const double *__restrict__ lon,
                                                         double *__restrict__ lat_m, double *__restrict__ lon_m,
                                                         double *__restrict__ lon_off) {
     const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    const double la = lat[i], lo = lon[i];
-    const double quarter = geo::meridian_arc(90.0);
-    const double arc_m = geo::meridian_arc(la);
-    const double over_pole = 2.0 * (quarter - arc_m);
-    const double sgn_la = (la > 0) - (la < 0), sgn_lo = (lo > 0) - (lo < 0);
-    const double dl = fabs(lo), U = fabs(geo::reduced_latitude(la)), Ls = dl * (geo::PI / 180.0);
-    double a_lo = 0.0, a_hi = 0.5 * geo::PI, L, len;
-    for (int it = 0; it < 70; ++it) {
-        const double mid = 0.5 * (a_lo + a_hi);
-        geo::symmetric(U, mid, L, len);
-        if (L > Ls) a_lo = mid; else a_hi = mid;
+    const geo::Planar p = geo::planar(lat[i], lon[i]);
+    lat_m[i] = p.lat_m;
+    lon_m[i] = p.lon_m;
+    lon_off[i] = p.lon_off;
+}
+
+// Target coordinates of the ocean-grid interpolation for point-wise targets (functions.py:998-1023), one target per thread:
+// the longitude folded to (-180, 180], the planar lengths evaluated on (|lat|, |lon|) and given the signs of lat and lon -
+// the arithmetic gauss_interp_fields applies to the distinct |lat| x |lon| of a mesh, so a mesh handed over point by point
+// gets the same bits.  A target with land[i] > 0.7 (`land` may be null; a NaN fraction is not > 0.7) or a NaN coordinate is
+// inactive: tx = ty = NaN, and the bisection is not run for it.
+__global__ __launch_bounds__(BLOCK) void k_ocean_targets(long long n, const double *__restrict__ lat, const double *__restrict__ lon,
+                                                        const double *__restrict__ land, double *__restrict__ tx,
+                                                        double *__restrict__ ty) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double la = lat[i];
+    double lo = lon[i];
+    if (lo > 180.0) lo -= 360.0;
+    double x = __builtin_nan(""), y = __builtin_nan("");
+    if (!((land && land[i] > 0.7) || la != la || lo != lo)) {
+        const geo::Planar p = geo::planar(fabs(la), fabs(lo));
+        x = p.lat_m * (double)((la > 0) - (la < 0));
+        y = p.lon_m * (double)((lo > 0) - (lo < 0));
     }
-    geo::symmetric(U, 0.5 * (a_lo + a_hi), L, len);
-    double s = len;
-    if (U < 1e-15 && Ls <= (1.0 - geo::F) * geo::PI) s = geo::A * Ls;      // the equator itself
-    if (dl >= 180.0) s = over_pole;
-    if (fabs(la) >= 90.0) s = 0.0;
-    if (dl == 0.0) s = 0.0;
-    if (la != la || lo != lo) s = __builtin_nan("");
-    lat_m[i] = arc_m * sgn_la;
-    lon_m[i] = s * sgn_lo;
-    lon_off[i] = over_pole;
+    tx[i] = x;
+    ty[i] = y;
 }
 
 template <bool SWAP>

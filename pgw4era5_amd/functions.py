@@ -1016,6 +1016,20 @@ def _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name):
     return out
 
 
+def _target_layout(lat_dims, lat_shape, lon_dims, lon_shape):
+    """How a target's lat / lon lie: (False, (lat, lon)) for two 1-D axes over dimensions of their own (a mesh),
+    (True, their dimensions) for coordinates over the same dimensions (2-D coordinates of a rotated-pole grid, one `cell`
+    dimension: point by point); any other combination is a ValueError.  The rule of regrid_lat_lon and of the ocean-grid
+    branch of interp_wrapper."""
+    lat_dims, lon_dims, lat_shape, lon_shape = tuple(lat_dims), tuple(lon_dims), tuple(lat_shape), tuple(lon_shape)
+    if len(lat_shape) == 1 and len(lon_shape) == 1 and lat_dims != lon_dims:
+        return False, (LAT_GCM, LON_GCM)
+    if len(lat_shape) >= 1 and lat_dims == lon_dims and lat_shape == lon_shape:
+        return True, lat_dims
+    raise ValueError('target %s %s over %s and %s %s over %s are neither two 1-D axes of a mesh nor point-wise coordinates '
+                     'over the same dimensions' % (LAT_ERA, lat_shape, lat_dims, LON_ERA, lon_shape, lon_dims))
+
+
 def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
     """Bilinear regridding onto the ERA5 grid of `ds_era5` (reference functions.py:748-898).  i_use_xesmf = 0: the xarray
     branch, every lat/lon variable of `ds_gcm` (1-D source coordinates) through the separable kernel when the target's lat
@@ -1034,14 +1048,7 @@ def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
     src_lat = np.asarray(ds_gcm[LAT_GCM].values, dtype=np.float64)
     # 1-D lat over its own dimension and 1-D lon over its own: a mesh.  lat and lon over the same dimensions (2-D coordinates
     # of a rotated-pole grid, one `cell` dimension): xarray interpolates point by point.
-    if targ_lat.ndim == 1 and targ_lon.ndim == 1 and tuple(t_lat.dims) != tuple(t_lon.dims):
-        points, tdims = False, (LAT_GCM, LON_GCM)
-    elif targ_lat.ndim >= 1 and tuple(t_lat.dims) == tuple(t_lon.dims) and targ_lat.shape == targ_lon.shape:
-        points, tdims = True, tuple(t_lat.dims)
-    else:
-        raise ValueError('target %s %s over %s and %s %s over %s are neither two 1-D axes of a mesh nor point-wise coordinates '
-                         'over the same dimensions' % (LAT_ERA, targ_lat.shape, tuple(t_lat.dims), LON_ERA, targ_lon.shape,
-                                                       tuple(t_lon.dims)))
+    points, tdims = _target_layout(t_lat.dims, targ_lat.shape, t_lon.dims, targ_lon.shape)
     out = ncio.Dataset(attrs=ds_gcm.attrs)
     for name, f in ds_gcm.variables.items():
         if name in (LAT_GCM, LON_GCM):
@@ -1163,27 +1170,78 @@ def planar_metres(lat_deg, lon_deg):
     return tuple(o.numpy() for o in outs)
 
 
+def _ocean_source_values(gcm_lat, gcm_lon, fields):
+    """The ocean grid's points as flat arrays: (lat (npoint), lon (npoint) folded, values (npoint, nfield))."""
+    vals = np.stack([np.asarray(f, dtype=np.float64).reshape(-1) for f in fields], axis=1)       # (npoint, nfield)
+    glat = np.asarray(gcm_lat, dtype=np.float64).reshape(-1)
+    glon = _fold_lon(np.asarray(gcm_lon).reshape(-1))
+    if not (glat.shape == glon.shape == vals.shape[:1]):
+        raise ValueError('ocean-grid coordinates and values must have the same number of points')
+    return glat, glon, vals
+
+
+class _OceanCloud:
+    """The source cloud of the ocean-grid interpolation on the device, as both gauss_interp_fields and gauss_interp_points
+    hand it to their kernels: the points that are not NaN in every field, in planar metres, with the two shifted copies,
+    sorted into square cells of one kernel radius (`cell_start`: first point of each cell)."""
+
+    def __init__(self, ctx, gcm_lat, gcm_lon, fields, kernel_radius):
+        glat, glon, vals = _ocean_source_values(gcm_lat, gcm_lon, fields)
+        self.nf = nf = vals.shape[1]
+        keep = ~np.isnan(vals).all(axis=1)                     # :944-948 (a point that is NaN in every field is in no cloud)
+        glat, glon, vals = glat[keep], glon[keep], vals[keep]
+        lat_m, lon_m, lon_off = planar_metres(glat, glon)                                       # :958-975
+        # :977-991 the whole field once more to the left and to the right, shifted by twice the half-way-round length
+        sx = np.tile(lat_m, 3)
+        sy = np.concatenate([lon_m - 2 * lon_off, lon_m, lon_m + 2 * lon_off])
+        sv = np.tile(vals, (3, 1))
+        # uniform cells of one kernel radius over the source cloud
+        self.h = h = float(kernel_radius)
+        if len(sx):
+            x0, y0 = float(sx.min()), float(sy.min())
+            ncx, ncy = int((sx.max() - x0) // h) + 1, int((sy.max() - y0) // h) + 1
+            cid = ((sx - x0) // h).astype(np.int64) * ncy + ((sy - y0) // h).astype(np.int64)
+            order = np.argsort(cid, kind='stable')
+            sx, sy, sv, cid = sx[order], sy[order], sv[order], cid[order]
+            cell_start = np.searchsorted(cid, np.arange(ncx * ncy + 1)).astype(np.int32)
+        else:
+            x0 = y0 = 0.0; ncx = ncy = 1
+            cell_start = np.zeros(2, dtype=np.int32)
+        self.x0, self.y0, self.ncx, self.ncy, self.nsrc, self.sv = x0, y0, ncx, ncy, len(sx), sv
+        f64 = np.dtype('float64')
+        self.d_sx = ctx.to_device(sx if len(sx) else np.zeros(1), f64)
+        self.d_sy = ctx.to_device(sy if len(sy) else np.zeros(1), f64)
+        self.d_sv = ctx.to_device(np.ascontiguousarray(sv) if len(sx) else np.zeros((1, nf)), f64)
+        self.d_cs = ctx.empty(cell_start.shape, np.int32).copy_from(cell_start)
+
+    def interp(self, ctx, entry, d_tx, d_ty, ntarg, kernel_radius, sharpness):
+        """`entry` (pgw_gauss_interp / pgw_gauss_interp_points) for every field, 16 per pass: (nfield, ntarg)."""
+        f64 = np.dtype('float64')
+        nf = self.nf
+        out = np.empty((nf, ntarg))
+        for k0 in range(0, nf, 16):                           # the kernel takes up to 16 fields per pass
+            k1 = min(k0 + 16, nf)
+            if k0 or k1 < nf:
+                d_sub = ctx.to_device(np.ascontiguousarray(self.sv[:, k0:k1]), f64)
+            else:
+                d_sub = self.d_sv
+            d_out = ctx.empty((k1 - k0, ntarg), f64)
+            ctx._check(entry(ctx.handle, ntarg, d_tx.ptr, d_ty.ptr, self.ncx, self.ncy, self.x0, self.y0, self.h, self.d_cs.ptr,
+                             self.nsrc, self.d_sx.ptr, self.d_sy.ptr, d_sub.ptr, k1 - k0, float(kernel_radius), float(sharpness),
+                             d_out.ptr))
+            out[k0:k1] = d_out.numpy()
+        return out
+
+
 def gauss_interp_fields(land_fr, era5_lat, era5_lon, gcm_lat, gcm_lon, fields, kernel_radius, sharpness):
     """The geometry and the GPU pass of nan_ignoring_interp for SEVERAL fields on the same source points (the twelve
     months of a variable: interp_wrapper calls nan_ignoring_interp once per month, functions.py:1102-1109, rebuilding
     the same two point clouds each time).
     land_fr (nlat, nlon); era5_lat (nlat), era5_lon (nlon); gcm_lat, gcm_lon, fields[k]: arrays of one common shape
     (curvilinear 2-D coordinates flattened like :931-933).  Returns (nfield, nlat, nlon) float64."""
-    from . import geodesy
     ctx = default_context()
-    vals = np.stack([np.asarray(f, dtype=np.float64).reshape(-1) for f in fields], axis=1)       # (npoint, nfield)
-    glat = np.asarray(gcm_lat, dtype=np.float64).reshape(-1)
-    glon = _fold_lon(np.asarray(gcm_lon).reshape(-1))
-    if not (glat.shape == glon.shape == vals.shape[:1]):
-        raise ValueError('ocean-grid coordinates and values must have the same number of points')
-    nf = vals.shape[1]
-    keep = ~np.isnan(vals).all(axis=1)                         # :944-948 (a point that is NaN in every field is in no cloud)
-    glat, glon, vals = glat[keep], glon[keep], vals[keep]
-    lat_m, lon_m, lon_off = planar_metres(glat, glon)                                           # :958-975
-    # :977-991 the whole field once more to the left and to the right, shifted by twice the half-way-round length
-    sx = np.tile(lat_m, 3)
-    sy = np.concatenate([lon_m - 2 * lon_off, lon_m, lon_m + 2 * lon_off])
-    sv = np.tile(vals, (3, 1))
+    cloud = _OceanCloud(ctx, gcm_lat, gcm_lon, fields, kernel_radius)
+    nf = cloud.nf
     elat = np.asarray(era5_lat, dtype=np.float64)
     elon = _fold_lon(era5_lon)
     tlat = np.repeat(elat, len(elon)); tlon = np.tile(elon, len(elat))                         # :1004-1005
@@ -1216,35 +1274,9 @@ def gauss_interp_fields(land_fr, era5_lat, era5_lon, gcm_lat, gcm_lon, fields, k
         return full.reshape(nty, TILE, ntx, TILE).transpose(0, 2, 1, 3).reshape(nty * ntx, TILE * TILE)[tile_order]
     tx, ty = tiles(tx), tiles(ty)
     tx, ty = np.ascontiguousarray(tx.reshape(-1)), np.ascontiguousarray(ty.reshape(-1))
-    # uniform cells of one kernel radius over the source cloud
-    h = float(kernel_radius)
-    if len(sx):
-        x0, y0 = float(sx.min()), float(sy.min())
-        ncx, ncy = int((sx.max() - x0) // h) + 1, int((sy.max() - y0) // h) + 1
-        cid = ((sx - x0) // h).astype(np.int64) * ncy + ((sy - y0) // h).astype(np.int64)
-        order = np.argsort(cid, kind='stable')
-        sx, sy, sv, cid = sx[order], sy[order], sv[order], cid[order]
-        cell_start = np.searchsorted(cid, np.arange(ncx * ncy + 1)).astype(np.int32)
-    else:
-        x0 = y0 = 0.0; ncx = ncy = 1
-        cell_start = np.zeros(2, dtype=np.int32)
     f64 = np.dtype('float64')
     d_tx, d_ty = ctx.to_device(tx, f64), ctx.to_device(ty, f64)
-    d_sx, d_sy = ctx.to_device(sx if len(sx) else np.zeros(1), f64), ctx.to_device(sy if len(sy) else np.zeros(1), f64)
-    d_sv = ctx.to_device(np.ascontiguousarray(sv) if len(sx) else np.zeros((1, nf)), f64)
-    d_cs = ctx.empty(cell_start.shape, np.int32).copy_from(cell_start)
-    ntarg = len(tx)
-    out = np.empty((nf, ntarg))
-    for k0 in range(0, nf, 16):                               # the kernel takes up to 16 fields per pass
-        k1 = min(k0 + 16, nf)
-        if k0 or k1 < nf:
-            d_sub = ctx.to_device(np.ascontiguousarray(sv[:, k0:k1]), f64)
-        else:
-            d_sub = d_sv
-        d_out = ctx.empty((k1 - k0, ntarg), f64)
-        ctx._check(ctx.lib.pgw_gauss_interp(ctx.handle, ntarg, d_tx.ptr, d_ty.ptr, ncx, ncy, x0, y0, h, d_cs.ptr, len(sx),
-                                            d_sx.ptr, d_sy.ptr, d_sub.ptr, k1 - k0, float(kernel_radius), float(sharpness), d_out.ptr))
-        out[k0:k1] = d_out.numpy()
+    out = cloud.interp(ctx, ctx.lib.pgw_gauss_interp, d_tx, d_ty, len(tx), kernel_radius, sharpness)
     back = np.empty_like(tile_order)
     back[tile_order] = np.arange(len(tile_order))
     out = out.reshape(nf, nty * ntx, TILE * TILE)[:, back]
@@ -1253,6 +1285,37 @@ def gauss_interp_fields(land_fr, era5_lat, era5_lon, gcm_lat, gcm_lon, fields, k
     land = np.asarray(land_fr, dtype=np.float64).reshape(-1)
     out[:, land > 0.7] = np.nan                               # :1032, 1055: no SST on land points
     return out.reshape(nf, len(elat), len(elon))
+
+
+def gauss_interp_points(land_fr, targ_lat, targ_lon, gcm_lat, gcm_lon, fields, kernel_radius, sharpness):
+    """gauss_interp_fields for POINT-WISE targets: targ_lat / targ_lon [deg] of one common shape of rank >= 1 (2-D
+    coordinates of a rotated-pole file, a cell list), land_fr of that shape or None.  The target side runs on the GPU:
+    planar metres (`pgw_ocean_targets`: targets with land_fr > 0.7 or a NaN coordinate are inactive and come back NaN),
+    then `pgw_gauss_interp_points`, which orders the targets by the source's cells on the device and writes every result
+    to its own place.  A mesh handed over point by point gives the bits of gauss_interp_fields.
+    Returns (nfield,) + targ_lat.shape float64."""
+    tlat = np.asarray(targ_lat, dtype=np.float64)
+    tlon = np.asarray(targ_lon, dtype=np.float64)
+    if tlat.ndim < 1 or tlat.shape != tlon.shape:
+        raise ValueError('target latitudes of shape %s and longitudes of shape %s must have one common shape of rank >= 1'
+                         % (tlat.shape, tlon.shape))
+    land = None if land_fr is None else np.asarray(land_fr, dtype=np.float64)
+    if land is not None and land.shape != tlat.shape:
+        raise ValueError('land fraction of shape %s does not lie on the targets of shape %s' % (land.shape, tlat.shape))
+    ntarg = tlat.size
+    if ntarg == 0:
+        return np.empty((_ocean_source_values(gcm_lat, gcm_lon, fields)[2].shape[1],) + tlat.shape)
+    _ocean_source_values(gcm_lat, gcm_lon, fields)            # its shape error comes before the context is touched
+    ctx = default_context()
+    cloud = _OceanCloud(ctx, gcm_lat, gcm_lon, fields, kernel_radius)
+    f64 = np.dtype('float64')
+    d_lat, d_lon = ctx.to_device(np.ascontiguousarray(tlat.reshape(-1)), f64), ctx.to_device(np.ascontiguousarray(tlon.reshape(-1)), f64)
+    d_land = None if land is None else ctx.to_device(np.ascontiguousarray(land.reshape(-1)), f64)
+    d_tx, d_ty = ctx.empty((ntarg,), f64), ctx.empty((ntarg,), f64)
+    ctx._check(ctx.lib.pgw_ocean_targets(ctx.handle, ntarg, d_lat.ptr, d_lon.ptr, None if d_land is None else d_land.ptr,
+                                         d_tx.ptr, d_ty.ptr))
+    out = cloud.interp(ctx, ctx.lib.pgw_gauss_interp_points, d_tx, d_ty, ntarg, kernel_radius, sharpness)
+    return out.reshape((cloud.nf,) + tlat.shape)
 
 
 def _ocean_coords(da_delta):
@@ -1273,20 +1336,48 @@ def nan_ignoring_interp(da_era5_land_fr, da_delta, kernel_radius, sharpness):
     (FR_LAND > 0.7) come back NaN.  reference functions.py:900-1060.  Labelled inputs like the reference's
     (`.values`, `.coords` with the ocean grid's `latitude` / `longitude`, ERA5 `lat` / `lon`)."""
     glat, glon = _ocean_coords(da_delta)
-    res = gauss_interp_fields(np.asarray(da_era5_land_fr.values), da_era5_land_fr.coords[LAT_ERA], da_era5_land_fr.coords[LON_ERA],
-                              glat, glon, [np.asarray(da_delta.values)], kernel_radius, sharpness)
+    t_lat, t_lon = da_era5_land_fr.coords[LAT_ERA], da_era5_land_fr.coords[LON_ERA]
+
+    def dims_of(c, name):                                       # a coordinate array: an axis of its own name, or over the field's dimensions
+        if hasattr(c, 'dims'):
+            return tuple(c.dims)
+        return (name,) if np.ndim(c) == 1 and name in da_era5_land_fr.dims else tuple(da_era5_land_fr.dims)
+    points, _ = _target_layout(dims_of(t_lat, LAT_ERA), np.shape(t_lat), dims_of(t_lon, LON_ERA), np.shape(t_lon))
+    t_lat = np.asarray(getattr(t_lat, 'values', t_lat))
+    t_lon = np.asarray(getattr(t_lon, 'values', t_lon))
+    interp = gauss_interp_points if points else gauss_interp_fields
+    res = interp(np.asarray(da_era5_land_fr.values), t_lat, t_lon, glat, glon, [np.asarray(da_delta.values)], kernel_radius, sharpness)
     return res[0]
+
+
+def _ocean_time_field(t):
+    from . import ncio
+    return ncio.Field(t.values, ('time',), {'time': t.values}, {k: v for k, v in t.attrs.items() if k not in ('units', 'calendar')}
+                      if t.values.dtype.kind == 'M' else t.attrs)
 
 
 def interp_wrapper(origin_grid, target_grid, var_name, i_use_xesmf=0,
                    nan_interp_kernel_radius=300000, nan_interp_sharpness=3):
     """Per-variable choice of the regridding scheme (reference functions.py:1062-1141).
     Atmospheric variables: bilinear on the GPU.  `tos` / `siconc` (ocean grid, NaN over land): the Gaussian-kernel
-    point-cloud interpolation, all twelve months in one pass."""
+    point-cloud interpolation, all twelve months in one pass - onto a mesh (1-D lat and lon axes) through
+    gauss_interp_fields, onto lat / lon over shared dimensions (rotated-pole extpar file, cell list; FR_LAND over those
+    dimensions or with a leading time axis of 1) through gauss_interp_points, the result laid out over ('time',) + those
+    dimensions with lat / lon as variables over them."""
     from . import ncio
     if var_name in ['tos', 'siconc']:
         land = target_grid['FR_LAND']
-        land2d = np.asarray(land.values)[0]                                        # target_grid["FR_LAND"][0,:,:]  :1097
+        t_lat, t_lon = target_grid[LAT_ERA], target_grid[LON_ERA]
+        points, tdims = _target_layout(t_lat.dims, t_lat.shape, t_lon.dims, t_lon.shape)
+        if points:                                              # an extpar file has no time axis: (1,) + tdims or tdims
+            land_pts = np.asarray(land.values)
+            if land_pts.shape == (1,) + tuple(t_lat.shape):
+                land_pts = land_pts[0]
+            elif land_pts.shape != tuple(t_lat.shape):
+                raise ValueError('FR_LAND of shape %s lies neither over the target coordinates of shape %s nor over one '
+                                 'time step of them' % (land_pts.shape, tuple(t_lat.shape)))
+        else:
+            land2d = np.asarray(land.values)[0]                                    # target_grid["FR_LAND"][0,:,:]  :1097
         values = origin_grid[var_name]
         glat, glon = _ocean_coords(ncio.Field(values.values[0], values.dims[1:],
                                               {LAT_GCM_OCEAN: np.asarray(origin_grid[LAT_GCM_OCEAN].values),
@@ -1296,14 +1387,21 @@ def interp_wrapper(origin_grid, target_grid, var_name, i_use_xesmf=0,
                              % (var_name, values.shape[0]))                         # result = np.empty((12, ...))  :1101
         tlat = np.asarray(target_grid[LAT_ERA].values, dtype=np.float64)
         tlon = np.asarray(target_grid[LON_ERA].values, dtype=np.float64)
+        if points:                                              # lat / lon over shared dimensions: laid out like regrid_lat_lon's points branch
+            result = gauss_interp_points(land_pts, tlat, tlon, glat, glon, [values.values[i] for i in range(12)],
+                                         nan_interp_kernel_radius, nan_interp_sharpness)
+            ds = ncio.Dataset(attrs=dict(description=str(var_name) + " on ERA5 grid", units="K", long_name=str(var_name)))
+            ds['lat'] = ncio.Field(tlat, tdims, {}, target_grid[LAT_ERA].attrs)
+            ds['lon'] = ncio.Field(tlon, tdims, {}, target_grid[LON_ERA].attrs)
+            ds['time'] = _ocean_time_field(origin_grid[TIME_GCM])
+            ds[var_name] = ncio.Field(result, ('time',) + tdims, {'time': ds['time'].values})
+            return ds
         result = gauss_interp_fields(land2d, tlat, tlon, glat, glon, [values.values[i] for i in range(12)],
                                      nan_interp_kernel_radius, nan_interp_sharpness)
         ds = ncio.Dataset(attrs=dict(description=str(var_name) + " on ERA5 grid", units="K", long_name=str(var_name)))   # :1121, 1134
         ds['lat'] = ncio.Field(tlat, ('lat',), {'lat': tlat}, target_grid[LAT_ERA].attrs)
         ds['lon'] = ncio.Field(tlon, ('lon',), {'lon': tlon}, target_grid[LON_ERA].attrs)
-        t = origin_grid[TIME_GCM]
-        ds['time'] = ncio.Field(t.values, ('time',), {'time': t.values}, {k: v for k, v in t.attrs.items() if k not in ('units', 'calendar')}
-                                if t.values.dtype.kind == 'M' else t.attrs)
-        ds[var_name] = ncio.Field(result, ('time', 'lat', 'lon'), {'time': t.values, 'lat': tlat, 'lon': tlon})
+        ds['time'] = _ocean_time_field(origin_grid[TIME_GCM])
+        ds[var_name] = ncio.Field(result, ('time', 'lat', 'lon'), {'time': ds['time'].values, 'lat': tlat, 'lon': tlon})
         return ds
     return regrid_lat_lon(origin_grid, target_grid, var_name, method='bilinear', i_use_xesmf=i_use_xesmf)

@@ -8,7 +8,8 @@ Command line of the reference's step_02_preproc_deltas.py (:27-87): positional
 point-wise form), or with settings.i_use_xesmf_regridding = 1 the cell-locate / sparse-apply kernels for source
 grids with 2-D coordinates; `smoothing` runs the annual-cycle filter for daily deltas
 (functions.filter_data, reference functions.py:603-740); tos / siconc on the ocean grid go through the
-NaN-ignoring Gaussian-kernel interpolation (functions.nan_ignoring_interp, reference functions.py:900-1060).
+NaN-ignoring Gaussian-kernel interpolation (functions.nan_ignoring_interp, reference functions.py:900-1060), onto a
+mesh or onto a target file with 2-D lat / lon alike.
 """
 import argparse
 import os
