@@ -88,10 +88,12 @@ static int fail(pgw_ctx *ctx, int code, const char *fmt, ...) {
                         __FILE__, __LINE__);                                                       \
     } while (0)
 
-#define NEED(ctx, cond, msg)                                                                       \
+// NEED_AS: in a helper that checks for several entries, under the name of the entry that called it
+#define NEED_AS(ctx, caller, cond, msg)                                                            \
     do {                                                                                           \
-        if (!(cond)) return fail(ctx, PGW_ERR_ARG, "%s: %s", __func__, msg);                       \
+        if (!(cond)) return fail(ctx, PGW_ERR_ARG, "%s: %s", caller, msg);                         \
     } while (0)
+#define NEED(ctx, cond, msg) NEED_AS(ctx, __func__, cond, msg)
 
 static const char *status_text(int code) {
     switch (code) {
@@ -528,7 +530,7 @@ template <typename T> static inline PairSrc<T> pair_src(const void *b0, const vo
 // `caller` names the entry in the status text.  soil_depth may be NULL where no soil output is asked for (the callers check
 // that after the layer count): the weights then stay 0 and no kernel reads them.
 static int soil_table(pgw_ctx *ctx, const char *caller, int nsoil, const double *soil_depth, SoilTable *st) {
-    if (nsoil < 0 || nsoil > MAX_SOIL) return fail(ctx, PGW_ERR_ARG, "%s: %s", caller, "nsoil must be in [0, 16]");
+    NEED_AS(ctx, caller, nsoil >= 0 && nsoil <= MAX_SOIL, "nsoil must be in [0, 16]");
     memset(st, 0, sizeof(*st));
     st->n = nsoil;
     for (int s = 0; soil_depth && s < nsoil; ++s) st->w[s] = exp(-soil_depth[s] / 2.8);      // step_03:140
@@ -2405,20 +2407,31 @@ extern "C" int pgw_harmonic_smooth(pgw_ctx *ctx, int dtype, int ntime, long long
     return PGW_OK;
 }
 
+// What pgw_gauss_interp and pgw_gauss_interp_points ask of their arguments alike (`caller` names the entry in the status text),
+// and the constants their kernels take: radius^2, vtkGaussianKernel's F2 = (Sharpness / Radius)^2, cells per metre
+struct GaussParams { double r2, f2, inv_h; };
+static int gauss_args(pgw_ctx *ctx, const char *caller, long long ntarg, const double *tx, const double *ty, int ncx, int ncy,
+                      double cell, const int *cell_start, long long nsrc, const double *sx, const double *sy, const double *sval,
+                      int nfield, double radius, double sharpness, const double *out, GaussParams *g) {
+    NEED_AS(ctx, caller, ntarg >= 1 && nsrc >= 0 && tx && ty && cell_start && out, "bad argument");
+    NEED_AS(ctx, caller, nsrc == 0 || (sx && sy && sval), "null source pointer");
+    NEED_AS(ctx, caller, ncx >= 1 && ncy >= 1 && cell > 0.0 && radius > 0.0, "bad cell grid");
+    NEED_AS(ctx, caller, cell >= radius, "cells must be at least one kernel radius wide (3 x 3 block search)");
+    NEED_AS(ctx, caller, nfield >= 1 && nfield <= GAUSS_MAX_FIELDS, "nfield must be in [1, 16]");
+    *g = {radius * radius, (sharpness * sharpness) / (radius * radius), 1.0 / cell};
+    return PGW_OK;
+}
+
 extern "C" int pgw_gauss_interp(pgw_ctx *ctx, long long ntarg, const double *tx, const double *ty, int ncx, int ncy,
                                 double x0, double y0, double cell, const int *cell_start, long long nsrc, const double *sx,
                                 const double *sy, const double *sval, int nfield, double radius, double sharpness, double *out) {
-    NEED(ctx, ntarg >= 1 && nsrc >= 0 && tx && ty && cell_start && out, "bad argument");
-    NEED(ctx, nsrc == 0 || (sx && sy && sval), "null source pointer");
-    NEED(ctx, ncx >= 1 && ncy >= 1 && cell > 0.0 && radius > 0.0, "bad cell grid");
-    NEED(ctx, cell >= radius, "cells must be at least one kernel radius wide (3 x 3 block search)");
-    NEED(ctx, nfield >= 1 && nfield <= GAUSS_MAX_FIELDS, "nfield must be in [1, 16]");
+    GaussParams g;
+    if (int rc = gauss_args(ctx, __func__, ntarg, tx, ty, ncx, ncy, cell, cell_start, nsrc, sx, sy, sval, nfield, radius, sharpness, out, &g)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const double r2 = radius * radius, f2 = (sharpness * sharpness) / (radius * radius);     // vtkGaussianKernel: F2 = (Sharpness / Radius)^2
     {
         Prof pr(ctx, PGW_K_GAUSS_INTERP);
         hipLaunchKernelGGL((k_gauss_interp<GAUSS_MAX_FIELDS>), dim3(nblocks(ntarg, BLOCK)), dim3(BLOCK), 0, ctx->stream, ntarg, tx, ty,
-                           ncx, ncy, x0, y0, 1.0 / cell, cell_start, sx, sy, sval, nfield, r2, f2, out);
+                           ncx, ncy, x0, y0, g.inv_h, cell_start, sx, sy, sval, nfield, g.r2, g.f2, out);
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -2448,11 +2461,8 @@ extern "C" int pgw_gauss_interp_points(pgw_ctx *ctx, long long ntarg, const doub
                                        double x0, double y0, double cell, const int *cell_start, long long nsrc, const double *sx,
                                        const double *sy, const double *sval, int nfield, double radius, double sharpness,
                                        double *out) {
-    NEED(ctx, ntarg >= 1 && nsrc >= 0 && tx && ty && cell_start && out, "bad argument");
-    NEED(ctx, nsrc == 0 || (sx && sy && sval), "null source pointer");
-    NEED(ctx, ncx >= 1 && ncy >= 1 && cell > 0.0 && radius > 0.0, "bad cell grid");
-    NEED(ctx, cell >= radius, "cells must be at least one kernel radius wide (3 x 3 block search)");
-    NEED(ctx, nfield >= 1 && nfield <= GAUSS_MAX_FIELDS, "nfield must be in [1, 16]");
+    GaussParams g;
+    if (int rc = gauss_args(ctx, __func__, ntarg, tx, ty, ncx, ncy, cell, cell_start, nsrc, sx, sy, sval, nfield, radius, sharpness, out, &g)) return rc;
     NEED(ctx, ntarg < (1ll << 31), "ntarg must be below 2^31 (the order of the targets is kept in 32-bit indices)");
     // keys: the cells and a ring around them, GAUSS_SUB x GAUSS_SUB parts of each, and one for the inactive targets
     const long long nkey = ((long long)ncx + 2) * ((long long)ncy + 2) * (GAUSS_SUB * GAUSS_SUB) + 1;
@@ -2460,21 +2470,18 @@ extern "C" int pgw_gauss_interp_points(pgw_ctx *ctx, long long ntarg, const doub
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // workspace: n_active (and padding) | key [ntarg] | order [ntarg] | count -> start [nkey]
     void *wsp = nullptr;
-    int rc = ws_get(ctx, 8, sizeof(int) * (4 + 2 * (size_t)ntarg + (size_t)nkey), &wsp);
-    if (rc) return rc;
+    if (int rc = ws_get(ctx, 8, sizeof(int) * (4 + 2 * (size_t)ntarg + (size_t)nkey), &wsp)) return rc;
     int *n_active = (int *)wsp, *key = n_active + 4, *order = key + ntarg, *count = order + ntarg;
-    const double r2 = radius * radius, f2 = (sharpness * sharpness) / (radius * radius);     // vtkGaussianKernel: F2 = (Sharpness / Radius)^2
-    const double inv_h = 1.0 / cell;
     const unsigned int nb = nblocks(ntarg, BLOCK);
     HIPCHK(ctx, hipMemsetAsync(count, 0, sizeof(int) * (size_t)nkey, ctx->stream));
-    hipLaunchKernelGGL(k_gauss_keys, dim3(nb), dim3(BLOCK), 0, ctx->stream, (int)ntarg, tx, ty, ncx, ncy, x0, y0, inv_h, key, count);
+    hipLaunchKernelGGL(k_gauss_keys, dim3(nb), dim3(BLOCK), 0, ctx->stream, (int)ntarg, tx, ty, ncx, ncy, x0, y0, g.inv_h, key, count);
     hipLaunchKernelGGL(k_gauss_scan, dim3(1), dim3(SCAN_BLOCK), 0, ctx->stream, (int)nkey, count, n_active);
     hipLaunchKernelGGL(k_gauss_scatter, dim3(nb), dim3(BLOCK), 0, ctx->stream, (int)ntarg, key, count, order);
     HIPCHK(ctx, hipGetLastError());
     {
         Prof pr(ctx, PGW_K_GAUSS_INTERP);
         hipLaunchKernelGGL((k_gauss_points<GAUSS_MAX_FIELDS>), dim3(nb), dim3(BLOCK), 0, ctx->stream, (int)ntarg, order, n_active, tx, ty,
-                           ncx, ncy, x0, y0, inv_h, cell_start, sx, sy, sval, nfield, r2, f2, out);
+                           ncx, ncy, x0, y0, g.inv_h, cell_start, sx, sy, sval, nfield, g.r2, g.f2, out);
     }
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
@@ -2603,6 +2610,61 @@ extern "C" int pgw_test_exp_reduced(pgw_ctx *ctx, long long n, const double *in,
 }
 
 // ------------------------------------------------------------------ regridding
+// The bracket tables over n targets - pgw_regrid_bilinear: one axis per call, the other NULL; pgw_regrid_points: both.  Rows lie
+// in [-1, nlat_s] (-1 / nlat_s: the pole rows), columns in [0, nlon_s); an entry whose `skip` flag is set is never read.
+static int check_brackets(pgw_ctx *ctx, const char *caller, long long n, const int *skip, const int *lat_lo, const int *lat_hi,
+                          const int *lon_lo, const int *lon_hi, int nlat_s, int nlon_s, int south_row, int north_row) {
+    NEED_AS(ctx, caller, !lat_lo || (south_row < nlat_s && north_row < nlat_s), "bad pole row");
+    for (long long g = 0; g < n; ++g) {
+        if (skip[g]) continue;
+        if (lon_lo) NEED_AS(ctx, caller, lon_lo[g] >= 0 && lon_lo[g] < nlon_s && lon_hi[g] >= 0 && lon_hi[g] < nlon_s, "lon index out of range");
+        if (!lat_lo) continue;
+        NEED_AS(ctx, caller, lat_lo[g] >= -1 && lat_lo[g] <= nlat_s && lat_hi[g] >= -1 && lat_hi[g] <= nlat_s, "lat index out of range");
+        // a pole row is only there when its zonal mean is taken: k_zonal_mean_rows leaves the pole value of a negative row unwritten
+        NEED_AS(ctx, caller, south_row >= 0 || (lat_lo[g] != -1 && lat_hi[g] != -1), "south-pole row in the tables but south_row < 0");
+        NEED_AS(ctx, caller, north_row >= 0 || (lat_lo[g] != nlat_s && lat_hi[g] != nlat_s), "north-pole row in the tables but north_row < 0");
+    }
+    return PGW_OK;
+}
+
+// Host tables -> device workspace slot 3 as [double tables][pole: 2 * nfield doubles][int tables], each list back to back in the
+// order given and every `*dev` set to where its table lies.  The host tables may be freed after the call.
+template <typename T> struct HostTable { const T *host; size_t n; const T **dev; };
+static int tables_to_slot3(pgw_ctx *ctx, std::initializer_list<HostTable<double>> dbl, std::initializer_list<HostTable<int>> ints,
+                           long long nfield, double **dpole) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    size_t td = 0, ti = 0, at = 0;
+    for (const auto &t : dbl) td += sizeof(double) * t.n;
+    for (const auto &t : ints) ti += sizeof(int) * t.n;
+    const size_t tp = sizeof(double) * 2 * (size_t)nfield;
+    char *tab = nullptr;
+    if (int rc = ws_get(ctx, 3, td + tp + ti + 64, (void **)&tab)) return rc;
+    std::vector<char> h(td + ti);                              // the pole values are the device's own: not staged, tp apart there
+    for (const auto &t : dbl) { memcpy(h.data() + at, t.host, sizeof(double) * t.n); *t.dev = (const double *)(tab + at); at += sizeof(double) * t.n; }
+    for (const auto &t : ints) { memcpy(h.data() + at, t.host, sizeof(int) * t.n); *t.dev = (const int *)(tab + tp + at); at += sizeof(int) * t.n; }
+    *dpole = (double *)(tab + td);
+    HIPCHK(ctx, hipMemcpyAsync(tab, h.data(), td, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(tab + td + tp, h.data() + td, ti, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PGW_OK;
+}
+
+// zonal means of the source rows next to the poles -> dpole [nfield][2]; nothing to do without a pole row
+static void launch_pole_means(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, const void *src, int south_row,
+                              int north_row, double *dpole) {
+    if (south_row >= 0 || north_row >= 0)
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_zonal_mean_rows<T>), dim3(nblocks(nfield * 2 * 64, BLOCK)), dim3(BLOCK), 0, ctx->stream, nfield,
+                               nlat_s, nlon_s, (const T *)src, south_row, north_row, dpole);
+        });
+}
+
+// z-slices of a launch with blocks_xy blocks per slice: enough blocks to fill 256 CUs several times over even for few targets
+static unsigned int z_slices(long long blocks_xy, long long nfield) {
+    return (unsigned int)std::clamp((8192 + blocks_xy - 1) / blocks_xy, 1ll, nfield);
+}
+
 extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, int nlat_t,
                                    int nlon_t, const void *src, const int *lat_lo, const int *lat_hi,
                                    const double *lat_dx, const double *lat_Dx, const int *lat_oob, const int *lon_lo,
@@ -2612,57 +2674,23 @@ extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, in
     NEED(ctx, nfield >= 1 && nlat_s >= 2 && nlon_s >= 2 && nlat_t >= 1 && nlon_t >= 1, "bad shape");
     NEED(ctx, src && out && lat_lo && lat_hi && lat_dx && lat_Dx && lat_oob && lon_lo && lon_hi && lon_dx && lon_Dx && lon_oob,
          "null pointer");
-    NEED(ctx, south_row < nlat_s && north_row < nlat_s, "bad pole row");
-    for (int j = 0; j < nlat_t; ++j)
-        NEED(ctx, lat_oob[j] || (lat_lo[j] >= -1 && lat_lo[j] <= nlat_s && lat_hi[j] >= -1 && lat_hi[j] <= nlat_s), "lat index out of range");
-    // a pole row is only there when its zonal mean is taken: k_zonal_mean_rows leaves the pole value of a negative row unwritten
-    for (int j = 0; j < nlat_t; ++j) {
-        if (lat_oob[j]) continue;
-        NEED(ctx, south_row >= 0 || (lat_lo[j] != -1 && lat_hi[j] != -1), "south-pole row in the tables but south_row < 0");
-        NEED(ctx, north_row >= 0 || (lat_lo[j] != nlat_s && lat_hi[j] != nlat_s), "north-pole row in the tables but north_row < 0");
-    }
-    for (int i = 0; i < nlon_t; ++i)
-        NEED(ctx, lon_oob[i] || (lon_lo[i] >= 0 && lon_lo[i] < nlon_s && lon_hi[i] >= 0 && lon_hi[i] < nlon_s), "lon index out of range");
-    // tables -> device workspace slot 3
-    size_t ti = sizeof(int) * (3 * (size_t)nlat_t + 3 * (size_t)nlon_t);
-    size_t td = sizeof(double) * (2 * (size_t)nlat_t + 2 * (size_t)nlon_t);
-    size_t tp = sizeof(double) * 2 * (size_t)nfield;
-    void *tab = nullptr;
-    int rc = ws_get(ctx, 3, td + tp + ti + 64, &tab);
-    if (rc) return rc;
-    std::vector<char> h(td + ti);
-    double *hd = (double *)h.data();
-    memcpy(hd, lat_dx, 8 * nlat_t); memcpy(hd + nlat_t, lat_Dx, 8 * nlat_t);
-    memcpy(hd + 2 * nlat_t, lon_dx, 8 * nlon_t); memcpy(hd + 2 * nlat_t + nlon_t, lon_Dx, 8 * nlon_t);
-    int *hi = (int *)(h.data() + td);
-    memcpy(hi, lat_lo, 4 * nlat_t); memcpy(hi + nlat_t, lat_hi, 4 * nlat_t); memcpy(hi + 2 * nlat_t, lat_oob, 4 * nlat_t);
-    int *hl = hi + 3 * nlat_t;
-    memcpy(hl, lon_lo, 4 * nlon_t); memcpy(hl + nlon_t, lon_hi, 4 * nlon_t); memcpy(hl + 2 * nlon_t, lon_oob, 4 * nlon_t);
-    double *dd = (double *)tab;
-    double *dpole = dd + 2 * nlat_t + 2 * nlon_t;
-    int *di = (int *)(dpole + 2 * nfield);
-    HIPCHK(ctx, hipMemcpyAsync(dd, hd, td, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(di, hi, ti, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = check_brackets(ctx, __func__, nlat_t, lat_oob, lat_lo, lat_hi, nullptr, nullptr, nlat_s, nlon_s, south_row, north_row)) return rc;
+    if (int rc = check_brackets(ctx, __func__, nlon_t, lon_oob, nullptr, nullptr, lon_lo, lon_hi, nlat_s, nlon_s, south_row, north_row)) return rc;
+    const size_t a = (size_t)nlat_t, o = (size_t)nlon_t;
     RegridTables tb;
-    tb.lat_dx = dd; tb.lat_Dx = dd + nlat_t; tb.lon_dx = dd + 2 * nlat_t; tb.lon_Dx = dd + 2 * nlat_t + nlon_t;
-    tb.lat_lo = di; tb.lat_hi = di + nlat_t; tb.lat_oob = di + 2 * nlat_t;
-    tb.lon_lo = di + 3 * nlat_t; tb.lon_hi = tb.lon_lo + nlon_t; tb.lon_oob = tb.lon_lo + 2 * nlon_t;
+    double *dpole;
+    if (int rc = tables_to_slot3(ctx, {{lat_dx, a, &tb.lat_dx}, {lat_Dx, a, &tb.lat_Dx}, {lon_dx, o, &tb.lon_dx}, {lon_Dx, o, &tb.lon_Dx}},
+                              {{lat_lo, a, &tb.lat_lo}, {lat_hi, a, &tb.lat_hi}, {lat_oob, a, &tb.lat_oob},
+                               {lon_lo, o, &tb.lon_lo}, {lon_hi, o, &tb.lon_hi}, {lon_oob, o, &tb.lon_oob}}, nfield, &dpole))
+        return rc;
     {
         Prof pr(ctx, PGW_K_REGRID);
-        if (south_row >= 0 || north_row >= 0)
-            with_type(dtype, [&](auto t_) {
-                using T = decltype(t_);
-                hipLaunchKernelGGL((k_zonal_mean_rows<T>), dim3(nblocks(nfield * 2 * 64, BLOCK)), dim3(BLOCK), 0, ctx->stream, nfield,
-                                   nlat_s, nlon_s, (const T *)src, south_row, north_row, dpole);
-            });
-        // two target longitudes per thread (one 16-B / 8-B store per plane) when the row length and the output
-        // alignment allow; z-slices: enough blocks to fill 256 CUs several times over even for small target grids
+        launch_pole_means(ctx, dtype, nfield, nlat_s, nlon_s, src, south_row, north_row, dpole);
+        // two target longitudes per thread (one 16-B / 8-B store per plane) when the row length and the output alignment allow
         const int W = (nlon_t % 2 == 0 && ((uintptr_t)out % (2 * elem_size(dtype))) == 0 && !ctx->opt[PGW_OPT_FORCE_VEC1]) ? 2 : 1;
         const unsigned int bx = nblocks(nlon_t, BLOCK * W);
         long long xy = (long long)bx * nlat_t;
-        long long want = (8192 + xy - 1) / xy;
-        unsigned int gz = (unsigned int)(want < 1 ? 1 : (want > nfield ? nfield : want));
+        unsigned int gz = z_slices(xy, nfield);
         // z-slices in multiples of 8 where there are planes for it: one XCD per slice group (k_regrid)
         if (nfield >= 8) gz = (gz + 7u) / 8u * 8u;
         if (gz > nfield) gz = (unsigned int)nfield;
@@ -2689,49 +2717,21 @@ extern "C" int pgw_regrid_points(pgw_ctx *ctx, int dtype, long long nfield, int 
     NEED(ctx, nlat_s >= 2 && nlon_s >= 2 && (long long)nlat_s * nlon_s < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
     NEED(ctx, src && out && lat_lo && lat_hi && lat_dx && lat_Dx && lon_lo && lon_hi && lon_dx && lon_Dx && oob, "null pointer");
     NEED(ctx, ((uintptr_t)src % elem_size(dtype)) == 0 && ((uintptr_t)out % elem_size(dtype)) == 0, "pointers must be element-aligned");
-    NEED(ctx, south_row < nlat_s && north_row < nlat_s, "bad pole row");
-    for (long long g = 0; g < ntarg; ++g) {
-        if (oob[g]) continue;
-        NEED(ctx, lat_lo[g] >= -1 && lat_lo[g] <= nlat_s && lat_hi[g] >= -1 && lat_hi[g] <= nlat_s, "lat index out of range");
-        NEED(ctx, lon_lo[g] >= 0 && lon_lo[g] < nlon_s && lon_hi[g] >= 0 && lon_hi[g] < nlon_s, "lon index out of range");
-        // a pole row is only there when its zonal mean is taken (pgw_regrid_bilinear)
-        NEED(ctx, south_row >= 0 || (lat_lo[g] != -1 && lat_hi[g] != -1), "south-pole row in the tables but south_row < 0");
-        NEED(ctx, north_row >= 0 || (lat_lo[g] != nlat_s && lat_hi[g] != nlat_s), "north-pole row in the tables but north_row < 0");
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // tables -> device workspace slot 3: [4 double tables][pole][5 int tables]
+    if (int rc = check_brackets(ctx, __func__, ntarg, oob, lat_lo, lat_hi, lon_lo, lon_hi, nlat_s, nlon_s, south_row, north_row)) return rc;
     const size_t n = (size_t)ntarg;
-    const size_t td = sizeof(double) * 4 * n, tp = sizeof(double) * 2 * (size_t)nfield, ti = sizeof(int) * 5 * n;
-    void *tab = nullptr;
-    int rc = ws_get(ctx, 3, td + tp + ti + 64, &tab);
-    if (rc) return rc;
-    std::vector<char> h(td + ti);
-    double *hd = (double *)h.data();
-    memcpy(hd, lat_dx, 8 * n); memcpy(hd + n, lat_Dx, 8 * n); memcpy(hd + 2 * n, lon_dx, 8 * n); memcpy(hd + 3 * n, lon_Dx, 8 * n);
-    int *hi = (int *)(h.data() + td);
-    memcpy(hi, lat_lo, 4 * n); memcpy(hi + n, lat_hi, 4 * n); memcpy(hi + 2 * n, lon_lo, 4 * n); memcpy(hi + 3 * n, lon_hi, 4 * n);
-    memcpy(hi + 4 * n, oob, 4 * n);
-    double *dd = (double *)tab;
-    double *dpole = dd + 4 * n;
-    int *di = (int *)(dpole + 2 * nfield);
-    HIPCHK(ctx, hipMemcpyAsync(dd, hd, td, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(di, hi, ti, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     PointTables tb;
-    tb.lat_dx = dd; tb.lat_Dx = dd + n; tb.lon_dx = dd + 2 * n; tb.lon_Dx = dd + 3 * n;
-    tb.lat_lo = di; tb.lat_hi = di + n; tb.lon_lo = di + 2 * n; tb.lon_hi = di + 3 * n; tb.oob = di + 4 * n;
+    double *dpole;
+    if (int rc = tables_to_slot3(ctx, {{lat_dx, n, &tb.lat_dx}, {lat_Dx, n, &tb.lat_Dx}, {lon_dx, n, &tb.lon_dx}, {lon_Dx, n, &tb.lon_Dx}},
+                              {{lat_lo, n, &tb.lat_lo}, {lat_hi, n, &tb.lat_hi}, {lon_lo, n, &tb.lon_lo}, {lon_hi, n, &tb.lon_hi}, {oob, n, &tb.oob}},
+                              nfield, &dpole))
+        return rc;
     const unsigned int bx = nblocks(ntarg, BLOCK);            // one target per thread (k_regrid_points)
-    // z-slices: enough blocks to fill 256 CUs several times over even for few targets
-    long long want = (8192 + (long long)bx - 1) / bx;
-    unsigned int gz = (unsigned int)(want < 1 ? 1 : (want > nfield ? nfield : want));
-    if (gz > 65535u) gz = 65535u;
+    const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
     {
         Prof pr(ctx, PGW_K_REGRID);
+        launch_pole_means(ctx, dtype, nfield, nlat_s, nlon_s, src, south_row, north_row, dpole);
         with_type(dtype, [&](auto t_) {
             using T = decltype(t_);
-            if (south_row >= 0 || north_row >= 0)
-                hipLaunchKernelGGL((k_zonal_mean_rows<T>), dim3(nblocks(nfield * 2 * 64, BLOCK)), dim3(BLOCK), 0, ctx->stream, nfield,
-                                   nlat_s, nlon_s, (const T *)src, south_row, north_row, dpole);
             hipLaunchKernelGGL((k_regrid_points<T>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s, ntarg, gz,
                                (const T *)src, tb, dpole, (T *)out);
         });
@@ -2777,17 +2777,13 @@ extern "C" int pgw_regrid_sparse(pgw_ctx *ctx, int dtype, long long nfield, int 
     NEED(ctx, ((uintptr_t)src % elem_size(dtype)) == 0 && ((uintptr_t)out % elem_size(dtype)) == 0, "pointers must be element-aligned");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     void *ws = nullptr;
-    int rc = ws_get(ctx, 3, 64 + sizeof(double) * 2 * (size_t)nfield, &ws);
-    if (rc) return rc;
+    if (int rc = ws_get(ctx, 3, 64 + sizeof(double) * 2 * (size_t)nfield, &ws)) return rc;
     double *dpole = (double *)((char *)ws + 64);
     // 16 bytes of a plane per thread when the plane length and the output's alignment allow
     const int wide = (int)(16 / elem_size(dtype));
     const int W = (ntarg % wide == 0 && aligned16(out) && !ctx->opt[PGW_OPT_FORCE_VEC1]) ? wide : 1;
     const unsigned int bx = nblocks(ntarg, BLOCK * W);
-    // z-slices: enough blocks to fill 256 CUs several times over even for few targets
-    long long want = (8192 + (long long)bx - 1) / bx;
-    unsigned int gz = (unsigned int)(want < 1 ? 1 : (want > nfield ? nfield : want));
-    if (gz > 65535u) gz = 65535u;
+    const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
     {
         Prof pr(ctx, PGW_K_REGRID_SPARSE);
         with_type(dtype, [&](auto t_) {

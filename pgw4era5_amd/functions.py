@@ -686,27 +686,36 @@ def regrid_tables(src_lat, src_lon, targ_lat, targ_lon):
                 south_row=south_row, north_row=north_row, periodic=bool(periodic))
 
 
-def regrid_field(field, src_lat, src_lon, targ_lat, targ_lon):
-    """Bilinear (lat, then lon) regridding of field (..., nlat_s, nlon_s) on the GPU."""
+def _regrid(function, field, src_lat, src_lon, targ_lat, targ_lon, points):
+    """regrid_field (`points` False: the targets are the mesh of two axes) and regrid_points (True: lat / lon of one common
+    shape): the tables of the flattened targets, then the field through pgw_regrid_bilinear / pgw_regrid_points."""
     ctx = default_context()
-    tb = regrid_tables(src_lat, src_lon, targ_lat, targ_lon)
+    tb = regrid_tables(src_lat, src_lon, targ_lat.ravel(), targ_lon.ravel())      # the extent errors, before any launch
     shp = raw(field).shape
-    ops = OperandPlan(ctx, 'regrid_field', field=field)
-    nlat_s, nlon_s = shp[-2], shp[-1]
-    if nlat_s != len(src_lat) or nlon_s != len(src_lon):
+    ops = OperandPlan(ctx, function, field=field)
+    if len(shp) < 2 or shp[-2] != len(src_lat) or shp[-1] != len(src_lon):
         raise ValueError('field shape does not match the source coordinates')
     nfield = int(np.prod(shp[:-2], dtype=np.int64)) if len(shp) > 2 else 1
-    d_src = ops.dev('field')
-    out = ctx.empty(shp[:-2] + (len(targ_lat), len(targ_lon)), ops.result)
     c = {k: np.ascontiguousarray(v) for k, v in tb.items() if isinstance(v, np.ndarray)}
-    ctx._check(ctx.lib.pgw_regrid_bilinear(
-        ctx.handle, ops.tag('field'), nfield, nlat_s, nlon_s, len(targ_lat), len(targ_lon), d_src.ptr,
-        c['lat_lo'].ctypes.data_as(_ip), c['lat_hi'].ctypes.data_as(_ip), c['lat_dx'].ctypes.data_as(_dp),
-        c['lat_Dx'].ctypes.data_as(_dp), c['lat_oob'].ctypes.data_as(_ip),
-        c['lon_lo'].ctypes.data_as(_ip), c['lon_hi'].ctypes.data_as(_ip), c['lon_dx'].ctypes.data_as(_dp),
-        c['lon_Dx'].ctypes.data_as(_dp), c['lon_oob'].ctypes.data_as(_ip),
-        tb['south_row'], tb['north_row'], out.ptr))
+    if points:
+        c['oob'] = np.ascontiguousarray(c['lat_oob'] | c['lon_oob'], dtype=np.int32)
+        entry, targ_shape, targ_n = ctx.lib.pgw_regrid_points, targ_lat.shape, (targ_lat.size,)
+        names = 'lat_lo lat_hi lat_dx lat_Dx lon_lo lon_hi lon_dx lon_Dx oob'
+    else:
+        entry, targ_shape, targ_n = ctx.lib.pgw_regrid_bilinear, (len(targ_lat), len(targ_lon)), (len(targ_lat), len(targ_lon))
+        names = 'lat_lo lat_hi lat_dx lat_Dx lat_oob lon_lo lon_hi lon_dx lon_Dx lon_oob'
+    d_src = ops.dev('field')
+    out = ctx.empty(tuple(shp[:-2]) + targ_shape, ops.result)
+    tabs = [c[k].ctypes.data_as(_ip if c[k].dtype == np.int32 else _dp) for k in names.split()]
+    ctx._check(entry(ctx.handle, ops.tag('field'), nfield, shp[-2], shp[-1], *targ_n, d_src.ptr, *tabs,
+                     tb['south_row'], tb['north_row'], out.ptr))
     return out_like(out, field)
+
+
+def regrid_field(field, src_lat, src_lon, targ_lat, targ_lon):
+    """Bilinear (lat, then lon) regridding of field (..., nlat_s, nlon_s) on the GPU."""
+    return _regrid('regrid_field', field, src_lat, src_lon, np.asarray(targ_lat, dtype=np.float64),
+                   np.asarray(targ_lon, dtype=np.float64), points=False)
 
 
 def regrid_points(field, src_lat, src_lon, targ_lat, targ_lon):
@@ -715,29 +724,11 @@ def regrid_points(field, src_lat, src_lon, targ_lat, targ_lon):
     lies at (targ_lat[g], targ_lon[g]) - what xarray's `.interp({lat: targ_lat}).interp({lon: targ_lon})` computes for
     coordinates over shared dimensions (reference functions.py:812-893).  Degrees.  Returns (...,) + the targets' shape;
     dtype and array kind as `regrid_field`, whose bits a mesh handed over as points reproduces."""
-    ctx = default_context()
     targ_lat, targ_lon = np.asarray(targ_lat, dtype=np.float64), np.asarray(targ_lon, dtype=np.float64)
     if targ_lat.ndim < 1 or targ_lat.shape != targ_lon.shape:
         raise ValueError('point-wise targets need lat and lon of one common shape (rank >= 1); got %s and %s'
                          % (targ_lat.shape, targ_lon.shape))
-    tb = regrid_tables(src_lat, src_lon, targ_lat.ravel(), targ_lon.ravel())      # the extent errors, before any launch
-    shp = raw(field).shape
-    ops = OperandPlan(ctx, 'regrid_points', field=field)
-    if len(shp) < 2 or shp[-2] != len(src_lat) or shp[-1] != len(src_lon):
-        raise ValueError('field shape does not match the source coordinates')
-    nlat_s, nlon_s = shp[-2], shp[-1]
-    nfield = int(np.prod(shp[:-2], dtype=np.int64)) if len(shp) > 2 else 1
-    d_src = ops.dev('field')
-    out = ctx.empty(tuple(shp[:-2]) + targ_lat.shape, ops.result)
-    c = {k: np.ascontiguousarray(v) for k, v in tb.items() if isinstance(v, np.ndarray)}
-    oob = np.ascontiguousarray(c['lat_oob'] | c['lon_oob'], dtype=np.int32)
-    ctx._check(ctx.lib.pgw_regrid_points(
-        ctx.handle, ops.tag('field'), nfield, nlat_s, nlon_s, targ_lat.size, d_src.ptr,
-        c['lat_lo'].ctypes.data_as(_ip), c['lat_hi'].ctypes.data_as(_ip), c['lat_dx'].ctypes.data_as(_dp),
-        c['lat_Dx'].ctypes.data_as(_dp), c['lon_lo'].ctypes.data_as(_ip), c['lon_hi'].ctypes.data_as(_ip),
-        c['lon_dx'].ctypes.data_as(_dp), c['lon_Dx'].ctypes.data_as(_dp), oob.ctypes.data_as(_ip),
-        tb['south_row'], tb['north_row'], out.ptr))
-    return out_like(out, field)
+    return _regrid('regrid_points', field, src_lat, src_lon, targ_lat, targ_lon, points=True)
 
 
 # ------------------------------------------------------------------------------- regridding, 2-D source coordinates
@@ -997,17 +988,10 @@ def _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name):
     for d in lead:
         if d in ds_gcm:
             out[d] = ds_gcm[d]
-    if targ_lat.ndim == 2:
-        tdims = tuple(t_lat.dims)
-        out[LAT_GCM] = ncio.Field(targ_lat, tdims, {}, None, LAT_GCM)
-        out[LON_GCM] = ncio.Field(targ_lon, tdims, {}, None, LON_GCM)
-        coords = {d: f.coords[d] for d in lead if d in f.coords}
-    else:
-        tdims = (LAT_GCM, LON_GCM)
-        out[LAT_GCM] = ncio.Field(targ_lat, (LAT_GCM,), {LAT_GCM: targ_lat}, None, LAT_GCM)
-        out[LON_GCM] = ncio.Field(targ_lon, (LON_GCM,), {LON_GCM: targ_lon}, None, LON_GCM)
-        coords = dict({d: f.coords[d] for d in lead if d in f.coords}, **{LAT_GCM: targ_lat, LON_GCM: targ_lon})
-    out[var_name] = ncio.Field(res, lead + tdims, coords, None, var_name)
+    # 2-D target coordinates lie over their own dimensions; 1-D ones are the axes of a mesh here, whatever their dimensions
+    tg = _Target(targ_lat, targ_lon, targ_lat.ndim == 2, t_lat.dims if targ_lat.ndim == 2 else (LAT_GCM, LON_GCM))
+    tg.put_coords(out)
+    tg.put_field(out, var_name, res, lead, {d: f.coords[d] for d in lead if d in f.coords})
     if 'height' in ds_gcm and 'height' not in out:
         out['height'] = ds_gcm['height']
     for name in [var_name, TIME_GCM, PLEV_GCM, LAT_GCM, LON_GCM, 'height']:                   # :805-808
@@ -1030,6 +1014,37 @@ def _target_layout(lat_dims, lat_shape, lon_dims, lon_shape):
                      'over the same dimensions' % (LAT_ERA, lat_shape, lat_dims, LON_ERA, lon_shape, lon_dims))
 
 
+class _Target:
+    """A target grid of step_02: `lat` / `lon` [deg] as float64 arrays, `points` and `dims` as _target_layout names them,
+    and how results are written onto it: lat / lon as 1-D axes that are their own coordinates (a mesh), or as variables
+    over the target's dimensions (point-wise), a result over its leading dimensions + `dims` either way."""
+
+    def __init__(self, lat, lon, points, dims):
+        self.lat, self.lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
+        self.points, self.dims = bool(points), tuple(dims)
+
+    @classmethod
+    def of(cls, t_lat, t_lon, field_dims=()):
+        """By the rule of _target_layout, from labelled lat / lon; a bare array is an axis of its own name when it is 1-D
+        and `field_dims` (the dimensions of the field it is a coordinate of) have that name, else it lies over them."""
+        def dims_of(c, name):
+            if hasattr(c, 'dims'):
+                return tuple(c.dims)
+            return (name,) if np.ndim(c) == 1 and name in field_dims else tuple(field_dims)
+        points, dims = _target_layout(dims_of(t_lat, LAT_ERA), np.shape(t_lat), dims_of(t_lon, LON_ERA), np.shape(t_lon))
+        return cls(getattr(t_lat, 'values', t_lat), getattr(t_lon, 'values', t_lon), points, dims)
+
+    def put_coords(self, ds, lat_attrs=None, lon_attrs=None):
+        from . import ncio
+        for name, x, attrs in ((LAT_GCM, self.lat, lat_attrs), (LON_GCM, self.lon, lon_attrs)):
+            ds[name] = ncio.Field(x, self.dims, {}, attrs) if self.points else ncio.Field(x, (name,), {name: x}, attrs)
+
+    def put_field(self, ds, name, values, lead, lead_coords, attrs=None):
+        from . import ncio
+        coords = dict(lead_coords) if self.points else dict(lead_coords, **{LAT_GCM: self.lat, LON_GCM: self.lon})
+        ds[name] = ncio.Field(values, tuple(lead) + self.dims, coords, attrs)
+
+
 def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
     """Bilinear regridding onto the ERA5 grid of `ds_era5` (reference functions.py:748-898).  i_use_xesmf = 0: the xarray
     branch, every lat/lon variable of `ds_gcm` (1-D source coordinates) through the separable kernel when the target's lat
@@ -1041,14 +1056,12 @@ def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
     from . import ncio
     if i_use_xesmf:
         return _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name)
-    t_lat, t_lon = ds_era5[LAT_ERA], ds_era5[LON_ERA]
-    targ_lon = np.asarray(t_lon.values, dtype=np.float64)
-    targ_lat = np.asarray(t_lat.values, dtype=np.float64)
     src_lon = np.asarray(ds_gcm[LON_GCM].values, dtype=np.float64)
     src_lat = np.asarray(ds_gcm[LAT_GCM].values, dtype=np.float64)
     # 1-D lat over its own dimension and 1-D lon over its own: a mesh.  lat and lon over the same dimensions (2-D coordinates
     # of a rotated-pole grid, one `cell` dimension): xarray interpolates point by point.
-    points, tdims = _target_layout(t_lat.dims, targ_lat.shape, t_lon.dims, targ_lon.shape)
+    tg = _Target.of(ds_era5[LAT_ERA], ds_era5[LON_ERA])
+    regrid = regrid_points if tg.points else regrid_field
     out = ncio.Dataset(attrs=ds_gcm.attrs)
     for name, f in ds_gcm.variables.items():
         if name in (LAT_GCM, LON_GCM):
@@ -1057,22 +1070,11 @@ def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
             lead = [d for d in f.dims if d not in (LAT_GCM, LON_GCM)]
             g = f.transpose(*(lead + [LAT_GCM, LON_GCM]))
             vals = g.values if g.values.dtype in (np.float32, np.float64) else g.values.astype(np.float64)
-            coords = {d: f.coords[d] for d in lead if d in f.coords}
-            if points:
-                res = regrid_points(vals, src_lat, src_lon, targ_lat, targ_lon)
-            else:
-                res = regrid_field(vals, src_lat, src_lon, targ_lat, targ_lon)
-                coords[LAT_GCM] = targ_lat
-                coords[LON_GCM] = targ_lon
-            out[name] = ncio.Field(res, tuple(lead) + tdims, coords, f.attrs, name)
+            tg.put_field(out, name, regrid(vals, src_lat, src_lon, tg.lat, tg.lon), lead,
+                         {d: f.coords[d] for d in lead if d in f.coords}, f.attrs)
         elif LAT_GCM not in f.dims and LON_GCM not in f.dims:
             out[name] = f
-    if points:                                                  # laid out like the xESMF branch's 2-D target
-        out[LAT_GCM] = ncio.Field(targ_lat, tdims, {}, ds_gcm[LAT_GCM].attrs, LAT_GCM)
-        out[LON_GCM] = ncio.Field(targ_lon, tdims, {}, ds_gcm[LON_GCM].attrs, LON_GCM)
-    else:
-        out[LAT_GCM] = ncio.Field(targ_lat, (LAT_GCM,), {LAT_GCM: targ_lat}, ds_gcm[LAT_GCM].attrs, LAT_GCM)
-        out[LON_GCM] = ncio.Field(targ_lon, (LON_GCM,), {LON_GCM: targ_lon}, ds_gcm[LON_GCM].attrs, LON_GCM)
+    tg.put_coords(out, ds_gcm[LAT_GCM].attrs, ds_gcm[LON_GCM].attrs)      # point-wise: laid out like the xESMF branch's 2-D target
     return out
 
 
@@ -1336,17 +1338,9 @@ def nan_ignoring_interp(da_era5_land_fr, da_delta, kernel_radius, sharpness):
     (FR_LAND > 0.7) come back NaN.  reference functions.py:900-1060.  Labelled inputs like the reference's
     (`.values`, `.coords` with the ocean grid's `latitude` / `longitude`, ERA5 `lat` / `lon`)."""
     glat, glon = _ocean_coords(da_delta)
-    t_lat, t_lon = da_era5_land_fr.coords[LAT_ERA], da_era5_land_fr.coords[LON_ERA]
-
-    def dims_of(c, name):                                       # a coordinate array: an axis of its own name, or over the field's dimensions
-        if hasattr(c, 'dims'):
-            return tuple(c.dims)
-        return (name,) if np.ndim(c) == 1 and name in da_era5_land_fr.dims else tuple(da_era5_land_fr.dims)
-    points, _ = _target_layout(dims_of(t_lat, LAT_ERA), np.shape(t_lat), dims_of(t_lon, LON_ERA), np.shape(t_lon))
-    t_lat = np.asarray(getattr(t_lat, 'values', t_lat))
-    t_lon = np.asarray(getattr(t_lon, 'values', t_lon))
-    interp = gauss_interp_points if points else gauss_interp_fields
-    res = interp(np.asarray(da_era5_land_fr.values), t_lat, t_lon, glat, glon, [np.asarray(da_delta.values)], kernel_radius, sharpness)
+    tg = _Target.of(da_era5_land_fr.coords[LAT_ERA], da_era5_land_fr.coords[LON_ERA], da_era5_land_fr.dims)
+    interp = gauss_interp_points if tg.points else gauss_interp_fields
+    res = interp(np.asarray(da_era5_land_fr.values), tg.lat, tg.lon, glat, glon, [np.asarray(da_delta.values)], kernel_radius, sharpness)
     return res[0]
 
 
@@ -1367,17 +1361,15 @@ def interp_wrapper(origin_grid, target_grid, var_name, i_use_xesmf=0,
     from . import ncio
     if var_name in ['tos', 'siconc']:
         land = target_grid['FR_LAND']
-        t_lat, t_lon = target_grid[LAT_ERA], target_grid[LON_ERA]
-        points, tdims = _target_layout(t_lat.dims, t_lat.shape, t_lon.dims, t_lon.shape)
-        if points:                                              # an extpar file has no time axis: (1,) + tdims or tdims
-            land_pts = np.asarray(land.values)
-            if land_pts.shape == (1,) + tuple(t_lat.shape):
-                land_pts = land_pts[0]
-            elif land_pts.shape != tuple(t_lat.shape):
-                raise ValueError('FR_LAND of shape %s lies neither over the target coordinates of shape %s nor over one '
-                                 'time step of them' % (land_pts.shape, tuple(t_lat.shape)))
-        else:
-            land2d = np.asarray(land.values)[0]                                    # target_grid["FR_LAND"][0,:,:]  :1097
+        tg = _Target.of(target_grid[LAT_ERA], target_grid[LON_ERA])
+        land = np.asarray(land.values)
+        if not tg.points:
+            land = land[0]                                                         # target_grid["FR_LAND"][0,:,:]  :1097
+        elif land.shape == (1,) + tg.lat.shape:                # an extpar file has no time axis: (1,) + tdims or tdims
+            land = land[0]
+        elif land.shape != tg.lat.shape:
+            raise ValueError('FR_LAND of shape %s lies neither over the target coordinates of shape %s nor over one '
+                             'time step of them' % (land.shape, tg.lat.shape))
         values = origin_grid[var_name]
         glat, glon = _ocean_coords(ncio.Field(values.values[0], values.dims[1:],
                                               {LAT_GCM_OCEAN: np.asarray(origin_grid[LAT_GCM_OCEAN].values),
@@ -1385,23 +1377,12 @@ def interp_wrapper(origin_grid, target_grid, var_name, i_use_xesmf=0,
         if values.shape[0] != 12:
             raise ValueError('could not broadcast input array: %s has %d time steps, the ocean-grid interpolation expects 12 months'
                              % (var_name, values.shape[0]))                         # result = np.empty((12, ...))  :1101
-        tlat = np.asarray(target_grid[LAT_ERA].values, dtype=np.float64)
-        tlon = np.asarray(target_grid[LON_ERA].values, dtype=np.float64)
-        if points:                                              # lat / lon over shared dimensions: laid out like regrid_lat_lon's points branch
-            result = gauss_interp_points(land_pts, tlat, tlon, glat, glon, [values.values[i] for i in range(12)],
-                                         nan_interp_kernel_radius, nan_interp_sharpness)
-            ds = ncio.Dataset(attrs=dict(description=str(var_name) + " on ERA5 grid", units="K", long_name=str(var_name)))
-            ds['lat'] = ncio.Field(tlat, tdims, {}, target_grid[LAT_ERA].attrs)
-            ds['lon'] = ncio.Field(tlon, tdims, {}, target_grid[LON_ERA].attrs)
-            ds['time'] = _ocean_time_field(origin_grid[TIME_GCM])
-            ds[var_name] = ncio.Field(result, ('time',) + tdims, {'time': ds['time'].values})
-            return ds
-        result = gauss_interp_fields(land2d, tlat, tlon, glat, glon, [values.values[i] for i in range(12)],
-                                     nan_interp_kernel_radius, nan_interp_sharpness)
+        interp = gauss_interp_points if tg.points else gauss_interp_fields
+        result = interp(land, tg.lat, tg.lon, glat, glon, [values.values[i] for i in range(12)],
+                        nan_interp_kernel_radius, nan_interp_sharpness)
         ds = ncio.Dataset(attrs=dict(description=str(var_name) + " on ERA5 grid", units="K", long_name=str(var_name)))   # :1121, 1134
-        ds['lat'] = ncio.Field(tlat, ('lat',), {'lat': tlat}, target_grid[LAT_ERA].attrs)
-        ds['lon'] = ncio.Field(tlon, ('lon',), {'lon': tlon}, target_grid[LON_ERA].attrs)
+        tg.put_coords(ds, target_grid[LAT_ERA].attrs, target_grid[LON_ERA].attrs)      # point-wise: as regrid_lat_lon lays them out
         ds['time'] = _ocean_time_field(origin_grid[TIME_GCM])
-        ds[var_name] = ncio.Field(result, ('time', 'lat', 'lon'), {'time': ds['time'].values, 'lat': tlat, 'lon': tlon})
+        tg.put_field(ds, var_name, result, ('time',), {'time': ds['time'].values})
         return ds
     return regrid_lat_lon(origin_grid, target_grid, var_name, method='bilinear', i_use_xesmf=i_use_xesmf)

@@ -251,3 +251,39 @@ def test_pole_rows_in_the_tables_need_their_source_row(ctx, which):
     rc, out = _call(ctx, field, tb)
     assert rc == 0 and (out != SENTINEL).all() and np.isnan(out[:, 2, :]).all()
     _check(c, _run(ctx, c, 'float64'), 'float64')                 # and the context serves the next call
+
+
+def test_argument_errors_leave_the_output_alone(ctx):
+    """The sibling of tests/test_regrid_points_hip.py::test_argument_errors_leave_the_output_alone: every argument error of
+    pgw_regrid_bilinear is PGW_ERR_ARG with the output untouched; out-of-range entries under lat_oob / lon_oob are not read."""
+    from pgw4era5_amd import _lib
+    c = H.Case(H._field(np.random.default_rng(58), (3, 5, 8)), np.array([-72.0, -36.5, 0.0, 36.5, 72.0]), np.arange(8) * 45.0,
+               np.array([-90.0, -40.5, 10.2, 80.0]), np.array([0.0, 50.5, 133.0, 200.2, 310.0, 359.0]))
+    assert c.tb['south_row'] == 0 and c.tb['north_row'] == 4 and c.pole_rows.tolist() == [True, False, False, True]
+    src = ctx.to_device(c.field)
+    sentinel = np.full((3, 4, 6), SENTINEL)
+    out = ctx.to_device(sentinel)
+    base = {k: np.ascontiguousarray(v) for k, v in c.tb.items() if isinstance(v, np.ndarray)}
+
+    def rc(dtype=_lib.PGW_F64, nfield=3, nlat_s=5, nlon_s=8, nlat_t=4, nlon_t=6, s=src.ptr, o=out.ptr, south=0, north=4, null=None, **edit):
+        t = {k: v.copy() for k, v in base.items()}
+        for k, (i, v) in edit.items():
+            t[k][i] = v
+        p = {k: (None if k == null else v.ctypes.data_as(_ip if v.dtype == np.int32 else _dp)) for k, v in t.items()}
+        return ctx.lib.pgw_regrid_bilinear(ctx.handle, dtype, nfield, nlat_s, nlon_s, nlat_t, nlon_t, s, p['lat_lo'], p['lat_hi'],
+                                           p['lat_dx'], p['lat_Dx'], p['lat_oob'], p['lon_lo'], p['lon_hi'], p['lon_dx'], p['lon_Dx'],
+                                           p['lon_oob'], south, north, o)
+    bad = [rc(dtype=7), rc(nfield=0), rc(nlat_s=1), rc(nlon_t=0), rc(s=None), rc(o=None), rc(null='lat_hi'), rc(null='lon_dx'),
+           rc(lat_lo=(1, -2)), rc(lat_hi=(1, 6)), rc(lon_lo=(2, -1)), rc(lon_hi=(2, 8)), rc(south=5), rc(north=5)]
+    assert bad == [PGW_ERR_ARG] * len(bad), bad
+    ctx.sync()
+    np.testing.assert_array_equal(out.numpy(), sentinel)                             # nothing ran
+    with pytest.raises(ValueError, match='pgw_regrid_bilinear'):
+        ctx._check(rc(lat_lo=(1, -2)))
+    # the same entries in a flagged row / column are not read
+    assert rc(lat_oob=(1, 1), lat_lo=(1, -2), lat_hi=(1, 6), lon_oob=(2, 1), lon_lo=(2, -1), lon_hi=(2, 8)) == _lib.PGW_OK
+    flagged = np.zeros(sentinel.shape, dtype=bool)
+    flagged[:, 1, :] = flagged[:, :, 2] = True
+    np.testing.assert_array_equal(np.isnan(out.numpy()), flagged)
+    assert rc() == _lib.PGW_OK
+    _check(c, out.numpy(), 'float64')
