@@ -208,9 +208,10 @@ static int status_check(pgw_ctx *ctx, const DevStatus *from = nullptr) {
     int rc = status_fetch(ctx, from);
     if (rc) return rc;
     if (ctx->h_status->code != 0) {
-        ctx->err_col = (long long)ctx->h_status->col;
-        ctx->err = status_text(ctx->h_status->code);
-        return ctx->h_status->code;
+        int code;
+        ordered_status(*ctx->h_status, &code, &ctx->err_col);
+        ctx->err = status_text(code);
+        return code;
     }
     return PGW_OK;
 }

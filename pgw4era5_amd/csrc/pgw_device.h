@@ -19,9 +19,9 @@ constexpr int BLOCK = 256;             // 4 waves of 64
 
 // device-resident status block of a context (zeroed before a launch that can report)
 struct DevStatus {
-    int code;                          // first pgw_status reported by a kernel
+    int code;                          // first pgw_status reported by a kernel (10: one of 10 .. 12, see report_ordered)
     int nan_seen;                      // bit 0: NaN in target min, bit 1: NaN in source min
-    unsigned long long col;            // min offending column (init ~0ull)
+    unsigned long long col;            // min offending column (init ~0ull); codes 10 .. 12: min of (column << 2 | code - 10)
     unsigned long long max_bits;       // max |err| as ordered bits of a non-negative double
     unsigned long long valid;          // number of non-NaN |err| contributions (>0 flag)
     unsigned long long min_targ_bits;  // min target pressure (bits of positive double)
@@ -141,6 +141,26 @@ __device__ __forceinline__ void st_off_nt(T *__restrict__ base, O byte_off, T v)
 __device__ __forceinline__ void report(DevStatus *st, int code, long long col) {
     int prev = atomicCAS(&st->code, 0, code);
     if (prev == 0 || prev == code) atomicMin(&st->col, (unsigned long long)col);
+}
+
+// The three errors of the reference's column loop (functions.py:493-508, 564-566) - 10 source ends, 11 target ends, 12 a target
+// out of range in 'off' mode: the reference walks the columns in (time, lat, lon) order and makes the checks in that
+// order within a column, so the call raises what the SMALLEST flat column holds, and the smallest code of that column.
+// `code` becomes ORDERED_CODE_FIRST as the mark of such a status and `col` the minimum of (column << 2 | code - 10) over
+// every report; `ordered_status` takes the pair apart on the host.  Like `report`, only for a status no other code is in.
+constexpr int ORDERED_CODE_FIRST = 10;
+__device__ __forceinline__ void report_ordered(DevStatus *st, int code, long long col) {
+    int prev = atomicCAS(&st->code, 0, ORDERED_CODE_FIRST);
+    if (prev == 0 || prev == ORDERED_CODE_FIRST)
+        atomicMin(&st->col, ((unsigned long long)col << 2) | (unsigned long long)(code - ORDERED_CODE_FIRST));
+}
+// code and column of a fetched status (host side)
+inline void ordered_status(const DevStatus &st, int *code, long long *col) {
+    *code = st.code; *col = (long long)st.col;
+    if (st.code == ORDERED_CODE_FIRST) {
+        *code = ORDERED_CODE_FIRST + (int)(st.col & 3ull);
+        *col = (long long)(st.col >> 2);
+    }
 }
 
 // ---- division by a value that many numerators share ---------------------------------------

@@ -750,10 +750,10 @@ __global__ __launch_bounds__(BLOCK, PGW_INTERP_MINB) void k_interp_logp_stream(i
     {
         double s_last = (double)pp[(long long)(S - 1) * ncol];
         if (!logp_in) s_last = PGW_LOGT(s_last);
-        if (s_last < s_first) { report(st, 10, flat); }              // :500-501
+        if (s_last < s_first) { report_ordered(st, 10, flat); }      // :500-501
         double x_first = (double)pt[0], x_last = (double)pt[(long long)(N - 1) * ncol];
         if (!logp_in) { x_first = PGW_LOGT(x_first); x_last = PGW_LOGT(x_last); }
-        if (x_last < x_first) { report(st, 11, flat); }              // :502-503
+        if (x_last < x_first) { report_ordered(st, 11, flat); }      // :502-503
     }
     // source window
     int j;
@@ -818,7 +818,7 @@ __global__ __launch_bounds__(BLOCK, PGW_INTERP_MINB) void k_interp_logp_stream(i
                 else if (same) y = y1;                                   // :572-573
                 else if constexpr (DY32) y = y1 + (x - x1) * (double)((float)y2 - (float)y1) / (x2 - x1);
                 else y = y1 + (x - x1) * (y2 - y1) / (x2 - x1);          // :575-578
-                if (MODE == 0 && extrap) report(st, 12, flat);           // :564-566
+                if (MODE == 0 && extrap) report_ordered(st, 12, flat);   // :564-566
                 SIG_ST((TO)y, po + (long long)l * ncol);
                 xprev = (x == x) ? x : __builtin_inf();                  // after a NaN target restart
             }
@@ -879,7 +879,7 @@ __global__ __launch_bounds__(BLOCK) void k_hybrid_to_plev(int ntime, int S, int 
     if (g >= (long long)ntime * ncol / V) return;
     const long long flat = g * V;                          // V | ncol: a group lies within one time step
     const long long t = flat / ncol, c = flat - t * ncol;
-    if (g == 0 && s_lx[N - 1] < s_lx[0]) report(st, 11, 0);               // functions.py:502-503 (the same list in every column)
+    if (g == 0 && s_lx[N - 1] < s_lx[0]) report_ordered(st, 11, 0);       // functions.py:502-503 (the same list in every column)
     double psv[V];
     loadv<TI, V>(ps + flat, psv);
     const O rowb_in = (O)((unsigned long long)ncol * sizeof(TI)), rowb_out = (O)((unsigned long long)ncol * sizeof(TO));
@@ -908,7 +908,7 @@ __global__ __launch_bounds__(BLOCK) void k_hybrid_to_plev(int ntime, int S, int 
 #pragma unroll
     for (int v = 0; v < V; ++v) {
         x_first[v] = srcx(0, v);
-        if (srcx(S - 1, v) < x_first[v]) report(st, 10, flat + v);        // functions.py:500-501
+        if (srcx(S - 1, v) < x_first[v]) report_ordered(st, 10, flat + v); // functions.py:500-501
     }
     auto reset = [&]() {
 #pragma unroll
@@ -963,7 +963,7 @@ __global__ __launch_bounds__(BLOCK) void k_hybrid_to_plev(int ntime, int S, int 
                 if (extrap && MODE == 3) y[v] = __builtin_nan("");         // :569-570
                 else if (same) y[v] = y1;                                  // :572-573
                 else y[v] = y1 + (xs - x1) * diff(y2, y1) / (x2 - x1);     // :575-578
-                if (MODE == 0 && extrap) report(st, 12, flat + v);         // :564-566
+                if (MODE == 0 && extrap) report_ordered(st, 12, flat + v); // :564-566
             }
         }
         const O orow = oo + (O)(out_rev ? N - 1 - l : l) * rowb_out;
