@@ -864,6 +864,22 @@ int pgw_select_box(pgw_ctx *ctx, int elem_bytes, int nrec, int nlev_src, int nla
                    int nlev_sel, const int *lev_index, int lat0, int nlat_sel, int lon0, int nlon_sel, int nlev_dst,
                    int lev_dst0, void *dst);
 
+/* s7 lon-lat box on a curvilinear grid                     step_01_extract_deltas/extract_climate_delta.sh:120-123, 194-208
+ * (`cdo sellonlatbox,$box` in front of the Omon / SImon tables, whose files carry 2-D latitude / longitude).  Marks the
+ * cells of lat / lon (nj, ni; device arrays of `dtype`) that lie inside box = (lon1, lon2, lat1, lat2) (HOST doubles):
+ *   inside[j, i] = lat and lon both finite, min(lat1, lat2) <= lat <= max(lat1, lat2), and lon + 360 k <= lon2 for the
+ *   smallest integer k with lon + 360 k >= lon1 (k = ceil((lon1 - lon) / 360), then k += (lon + 360 k < lon1), then
+ *   k -= (lon + 360 (k - 1) >= lon1)).  float64 arithmetic, float32 coordinates widened exactly; edges inclusive; NaN and
+ *   +-inf coordinates are never inside.
+ * Outputs (DEVICE): row_any (nj) and col_any (ni), int, 1 where a cell of that row / column is inside and 0 elsewhere;
+ * n_inside, one long long, the number of inside cells.  The entry zeroes all three on the stream before the launch and
+ * does not synchronise.  Finding the index window from the flags is the caller's (step_01_extract_deltas.curvilinear_box);
+ * the cut itself is pgw_select_box.  Not timed by the launch profiler.
+ * PGW_ERR_ARG, and nothing written, for: an unknown dtype, nj < 1, ni < 1, nj * ni >= 2^31, a NULL pointer, a NaN in the
+ * box, lon1 >= lon2, lon2 - lon1 > 360. */
+int pgw_box_mark_2d(pgw_ctx *ctx, int dtype, int nj, int ni, const void *lat, const void *lon, double lon1, double lon2,
+                    double lat1, double lat2, int *row_any, int *col_any, long long *n_inside);
+
 /* Diagnostic: the loads of pgw_clim_accumulate on x (nrec, inner) and nothing else, on the same grid, timed under
  * PGW_K_CLIM_READ - what the card gives this access pattern (tools/clim_time.py); no reference counterpart. */
 int pgw_test_read_records(pgw_ctx *ctx, int dtype, int nrec, long long inner, const void *x);

@@ -205,6 +205,7 @@ SIGNATURES['pgw_hur_merge_levels'] = (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _vp, _
 SIGNATURES['pgw_clim_accumulate'] = (_i, [_vp, _i, _i, _i, _ll, _vp, _i, _i, _vp, _vp, _vp])
 SIGNATURES['pgw_field_sub'] = (_i, [_vp, _i, _ll, _vp, _vp, _vp])
 SIGNATURES['pgw_select_box'] = (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _ip, _i, _i, _i, _i, _i, _i, _vp])
+SIGNATURES['pgw_box_mark_2d'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _d, _d, _d, _d, _vp, _vp, _vp])
 SIGNATURES['pgw_test_read_records'] =(_i, [_vp, _i, _i, _ll, _vp])
 # step_03 --debug_mode interpolate_full: the deltas as float64 arrays
 SIGNATURES['pgw_delta_fields'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _dp, _vp] + [_vp] * 14 + [_d, _d, _i, _vp, _vp, _vp, _vp])

@@ -1053,6 +1053,30 @@ extern "C" int pgw_select_box(pgw_ctx *ctx, int elem_bytes, int nrec, int nlev_s
     return PGW_OK;
 }
 
+// ------------------------------------------------------------------ step_01: lon-lat box on a curvilinear grid
+extern "C" int pgw_box_mark_2d(pgw_ctx *ctx, int dtype, int nj, int ni, const void *lat, const void *lon, double lon1, double lon2,
+                               double lat1, double lat2, int *row_any, int *col_any, long long *n_inside) {
+    NEED(ctx, TAG_OK(dtype), "dtype must be PGW_F32 or PGW_F64");
+    NEED(ctx, nj >= 1 && ni >= 1, "nj and ni must be positive");
+    NEED(ctx, (long long)nj * ni < (1ll << 31), "nj * ni must be below 2^31 cells");
+    NEED(ctx, lat && lon && row_any && col_any && n_inside, "null pointer");
+    NEED(ctx, lon1 == lon1 && lon2 == lon2 && lat1 == lat1 && lat2 == lat2, "the box must not hold a NaN");
+    NEED(ctx, lon1 < lon2 && lon2 - lon1 <= 360.0, "the box needs lon1 < lon2 and lon2 - lon1 <= 360");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long long n = (long long)nj * ni;
+    const BoxMark b = {lon1, lon2, lat1 < lat2 ? lat1 : lat2, lat1 < lat2 ? lat2 : lat1};
+    HIPCHK(ctx, hipMemsetAsync(row_any, 0, sizeof(int) * (size_t)nj, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(col_any, 0, sizeof(int) * (size_t)ni, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(n_inside, 0, sizeof(long long), ctx->stream));
+    with_type(dtype, [&](auto t_) {
+        using T = decltype(t_);
+        hipLaunchKernelGGL((k_box_mark_2d<T>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, ni, b, (const T *)lat,
+                           (const T *)lon, row_any, col_any, (unsigned long long *)n_inside);
+    });
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
 // ------------------------------------------------------------------ time lerp
 extern "C" int pgw_time_lerp(pgw_ctx *ctx, int dtype, long long n, const void *v_before, const void *v_after,
                              double x_hi, double x_new, void *out) {

@@ -1351,6 +1351,45 @@ __global__ __launch_bounds__(BLOCK) void k_select_box(SelBox<O> a, SelLevels tab
 }
 
 // =====================================================================================
+// s7  lon-lat box on a curvilinear grid (`cdo sellonlatbox` on   step_01_extract_deltas/extract_climate_delta.sh:120-123,
+//     the Omon / SImon tables: 2-D latitude / longitude)          194-208
+// Cell (j, i) of lat / lon (nj, ni) is inside the box when both coordinates are finite, lat_lo <= lat <= lat_hi and
+// lon + 360 k <= lon2 for the smallest integer k with lon + 360 k >= lon1 - k by the three lines of the host's
+// `lonlat_box` (a quotient rounded up, then corrected by one either way), every operation IEEE float64 in the order written
+// (contraction is off; float32 coordinates widen exactly), so numpy restates it bit for bit.
+// One thread per cell, consecutive lanes along i.  An inside cell stores 1 into row_any[j] and col_any[i]: plain stores,
+// several lanes may store the same 1.  n_inside: the wave's ballot is counted and lane 0 adds it with one atomic, outside
+// the divergent code (no early return: the ballot needs every lane).  The entry zeroes the three outputs.
+// =====================================================================================
+struct BoxMark { double lon1, lon2, lat_lo, lat_hi; };
+__device__ __forceinline__ bool box_inside(double lat, double lon, const BoxMark &b) {
+    const double big = 1.7976931348623157e308;
+    if (!(fabs(lat) <= big && fabs(lon) <= big)) return false;   // NaN and +-inf
+    if (!(lat >= b.lat_lo && lat <= b.lat_hi)) return false;
+    double k = ceil((b.lon1 - lon) / 360.0);
+    k += (lon + 360.0 * k) < b.lon1 ? 1.0 : 0.0;
+    k -= (lon + 360.0 * (k - 1.0)) >= b.lon1 ? 1.0 : 0.0;
+    return lon + 360.0 * k <= b.lon2;
+}
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_box_mark_2d(long long n, int ni, BoxMark b, const T *__restrict__ lat,
+                                                       const T *__restrict__ lon, int *__restrict__ row_any,
+                                                       int *__restrict__ col_any, unsigned long long *__restrict__ n_inside) {
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    bool in = false;
+    if (g < n) {
+        in = box_inside((double)lat[g], (double)lon[g], b);
+        if (in) {
+            const long long j = g / ni;
+            row_any[j] = 1;
+            col_any[g - j * ni] = 1;
+        }
+    }
+    const unsigned long long m = __ballot(in);
+    if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_inside, (unsigned long long)__popcll(m));
+}
+
+// =====================================================================================
 // a7  time lerp of load_delta                                  functions.py:288-292
 // =====================================================================================
 // TB / TA / TO: storage types of the two records and of the result.  REF (settings.function_dtype_flow = 'reference'):

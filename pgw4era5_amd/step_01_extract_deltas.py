@@ -26,6 +26,9 @@ step_01: the array programs of the reference's step_01_extract_deltas directory 
   `merge_levels_files`, sub-commands `select` and `merge_levels`, and `climatology_files(box=...)`.  One kernel that moves
   words (`pgw_select_box`): the variable goes through the card as the raw bytes of the file, so its NetCDF type, fill
   values and packing are kept bit for bit.  Parity with cdo is unpinned here too; the docstrings are the contract.
+  The ocean tables (`tos`, `siconc`, extract_climate_delta.sh:120-123) come on curvilinear grids with 2-D latitude /
+  longitude: there the box is an index rectangle (`curvilinear_box`: the cells are marked on the card by
+  `pgw_box_mark_2d`, the window found from the row and column flags), cut by the same kernel, coordinates unshifted.
 
 The rest of the shell templates of step_01 (site paths, `wget`) are site scripts and stay out of scope (DESIGN.md
 section 7).
@@ -43,9 +46,10 @@ from . import _lib, ncio
 from .device import DeviceArray, default_context, dtype_tag
 from ._lib import _dp, _ip
 from .operands import F32, F64, check_extrapolate, dev, is_labelled, out_like, raw
-from .settings import LAT_GCM, LEV_GCM, LON_GCM, PLEV_GCM, TIME_GCM
+from .settings import LAT_GCM, LAT_GCM_OCEAN, LEV_GCM, LON_GCM, LON_GCM_OCEAN, PLEV_GCM, TIME_GCM
 
 MAX_LEVELS = 256          # nsrc, ntarg, nplev limit of the kernels (include/pgw_hip.h)
+COORD_PAIRS = ((LAT_GCM, LON_GCM), (LAT_GCM_OCEAN, LON_GCM_OCEAN))    # names of 2-D coordinates of a curvilinear grid
 
 
 def _f64(x, name):
@@ -377,6 +381,120 @@ def lonlat_box(lat, lon, box):
     return int(rows[0]), int(len(rows)), int(cols[0]), int(len(cols)), shifted[cols].astype(out_dtype)
 
 
+def _box_values(box):
+    """(lon1, lon2, lat1, lat2) as floats with the checks of `lonlat_box`."""
+    try:
+        lon1, lon2, lat1, lat2 = (float(b) for b in box)
+    except (TypeError, ValueError):
+        raise ValueError('box must be (lon1, lon2, lat1, lat2), got %r' % (box,)) from None
+    if lat1 != lat1 or lat2 != lat2:
+        raise ValueError('box must not hold a NaN, got %r' % (box,))
+    if not lon1 < lon2 or lon2 - lon1 > 360.0:
+        raise ValueError('box needs lon1 < lon2 and lon2 - lon1 <= 360, got %r, %r' % (lon1, lon2))
+    return lon1, lon2, lat1, lat2
+
+
+CYCLIC_CHOICES = {'auto': 'auto', 'yes': True, 'no': False}
+
+
+def _check_cyclic(cyclic):
+    if isinstance(cyclic, str) and cyclic in CYCLIC_CHOICES:
+        return CYCLIC_CHOICES[cyclic]
+    if cyclic is True or cyclic is False:
+        return cyclic
+    raise ValueError("cyclic must be 'auto', True or False, got %r" % (cyclic,))
+
+
+def _chord(lat_a, lon_a, lat_b, lon_b):
+    """Chord length on the unit sphere between two lists of points in degrees."""
+    def xyz(lat, lon):
+        la, lo = np.deg2rad(lat), np.deg2rad(lon)
+        return np.stack([np.cos(la) * np.cos(lo), np.cos(la) * np.sin(lo), np.sin(la)])
+    return np.sqrt(np.sum((xyz(lat_a, lon_a) - xyz(lat_b, lon_b)) ** 2, axis=0))
+
+
+def grid_is_cyclic(lat2d, lon2d):
+    """Does the curvilinear grid (nj, ni) close on itself along i?  Decided from three cells at each end of every row whose
+    four end cells (columns 0, 1, ni - 2, ni - 1) are finite: the row votes yes when the chord from its last cell to its
+    first is at most 1.5 times the longer of its first and last cell-to-cell chords; the grid is cyclic when more than half
+    of those rows vote yes.  ni < 3, or no such row: not cyclic.  A global grid is cyclic, with or without duplicated halo
+    columns at its ends (NEMO, MPI-ESM); a regional or rotated-pole grid is not."""
+    lat, lon = np.asarray(lat2d, dtype=np.float64), np.asarray(lon2d, dtype=np.float64)
+    if lat.ndim != 2 or lat.shape != lon.shape:
+        raise ValueError('lat2d and lon2d must be 2-D arrays of one shape, got %s and %s' % (lat.shape, lon.shape))
+    ni = lat.shape[1]
+    if ni < 3:
+        return False
+    ends = [0, 1, ni - 2, ni - 1]
+    ok = np.all(np.isfinite(lat[:, ends]) & np.isfinite(lon[:, ends]), axis=1)
+    if not np.any(ok):
+        return False
+    la, lo = lat[ok], lon[ok]
+    seam = _chord(la[:, ni - 1], lo[:, ni - 1], la[:, 0], lo[:, 0])
+    step = np.maximum(_chord(la[:, 0], lo[:, 0], la[:, 1], lo[:, 1]), _chord(la[:, ni - 2], lo[:, ni - 2], la[:, ni - 1], lo[:, ni - 1]))
+    return bool(2 * int(np.count_nonzero(seam <= 1.5 * step)) > len(seam))
+
+
+def flag_windows(row_any, col_any, cyclic):
+    """The index rectangle of the flags of `pgw_box_mark_2d` -> (j0, nj_sel, i0, ni_sel).
+    Rows: first flagged row to last flagged row, unflagged rows between them kept.  Columns of a grid that is not cyclic:
+    the same.  Columns of a cyclic grid: the complement of the longest cyclic run of unflagged columns (a tie goes to the
+    run that starts at the lowest index), as the cyclic run (i0 + c) % ni, c < ni_sel, that `pgw_select_box` takes; all
+    columns flagged gives (0, ni).  ValueError: no flagged row or column."""
+    rows, cols = np.nonzero(np.asarray(row_any).reshape(-1))[0], np.asarray(col_any).reshape(-1) != 0
+    ni = len(cols)
+    on = np.nonzero(cols)[0]
+    if not len(rows) or not len(on):
+        raise ValueError('no row or column is flagged')
+    j0, nj_sel = int(rows[0]), int(rows[-1] - rows[0] + 1)
+    if not cyclic:
+        return j0, nj_sel, int(on[0]), int(on[-1] - on[0] + 1)
+    if len(on) == ni:
+        return j0, nj_sel, 0, ni
+    # an unflagged run starts behind every flagged column that is followed by an unflagged one and lasts up to the next
+    # flagged column (cyclically)
+    nxt = np.concatenate([on[1:], on[:1] + ni])
+    length = nxt - on - 1
+    start = (on + 1) % ni
+    best = np.lexsort((start, -length))[0]                         # longest, then the lowest start
+    return j0, nj_sel, int((start[best] + length[best]) % ni), int(ni - length[best])
+
+
+def curvilinear_box(lat2d, lon2d, box, cyclic='auto'):
+    """`cdo sellonlatbox,lon1,lon2,lat1,lat2` on a curvilinear grid with 2-D coordinates lat2d, lon2d (nj, ni), float32 or
+    float64 in degrees (extract_climate_delta.sh:120-123, 194-208: the Omon / SImon tables) -> (j0, nj_sel, i0, ni_sel,
+    n_inside): the index rectangle of rows j0 .. j0 + nj_sel - 1 and the run of columns (i0 + c) % ni, c < ni_sel, that holds
+    every cell inside the box; the output stays curvilinear and its coordinates keep their bits (no 360 k shift).
+    box as in `lonlat_box`.  A cell is inside when its coordinates are finite, min(lat1, lat2) <= lat <= max(lat1, lat2)
+    and lon1 <= lon + 360 k <= lon2 for an integer k (the smallest k with lon + 360 k >= lon1 is tried; edges inclusive;
+    float64 arithmetic).  The cells are marked on the card (`pgw_box_mark_2d`); the rectangle is found on the host from the
+    nj + ni flags (`flag_windows`).  Cells of the rectangle that lie outside the box are kept, as cdo keeps them.
+    cyclic: does the grid close on itself along i - 'auto' (`grid_is_cyclic`), True or False.  On a cyclic grid a box
+    across the seam gives a short run of columns that wraps; on any other grid first to last flagged column.
+    ValueError: a bad box, coordinates that are not 2-D arrays of one shape, no cell inside the box."""
+    lon1, lon2, lat1, lat2 = _box_values(box)
+    cyclic = _check_cyclic(cyclic)
+    rla, rlo = raw(lat2d), raw(lon2d)
+    rla = rla.numpy() if isinstance(rla, DeviceArray) else np.asarray(rla)
+    rlo = rlo.numpy() if isinstance(rlo, DeviceArray) else np.asarray(rlo)
+    if rla.ndim != 2 or rla.shape != rlo.shape or rla.size < 1:
+        raise ValueError('lat2d and lon2d must be 2-D arrays of one shape, got %s and %s' % (rla.shape, rlo.shape))
+    dt = F32 if (rla.dtype == F32 and rlo.dtype == F32) else F64
+    nj, ni = rla.shape
+    if cyclic == 'auto':
+        cyclic = grid_is_cyclic(rla, rlo)
+    ctx = default_context()
+    d_lat, d_lon = dev(ctx, rla, dt), dev(ctx, rlo, dt)
+    d_out = ctx.empty((2 + nj + ni,), np.int32)                     # n_inside (8 bytes), row_any, col_any
+    ctx._check(ctx.lib.pgw_box_mark_2d(ctx.handle, dtype_tag(dt), nj, ni, d_lat.ptr, d_lon.ptr, lon1, lon2, lat1, lat2,
+                                       d_out.ptr + 8, d_out.ptr + 8 + 4 * nj, d_out.ptr))
+    flags = d_out.numpy()
+    n_inside = int(flags[:2].view(np.int64)[0])
+    if n_inside == 0:
+        raise ValueError('no cell lies within the box %r' % ((lon1, lon2, lat1, lat2),))
+    return flag_windows(flags[2:2 + nj], flags[2 + nj:], cyclic) + (n_inside,)
+
+
 def level_indices(plev, levels):
     """`cdo sellevel,levels`: the indices into `plev` of the requested values IN FILE ORDER (cdo keeps the file's order
     whatever the order of the request).  Exact equality.  ValueError: a requested level that is absent (named), a level
@@ -422,26 +540,48 @@ def _word_size(dtype):
     return n
 
 
-def select(field, levels=None, box=None, plev=None, lat=None, lon=None):
+def _coord_pair_2d(coords, shape2):
+    """The names of a pair of 2-D coordinates of shape `shape2` among `coords` (name -> array), or None."""
+    for la, lo in COORD_PAIRS:
+        if la in coords and lo in coords and np.shape(raw(coords[la])) == np.shape(raw(coords[lo])) == tuple(shape2) and len(shape2) == 2:
+            return la, lo
+    return None
+
+
+def select(field, levels=None, box=None, plev=None, lat=None, lon=None, cyclic='auto'):
     """`cdo sellevel` and / or `cdo sellonlatbox` on an array (..., [plev,] lat, lon): a numpy array, an `ncio.Field` or a
     `DeviceArray` in, the same kind and the same dtype out (elements of 2, 4 or 8 bytes are moved as words, any byte
     order).  levels: the level values to keep (`level_indices`, file order); box = (lon1, lon2, lat1, lat2)
     (`lonlat_box`).  plev / lat / lon: the 1-D coordinates; a labelled input brings its own and comes back with the cut /
-    shifted ones.  The array has a level axis - third from the end - when `plev` is given or a labelled input names it."""
+    shifted ones.  The array has a level axis - third from the end - when `plev` is given or a labelled input names it.
+    A curvilinear grid: `lat` and `lon` are 2-D arrays of the shape of the last two axes (..., [plev,] j, i) - given, or
+    found among a labelled input's coordinates under the names lat / lon or latitude / longitude.  The box then selects
+    the index rectangle of `curvilinear_box` (`cyclic` as there; anything but 'auto' is a ValueError with 1-D
+    coordinates); a labelled input comes back with its 2-D coordinates cut, bits kept."""
+    cyclic = _check_cyclic(cyclic)
     r = raw(field)
     shape = tuple(r.shape)
     labelled = is_labelled(field)
     coords = dict(getattr(field, 'coords', {})) if labelled else {}
     dims = tuple(field.dims) if labelled else None
+    pair = None
+    if labelled and lat is None and lon is None and len(shape) >= 2:
+        pair = _coord_pair_2d(coords, shape[-2:])
+        if pair is not None:
+            lat, lon = coords[pair[0]], coords[pair[1]]
+    curv = lat is not None and lon is not None and np.ndim(raw(lat)) == 2 and np.ndim(raw(lon)) == 2
     if labelled:
-        if len(dims) < 2 or dims[-2:] != (LAT_GCM, LON_GCM):
+        if len(dims) < 2 or (dims[-2:] != (LAT_GCM, LON_GCM) and not curv):
             raise ValueError('the dimensions must end in ([%s,] %s, %s), got %s' % (PLEV_GCM, LAT_GCM, LON_GCM, dims))
         has_lev = len(dims) >= 3 and dims[-3] == PLEV_GCM
         plev = coords.get(PLEV_GCM) if plev is None and has_lev else plev
-        lat = coords.get(LAT_GCM) if lat is None else lat
-        lon = coords.get(LON_GCM) if lon is None else lon
+        if not curv:
+            lat = coords.get(LAT_GCM) if lat is None else lat
+            lon = coords.get(LON_GCM) if lon is None else lon
     else:
         has_lev = plev is not None
+    if not curv and cyclic != 'auto':
+        raise ValueError('cyclic applies to 2-D (curvilinear) coordinates only; with 1-D lat / lon it must be auto')
     if len(shape) < (3 if has_lev else 2):
         raise ValueError('expected an array (..., %slat, lon), got shape %s' % ('plev, ' if has_lev else '', shape))
     nlat, nlon = shape[-2:]
@@ -456,9 +596,14 @@ def select(field, levels=None, box=None, plev=None, lat=None, lon=None):
     if box is not None:
         if lat is None or lon is None:
             raise ValueError('a box needs the lat and lon coordinates')
-        if np.shape(raw(lat)) != (nlat,) or np.shape(raw(lon)) != (nlon,):
-            raise ValueError('lat / lon do not match the last two axes %s' % ((nlat, nlon),))
-        lat0, nlat_sel, lon0, nlon_sel, lon_out = lonlat_box(lat, lon, box)
+        if curv:
+            if np.shape(raw(lat)) != (nlat, nlon) or np.shape(raw(lon)) != (nlat, nlon):
+                raise ValueError('2-D lat / lon do not match the last two axes %s' % ((nlat, nlon),))
+            lat0, nlat_sel, lon0, nlon_sel, _ = curvilinear_box(lat, lon, box, cyclic)
+        else:
+            if np.shape(raw(lat)) != (nlat,) or np.shape(raw(lon)) != (nlon,):
+                raise ValueError('lat / lon do not match the last two axes %s' % ((nlat, nlon),))
+            lat0, nlat_sel, lon0, nlon_sel, lon_out = lonlat_box(lat, lon, box)
         rows, cols = (lat0, nlat_sel), (lon0, nlon_sel)
     item = _word_size(r.dtype)
     lead = shape[:-3] if has_lev else shape[:-2]
@@ -482,21 +627,55 @@ def select(field, levels=None, box=None, plev=None, lat=None, lon=None):
         return host
     if lev_idx is not None:
         coords[PLEV_GCM] = np.asarray(raw(plev)).reshape(-1)[lev_idx]
-    if box is not None:
+    if box is not None and curv:
+        jj, ii = slice(rows[0], rows[0] + rows[1]), (cols[0] + np.arange(cols[1])) % nlon
+        for d, idx in ((dims[-2], jj), (dims[-1], ii)):           # 1-D index coordinates of the two grid dimensions
+            if d in coords and np.ndim(coords[d]) == 1:
+                coords[d] = np.asarray(coords[d])[idx]
+        if pair is not None:
+            for name in pair:
+                coords[name] = np.asarray(raw(coords[name]))[jj][:, ii]
+    elif box is not None:
         coords[LAT_GCM] = np.asarray(raw(lat))[rows[0]:rows[0] + rows[1]]
         coords[LON_GCM] = lon_out
     return ncio.Field(host, dims, coords, dict(getattr(field, 'attrs', {})), getattr(field, 'name', None))
 
 
+def _curvilinear_pair(ds, dims):
+    """The names (lat, lon) of the pair of 2-D coordinate variables of the file whose dimensions are exactly the last two
+    of `dims` - the variable is on a curvilinear grid - or None."""
+    dims = tuple(dims)
+    if len(dims) >= 2:
+        for la, lo in COORD_PAIRS:
+            if la in ds and lo in ds and tuple(ds[la].dims) == tuple(ds[lo].dims) == dims[-2:]:
+                return la, lo
+    return None
+
+
 class _Cut:
     """What a selection does to every OTHER variable of a file, on the host: the level indices along `plev`, the rows along
-    `lat`, the cyclic run of columns along `lon`; the longitude coordinate and its bounds take the +360 k shift."""
+    `lat`, the cyclic run of columns along `lon`; the longitude coordinate and its bounds take the +360 k shift.
+    `dims`: the dimensions of the selected variable.  When the file holds 2-D coordinates on its last two dimensions
+    (`_curvilinear_pair`) the box is the index rectangle of `curvilinear_box`: the row run and the cyclic column run go along
+    those two grid dimensions - through the 2-D coordinates and `vertices_latitude` / `vertices_longitude` too - and nothing
+    is shifted."""
 
-    def __init__(self, ds, lev_idx=None, box=None):
+    def __init__(self, ds, lev_idx=None, box=None, dims=None, cyclic='auto'):
         self.lev_idx = None if lev_idx is None else np.asarray(lev_idx, dtype=np.int64)
         self.rows = self.cols = self.shift = None
         self.lon_names = ()
-        if box is not None:
+        self.row_dim, self.col_dim = LAT_GCM, LON_GCM
+        cyclic = _check_cyclic(cyclic)
+        pair = _curvilinear_pair(ds, dims) if (box is not None and dims is not None) else None
+        if pair is None and cyclic != 'auto':
+            raise ValueError('cyclic applies to 2-D (curvilinear) coordinates only; with 1-D lat / lon it must be auto')
+        if pair is not None:
+            self.row_dim, self.col_dim = tuple(dims)[-2:]
+            lat, lon = ds[pair[0]].values, ds[pair[1]].values
+            self.lat0, self.nlat_sel, self.lon0, self.nlon_sel, _ = curvilinear_box(lat, lon, box, cyclic)
+            self.rows = slice(self.lat0, self.lat0 + self.nlat_sel)
+            self.cols = (self.lon0 + np.arange(self.nlon_sel)) % np.shape(lon)[1]
+        elif box is not None:
             for d in (LAT_GCM, LON_GCM):
                 if d not in ds:
                     raise ValueError('a box needs the coordinate variable %s in the file' % d)
@@ -509,7 +688,7 @@ class _Cut:
 
     def touches(self, f):
         return ((self.lev_idx is not None and PLEV_GCM in f.dims) or
-                (self.rows is not None and (LAT_GCM in f.dims or LON_GCM in f.dims)))
+                (self.rows is not None and (self.row_dim in f.dims or self.col_dim in f.dims)))
 
     def field(self, name, f):
         """The variable `f` of the input cut with the selection's indices."""
@@ -519,9 +698,9 @@ class _Cut:
         for ax, d in enumerate(f.dims):
             if d == PLEV_GCM and self.lev_idx is not None:
                 v = np.take(v, self.lev_idx, axis=ax)
-            elif d == LAT_GCM and self.rows is not None:
+            elif d == self.row_dim and self.rows is not None:
                 v = v[(slice(None),) * ax + (self.rows,)]
-            elif d == LON_GCM and self.cols is not None:
+            elif d == self.col_dim and self.cols is not None:
                 v = np.take(v, self.cols, axis=ax)
                 if name in self.lon_names and v.dtype.kind == 'f':
                     sh = self.shift.reshape((-1,) + (1,) * (v.ndim - ax - 1))
@@ -529,10 +708,12 @@ class _Cut:
         return ncio.Field(v, f.dims, {}, dict(f.attrs))
 
 
-def _grid_dims(dims, what):
-    """(number of leading dimensions, has a level axis) of a variable whose dimensions end in ([plev,] lat, lon)."""
+def _grid_dims(dims, what, ds=None):
+    """(number of leading dimensions, has a level axis) of a variable whose dimensions end in ([plev,] lat, lon) - or, with
+    the file `ds` given, in ([plev,] j, i) of a curvilinear grid (`_curvilinear_pair`)."""
     dims = tuple(dims)
-    if len(dims) < 2 or dims[-2:] != (LAT_GCM, LON_GCM):
+    curv = ds is not None and _curvilinear_pair(ds, dims) is not None
+    if len(dims) < 2 or (dims[-2:] != (LAT_GCM, LON_GCM) and not curv):
         raise ValueError('%s: the dimensions must end in ([%s,] %s, %s), got %s' % (what, PLEV_GCM, LAT_GCM, LON_GCM, dims))
     has_lev = len(dims) >= 3 and dims[-3] == PLEV_GCM
     nlead = len(dims) - (3 if has_lev else 2)
@@ -560,7 +741,7 @@ class _RawChunks:
         return self.dev.ptr
 
 
-def select_file(inp, out, var_name, levels=None, box=None, max_records=None):
+def select_file(inp, out, var_name, levels=None, box=None, max_records=None, cyclic='auto'):
     """`cdo sellevel,levels` and / or `cdo sellonlatbox,box` of one NetCDF-3 file (CFday_cut_subdomain.sh:28-30,
     extract_climate_delta.sh:194-208, Emon_add_top_from_Amon.sh:45-52) -> `out`.
     `var_name`, on (time, ..., [plev,] lat, lon) as named by settings, goes through the card in chunks of records
@@ -568,17 +749,22 @@ def select_file(inp, out, var_name, levels=None, box=None, max_records=None):
     AS THE RAW WORDS OF THE FILE: the output variable keeps its NetCDF type, every attribute, `_FillValue` and packing, and
     its bytes are the input's.  Every other variable with the level, latitude or longitude dimension - the coordinates,
     `lat_bnds`, `lon_bnds`, `plev_bnds` - is cut on the host with the same indices, `lon` and its bounds variable shifted by
-    the same 360 k (`lonlat_box`); everything else, the global attributes and the record dimension are carried over."""
+    the same 360 k (`lonlat_box`); everything else, the global attributes and the record dimension are carried over.
+    A curvilinear file (extract_climate_delta.sh:120-123, the Omon / SImon tables): when the file holds 2-D coordinate
+    variables lat / lon or latitude / longitude whose dimensions are exactly the variable's last two, (..., [plev,] j, i),
+    the box selects the index rectangle of `curvilinear_box` (`cyclic` as there) and every other variable on either grid
+    dimension - the 2-D coordinates, `vertices_latitude` / `vertices_longitude` - is cut with the same row run and cyclic
+    column run; no longitude is shifted, the coordinates keep their bits.  With 1-D coordinates `cyclic` must be 'auto'."""
     ds, rd = _open_series(inp, var_name)
     try:
-        nlead, has_lev = _grid_dims(rd.dims, var_name)
+        nlead, has_lev = _grid_dims(rd.dims, var_name, ds)
         item = _word_size(rd.file_dtype)
         lev_idx = None
         if levels is not None:
             if not has_lev or PLEV_GCM not in ds:
                 raise ValueError('%s: levels need the %s dimension and its coordinate variable' % (var_name, PLEV_GCM))
             lev_idx = level_indices(ds[PLEV_GCM].values, levels)
-        cut = _Cut(ds, lev_idx, box)
+        cut = _Cut(ds, lev_idx, box, rd.dims, cyclic)
         nrec, rec_shape = rd.nrec, rd.rec_shape
         nlat, nlon = rec_shape[-2:]
         nlev = rec_shape[-3] if has_lev else 1
@@ -849,14 +1035,16 @@ def _encoded(values, raw_attrs):
     return values, attrs
 
 
-def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=None, out_dtype=None, box=None):
+def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=None, out_dtype=None, box=None, cyclic='auto'):
     """extract_climate_delta.sh:194-219: `cdo -cat` of the files `inputs` (one path, or a list in
     time order - CMIP series come in multi-year pieces), `-selyear` (years=(y0, y1)), `ymonmean` / `ydaymean` (mode) of
     `var_name` -> `out_path`.
     box = (lon1, lon2, lat1, lat2): the `sellonlatbox,$box` in front of it (:194, :204; `lonlat_box`) - every uploaded chunk
     of decoded records is cut on the device (`pgw_select_box`) before it is accumulated, the dimensions must end in
     ([plev,] lat, lon), and the coordinates and bounds of the output are cut as `select_file` cuts them: the result is, bit
-    for bit, the climatology of the `select_file(box=box)` files.  None (default): no cut.
+    for bit, the climatology of the `select_file(box=box)` files.  None (default): no cut.  On a curvilinear file (2-D
+    coordinates on the variable's last two dimensions) the box is the index rectangle of `curvilinear_box`, `cyclic` as
+    there, under the same invariant.
     The files must share the time units, the calendar and the record shape (ValueError).  Bin by bin (`calendar_bins`) the
     records are read in time order (`ncio.RecordReader`), uploaded in chunks of what fits into 80 % of the card's free
     memory, at most `max_records` (the results do not depend on it), and accumulated; records outside `years` are never
@@ -895,9 +1083,11 @@ def climatology_files(inputs, out_path, var_name, mode, years=None, max_records=
         dt, odt = _clim_dtypes(r0.dtype, out_dtype)
         rec_shape = read_shape = r0.rec_shape
         cut, inner_read = None, 0
+        if box is None and _check_cyclic(cyclic) != 'auto':
+            raise ValueError('cyclic needs a box')
         if box is not None:                                       # records are read whole and cut on the device
-            _grid_dims(r0.dims, var_name)
-            cut = _Cut(ds0, None, box)
+            _grid_dims(r0.dims, var_name, ds0)
+            cut = _Cut(ds0, None, box, r0.dims, cyclic)
             rec_shape = read_shape[:-2] + (cut.nlat_sel, cut.nlon_sel)
             inner_read = int(np.prod(read_shape, dtype=np.int64))
         inner = int(np.prod(rec_shape, dtype=np.int64))
@@ -1033,6 +1223,8 @@ def build_parser():
                                             'model-top merge.')
     sub = p.add_subparsers(dest='command', required=True)
     box_help = 'LON1,LON2,LAT1,LAT2: cut to this longitude-latitude box (cdo sellonlatbox; may wrap across 0 deg)'
+    cyclic_help = ('with a box on a curvilinear grid (2-D latitude / longitude): does the grid close on itself along its last '
+                   'dimension - decided from the coordinates (auto), yes or no; with 1-D coordinates only auto is allowed')
     a = sub.add_parser('interp_to_plev', help='Interpolate CFday output to pressure levels (CFday_interp_to_plev.py)')
     a.add_argument('-i', '--input', type=str, required=True,
                    help='NetCDF-3 input file with the variable, ap, b (lev) and ps; {} is replaced by the variable name')
@@ -1057,6 +1249,7 @@ def build_parser():
     c.add_argument('--max_records', type=int, default=None, help='at most this many time records per launch')
     c.add_argument('--out_dtype', type=str, default=None, choices=['float32', 'float64'])
     c.add_argument('-b', '--box', type=str, default=None, help=box_help + ' in front of the climatology')
+    c.add_argument('--cyclic', type=str, default='auto', choices=list(CYCLIC_CHOICES), help=cyclic_help)
     d = sub.add_parser('delta', help='Scenario climatology minus historical climatology (cdo sub)')
     d.add_argument('scen_file', type=str, help='{} is replaced by the variable name (also in the other two paths)')
     d.add_argument('hist_file', type=str)
@@ -1068,6 +1261,7 @@ def build_parser():
     s.add_argument('-v', '--var_names', type=str, required=True, help='comma separated variable names, e.g. ta,hur,ua,va')
     s.add_argument('-l', '--levels', type=str, default=None, help='comma separated level values to keep, e.g. 100000,85000,50000')
     s.add_argument('-b', '--box', type=str, default=None, help=box_help)
+    s.add_argument('--cyclic', type=str, default='auto', choices=list(CYCLIC_CHOICES), help=cyclic_help)
     s.add_argument('--max_records', type=int, default=None, help='at most this many time records per launch')
     m = sub.add_parser('merge_levels', help='Levels of FILE_A, then levels of FILE_B, as one variable (cdo sellevel, sellevel, '
                                             'merge: Emon_add_top_from_Amon.sh)')
@@ -1103,7 +1297,7 @@ def main(argv=None):
         for name in names:
             done.append(climatology_files([i.replace('{}', name) for i in args.input], args.output.replace('{}', name), name,
                                           args.mode, years=years, max_records=args.max_records, out_dtype=args.out_dtype,
-                                          box=_parse_floats(args.box, 'box', 4)))
+                                          box=_parse_floats(args.box, 'box', 4), cyclic=args.cyclic))
     elif args.command == 'delta':
         names = args.var_names.split(',')
         paths = (args.scen_file, args.hist_file, args.delta_file)
@@ -1120,7 +1314,7 @@ def main(argv=None):
             raise ValueError('select needs --levels and / or --box')
         for name in names:
             done.append(select_file(args.input.replace('{}', name), args.output.replace('{}', name), name, levels=levels, box=box,
-                                    max_records=args.max_records))
+                                    max_records=args.max_records, cyclic=args.cyclic))
     elif args.command == 'merge_levels':
         names = args.var_names.split(',')
         paths = (args.file_a, args.file_b, args.out_file)
