@@ -495,6 +495,32 @@ int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, i
                         const int *lon_oob,
                         int south_row, int north_row, void *out);
 
+/* The same regridding from a plan: the ten tables of one (source grid, target mesh) pair uploaded once into device memory the
+ * plan owns, with the pole scratch for up to max_nfield planes - for a caller that regrids many records of one grid pair in
+ * the middle of other work on the context's stream (step_03 with settings.delta_grid = 'source': a delta record is regridded
+ * straight into its slot of the DeltaSet's window).
+ *  pgw_regrid_plan_create: the ten tables HOST, as for pgw_regrid_bilinear and checked like them (shapes, null pointers, table
+ *    entries, pole rows; max_nfield >= 1): PGW_ERR_ARG with *plan = NULL and nothing allocated.  Synchronises the stream once;
+ *    the host tables may be freed after the call.
+ *  pgw_regrid_plan_apply: src (nfield, nlat_s, nlon_s) of dtype_src, out (nfield, nlat_t, nlon_t) of dtype_out, both DEVICE.
+ *    Every value is computed as pgw_regrid_bilinear computes it for dtype_src (the same kernel, the same bits) and rounded to
+ *    dtype_src; where dtype_out differs, that value is then converted to dtype_out - what a file written by step_02 in the
+ *    source's type holds after the host's astype(dtype_out).  Launches on the context's stream and returns: no allocation,
+ *    no workspace slot, no synchronisation.  PGW_ERR_ARG before any launch, the output untouched, for: a null plan or pointer,
+ *    a dtype tag other than PGW_F32 / PGW_F64, nfield outside [1, max_nfield], src or out not aligned to its element size.
+ *    Timed under PGW_K_REGRID.
+ *  pgw_regrid_plan_destroy: waits for the stream, frees the plan (NULL: nothing to do). */
+typedef struct pgw_regrid_plan pgw_regrid_plan;
+int pgw_regrid_plan_create(pgw_ctx *ctx, int nlat_s, int nlon_s, int nlat_t, int nlon_t,
+                           const int *lat_lo, const int *lat_hi, const double *lat_dx, const double *lat_Dx,
+                           const int *lat_oob,
+                           const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
+                           const int *lon_oob,
+                           int south_row, int north_row, long long max_nfield, pgw_regrid_plan **plan);
+int pgw_regrid_plan_apply(pgw_ctx *ctx, const pgw_regrid_plan *plan, int dtype_src, int dtype_out, long long nfield,
+                          const void *src, void *out);
+int pgw_regrid_plan_destroy(pgw_ctx *ctx, pgw_regrid_plan *plan);
+
 /* a10 with point-wise targets (functions.py:812-893 where `targ_lat` / `targ_lon` are 2-D over shared dimensions, or 1-D
  * over one shared dimension: `.interp({lat: targ_lat})` then `.interp({lon: targ_lon})` is xarray's point-wise
  * interpolation): every target g has its own latitude and its own longitude bracket.  Same arithmetic, same order and

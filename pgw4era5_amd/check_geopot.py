@@ -110,7 +110,7 @@ def check_file(inp_era_file_path, pgw_era_file_path, delta_input_dir, era_step_d
     if nt != 1:
         raise ValueError('Time dimension of input files is inconsistent!')          # one instant per file, like step_03
     ctx = default_context()
-    deltas = s3.load_delta_set(ctx, delta_input_dir, a['T'].dtype)
+    deltas = s3.load_delta_set(ctx, delta_input_dir, a['T'].dtype, era5=(era_file, inp_era_file_path))
     plev = F.check_plev(deltas.plev_zg)
     zb, za, x_hi, x_new = deltas.pair('zg', era_step_dt, None)
     sz = (1, len(plev), nlat, nlon)

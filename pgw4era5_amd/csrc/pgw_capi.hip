@@ -2690,6 +2690,36 @@ static unsigned int z_slices(long long blocks_xy, long long nfield) {
     return (unsigned int)std::clamp((8192 + blocks_xy - 1) / blocks_xy, 1ll, nfield);
 }
 
+// The launch geometry of k_regrid for nfield planes onto an nlat_t x nlon_t mesh at `out` (elements of dtype_out)
+struct RegridGrid {
+    int W;
+    unsigned int bx, gz, nb;
+    bool fits;
+    RegridGrid(pgw_ctx *ctx, long long nfield, int nlat_t, int nlon_t, const void *out, int dtype_out) {
+        // two target longitudes per thread (one 16-B / 8-B store per plane) when the row length and the output alignment allow
+        W = (nlon_t % 2 == 0 && ((uintptr_t)out % (2 * elem_size(dtype_out))) == 0 && !ctx->opt[PGW_OPT_FORCE_VEC1]) ? 2 : 1;
+        bx = nblocks(nlon_t, BLOCK * W);
+        const long long xy = (long long)bx * nlat_t;
+        gz = z_slices(xy, nfield);
+        // z-slices in multiples of 8 where there are planes for it: one XCD per slice group (k_regrid)
+        if (nfield >= 8) gz = (gz + 7u) / 8u * 8u;
+        if (gz > nfield) gz = (unsigned int)nfield;
+        fits = xy * gz < (1ll << 31);
+        nb = fits ? (unsigned int)(xy * gz) : 0u;
+    }
+};
+
+static void launch_regrid(pgw_ctx *ctx, const RegridGrid &g, int dtype_src, int dtype_out, long long nfield, int nlat_s, int nlon_s,
+                          int nlat_t, int nlon_t, const void *src, const RegridTables &tb, const double *dpole, void *out) {
+    with_type(dtype_src, [&](auto t_) { with_type(dtype_out, [&](auto o_) { with_int<2>(g.W - 1, [&](auto w_) {
+        using T = decltype(t_);
+        using TOUT = decltype(o_);
+        // 4 planes per step (2: 6 % slower, 8: the same)
+        hipLaunchKernelGGL((k_regrid<T, 4, decltype(w_)::value + 1, TOUT>), dim3(g.nb), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s,
+                           nlon_s, nlat_t, nlon_t, g.bx, g.gz, (const T *)src, tb, dpole, (TOUT *)out);
+    }); }); });
+}
+
 extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, int nlat_t,
                                    int nlon_t, const void *src, const int *lat_lo, const int *lat_hi,
                                    const double *lat_dx, const double *lat_Dx, const int *lat_oob, const int *lon_lo,
@@ -2711,24 +2741,93 @@ extern "C" int pgw_regrid_bilinear(pgw_ctx *ctx, int dtype, long long nfield, in
     {
         Prof pr(ctx, PGW_K_REGRID);
         launch_pole_means(ctx, dtype, nfield, nlat_s, nlon_s, src, south_row, north_row, dpole);
-        // two target longitudes per thread (one 16-B / 8-B store per plane) when the row length and the output alignment allow
-        const int W = (nlon_t % 2 == 0 && ((uintptr_t)out % (2 * elem_size(dtype))) == 0 && !ctx->opt[PGW_OPT_FORCE_VEC1]) ? 2 : 1;
-        const unsigned int bx = nblocks(nlon_t, BLOCK * W);
-        long long xy = (long long)bx * nlat_t;
-        unsigned int gz = z_slices(xy, nfield);
-        // z-slices in multiples of 8 where there are planes for it: one XCD per slice group (k_regrid)
-        if (nfield >= 8) gz = (gz + 7u) / 8u * 8u;
-        if (gz > nfield) gz = (unsigned int)nfield;
-        NEED(ctx, xy * gz < (1ll << 31), "regrid: too many blocks");
-        const unsigned int nb = (unsigned int)(xy * gz);
-        with_type(dtype, [&](auto t_) { with_int<2>(W - 1, [&](auto w_) {
-            using T = decltype(t_);
-            // 4 planes per step (2: 6 % slower, 8: the same)
-            hipLaunchKernelGGL((k_regrid<T, 4, decltype(w_)::value + 1>), dim3(nb), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s,
-                               nlat_t, nlon_t, bx, gz, (const T *)src, tb, dpole, (T *)out);
-        }); });
+        const RegridGrid g(ctx, nfield, nlat_t, nlon_t, out, dtype);
+        NEED(ctx, g.fits, "regrid: too many blocks");
+        launch_regrid(ctx, g, dtype, dtype, nfield, nlat_s, nlon_s, nlat_t, nlon_t, src, tb, dpole, out);
     }
     HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// A regrid plan: the ten tables of one (source grid, target mesh) pair resident on the device, with the pole scratch of up
+// to max_nfield planes behind them - what pgw_regrid_bilinear lays into workspace slot 3 on every call, held once.
+struct pgw_regrid_plan {
+    int nlat_s, nlon_s, nlat_t, nlon_t, south_row, north_row;
+    long long max_nfield;
+    RegridTables tb;
+    double *dpole;
+    char *mem;                                                 // one allocation: [double tables][pole][int tables]
+};
+
+extern "C" int pgw_regrid_plan_create(pgw_ctx *ctx, int nlat_s, int nlon_s, int nlat_t, int nlon_t, const int *lat_lo,
+                                      const int *lat_hi, const double *lat_dx, const double *lat_Dx, const int *lat_oob,
+                                      const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
+                                      const int *lon_oob, int south_row, int north_row, long long max_nfield,
+                                      pgw_regrid_plan **plan) {
+    NEED(ctx, plan, "null pointer");
+    *plan = nullptr;
+    NEED(ctx, max_nfield >= 1 && max_nfield < (1ll << 40) && nlat_s >= 2 && nlon_s >= 2 && nlat_t >= 1 && nlon_t >= 1, "bad shape");
+    NEED(ctx, lat_lo && lat_hi && lat_dx && lat_Dx && lat_oob && lon_lo && lon_hi && lon_dx && lon_Dx && lon_oob, "null pointer");
+    if (int rc = check_brackets(ctx, __func__, nlat_t, lat_oob, lat_lo, lat_hi, nullptr, nullptr, nlat_s, nlon_s, south_row, north_row)) return rc;
+    if (int rc = check_brackets(ctx, __func__, nlon_t, lon_oob, nullptr, nullptr, lon_lo, lon_hi, nlat_s, nlon_s, south_row, north_row)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t a = (size_t)nlat_t, o = (size_t)nlon_t;
+    const size_t td = sizeof(double) * 2 * (a + o), tp = sizeof(double) * 2 * (size_t)max_nfield, ti = sizeof(int) * 3 * (a + o);
+    std::vector<char> h(td + ti);
+    pgw_regrid_plan *p = new pgw_regrid_plan{nlat_s, nlon_s, nlat_t, nlon_t, south_row, north_row, max_nfield, {}, nullptr, nullptr};
+    const hipError_t e = hipMalloc((void **)&p->mem, td + tp + ti);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();                               // as pgw_malloc: an allocation that does not fit is an answer
+        delete p;
+        return fail(ctx, PGW_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", td + tp + ti, hipGetErrorString(e));
+    }
+    size_t at = 0;
+    auto put = [&](const auto *host, size_t n, auto **dev, size_t gap) {
+        memcpy(h.data() + at, host, sizeof(*host) * n);
+        *dev = (std::remove_reference_t<decltype(*dev)>)(p->mem + gap + at);
+        at += sizeof(*host) * n;
+    };
+    put(lat_dx, a, &p->tb.lat_dx, 0); put(lat_Dx, a, &p->tb.lat_Dx, 0); put(lon_dx, o, &p->tb.lon_dx, 0); put(lon_Dx, o, &p->tb.lon_Dx, 0);
+    p->dpole = (double *)(p->mem + td);
+    put(lat_lo, a, &p->tb.lat_lo, tp); put(lat_hi, a, &p->tb.lat_hi, tp); put(lat_oob, a, &p->tb.lat_oob, tp);
+    put(lon_lo, o, &p->tb.lon_lo, tp); put(lon_hi, o, &p->tb.lon_hi, tp); put(lon_oob, o, &p->tb.lon_oob, tp);
+    hipError_t c = hipMemcpyAsync(p->mem, h.data(), td, hipMemcpyHostToDevice, ctx->stream);
+    if (c == hipSuccess) c = hipMemcpyAsync(p->mem + td + tp, h.data() + td, ti, hipMemcpyHostToDevice, ctx->stream);
+    if (c == hipSuccess) c = hipStreamSynchronize(ctx->stream);        // once per plan: the host tables may be freed after the call
+    if (c != hipSuccess) {
+        (void)hipFree(p->mem);
+        delete p;
+        return fail(ctx, PGW_ERR_HIP, "upload of the regrid tables failed: %s", hipGetErrorString(c));
+    }
+    *plan = p;
+    return PGW_OK;
+}
+
+extern "C" int pgw_regrid_plan_apply(pgw_ctx *ctx, const pgw_regrid_plan *plan, int dtype_src, int dtype_out, long long nfield,
+                                     const void *src, void *out) {
+    NEED(ctx, plan, "null plan");
+    NEED(ctx, (dtype_src == PGW_F32 || dtype_src == PGW_F64) && (dtype_out == PGW_F32 || dtype_out == PGW_F64),
+         "dtypes must be PGW_F32 or PGW_F64");
+    NEED(ctx, nfield >= 1 && nfield <= plan->max_nfield, "nfield must be in [1, max_nfield of the plan]");
+    NEED(ctx, src && out, "null pointer");
+    NEED(ctx, ((uintptr_t)src % elem_size(dtype_src)) == 0 && ((uintptr_t)out % elem_size(dtype_out)) == 0, "pointers must be element-aligned");
+    const RegridGrid g(ctx, nfield, plan->nlat_t, plan->nlon_t, out, dtype_out);
+    NEED(ctx, g.fits, "regrid: too many blocks");
+    {
+        Prof pr(ctx, PGW_K_REGRID);
+        launch_pole_means(ctx, dtype_src, nfield, plan->nlat_s, plan->nlon_s, src, plan->south_row, plan->north_row, plan->dpole);
+        launch_regrid(ctx, g, dtype_src, dtype_out, nfield, plan->nlat_s, plan->nlon_s, plan->nlat_t, plan->nlon_t, src, plan->tb,
+                      plan->dpole, out);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_regrid_plan_destroy(pgw_ctx *ctx, pgw_regrid_plan *plan) {
+    if (!plan) return PGW_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // no launch may still read the tables
+    HIPCHK(ctx, hipFree(plan->mem));
+    delete plan;
     return PGW_OK;
 }
 

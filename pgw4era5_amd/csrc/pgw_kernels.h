@@ -2633,10 +2633,14 @@ struct RegridTables {
 // step's stores.
 constexpr int REGRID_SPAN = BLOCK;       // one source column per thread
 
-template <typename T, int FU, int W>
+// TOUT: the element type of `out` where it is not the source's (a float32 delta file under a float64 ERA5 file and the other
+// way round, DeltaSet records regridded on the device): every value is rounded to T first - what the regridded FILE would
+// hold - and that T value converted to TOUT - what the host's astype makes of the file.  float -> double is exact, double ->
+// float one rounding.  TOUT = T is the kernel as it was.
+template <typename T, int FU, int W, typename TOUT = T>
 __global__ __launch_bounds__(BLOCK) void k_regrid(long long nfield, int nlat_s, int nlon_s, int nlat_t, int nlon_t,
                                                   unsigned int bx, unsigned int gz, const T *__restrict__ src, RegridTables tb,
-                                                  const double *__restrict__ pole, T *__restrict__ out) {
+                                                  const double *__restrict__ pole, TOUT *__restrict__ out) {
     __shared__ double s_y[FU][REGRID_SPAN];
     __shared__ int s_first, s_span;
     // 1-D grid of bx * nlat_t * gz blocks.  Blocks b and b + 8 run on the same XCD (MI355X_MICROARCH.md, workgroup
@@ -2703,10 +2707,17 @@ __global__ __launch_bounds__(BLOCK) void k_regrid(long long nfield, int nlat_s, 
     // fields of this z-slice
     long long per = (nfield + gz - 1) / gz;
     long long f0 = (long long)bz * per, f1 = f0 + per < nfield ? f0 + per : nfield;
-    T *po = out + (long long)j * nlon_t + (active ? i0 : 0);
+    TOUT *po = out + (long long)j * nlon_t + (active ? i0 : 0);
     auto store = [&](long long f, const double (&r)[W]) {
-        storev_nt<T, W>(po + f * plane_t, r);             // W * sizeof(T) aligned: W | nlon_t and W | i0; streaming: the output
-                                                          // must not push the source planes out of L2
+        // W * sizeof(TOUT) aligned: W | nlon_t, W | i0 and `out` itself (the host picks W); streaming: the output must not
+        // push the source planes out of L2
+        if constexpr (std::is_same<T, TOUT>::value) storev_nt<T, W>(po + f * plane_t, r);
+        else {
+            double rt[W];
+#pragma unroll
+            for (int w = 0; w < W; ++w) rt[w] = (double)(T)r[w];
+            storev_nt<TOUT, W>(po + f * plane_t, rt);
+        }
     };
     if (staged) {
         // this thread's source column of the window (threads >= span idle in the latitude pass)

@@ -718,6 +718,55 @@ def regrid_field(field, src_lat, src_lon, targ_lat, targ_lon):
                    np.asarray(targ_lon, dtype=np.float64), points=False)
 
 
+class RegridPlan:
+    """`regrid_field` for many calls on one (source grid, target mesh) pair: the tables of `regrid_tables` - the reference's
+    extent errors are raised here, before anything is launched - uploaded once into device memory the plan owns
+    (pgw_regrid_plan_create), and `apply` launches on the context's stream without allocating or synchronising
+    (pgw_regrid_plan_apply).  Source and output are DeviceArrays and may differ in dtype: the output holds
+    `regrid_field(src).astype(out.dtype)`, bit for bit - what a regridded file holds after the host's astype."""
+
+    def __init__(self, src_lat, src_lon, targ_lat, targ_lon, max_nfield, ctx=None):
+        self.ctx = ctx or default_context()
+        targ_lat, targ_lon = np.asarray(targ_lat, dtype=np.float64), np.asarray(targ_lon, dtype=np.float64)
+        if targ_lat.ndim != 1 or targ_lon.ndim != 1:
+            raise ValueError('a regrid plan takes the two 1-D axes of a target mesh; got lat %s and lon %s'
+                             % (targ_lat.shape, targ_lon.shape))
+        tb = regrid_tables(src_lat, src_lon, targ_lat, targ_lon)
+        self.src_shape, self.targ_shape = (len(src_lat), len(src_lon)), (len(targ_lat), len(targ_lon))
+        self.max_nfield = int(max_nfield)
+        c = {k: np.ascontiguousarray(v) for k, v in tb.items() if isinstance(v, np.ndarray)}
+        names = 'lat_lo lat_hi lat_dx lat_Dx lat_oob lon_lo lon_hi lon_dx lon_Dx lon_oob'
+        tabs = [c[k].ctypes.data_as(_ip if c[k].dtype == np.int32 else _dp) for k in names.split()]
+        handle = C.c_void_p()
+        self.ctx._check(self.ctx.lib.pgw_regrid_plan_create(self.ctx.handle, *self.src_shape, *self.targ_shape, *tabs,
+                                                            tb['south_row'], tb['north_row'], self.max_nfield, C.byref(handle)))
+        self.handle = handle.value
+
+    def apply(self, src, out):
+        """src (..., nlat_s, nlon_s) -> out (..., nlat_t, nlon_t), DeviceArrays with the same leading shape."""
+        if self.handle is None:
+            raise ValueError('the regrid plan has been freed')
+        if (len(src.shape) < 2 or tuple(src.shape[-2:]) != self.src_shape or tuple(out.shape[-2:]) != self.targ_shape
+                or tuple(src.shape[:-2]) != tuple(out.shape[:-2])):
+            raise ValueError('regrid plan %s -> %s: source %s and output %s do not fit' % (self.src_shape, self.targ_shape,
+                                                                                         src.shape, out.shape))
+        nfield = int(np.prod(src.shape[:-2], dtype=np.int64))
+        self.ctx._check(self.ctx.lib.pgw_regrid_plan_apply(self.ctx.handle, self.handle, dtype_tag(src.dtype), dtype_tag(out.dtype),
+                                                           nfield, src.ptr, out.ptr))
+        return out
+
+    def free(self):
+        if self.handle is not None and self.ctx.handle:
+            self.ctx.lib.pgw_regrid_plan_destroy(self.ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:                                       # noqa: BLE001 - interpreter shutdown
+            pass
+
+
 def regrid_points(field, src_lat, src_lon, targ_lat, targ_lon):
     """Bilinear (lat, then lon) regridding of field (..., nlat_s, nlon_s) onto point-wise targets on the GPU: `targ_lat` and
     `targ_lon` have one common shape of any rank >= 1 (2-D coordinates of a rotated-pole grid, a list of cells), target g

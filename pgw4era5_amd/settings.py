@@ -67,6 +67,16 @@ function_dtype_flow = 'common'
 # reference's either way.
 f32_out_dtype = 'float64'
 
+# ---- not in the reference: the grid of the climate deltas step_03 reads (`-d`) ----------------------------------------------
+# 'era5': the files `step_02 regridding` wrote, on the grid of the ERA5 files (the reference's chain).
+# 'source': the files `step_02 regridding` would take as `-i` - the smoothed deltas on the GCM's regular lat / lon grid (1-D
+#     lat / lon), same file names - regridded on the GPU as they are needed: the surface deltas whole at load, by the calls
+#     step_02 makes; a record of ta, hur, ua, va, zg when the instant moves past one (pgw_regrid_plan_apply into the record
+#     window of the DeltaSet).  No intermediate files; every output byte is that of the two-step run.  Not with --bands, not
+#     with i_use_xesmf_regridding = 1, ERA5 files with 1-D lat / lon axes only.
+# `--delta_grid` on the step_03 command line (or PGW_DELTA_GRID) overrides; any other value: ValueError.
+delta_grid = 'era5'
+
 # The host side of a file call.  True: process_file_device keeps, per context, a plan of everything that stays the same from file
 # to file (pointers, shapes, tables, loop controls) and the library brackets the delta records for the instant itself
 # (pgw_step03_file_at): one C call per file.  False: the argument struct is put together in Python for every file, as it is

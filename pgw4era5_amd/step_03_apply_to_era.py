@@ -85,8 +85,10 @@ class DeltaSet:
     """The climate deltas of one run on the device.
 
     arrays: dict var -> [nrec, (nplev,) nlat, nlon] for ta,hur,ua,va,zg (4-D) and tas,hurs,ts,tos,siconc,ps_hist (3-D): a
-    host array, a DeviceArray, or a record provider (`ncio.RecordReader`: .nrec, .rec_shape, .read_record(r)).  `plev` in
-    file order (descending for CMIP).
+    host array, a DeviceArray, or a record provider (`ncio.RecordReader`: .nrec, .rec_shape, .read_record(r)).  A provider
+    with `.device_record(r, out)` (`SourceRecords`: records of a delta on the GCM's grid, regridded on the device) fills a
+    record's DeviceArray itself, in stream order; such a variable always keeps the window.  `plev` in file order (descending
+    for CMIP).
 
     Time axes: the reference loads every delta file on its own (load_delta, functions.py:195-303), so each variable has
     its own time axis - `times_by_var[var]`, default `delta_times` - and is bracketed on it (monthly tos / siconc beside
@@ -146,6 +148,9 @@ class DeltaSet:
             a = arrays[k]
             if isinstance(a, DeviceArray):
                 self.dev[k] = a
+            elif hasattr(a, 'device_record'):
+                self._src[k] = a
+                self._cache[k] = {}
             elif self.resident:
                 if hasattr(a, 'read_record'):
                     a = np.stack([a.read_record(r) for r in range(a.nrec)])
@@ -172,11 +177,11 @@ class DeltaSet:
 
     @staticmethod
     def _nrec(a):
-        return int(a.nrec) if hasattr(a, 'read_record') else int(a.shape[0])
+        return int(a.nrec) if hasattr(a, 'rec_shape') else int(a.shape[0])
 
     @staticmethod
     def _rec_elems(a):
-        shape = a.rec_shape if hasattr(a, 'read_record') else a.shape[1:]
+        shape = a.rec_shape if hasattr(a, 'rec_shape') else a.shape[1:]
         return int(np.prod(shape, dtype=np.int64))
 
     @staticmethod
@@ -200,6 +205,13 @@ class DeltaSet:
                 cache[r] = cache.pop(r)                             # most recently used last
                 return cache[r]
             src = self._src[var]
+            if hasattr(src, 'device_record'):
+                # the provider writes the record on the context's stream: every kernel that reads the slot of the least
+                # recently used record was launched on it before, so the slot is reused without a host synchronisation
+                arr = cache.pop(next(iter(cache))) if len(cache) >= self.WINDOW else self.ctx.empty(src.rec_shape, self.dtype)
+                src.device_record(r, arr)
+                cache[r] = arr
+                return arr
             host = src.read_record(r) if hasattr(src, 'read_record') else src[r]
             if len(cache) >= self.WINDOW:
                 old = next(iter(cache))
@@ -263,7 +275,10 @@ class DeltaSet:
         for v in list(self.dev.values()) + [x for c in self._cache.values() for x in c.values()] + [self.ts_clim]:
             if v is not None:
                 v.free()
-        self.dev, self._cache, self.ts_clim = {}, {}, None
+        for src in self._src.values():
+            if hasattr(src, 'device_record'):
+                src.free()
+        self.dev, self._cache, self._src, self.ts_clim = {}, {}, {}, None
 
 
 # Placement classes of the level arrays (device.SpreadPool; only their balance matters): the write streams
@@ -749,13 +764,153 @@ class _BandOfRecords:
         return self.reader.read_record(r)[..., self.j0:self.j1, :]
 
 
-def load_delta_set(ctx, delta_input_dir, dtype, band=None):
+def delta_grid_mode(bands=False):
+    """settings.delta_grid (PGW_DELTA_GRID, which the command line sets for the ranks it starts, overrides): 'era5' or
+    'source', with what 'source' excludes - all ValueErrors, raised before anything is read, copied or launched."""
+    mode = os.environ.get('PGW_DELTA_GRID') or S.delta_grid
+    if mode not in ('era5', 'source'):
+        raise ValueError("settings.delta_grid must be 'era5' or 'source', got %r" % (mode,))
+    if mode == 'source':
+        if bands:
+            raise ValueError("delta_grid = 'source' regrids whole records and does not run with --bands")
+        if S.i_use_xesmf_regridding:
+            raise ValueError("delta_grid = 'source' takes deltas on a regular lat / lon grid (the separable bilinear regridding); "
+                             'with settings.i_use_xesmf_regridding = 1 run step_02 regridding and use the files it writes')
+    return mode
+
+
+class SourceRecords:
+    """Record provider of a DeltaSet over one level variable of a delta file on the GCM's grid: record r is read and decoded
+    like step_02 reads it (ncio.RecordReader: `_FillValue` / packing), uploaded into a staging buffer of one source record and
+    regridded straight into the DeviceArray the DeltaSet hands over (functions.RegridPlan.apply: the bits of the regridded
+    file cast to the DeltaSet's dtype) - all on the context's stream, nothing waits.  `rec_shape` is the regridded record's."""
+
+    KEPT = 8                       # host records held after their upload was queued (each file call synchronises the stream)
+
+    def __init__(self, ctx, reader, plan):
+        self.ctx, self.reader, self.plan = ctx, reader, plan
+        self.nrec = int(reader.nrec)
+        self.rec_shape = tuple(reader.rec_shape[:-2]) + tuple(plan.targ_shape)
+        self.src_dtype = reader.dtype if reader.dtype in (np.dtype('float32'), np.dtype('float64')) else np.dtype('float64')
+        self._stage = None
+        self._held = __import__('collections').deque(maxlen=self.KEPT)
+
+    def device_record(self, r, out):
+        host = np.ascontiguousarray(self.reader.read_record(int(r)), dtype=self.src_dtype)
+        if self._stage is None:
+            self._stage = self.ctx.empty(host.shape, self.src_dtype)
+        self._held.append(host)
+        self.ctx._check(self.ctx.lib.pgw_memcpy_h2d(self.ctx.handle, self._stage.ptr, host.ctypes.data, host.nbytes))
+        self.plan.apply(self._stage, out)
+        return out
+
+    def free(self):
+        if self._stage is not None:
+            self._stage.free()                                  # waits for the stream
+            self._stage = None
+        self._held.clear()
+        self.plan.free()
+        self.reader.close()
+
+
+def _open_era5_target(path):
+    """The ERA5 file as step_02 opens its `-e` file, without the level fields: the axes and FR_LAND are what is needed."""
+    from . import ncio
+    vm = S.var_name_map
+    return ncio.open_dataset(path, decode_times=False, skip=tuple(vm[k] for k in ('ta', 'hus', 'ua', 'va', 'st')))
+
+
+def _mesh_axes(era5):
+    """lat / lon of an ERA5 Dataset as float64 axes; ValueError unless they are 1-D axes of their own (a mesh)."""
+    t_lat, t_lon = era5[S.LAT_ERA], era5[S.LON_ERA]
+    if (len(t_lat.shape) != 1 or len(t_lon.shape) != 1 or tuple(t_lat.dims) != (S.LAT_ERA,) or tuple(t_lon.dims) != (S.LON_ERA,)):
+        raise ValueError("delta_grid = 'source' needs an ERA5 file whose %s / %s are 1-D axes of their own; got %s over %s and %s "
+                         'over %s' % (S.LAT_ERA, S.LON_ERA, t_lat.shape, tuple(t_lat.dims), t_lon.shape, tuple(t_lon.dims)))
+    return np.asarray(t_lat.values, dtype=np.float64), np.asarray(t_lon.values, dtype=np.float64)
+
+
+def _load_source_delta_set(ctx, delta_input_dir, dtype, era5):
+    """load_delta_set with delta_grid = 'source': `delta_input_dir` holds what `step_02 regridding` takes as `-i`; the target is
+    the mesh of the lat / lon axes of `era5` (the path of the ERA5 file being processed, or (opened Dataset, path): the
+    Dataset is asked for the axes, the file is opened like step_02's `-e` only when the deltas are not loaded yet)."""
+    from . import functions as F, ncio
+    if era5 is None:
+        raise ValueError("delta_grid = 'source' needs the ERA5 file whose lat / lon axes are the target")
+    era5, era5_path = era5 if isinstance(era5, tuple) else (_open_era5_target(era5), None)
+    targ_lat, targ_lon = _mesh_axes(era5)
+    key =(os.path.abspath(delta_input_dir), np.dtype(dtype).str, ctx.device, None, 'source', targ_lat.tobytes(), targ_lon.tobytes())
+    if key in _DELTASETS:
+        return _DELTASETS[key]
+    if era5_path is not None:
+        era5 = _open_era5_target(era5_path)
+    base = S.file_name_bases
+    readers = {var: ncio.RecordReader(os.path.join(delta_input_dir, base['SCEN-HIST'].format(var)), var) for var in DeltaSet.VARS_3D}
+    times, plevs, plans, arrays = {}, {}, {}, {}
+    try:
+        for var, r in readers.items():
+            if not r.dims or r.dims[0] != S.TIME_GCM or S.TIME_GCM not in r.coords:
+                raise ValueError('%s: the first dimension of %s must be %s with a coordinate variable' % (r.path, r.var, S.TIME_GCM))
+            if tuple(r.dims[-2:]) != (S.LAT_GCM, S.LON_GCM) or S.LAT_GCM not in r.coords or S.LON_GCM not in r.coords:
+                raise ValueError('%s: %s must end in the dimensions (%s, %s), 1-D coordinates of their own'
+                                 % (r.path, r.var, S.LAT_GCM, S.LON_GCM))
+            times[var] = np.asarray(r.coords[S.TIME_GCM])
+            plevs[var] = np.asarray(r.coords[S.PLEV_GCM], dtype=np.float64)
+        plev = plevs['ta']
+        for var in ('hur', 'ua', 'va'):
+            if len(plevs[var]) != len(plev) or np.any(plevs[var] != plev):
+                raise ValueError('plev axis of %s differs from that of ta (the four model-level deltas are interpolated together)' % var)
+        # one plan per source grid: regrid_tables runs here, the reference's extent errors come before any file is processed
+        grids = {}
+        for var, r in readers.items():
+            lat, lon = np.asarray(r.coords[S.LAT_GCM], dtype=np.float64), np.asarray(r.coords[S.LON_GCM], dtype=np.float64)
+            g = grids.setdefault((lat.tobytes(), lon.tobytes()), dict(lat=lat, lon=lon, nfield=1, vars=[]))
+            g['nfield'] = max(g['nfield'], int(np.prod(r.rec_shape[:-2], dtype=np.int64)))
+            g['vars'].append(var)
+        for gkey, g in grids.items():
+            plans[gkey] = F.RegridPlan(g['lat'], g['lon'], targ_lat, targ_lon, g['nfield'], ctx=ctx)
+            for var in g['vars']:
+                arrays[var] = SourceRecords(ctx, readers[var], plans[gkey])
+        # the surface deltas whole, by the calls of step_02 (step_02_preproc_deltas.main)
+        surface = [(v, base['SCEN-HIST'].format(v), v) for v in ('tas', 'hurs', 'ts', 'tos', 'siconc')]
+        for var, fname, name in surface + [('ps_hist', base['HIST'].format('ps'), 'ps')]:
+            path = os.path.join(delta_input_dir, fname)
+            if not os.path.exists(path):
+                raise ValueError('Files for variable ' + name + ' are missing')
+            out = F.interp_wrapper(ncio.open_dataset(path), era5, name, i_use_xesmf=0,
+                                   nan_interp_kernel_radius=S.nan_interp_kernel_radius, nan_interp_sharpness=S.nan_interp_sharpness)
+            f = out[name]
+            if not f.dims or f.dims[0] != S.TIME_GCM or S.TIME_GCM not in f.coords:
+                raise ValueError('%s: the first dimension of %s must be %s with a coordinate variable' % (path, name, S.TIME_GCM))
+            if f.shape[0] > 365 + 1:
+                raise ValueError('%s: %d records of %s; a surface delta stays on the device whole, a year of days at most'
+                                 % (path, f.shape[0], name))
+            arrays[var], times[var] = np.asarray(f.values), np.asarray(f.coords[S.TIME_GCM])
+        dset = DeltaSet(ctx, arrays, times['ta'], plev, dtype, times_by_var=times, resident=True)
+    except BaseException:
+        for a in arrays.values():
+            if hasattr(a, 'device_record'):
+                a.free()
+        for pl in plans.values():
+            pl.free()
+        for r in readers.values():
+            r.close()
+        raise
+    dset.plev_zg = plevs['zg']
+    _DELTASETS[key] = dset
+    return dset
+
+
+def load_delta_set(ctx, delta_input_dir, dtype, band=None, era5=None):
     """All delta files of a directory -> DeltaSet on the device, cached per process (every ERA5 file of a run uses the
     same deltas).  Like the reference's load_delta (functions.py:195-303) every file brings its own time axis; the four
     model-level variables must share one plev axis (the quad kernel interpolates them together), zg may have its own.
     When all records fit the HBM budget (DeltaSet) the files are read whole; otherwise they are opened record-wise and
-    the DeltaSet keeps a window of records per variable on the device."""
+    the DeltaSet keeps a window of records per variable on the device.
+    settings.delta_grid = 'source': the directory holds the deltas on the GCM's grid and `era5` (path or opened Dataset of the
+    ERA5 file being processed) gives the target axes (_load_source_delta_set)."""
     from . import ncio
+    if delta_grid_mode(bands=band is not None) == 'source':
+        return _load_source_delta_set(ctx, delta_input_dir, dtype, era5)
     key = (os.path.abspath(delta_input_dir), np.dtype(dtype).str, ctx.device, band)
     if key in _DELTASETS:
         return _DELTASETS[key]
@@ -841,6 +996,7 @@ def _stage_load(inp_era_file_path, out_era_file_path, delta_input_dir, era_step_
                                   'the reference and not part of the MI355X hot path')
     if S.f32_out_dtype not in ('float64', 'float32'):                  # checked before any buffer is taken
         raise ValueError("settings.f32_out_dtype must be 'float64' or 'float32'")
+    delta_grid_mode()
     if S.i_debug >= 0:
         print('Start working on input file {}'.format(inp_era_file_path))
     raw = _io_raw()
@@ -945,7 +1101,7 @@ def _stage_upload(item):
     ctx = default_context()
     up = ctx.side('h2d')
     dtype = item['dtype']
-    item['deltas'] = load_delta_set(ctx, item['delta_input_dir'], dtype)
+    item['deltas'] = load_delta_set(ctx, item['delta_input_dir'], dtype, era5=(item['era_file'], item['inp_path']))
     sets = _buffer_sets((item['era']['T'].shape, dtype.str))
     with _BUFFER_LOCK:                              # once per process and grid: where the level arrays of the buffer sets lie
         ctx.enable_placement(int(np.prod(item['era']['T'].shape, dtype=np.int64)) * 8, 8 * len(sets.all_inp) + 1)
@@ -1110,6 +1266,7 @@ def pgw_for_era5_banded(inp_era_file_path, out_era_file_path, delta_input_dir, e
     byte.  Every rank returns the pass count.  `barrier`: a callable all ranks meet in."""
     from . import ncio
     from .parallel import band_rows
+    delta_grid_mode(bands=True)
     if S.i_reinterp:
         raise ValueError('latitude-band sharding of one file needs the multi-pass loop (settings.i_reinterp = 0)')
     if S.f32_out_dtype not in ('float64', 'float32'):
@@ -1140,7 +1297,7 @@ def pgw_for_era5_banded(inp_era_file_path, out_era_file_path, delta_input_dir, e
             if 'akm' in ds:                                                                              # step_03:68-70
                 coeffs['akm'] = np.asarray(ds['akm'].values, dtype=np.float64)
                 coeffs['bkm'] = np.asarray(ds['bkm'].values, dtype=np.float64)
-            deltas = load_delta_set(ctx, delta_input_dir, dtype, band=(j0, j1))
+            deltas = load_delta_set(ctx, delta_input_dir, dtype, band=(j0, j1), era5=inp_era_file_path)
             e = _upload_era(ctx, era, dtype)
         except BaseException:
             ctx.band_abort()                  # the other bands are on their way into the loop's first reduce: tell them
@@ -1180,8 +1337,6 @@ pgw_for_era5.reset = reset_after_abort
 
 def _cli(argv=None):
     import argparse
-    from pathlib import Path
-    from .parallel import IterMP
     p = argparse.ArgumentParser(description='Perturb ERA5 files with PGW climate deltas on MI355X GPUs '
                                             '(flags of the reference step_03_apply_to_era.py:505-568; settings in settings.py).')
     p.add_argument('-i', '--input_dir', type=str, default=None, help='directory with the ERA5 input files')
@@ -1201,6 +1356,10 @@ def _cli(argv=None):
                         'interpolate_full: the deltas the run adds, on the model levels, {VAR}_delta_{file} for PS, T, RELHUM, '
                         'U, V, T_SO, T_SKIN (:350-361).  NetCDF-3 files beside the output path; one file at a time per rank; '
                         'not with --bands')
+    p.add_argument('--delta_grid', type=str, default=None, choices=['era5', 'source'],
+                   help="the grid of the deltas under -d (default: settings.delta_grid).  era5: the files step_02 regridding wrote.  "
+                        'source: the files step_02 regridding takes as -i, on the GCM\'s regular lat / lon grid - regridded on the GPU '
+                        'as they are needed, no intermediate files, the same output bytes.  Not with --bands.')
     p.add_argument('--bands', action='store_true',
                    help='latency mode: EVERY file is split over all ranks in latitude bands (each rank reads, computes and '
                         'writes its rows; one MAX all-reduce per loop launch) instead of file i -> rank i mod W.  Needs the '
@@ -1215,6 +1374,22 @@ def _cli(argv=None):
         raise ValueError('Delta input directory (-d) is required.')
     if args.debug_mode is not None and args.debug_mode not in ['interpolate_time', 'interpolate_full']:
         raise ValueError('Invalid input for argument --debug_mode! Valid arguments are: "interpolate_time" or "interpolate_full"')
+    if args.delta_grid is None:
+        return _run_cli(args)
+    found = os.environ.get('PGW_DELTA_GRID')
+    os.environ['PGW_DELTA_GRID'] = args.delta_grid              # the ranks of -p N are new processes: they inherit it
+    try:
+        return _run_cli(args)
+    finally:                                                    # a caller of _cli in a longer-lived process finds what it had
+        os.environ.pop('PGW_DELTA_GRID')
+        if found is not None:
+            os.environ['PGW_DELTA_GRID'] = found
+
+
+def _run_cli(args):
+    from pathlib import Path
+    from .parallel import IterMP
+    delta_grid_mode(bands=args.bands)                           # before a directory is made or a rank started
     first = _dt.datetime.strptime(args.first_era_step, '%Y%m%d%H')
     last = _dt.datetime.strptime(args.last_era_step, '%Y%m%d%H')
     inc = _dt.timedelta(hours=args.hour_inc_step)

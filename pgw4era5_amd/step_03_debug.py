@@ -93,8 +93,17 @@ def debug_interpolate_time(inp_era_file_path, out_era_file_path, delta_input_dir
     era_time = ncio.RecordReader(inp_era_file_path, S.TIME_ERA, decode_times=False)          # header and time axis only
     time_field = ncio.Field(np.asarray(era_time.coords[S.TIME_ERA]).reshape(-1)[:1], (S.TIME_GCM,), {}, era_time.attrs)
     era_time.close()
+    from . import step_03_apply_to_era as s3
+    era5 = None
+    if s3.delta_grid_mode() == 'source':                    # the deltas lie on the GCM's grid: regridded here, by step_02's call
+        from .functions import interp_wrapper
+        era5 = s3._open_era5_target(inp_era_file_path)
+        s3._mesh_axes(era5)
     for var in TIME_VARS:
         ds = ncio.open_dataset(os.path.join(delta_input_dir, S.file_name_bases['SCEN-HIST'].format(var)))      # functions.py:203
+        if era5 is not None:
+            ds = interp_wrapper(ds, era5, var, i_use_xesmf=0, nan_interp_kernel_radius=S.nan_interp_kernel_radius,
+                                nan_interp_sharpness=S.nan_interp_sharpness)
         fld = ds[var]
         if fld.dims[0] != S.TIME_GCM or S.TIME_GCM not in ds:
             raise ValueError('first dimension of %s must be %s with a coordinate variable' % (var, S.TIME_GCM))
@@ -178,7 +187,7 @@ def debug_interpolate_full(inp_era_file_path, out_era_file_path, delta_input_dir
     if 'akm' in era_file:                                                                        # step_03:68-70
         coeffs['akm'] = np.asarray(era_file['akm'].values, dtype=np.float64)
         coeffs['bkm'] = np.asarray(era_file['bkm'].values, dtype=np.float64)
-    deltas = s3.load_delta_set(ctx, delta_input_dir, dtype)
+    deltas = s3.load_delta_set(ctx, delta_input_dir, dtype, era5=(era_file, inp_era_file_path))
     e = s3._upload_era(ctx, era, dtype)
     ref = s3.ref_dtype_mode(dtype)
     try:

@@ -44,7 +44,9 @@ def demangle(names):
 
 def canonical(name):
     name = name.replace('pgw::PlevTableT<64>', 'pgw::PlevTable')
-    return re.sub(r',\s*pgw::PlevTable\s*>\(', '>(', name)         # the trailing template argument at its default
+    name = re.sub(r',\s*pgw::PlevTable\s*>\(', '>(', name)         # the trailing template argument at its default
+    # k_regrid<T, FU, W, TOUT = T>: a build that names the store type spells the same-type kernels with it
+    return re.sub(r'(pgw::k_regrid<(\w+), (\d+), (\d+)), \2>\(', r'\1>(', name)
 
 
 def table(path):
