@@ -79,8 +79,8 @@ def check_file(inp_era_file_path, pgw_era_file_path, delta_input_dir, era_step_d
     """The check of one file pair: `inp_era_file_path` (what step_03 read) and `pgw_era_file_path` (what it wrote), with the
     zg delta of `delta_input_dir` interpolated to `era_step_dt` on the zg file's own plev and time axis.  Writes the NetCDF-3
     file `out_path` with phi_change = phi_pgw - phi_era, phi_delta = g * zg_delta and phi_error = phi_change - phi_delta
-    (time, plev, lat, lon) float64 [m2 s-2] and returns the per-level table (`table_from_partials`).  ValueError when the two
-    files differ in grid or level count."""
+    (time, plev, lat, lon - or the horizontal dimensions of a file with 2-D lat / lon or a cell list) float64 [m2 s-2] and
+    returns the per-level table (`table_from_partials`).  ValueError when the two files differ in grid or level count."""
     from . import ncio
     from . import functions as F
     from . import step_03_apply_to_era as s3
@@ -88,12 +88,15 @@ def check_file(inp_era_file_path, pgw_era_file_path, delta_input_dir, era_step_d
     vm = S.var_name_map
     era_file = ncio.open_dataset(inp_era_file_path, decode_times=False)
     pgw_file = ncio.open_dataset(pgw_era_file_path, decode_times=False)
-    dims4 = (S.TIME_ERA, S.LEV_ERA, S.LAT_ERA, S.LON_ERA)
-    dims3 = (S.TIME_ERA, S.LAT_ERA, S.LON_ERA)
+    H = s3.era_layout(era_file)                             # (lat, lon), or the dimensions of 2-D lat / lon, or (cell,)
+    hdims = s3.layout_dims(H)
+    dims3, dims4 = hdims['d3'], hdims['d4']
 
     def get(ds, name, dims):
+        if not s3.is_mesh(H):
+            s3._check_dims(name, ds[name], dims)
         v = np.asarray(ds[name].transpose(*dims).values)
-        return np.ascontiguousarray(v, dtype=np.float64 if v.dtype.itemsize == 8 else np.float32)
+        return s3._as_grid(np.ascontiguousarray(v, dtype=np.float64 if v.dtype.itemsize == 8 else np.float32), H)
 
     a = dict(PS=get(era_file, vm['ps'], dims3), FIS=get(era_file, vm['zgs'], dims3), T=get(era_file, vm['ta'], dims4),
              QV=get(era_file, vm['hus'], dims4))
@@ -131,8 +134,8 @@ def check_file(inp_era_file_path, pgw_era_file_path, delta_input_dir, era_step_d
     else:
         delta = ((za.numpy().astype(np.float64) - zb_h) / x_hi * x_new + zb_h) * CON_G
     ds = ncio.Dataset()
-    dims = (S.TIME_ERA, S.PLEV_GCM, S.LAT_ERA, S.LON_ERA)
-    for d in (S.TIME_ERA, S.LAT_ERA, S.LON_ERA):
+    dims = (S.TIME_ERA, S.PLEV_GCM) + H
+    for d in (S.TIME_ERA,) + H:
         if d in era_file and era_file[d].dims == (d,):
             ds[d] = ncio.Field(era_file[d].values, (d,), {}, era_file[d].attrs)
     ds[S.PLEV_GCM] = ncio.Field(plev, (S.PLEV_GCM,), {}, dict(units='Pa'))
@@ -140,7 +143,7 @@ def check_file(inp_era_file_path, pgw_era_file_path, delta_input_dir, era_step_d
     names = dict(phi_change='geopotential change of the PGW state against the ERA5 state',
                  phi_delta='g times the zg climate delta', phi_error='phi_change - phi_delta')
     for name, arr in (('phi_change', change.numpy()), ('phi_delta', delta.reshape(sz)), ('phi_error', error.numpy())):
-        ds[name] = ncio.Field(arr, dims, coords, dict(units='m2 s-2', long_name=names[name]))
+        ds[name] = ncio.Field(s3._as_file(arr, H), dims, coords, dict(units='m2 s-2', long_name=names[name]))
     ncio.to_netcdf(ds, out_path)
     for v in list(dev.values()) + [change, error]:
         v.free()

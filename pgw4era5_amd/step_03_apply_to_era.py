@@ -935,12 +935,22 @@ def load_delta_set(ctx, delta_input_dir, dtype, band=None, era5=None):
         total = total * (band[1] - band[0]) // max(nlat, 1)
     forced = os.environ.get('PGW_DELTA_RESIDENT')
     resident = (forced == '1') if forced in ('0', '1') else total <= DeltaSet.budget_bytes(ctx)
+    # records over one horizontal dimension (step_02 wrote them onto a cell list): (plev, cell) is taken as (plev, 1, cell)
+    cells = {var for var, r in readers.items() if len(r.rec_shape) == (2 if var in DeltaSet.VARS_3D else 1)}
+    if cells and band is not None:
+        for r in readers.values():
+            r.close()
+        raise ValueError('--bands on a point-wise file (deltas over a cell list) is not built')
     if resident:
         arrays = {}
         for var, r in readers.items():
             a = ncio.open_dataset(r.path)[r.var].values                         # whole file, threaded reads
+            if var in cells:
+                a = _as_grid(a, ('cell',))
             arrays[var] = a if band is None else np.ascontiguousarray(a[..., band[0]:band[1], :])
             r.close()
+    elif cells:
+        arrays = {k: _GridRecords(r) if k in cells else r for k, r in readers.items()}
     else:
         arrays = readers if band is None else {k: _BandOfRecords(r, band[0], band[1]) for k, r in readers.items()}
     dset = DeltaSet(ctx, arrays, times['ta'], plev, dtype, times_by_var=times, resident=resident)
@@ -951,6 +961,87 @@ def load_delta_set(ctx, delta_input_dir, dtype, band=None, era5=None):
 
 _POOLS = {}
 _BIG_OUT = ('T', 'QV', 'U', 'V')
+
+
+# ----------------------------------------------------------------------------------------
+# the horizontal layout of an ERA5 file
+# ----------------------------------------------------------------------------------------
+def _layout_of(lat_dims, lat_shape, lon_dims, lon_shape):
+    from .functions import _target_layout
+    points, dims = _target_layout(lat_dims, lat_shape, lon_dims, lon_shape)
+    if not points:
+        return (S.LAT_ERA, S.LON_ERA)
+    if len(dims) > 2:
+        raise ValueError('%s / %s over %s: the horizontal layout of a file has one dimension (a cell list) or two'
+                         % (S.LAT_ERA, S.LON_ERA, dims))
+    return tuple(dims)
+
+
+def era_layout(ds):
+    """The horizontal dimensions H of the fields of an ERA5 Dataset, by the rule of functions._target_layout on its
+    settings.LAT_ERA / LON_ERA: (LAT_ERA, LON_ERA) where they are 1-D axes of their own (a mesh); their dimensions where
+    both lie over the same one or two (2-D coordinates of a rotated-pole file: (rlat, rlon); a cell list: (cell,)); any
+    other combination is the ValueError of _target_layout.  Every kernel of the per-file path works on independent columns:
+    fields go to the device as (time, level, H0, H1), a cell list as a grid of one row (_as_grid).  A file without the two
+    coordinate variables is the mesh it was taken for before there were layouts."""
+    if S.LAT_ERA not in ds or S.LON_ERA not in ds:
+        return (S.LAT_ERA, S.LON_ERA)
+    lat, lon = ds[S.LAT_ERA], ds[S.LON_ERA]
+    return _layout_of(lat.dims, lat.shape, lon.dims, lon.shape)
+
+
+def file_layout(path):
+    """era_layout from the header of the file at `path` (no field is read)."""
+    from . import ncio
+    got = []
+    for name in (S.LAT_ERA, S.LON_ERA):
+        try:
+            r = ncio.RecordReader(path, name, decode_times=False)
+        except KeyError:                                        # no such variable: a mesh, as era_layout takes it
+            return (S.LAT_ERA, S.LON_ERA)
+        got += [tuple(r.dims), (r.nrec,) + tuple(r.rec_shape)]
+        r.close()
+    return _layout_of(*got)
+
+
+def is_mesh(H):
+    return tuple(H) == (S.LAT_ERA, S.LON_ERA)
+
+
+def layout_dims(H):
+    """The dimension tuples of the 3-D, 4-D and soil fields of a file with horizontal dimensions H: dict d3, d4, so."""
+    H = tuple(H)
+    return dict(d3=(S.TIME_ERA,) + H, d4=(S.TIME_ERA, S.LEV_ERA) + H, so=(S.TIME_ERA, S.SOIL_HLEV_ERA) + H)
+
+
+def _as_grid(v, H):
+    """A field over (..., cell) as (..., 1, cell): a view of the same memory (a grid of one row); a field over two horizontal
+    dimensions as it is."""
+    return v.reshape(v.shape[:-1] + (1, v.shape[-1])) if len(H) == 1 else v
+
+
+def _as_file(v, H):
+    """The reverse of _as_grid: (..., 1, cell) back in the file's own shape (..., cell)."""
+    return v.reshape(v.shape[:-2] + v.shape[-1:]) if len(H) == 1 else v
+
+
+def _check_dims(name, field, dims, path=None):
+    """ValueError where the field does not lie over exactly `dims` (a field of a point-wise file that lacks one of the
+    horizontal dimensions), before anything is uploaded."""
+    if sorted(field.dims) != sorted(dims):
+        raise ValueError('%s%s lies over %s; the horizontal layout of the file asks for %s'
+                         % ('' if path is None else path + ': ', name, tuple(field.dims), tuple(dims)))
+
+
+class _GridRecords:
+    """A record provider over a cell list, its records (..., cell) handed out as (..., 1, cell)."""
+
+    def __init__(self, reader):
+        self.reader, self.nrec = reader, reader.nrec
+        self.rec_shape = tuple(reader.rec_shape[:-1]) + (1, reader.rec_shape[-1])
+
+    def read_record(self, r):
+        return self.reader.read_record(r).reshape(self.rec_shape)
 
 
 def _io_raw():
@@ -1009,23 +1100,26 @@ def _stage_load(inp_era_file_path, out_era_file_path, delta_input_dir, era_step_
             buf = pool.acquire(nbytes)
             pinned.append(buf)
             return buf
+    vm = S.var_name_map
     try:
         era_file = ncio.open_dataset(inp_era_file_path, decode_times=False, raw_big=raw, alloc=alloc)   # step_03:60
+        H = era_layout(era_file)
+        dims = layout_dims(H)
+        if not is_mesh(H):
+            for key, d in _FIELD_DIMS.items():
+                _check_dims(vm[key], era_file[vm[key]], dims[d], inp_era_file_path)
     except BaseException:
         for b_ in pinned:
             _release_pinned(pool, b_)
         raise
-    vm = S.var_name_map
     dtype = np.dtype('float64') if era_file[vm['ta']].dtype.itemsize == 8 else np.dtype('float32')
-    dims4 = (S.TIME_ERA, S.LEV_ERA, S.LAT_ERA, S.LON_ERA)
-    dims3 = (S.TIME_ERA, S.LAT_ERA, S.LON_ERA)
-    dims_so = (S.TIME_ERA, S.SOIL_HLEV_ERA, S.LAT_ERA, S.LON_ERA)
+    dims3, dims4, dims_so = dims['d3'], dims['d4'], dims['so']
 
     def get(name, dims):
         v = era_file[name].transpose(*dims).values
         if (not v.dtype.isnative) and v.dtype.kind == 'f' and v.dtype.itemsize == dtype.itemsize and v.flags.c_contiguous:
-            return v                                                         # file byte order; converted on the GPU
-        return np.ascontiguousarray(v, dtype=dtype)
+            return _as_grid(v, H)                                            # file byte order; converted on the GPU
+        return _as_grid(np.ascontiguousarray(v, dtype=dtype), H)
 
     era = dict(PS=get(vm['ps'], dims3), FIS=get(vm['zgs'], dims3), T=get(vm['ta'], dims4), QV=get(vm['hus'], dims4),
                U=get(vm['ua'], dims4), V=get(vm['va'], dims4), T_SKIN=get(vm['ts'], dims3),
@@ -1037,7 +1131,7 @@ def _stage_load(inp_era_file_path, out_era_file_path, delta_input_dir, era_step_
         coeffs['bkm'] = np.asarray(era_file['bkm'].values, dtype=np.float64)
     return dict(era_file=era_file, era=era, coeffs=coeffs, dtype=dtype, out_path=out_era_file_path, inp_path=inp_era_file_path,
                 delta_input_dir=delta_input_dir, era_step_dt=era_step_dt, ignore_top=ignore_top_pressure_error,
-                dims=dict(d3=dims3, d4=dims4, so=dims_so), pinned=pinned)
+                dims=dims, layout=H, pinned=pinned)
 
 
 class _BufferSets:
@@ -1065,6 +1159,9 @@ class _BufferSets:
             for x in sets:
                 q.put(x)
 
+
+# the fields the per-file path reads (keys of settings.var_name_map) and the dimension tuple each lies over (layout_dims)
+_FIELD_DIMS = dict(ps='d3', zgs='d3', ta='d4', hus='d4', ua='d4', va='d4', ts='d3', st='so', sftlf='d3', sic='d3')
 
 _DEVICE_BUFFERS = {}
 _BUFFER_LOCK = __import__('threading').Lock()
@@ -1225,7 +1322,8 @@ def _stage_store(item):
     try:
         for key, (name, dims) in names.items():
             old = era_file[name]
-            era_file[name] = ncio.Field(item['result'][key], dims, {k: old.coords[k] for k in dims if k in old.coords}, old.attrs)
+            era_file[name] = ncio.Field(_as_file(item['result'][key], item['layout']), dims,
+                                        {k: old.coords[k] for k in dims if k in old.coords}, old.attrs)
         ncio.to_netcdf(era_file, item['out_path'])
     finally:
         bufs = item.get('pinned', []) + item.get('pinned_out', [])
@@ -1256,6 +1354,14 @@ def pgw_for_era5(inp_era_file_path, out_era_file_path, delta_input_dir, era_step
         inp_era_file_path, out_era_file_path, delta_input_dir, era_step_dt, ignore_top_pressure_error, debug_mode)))))
 
 
+def _no_bands_on_points(path):
+    """`--bands` cuts latitude rows of a mesh: ValueError for a point-wise file, from its header, before a field is read."""
+    H = file_layout(path)
+    if not is_mesh(H):
+        raise ValueError('--bands on a point-wise file is not built: %s has %s / %s over %s (latitude bands are rows of a mesh)'
+                         % (path, S.LAT_ERA, S.LON_ERA, H))
+
+
 def pgw_for_era5_banded(inp_era_file_path, out_era_file_path, delta_input_dir, era_step_dt, ignore_top_pressure_error,
                         rank, world, reduce_max, barrier):
     """ONE ERA5 file over `world` ranks in latitude bands (the latency mode) from file to file:
@@ -1267,6 +1373,7 @@ def pgw_for_era5_banded(inp_era_file_path, out_era_file_path, delta_input_dir, e
     from . import ncio
     from .parallel import band_rows
     delta_grid_mode(bands=True)
+    _no_bands_on_points(inp_era_file_path)
     if S.i_reinterp:
         raise ValueError('latitude-band sharding of one file needs the multi-pass loop (settings.i_reinterp = 0)')
     if S.f32_out_dtype not in ('float64', 'float32'):
@@ -1398,12 +1505,16 @@ def _run_cli(args):
     while t < last + inc:                                   # np.arange(first, last + inc, inc), step_03:594-596
         steps.append(t)
         t += inc
-    Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     fargs = dict(delta_input_dir=args.delta_input_dir, ignore_top_pressure_error=args.ignore_top_pressure_error,
                  debug_mode=args.debug_mode)
     step_args = [dict(inp_era_file_path=os.path.join(args.input_dir, S.era5_file_name_base.format(s)),
                       out_era_file_path=os.path.join(args.output_dir, S.era5_file_name_base.format(s)),
                       era_step_dt=s) for s in steps]
+    if args.bands:                                              # from the headers, before a directory is made or a rank works
+        for s in step_args:
+            if os.path.exists(s['inp_era_file_path']):
+                _no_bands_on_points(s['inp_era_file_path'])
+    Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     if args.bands:
         return _run_banded(fargs, step_args)
     func = pgw_for_era5

@@ -172,12 +172,15 @@ def debug_interpolate_full(inp_era_file_path, out_era_file_path, delta_input_dir
     era_file = ncio.open_dataset(inp_era_file_path, decode_times=False)                          # step_03:60
     vm = S.var_name_map
     dtype = np.dtype('float64') if era_file[vm['ta']].dtype.itemsize == 8 else np.dtype('float32')
-    dims4 = (S.TIME_ERA, S.LEV_ERA, S.LAT_ERA, S.LON_ERA)
-    dims3 = (S.TIME_ERA, S.LAT_ERA, S.LON_ERA)
-    dims_so = (S.TIME_ERA, S.SOIL_HLEV_ERA, S.LAT_ERA, S.LON_ERA)
+    H = s3.era_layout(era_file)                             # (lat, lon), or the dimensions of 2-D lat / lon, or (cell,)
+    dims = s3.layout_dims(H)
+    dims3, dims4, dims_so = dims['d3'], dims['d4'], dims['so']
+    if not s3.is_mesh(H):
+        for key, d in s3._FIELD_DIMS.items():
+            s3._check_dims(vm[key], era_file[vm[key]], dims[d], inp_era_file_path)
 
     def get(name, dims):
-        return np.ascontiguousarray(era_file[name].transpose(*dims).values, dtype=dtype)
+        return s3._as_grid(np.ascontiguousarray(era_file[name].transpose(*dims).values, dtype=dtype), H)
 
     era = dict(PS=get(vm['ps'], dims3), FIS=get(vm['zgs'], dims3), T=get(vm['ta'], dims4), QV=get(vm['hus'], dims4),
                U=get(vm['ua'], dims4), V=get(vm['va'], dims4), T_SKIN=get(vm['ts'], dims3),
@@ -211,7 +214,7 @@ def debug_interpolate_full(inp_era_file_path, out_era_file_path, delta_input_dir
         arr, dims = results[var]
         name = vm[var]
         attrs = era_file[name].attrs if name in era_file else {}
-        _write(full_delta_path(out_era_file_path, var), name, arr.numpy(), dims, era_file, attrs)
+        _write(full_delta_path(out_era_file_path, var), name, s3._as_file(arr.numpy(), H), dims, era_file, attrs)
     if S.i_debug >= 2:
         for it, err in enumerate(info['max_err']):
             print('### iteration {:03d}, phi max error: {}'.format(it + 1, err))

@@ -351,14 +351,40 @@ def write_gcm_files(gcm_dir, nlat=24, nlon=48, plev=None, seed=0, ocean=(30, 44)
     return dict(lat=lat, lon=lon, plev=plev, times=times)
 
 
-def write_case_files(case, era_dir, delta_dir, era_name=None):
+def _horizontal_layout(case, layout):
+    """The horizontal dimensions, the coordinate variables to write ((name, values, dims) in file order) and the shape of the
+    horizontal part of a field for write_case_files' point-wise layouts."""
+    nlat, nlon = case['era']['PS'].shape[-2:]
+    if layout == 'rotated':
+        rlat, rlon, lat2, lon2 = rotated_pole_grid(nlat, nlon)
+        lat2, lon2 = case.get('lat2d', lat2), case.get('lon2d', lon2)
+        H = ('rlat', 'rlon')
+        return H, [('rlat', rlat, ('rlat',)), ('rlon', rlon, ('rlon',)), ('lat', np.asarray(lat2, dtype=np.float64), H),
+                   ('lon', np.asarray(lon2, dtype=np.float64), H)], (nlat, nlon)
+    if layout == 'cells':
+        la, lo = np.meshgrid(np.asarray(case['lat'], dtype=np.float64), np.asarray(case['lon'], dtype=np.float64), indexing='ij')
+        la, lo = case.get('lat2d', la), case.get('lon2d', lo)
+        H = ('cell',)
+        return H, [('lat', np.asarray(la, dtype=np.float64).reshape(-1), H),
+                   ('lon', np.asarray(lo, dtype=np.float64).reshape(-1), H)], (nlat * nlon,)
+    raise ValueError("layout must be 'mesh', 'rotated' or 'cells', got %r" % (layout,))
+
+
+def write_case_files(case, era_dir, delta_dir, era_name=None, layout='mesh'):
     """Write a make_case() result as the NetCDF-3 files the step_03 driver reads: one ERA5 file
     (reference file schema) and the delta directory ({var}_delta.nc,
-    ps_historical.nc).  Returns the ERA5 file path."""
+    ps_historical.nc).  Returns the ERA5 file path.
+    layout: 'mesh' - `lat` / `lon` as 1-D axes of their own; 'rotated' - the case's (nlat, nlon) columns as a rotated-pole
+    regional file, dimensions `rlat`, `rlon` with their 1-D rotated axes and 2-D `lat` / `lon` (rotated_pole_grid, or
+    case['lat2d'] / case['lon2d']); 'cells' - the columns as a list over ONE dimension `cell` with 1-D `lat` / `lon` over it
+    (the mesh of case['lat'] / case['lon'] row by row, or case['lat2d'] / case['lon2d']).  The delta files lie on the same
+    layout."""
     import os
     from . import ncio, settings as S
     os.makedirs(era_dir, exist_ok=True)
     os.makedirs(delta_dir, exist_ok=True)
+    if layout != 'mesh':
+        return _write_case_files_points(case, era_dir, delta_dir, era_name, layout)
     era, lat, lon = case['era'], case['lat'], case['lon']
     nlev = era['T'].shape[1]
     F = ncio.Field
@@ -403,6 +429,65 @@ def write_case_files(case, era_dir, delta_dir, era_name=None):
         vname, fname = (('ps', S.file_name_bases['HIST'].format('ps')) if var == 'ps_hist'
                         else (var, S.file_name_bases['SCEN-HIST'].format(var)))
         dd[vname] = F(arr, dims)
+        ncio.to_netcdf(dd, os.path.join(delta_dir, fname))
+    return path
+
+
+def _write_case_files_points(case, era_dir, delta_dir, era_name, layout):
+    """write_case_files for the layouts 'rotated' and 'cells': the same variables, attributes and order, the horizontal
+    dimensions and coordinate variables of _horizontal_layout."""
+    import os
+    from . import ncio, settings as S
+    era = case['era']
+    nlev = era['T'].shape[1]
+    H, hcoords, hshape = _horizontal_layout(case, layout)
+    F = ncio.Field
+
+    def on(a):
+        a = np.asarray(a)
+        return a.reshape(a.shape[:-2] + hshape)
+
+    ds = ncio.Dataset(attrs=dict(title='synthetic ERA5 file (pgw4era5_amd.synthetic)'))
+    tsec = (np.datetime64(case['target_dt']).astype('datetime64[s]') - np.datetime64('1970-01-01T00:00:00')).astype(np.float64)
+    cv = dict(time=np.array([tsec]), level=np.arange(1, nlev + 1, dtype=np.float64),
+              level1=np.arange(1, nlev + 2, dtype=np.float64), soil1=np.asarray(era['soil1'], dtype=np.float64))
+    for k, v in cv.items():
+        attrs = dict(units='seconds since 1970-01-01 00:00:00') if k == 'time' else {}
+        ds[k] = F(v, (k,), {k: v}, attrs)
+    for k, v, dims in hcoords:
+        if dims == (k,):
+            cv[k] = v
+            ds[k] = F(v, (k,), {k: v}, dict(units='degrees'))
+        else:
+            ds[k] = F(v, dims, {}, dict(units='degrees_north' if k == 'lat' else 'degrees_east'))
+    ds['ak'] = F(era['ak'], ('level1',), {'level1': cv['level1']})
+    ds['bk'] = F(era['bk'], ('level1',), {'level1': cv['level1']})
+    d4, d3, dso = ('time', 'level') + H, ('time',) + H, ('time', 'soil1') + H
+    ds['rotated_pole'] = F(np.array(b'', dtype='S1'), (), attrs=dict(grid_mapping_name='rotated_latitude_longitude',
+                                                                     grid_north_pole_latitude=np.float32(39.25),
+                                                                     grid_north_pole_longitude=np.float32(-162.0)))
+    for name in ('T', 'QV', 'U', 'V'):
+        ds[name] = F(on(era[name]), d4, {d: cv[d] for d in d4 if d in cv}, attrs=dict(grid_mapping='rotated_pole'))
+    for name in ('PS', 'FIS', 'T_SKIN', 'FR_LAND', 'FR_SEA_ICE'):
+        ds[name] = F(on(era[name]), d3, {d: cv[d] for d in d3 if d in cv})
+    ds['T_SO'] = F(on(era['T_SO']), dso, {d: cv[d] for d in dso if d in cv})
+    path = os.path.join(era_dir, era_name or S.era5_file_name_base.format(case['target_dt']))
+    ncio.to_netcdf(ds, path)
+    for var, arr in case['deltas'].items():
+        times = case['delta_times'][var] if isinstance(case['delta_times'], dict) else case['delta_times']
+        tdays = (np.asarray(times).astype('datetime64[s]') - np.datetime64('1850-01-01T00:00:00')).astype('timedelta64[s]').astype(np.float64) / 86400.0
+        dd = ncio.Dataset()
+        dd['time'] = F(tdays, ('time',), attrs=dict(units='days since 1850-01-01 00:00:00', calendar='proleptic_gregorian'))
+        for k, v, dims in hcoords:
+            dd[k] = F(v, dims)
+        if arr.ndim == 4:
+            dd['plev'] = F(np.asarray(case['plev'], dtype=np.float64), ('plev',), attrs=dict(units='Pa'))
+            dims = ('time', 'plev') + H
+        else:
+            dims = ('time',) + H
+        vname, fname = (('ps', S.file_name_bases['HIST'].format('ps')) if var == 'ps_hist'
+                        else (var, S.file_name_bases['SCEN-HIST'].format(var)))
+        dd[vname] = F(on(arr), dims)
         ncio.to_netcdf(dd, os.path.join(delta_dir, fname))
     return path
 
