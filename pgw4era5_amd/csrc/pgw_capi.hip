@@ -2,6 +2,7 @@
 // Built as libpgw_hip.so with hipcc --offload-arch=gfx950 (pgw4era5_amd/csrc/Makefile).
 #include "../../include/pgw_hip.h"
 #include "pgw_kernels.h"
+#include "pgw_loop_control.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -14,6 +15,8 @@
 #include <vector>
 
 using namespace pgw;
+
+static_assert(LOOP_MAX_PASS == MULTI_MAX_PASS, "pgw_loop_control.h plans launches of up to MULTI_MAX_PASS passes");
 
 struct ProfRec { int kid; hipEvent_t e0, e1; };
 
@@ -120,6 +123,13 @@ static const char *status_text(int code) {
     }
 }
 
+// a status code ends the call: the reference's text for it and the column it was found in (-1: none)
+static int fail_status(pgw_ctx *ctx, int code, long long col = -1) {
+    ctx->err = status_text(code);
+    ctx->err_col = col;
+    return code;
+}
+
 // ------------------------------------------------------------------ launch helpers
 struct Prof {
     pgw_ctx *c; int kid; hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -210,8 +220,7 @@ static int status_check(pgw_ctx *ctx, const DevStatus *from = nullptr) {
     if (ctx->h_status->code != 0) {
         int code;
         ordered_status(*ctx->h_status, &code, &ctx->err_col);
-        ctx->err = status_text(code);
-        return code;
+        return fail_status(ctx, code, ctx->err_col);
     }
     return PGW_OK;
 }
@@ -1176,7 +1185,7 @@ static int top_pressure_check(pgw_ctx *ctx, int ignore_top) {
             double mt, ms;
             memcpy(&mt, &h->min_targ_bits, 8);
             memcpy(&ms, &h->min_src_bits, 8);
-            if (mt < ms) { ctx->err = status_text(PGW_ERR_TOP_PRESSURE); ctx->err_col = -1; return PGW_ERR_TOP_PRESSURE; }
+            if (mt < ms) return fail_status(ctx, PGW_ERR_TOP_PRESSURE);
         }
     }
     return PGW_OK;
@@ -1555,18 +1564,10 @@ extern "C" int pgw_phi_ref_hybrid(pgw_ctx *ctx, int dtype, int ntime, long long 
     return status_check(ctx);
 }
 
-// ---- latitude-band sharding (pgw_set_reduce_hook).  One vector per loop launch: [status of the kernels before the
-// loop | per pass: status, any-valid flag, max |err| (-inf when the band has no valid column)].
-static int first_launch_passes(pgw_ctx *ctx, int max_n_iter) {
-    int np = ctx->opt[PGW_OPT_LOOP_GUESS];
-    if (np > MULTI_MAX_PASS) np = MULTI_MAX_PASS;
-    if (np > max_n_iter) np = max_n_iter;
-    return np < 1 ? 1 : np;
-}
-
-static int call_reduce(pgw_ctx *ctx, double *v, int n) {
+// ---- latitude-band sharding (pgw_set_reduce_hook).  One vector per loop launch: BandVector of pgw_loop_control.h.
+static int call_reduce(pgw_ctx *ctx, BandVector &v, int np) {
     ctx->band_reduces += 1;
-    if (ctx->reduce_fn(v, n, ctx->reduce_user) != 0) {
+    if (ctx->reduce_fn(v.v, BandVector::length(np), ctx->reduce_user) != 0) {
         ctx->band_agreed = true;                    // the exchange itself is broken: nobody is met by sending more
         ctx->err = "the reduce hook (pgw_set_reduce_hook) failed";
         ctx->err_col = -1;
@@ -1584,13 +1585,11 @@ static int band_fail(pgw_ctx *ctx, int code, int max_n_iter) {
     const std::string text = ctx->err;
     const long long col = ctx->err_col;
     const bool first = ctx->band_reduces == 0;
-    int np = first ? first_launch_passes(ctx, max_n_iter) : ctx->band_next_np;
-    if (np < 1) np = 1;
-    double v[1 + 3 * MULTI_MAX_PASS];
-    v[0] = first ? (double)code : 0.0;
-    for (int k = 0; k < np; ++k) { v[1 + 3 * k] = 0.0; v[2 + 3 * k] = 0.0; v[3 + 3 * k] = -INFINITY; }
-    if (!first) v[1] = (double)code;
-    call_reduce(ctx, v, 1 + 3 * np);
+    const int np = first ? launch_passes(true, ctx->opt[PGW_OPT_LOOP_GUESS], max_n_iter, max_n_iter) : std::max(ctx->band_next_np, 1);
+    BandVector v;
+    v.blank(np);
+    if (first) v.set_pre(code); else v.set(0, code, false, -INFINITY);
+    call_reduce(ctx, v, np);
     ctx->band_agreed = true;
     ctx->err = text;
     ctx->err_col = col;
@@ -1693,12 +1692,10 @@ struct PsLoopArgs {
     // zg delta records bracketing the instant: at p_ref (ntime, ncol), or with local_nplev > 0 the full (ntime, nplev, ncol)
     const void *dzg_b = nullptr, *dzg_a = nullptr;
     double x_hi = 0.0, x_new = 0.0;
-    double p_ref = 0.0, adj_factor = 0.0, thresh = 0.0;
-    int max_n_iter = 0;
+    double p_ref = 0.0, adj_factor = 0.0;
+    LoopControl ctl{0.0, 0};                                                   // thresh, max_n_iter, where max |err| per pass goes
     void *ps_pgw = nullptr, *hus_pgw = nullptr;                                // outputs (may be null)
     int *n_iter = nullptr;
-    double *max_err_hist = nullptr;
-    int hist_len = 0;
     // local_nplev > 0 selects p_ref_inp = None (step_03:219-253); `plev_file` is then the plev coordinate in file order
     int local_nplev = 0;
     const double *plev_file = nullptr;
@@ -1717,23 +1714,158 @@ struct PsLoopArgs {
     bool qv_from_pass = true;
 };
 
-static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
+// The loop has stopped: the pass count goes to the caller; out of passes is the reference's error (:315-319).
+static int loop_end(pgw_ctx *ctx, const LoopControl &lc, LoopControl::Verdict verdict, int *n_iter) {
+    if (n_iter) *n_iter = lc.n_iter();
+    return verdict == LoopControl::NOT_CONVERGED ? fail_status(ctx, PGW_ERR_NOT_CONVERGED) : PGW_OK;
+}
+
+// Loop control of a whole-file call: its results go to the argument struct, the history NaN where no pass is recorded.
+static LoopControl file_loop_control(pgw_file_args *a) {
+    const int hist_len = (int)(sizeof(a->max_err_hist) / sizeof(a->max_err_hist[0]));
+    a->n_iter = 0;
+    for (int i = 0; i < hist_len; ++i) a->max_err_hist[i] = NAN;
+    return LoopControl{a->thresh, a->max_n_iter, 1, a->max_err_hist, hist_len};
+}
+
+// ---- several passes per launch (k_ps_loop_multi): fixed or local p_ref, wave-level early exit.  phi_ref of the ERA state,
+// g * dzg and the zeroed state are produced by the first launch; LoopControl is applied to the recorded maxima.
+static int ps_loop_multi(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls) {
     const int dtype = a.dtype, ntime = a.ntime;
     const long long ncol = a.ncol, n2 = (long long)ntime * ncol;
-    int rc;
-    if (ctx->opt[PGW_OPT_TEST_FAIL] == 1) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 1: forced workspace failure (ws_get)");
-    LoopState ls;
-    if ((rc = loop_state(ctx, n2, &ls))) return rc;
-    const int full_column = ctx->opt[PGW_OPT_FULL_COLUMN];
     const bool local = a.local_nplev > 0;
-    // several passes per launch: fixed p_ref, wave-level early exit (the full-column option is a per-pass traffic probe)
-    const bool multipass = ctx->opt[PGW_OPT_MULTIPASS] && !full_column;
-    NEED(ctx, !ctx->reduce_fn || multipass, "a reduce hook (latitude-band sharding) needs the multi-pass loop: "
-                                            "PGW_OPT_MULTIPASS = 1, PGW_OPT_FULL_COLUMN = 0");
     const PlevTable ptf = file_order_table(a.local_nplev, a.plev_file);
-    if (multipass) {
-        // phi_ref of the ERA state, g * dzg and the zeroed state are produced by the first k_ps_loop_multi launch
-    } else if (local) {
+    int rc;
+    void *histv = nullptr;
+    if ((rc = ws_get(ctx, 6, (size_t)n2 * MULTI_MAX_PASS * sizeof(double), &histv))) return rc;
+    double *dps_hist = (double *)histv;
+    DevStatus *mst = ctx->d_status + 2;                                // device per-pass blocks
+    DevStatus *hback = ctx->h_status + 1;                              // [0] = block 0 (ERA-state scan / earlier kernels), [1..] passes
+    DevStatus *hzero = blank_blocks(ctx, MULTI_MAX_PASS);
+    // PGW_OPT_QV_FROM_PASS: the last pass of every launch of the FLAGGED = false, fixed-p_ref kernel stores the QV it
+    // forms below p_ref into hus_pgw and marks how far each column got.  When that pass turns out to be the converged one
+    // (the host predicts it: loop_guess), the finalize kernel has only the levels above the marks left; otherwise it
+    // runs over all of them as before and overwrites what was speculated.  hus_pgw must not be an array the loop reads.
+    unsigned short *marks = nullptr;
+    if (ctx->opt[PGW_OPT_QV_FROM_PASS] && a.qv_from_pass && !local && a.hus_pgw && a.hus_pgw != a.QV && a.hus_pgw != a.T && a.hus_pgw != a.ta_pgw &&
+        a.hus_pgw != a.evap) {
+        void *m = nullptr;
+        if ((rc = ws_get(ctx, 4, (size_t)n2 * sizeof(unsigned short), &m))) return rc;
+        marks = (unsigned short *)m;
+    }
+    int stored_k = -1;             // pass index, within the launch just read back, of the pass that stored QV (-1: none)
+    bool marks_valid = false;
+    ctx->last_qv_from_pass = false; ctx->last_qv_skipped = 0;
+    if (!a.status_armed && (rc = status_reset(ctx))) return rc;
+    LoopControl lc = a.ctl;
+    LoopControl::Verdict verdict = LoopControl::CONTINUE;
+    bool first = true;
+    unsigned long long touched = 0;
+    const double *conv = nullptr;  // delta_ps the converged pass used
+    int launched = 0;
+    while (verdict == LoopControl::CONTINUE) {
+        const int np = launch_passes(first, ctx->opt[PGW_OPT_LOOP_GUESS], lc.max_n_iter, lc.allowed());
+        ctx->band_next_np = np;
+        if (first && ctx->opt[PGW_OPT_TEST_FAIL] == 2) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 2: forced failure before the first loop launch");
+        if (!first && ctx->opt[PGW_OPT_TEST_FAIL] == 3) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 3: forced failure before a continuation launch");
+        const bool fused_launch = first && a.fused_first;              // (block of pass 1: armed before the delta kernel)
+        if (!fused_launch) HIPCHK(ctx, hipMemcpyAsync(mst, hzero, sizeof(DevStatus) * np, hipMemcpyHostToDevice, ctx->stream));
+        else if (np > 1) HIPCHK(ctx, hipMemcpyAsync(mst + 1, hzero + 1, sizeof(DevStatus) * (np - 1), hipMemcpyHostToDevice, ctx->stream));
+        {
+            // one column per lane (two columns: 168 VGPRs + scratch; measured 1.36 vs 1.39 ms before the log table)
+            constexpr int MULTI_MAXV = 1;
+            int vec = pick_vec(ctx, dtype, ncol, {a.ta_pgw, a.evap, a.T, a.QV, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, dps_hist,
+                                                   marks ? a.hus_pgw : nullptr /* the storing pass writes V-wide rows */}, MULTI_MAXV);
+            Levels lv = levels_of(ctx);
+            Prof pr(ctx, PGW_K_PS_LOOP_MULTI);
+            const LocalPRef loc{ptf, ctx->h_akN, ctx->h_bkN, ls.pref_f, ls.pref_idx};
+            with_flow_vec(dtype, a.ref, vec, [&](auto t_, auto l_, auto ref_, auto v_) {
+                using T = decltype(t_); using TL = decltype(l_);
+                constexpr int V = decltype(v_)::value;
+                // `n` passes from the state as it stands (init: from the ERA state) into `blocks` and the rows of `hist`
+                constexpr bool qv_pass = QV_FROM_PASS<TL, decltype(ref_)::value>;
+                stored_k = -1;
+                auto launch = [&](auto local_, auto flagged_, double p_ref, int init, int n, DevStatus *blocks, double *hist,
+                                  unsigned char *flags, DevStatus *st_era) {
+                    const bool store = qv_pass && marks && !decltype(local_)::value && !decltype(flagged_)::value;
+                    if (store) stored_k = (int)(blocks - mst) + n - 1;
+                    hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, decltype(ref_)::value, decltype(local_)::value, decltype(flagged_)::value>),
+                                       dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)a.T,
+                                       (const T *)a.QV, (const TL *)a.ta_pgw, (const TL *)a.evap, (const T *)a.PS, (const T *)a.FIS,
+                                       delta_src<T>(a.dzg_b, a.dzg_a, a.x_hi, a.x_new), ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps,
+                                       hist, p_ref, a.adj_factor, init, n, ctx->d_status, blocks, loc, flags, st_era,
+                                       store ? (TL *)a.hus_pgw : nullptr, a.qv_done_levels, marks);
+                };
+                constexpr std::true_type yes{};
+                constexpr std::false_type no{};
+                if (fused_launch) {
+                    launch(no, yes, a.p_ref, 1, 1, mst, dps_hist, ls.era_flags, ctx->d_status + 1);
+                    if (np > 1) launch(no, no, a.p_ref, 0, np - 1, mst + 1, dps_hist + n2, nullptr, nullptr);
+                } else if (!local)
+                    launch(no, no, a.p_ref, first ? 1 : 0, np, mst, dps_hist, nullptr, nullptr);
+                else if constexpr (V == 1)                                 // MULTI_MAXV = 1: always this branch
+                    launch(yes, no, 0.0, first ? 1 : 0, np, mst, dps_hist, nullptr, nullptr);
+            });
+        }
+        HIPCHK(ctx, hipGetLastError());
+        launched += np;
+        HIPCHK(ctx, hipMemcpyAsync(hback, ctx->d_status, sizeof(DevStatus), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(hback + 1, mst, sizeof(DevStatus) * np, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        // figures of this launch; with a reduce hook: their maxima over the bands of the file
+        BandVector red;
+        red.set_pre(first ? hback[0].code : 0);
+        for (int k = 0; k < np; ++k) {
+            const DevStatus &h = hback[1 + k];
+            double e = -INFINITY;
+            if (h.valid) memcpy(&e, &h.max_bits, 8);
+            red.set(k, h.code, h.valid != 0, e);
+        }
+        if (ctx->reduce_fn && (rc = call_reduce(ctx, red, np))) return rc;
+        if (first && red.pre() != 0) {                                 // earlier kernels of the file / the ERA-state scan
+            ctx->band_agreed = true;                                   // every band has this status now
+            if (hback[0].code == 0) return fail_status(ctx, red.pre());        // another band's status
+            *ctx->h_status = hback[0];
+            return fail_status(ctx, hback[0].code, (long long)hback[0].col);
+        }
+        for (int k = 0; k < np && verdict == LoopControl::CONTINUE; ++k) {
+            const DevStatus &h = hback[1 + k];
+            if (red.code(k) != 0) {
+                ctx->band_agreed = true;
+                return h.code != 0 ? fail_status(ctx, h.code, (long long)h.col) : fail_status(ctx, red.code(k));
+            }
+            touched += h.levels_touched;
+            verdict = lc.record(red.err(k));
+            if (verdict == LoopControl::CONVERGED) {
+                conv = dps_hist + (size_t)k * n2;
+                marks_valid = k == stored_k;                           // hus_pgw holds this pass's QV from the marks on
+                if (marks_valid) ctx->last_qv_skipped = h.qv_stored;
+            }
+        }
+        first = false;
+    }
+    // every band leaves the loop here, on figures all of them have: nobody waits in a reduce of this file any more
+    ctx->band_agreed = true;
+    ctx->last_passes_launched = launched;
+    if ((rc = loop_end(ctx, lc, verdict, a.n_iter))) return rc;
+    ctx->opt[PGW_OPT_LOOP_GUESS] = std::min(std::max(lc.n_iter(), 1), MULTI_MAX_PASS);
+    ctx->last_levels_touched = touched;
+    ctx->last_qv_from_pass = marks_valid;
+    if (a.ps_pgw || a.hus_pgw)
+        launch_finalize(ctx, dtype, a.ref, ntime, ncol, a.PS, conv, a.evap, a.ps_pgw, a.hus_pgw, a.qv_done_levels,
+                        marks_valid ? marks : nullptr);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// ---- one pass per launch (PGW_OPT_MULTIPASS = 0, or the full-column option: a per-pass traffic probe)
+static int ps_loop_single(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls) {
+    const int dtype = a.dtype, ntime = a.ntime, full_column = ctx->opt[PGW_OPT_FULL_COLUMN];
+    const long long ncol = a.ncol, n2 = (long long)ntime * ncol;
+    const bool local = a.local_nplev > 0;
+    const PlevTable ptf = file_order_table(a.local_nplev, a.plev_file);
+    int rc;
+    if (local) {
         HIPCHK(ctx, hipMemsetAsync(ls.delta_ps, 0, sizeof(double) * 2 * n2, ctx->stream));    // :182-184
     } else {
         // phi_ref_era: constant over the iterations for a fixed p_ref (step_03:280-287 recomputes it).
@@ -1743,188 +1875,52 @@ static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
         if (!a.status_armed && (rc = status_check(ctx))) return rc;
         launch_dphi_clim(ctx, dtype, a.ref, n2, a.dzg_b, a.dzg_a, a.x_hi, a.x_new, ls);
     }
-
-    if (multipass) {
-        // ---- several passes per launch (k_ps_loop_multi); the reference's control flow is applied to the recorded maxima
-        void *histv = nullptr;
-        if ((rc = ws_get(ctx, 6, (size_t)n2 * MULTI_MAX_PASS * sizeof(double), &histv))) return rc;
-        double *dps_hist = (double *)histv;
-        DevStatus *mst = ctx->d_status + 2;                                // device per-pass blocks
-        DevStatus *hback = ctx->h_status + 1;                              // [0] = block 0 (ERA-state scan / earlier kernels), [1..] passes
-        DevStatus *hzero = blank_blocks(ctx, MULTI_MAX_PASS);
-        // PGW_OPT_QV_FROM_PASS: the last pass of every launch of the FLAGGED = false, fixed-p_ref kernel stores the QV it
-        // forms below p_ref into hus_pgw and marks how far each column got.  When that pass turns out to be the converged one
-        // (the host predicts it: loop_guess), the finalize kernel has only the levels above the marks left; otherwise it
-        // runs over all of them as before and overwrites what was speculated.  hus_pgw must not be an array the loop reads.
-        unsigned short *marks = nullptr;
-        if (ctx->opt[PGW_OPT_QV_FROM_PASS] && a.qv_from_pass && !local && a.hus_pgw && a.hus_pgw != a.QV && a.hus_pgw != a.T && a.hus_pgw != a.ta_pgw &&
-            a.hus_pgw != a.evap) {
-            void *m = nullptr;
-            if ((rc = ws_get(ctx, 4, (size_t)n2 * sizeof(unsigned short), &m))) return rc;
-            marks = (unsigned short *)m;
-        }
-        int stored_k = -1;             // pass index, within the launch just read back, of the pass that stored QV (-1: none)
-        bool marks_valid = false;
-        ctx->last_qv_from_pass = false; ctx->last_qv_skipped = 0;
-        if (!a.status_armed && (rc = status_reset(ctx))) return rc;
-        int it = 1;
-        bool first = true;
-        unsigned long long touched = 0;
-        const double *conv = nullptr;
-        int launched = 0;
-        while (!conv) {
-            const int allowed = a.max_n_iter - (it - 1);                   // passes it .. max_n_iter may still run (:313-319)
-            int np = first ? first_launch_passes(ctx, a.max_n_iter) : 2;  // (a caller-set guess <= 0 counts as 1)
-            if (np > allowed) np = allowed;
-            if (np < 1) np = 1;
-            ctx->band_next_np = np;
-            if (first && ctx->opt[PGW_OPT_TEST_FAIL] == 2) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 2: forced failure before the first loop launch");
-            if (!first && ctx->opt[PGW_OPT_TEST_FAIL] == 3) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 3: forced failure before a continuation launch");
-            const bool fused_launch = first && a.fused_first;              // (block of pass 1: armed before the delta kernel)
-            if (!fused_launch) HIPCHK(ctx, hipMemcpyAsync(mst, hzero, sizeof(DevStatus) * np, hipMemcpyHostToDevice, ctx->stream));
-            else if (np > 1) HIPCHK(ctx, hipMemcpyAsync(mst + 1, hzero + 1, sizeof(DevStatus) * (np - 1), hipMemcpyHostToDevice, ctx->stream));
-            {
-                // one column per lane (two columns: 168 VGPRs + scratch; measured 1.36 vs 1.39 ms before the log table)
-                constexpr int MULTI_MAXV = 1;
-                int vec = pick_vec(ctx, dtype, ncol, {a.ta_pgw, a.evap, a.T, a.QV, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, dps_hist,
-                                                       marks ? a.hus_pgw : nullptr /* the storing pass writes V-wide rows */}, MULTI_MAXV);
-                Levels lv = levels_of(ctx);
-                Prof pr(ctx, PGW_K_PS_LOOP_MULTI);
-                const LocalPRef loc{ptf, ctx->h_akN, ctx->h_bkN, ls.pref_f, ls.pref_idx};
-                with_flow_vec(dtype, a.ref, vec, [&](auto t_, auto l_, auto ref_, auto v_) {
-                    using T = decltype(t_); using TL = decltype(l_);
-                    constexpr int V = decltype(v_)::value;
-                    // `n` passes from the state as it stands (init: from the ERA state) into `blocks` and the rows of `hist`
-                    constexpr bool qv_pass = QV_FROM_PASS<TL, decltype(ref_)::value>;
-                    stored_k = -1;
-                    auto launch = [&](auto local_, auto flagged_, double p_ref, int init, int n, DevStatus *blocks, double *hist,
-                                      unsigned char *flags, DevStatus *st_era) {
-                        const bool store = qv_pass && marks && !decltype(local_)::value && !decltype(flagged_)::value;
-                        if (store) stored_k = (int)(blocks - mst) + n - 1;
-                        hipLaunchKernelGGL((k_ps_loop_multi<T, TL, V, STEP_U, decltype(ref_)::value, decltype(local_)::value, decltype(flagged_)::value>),
-                                           dim3(nblocks(n2 / V, BLOCK)), dim3(BLOCK), 0, ctx->stream, lv, ntime, ncol, (const T *)a.T,
-                                           (const T *)a.QV, (const TL *)a.ta_pgw, (const TL *)a.evap, (const T *)a.PS, (const T *)a.FIS,
-                                           delta_src<T>(a.dzg_b, a.dzg_a, a.x_hi, a.x_new), ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps,
-                                           hist, p_ref, a.adj_factor, init, n, ctx->d_status, blocks, loc, flags, st_era,
-                                           store ? (TL *)a.hus_pgw : nullptr, a.qv_done_levels, marks);
-                    };
-                    constexpr std::true_type yes{};
-                    constexpr std::false_type no{};
-                    if (fused_launch) {
-                        launch(no, yes, a.p_ref, 1, 1, mst, dps_hist, ls.era_flags, ctx->d_status + 1);
-                        if (np > 1) launch(no, no, a.p_ref, 0, np - 1, mst + 1, dps_hist + n2, nullptr, nullptr);
-                    } else if (!local)
-                        launch(no, no, a.p_ref, first ? 1 : 0, np, mst, dps_hist, nullptr, nullptr);
-                    else if constexpr (V == 1)                                 // MULTI_MAXV = 1: always this branch
-                        launch(yes, no, 0.0, first ? 1 : 0, np, mst, dps_hist, nullptr, nullptr);
-                });
-            }
-            HIPCHK(ctx, hipGetLastError());
-            launched += np;
-            HIPCHK(ctx, hipMemcpyAsync(hback, ctx->d_status, sizeof(DevStatus), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(hback + 1, mst, sizeof(DevStatus) * np, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            // figures of this launch; with a reduce hook: their maxima over the bands of the file
-            double red[1 + 3 * MULTI_MAX_PASS];
-            red[0] = first ? (double)hback[0].code : 0.0;
-            for (int k = 0; k < np; ++k) {
-                const DevStatus &h = hback[1 + k];
-                double e = -INFINITY;
-                if (h.valid) memcpy(&e, &h.max_bits, 8);
-                red[1 + 3 * k] = (double)h.code; red[2 + 3 * k] = h.valid ? 1.0 : 0.0; red[3 + 3 * k] = e;
-            }
-            if (ctx->reduce_fn && (rc = call_reduce(ctx, red, 1 + 3 * np))) return rc;
-            if (first && red[0] != 0.0) {                                  // earlier kernels of the file / the ERA-state scan
-                ctx->band_agreed = true;                                   // every band has this status now
-                const bool mine = hback[0].code != 0;                      // (else: another band's status)
-                if (mine) *ctx->h_status = hback[0];
-                const int code = mine ? (int)hback[0].code : (int)red[0];
-                ctx->err_col = mine ? (long long)hback[0].col : -1;
-                ctx->err = status_text(code);
-                return code;
-            }
-            for (int k = 0; k < np && !conv; ++k) {
-                const DevStatus &h = hback[1 + k];
-                if (red[1 + 3 * k] != 0.0) {
-                    ctx->band_agreed = true;
-                    const int code = h.code != 0 ? (int)h.code : (int)red[1 + 3 * k];
-                    ctx->err_col = h.code != 0 ? (long long)h.col : -1;
-                    ctx->err = status_text(code);
-                    return code;
-                }
-                const double err_k = red[2 + 3 * k] != 0.0 ? red[3 + 3 * k] : NAN;   // NaN: xarray .max() of an all-NaN field
-                touched += h.levels_touched;
-                if (a.max_err_hist && it - 1 < a.hist_len) a.max_err_hist[it - 1] = err_k;
-                it += 1;                                                   // :313
-                if (it > a.max_n_iter) {                                   // :315-319
-                    ctx->band_agreed = true;                               // decided from reduced figures: all bands stop here
-                    if (a.n_iter) *a.n_iter = it - 1;
-                    ctx->last_passes_launched = launched;
-                    ctx->err = status_text(PGW_ERR_NOT_CONVERGED);
-                    ctx->err_col = -1;
-                    return PGW_ERR_NOT_CONVERGED;
-                }
-                if (!(err_k > a.thresh)) {                                 // :189  (NaN stops the loop too)
-                    conv = dps_hist + (size_t)k * n2;
-                    marks_valid = k == stored_k;                           // hus_pgw holds this pass's QV from the marks on
-                    if (marks_valid) ctx->last_qv_skipped = h.qv_stored;
-                }
-            }
-            first = false;
-        }
-        ctx->band_agreed = true;       // every band leaves the loop here: nobody waits in a reduce of this file any more
-        ctx->opt[PGW_OPT_LOOP_GUESS] = (it - 1) < 1 ? 1 : ((it - 1) > MULTI_MAX_PASS ? MULTI_MAX_PASS : (it - 1));
-        ctx->last_levels_touched = touched;
-        ctx->last_passes_launched = launched;
-        if (a.n_iter) *a.n_iter = it - 1;
-        ctx->last_qv_from_pass = marks_valid;
-        if (a.ps_pgw || a.hus_pgw)
-            launch_finalize(ctx, dtype, a.ref, ntime, ncol, a.PS, conv, a.evap, a.ps_pgw, a.hus_pgw, a.qv_done_levels,
-                            marks_valid ? marks : nullptr);
-        HIPCHK(ctx, hipGetLastError());
-        return PGW_OK;
-    }
     ctx->last_qv_from_pass = false; ctx->last_qv_skipped = 0;
 
-    double phi_ref_max_error = INFINITY;                                   // :186
-    int it = 1;                                                            // :188
+    LoopControl lc = a.ctl;
+    // :186, 189: the reference enters the loop on inf > thresh (no pass at all for a threshold of inf or NaN)
+    LoopControl::Verdict verdict = INFINITY > lc.thresh ? LoopControl::CONTINUE : LoopControl::CONVERGED;
     unsigned long long touched = 0;
     // Fixed p_ref: the passes alternate between the two status blocks and each pass clears the other one for its
     // successor, so no reset copy is enqueued per pass (the read-back of the block being cleared was enqueued
     // before this pass was launched).
     DevStatus *blk[2] = {ctx->d_status, ctx->d_status + 1};
-    while (phi_ref_max_error > a.thresh) {                                 // :189
-        const bool reset_here = local || it == 1;
-        if (reset_here && !(a.status_armed && it == 1) && (rc = status_reset(ctx))) return rc;
-        DevStatus *cur = local ? ctx->d_status : blk[(it - 1) & 1];
+    while (verdict == LoopControl::CONTINUE) {
+        const int done = lc.n_iter();                                      // passes before this one
+        const bool reset_here = local || done == 0;
+        if (reset_here && !(a.status_armed && done == 0) && (rc = status_reset(ctx))) return rc;
+        DevStatus *cur = local ? ctx->d_status : blk[done & 1];
         if (local) {
-            launch_local_p_ref(ctx, dtype, a.ref, ptf, n2, ncol, a.PS, a.dzg_b, a.dzg_a, a.x_hi, a.x_new, it == 1 ? 1 : 0, ls);
+            launch_local_p_ref(ctx, dtype, a.ref, ptf, n2, ncol, a.PS, a.dzg_b, a.dzg_a, a.x_hi, a.x_new, done == 0 ? 1 : 0, ls);
             launch_phi_ref_hybrid(ctx, dtype, ntime, ncol, a.T, a.QV, a.PS, a.FIS, 0.0, ls.phi_era, full_column, ls.pref_f, a.ref);   // :280-287
             launch_step(ctx, dtype, ntime, ncol, a.ta_pgw, a.evap, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, 0.0,
                         ls.pref_f, a.adj_factor, full_column, 0, nullptr, nullptr, a.ref);
         } else {
             launch_step(ctx, dtype, ntime, ncol, a.ta_pgw, a.evap, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, a.p_ref,
-                        nullptr, a.adj_factor, full_column, 1, cur, blk[it & 1], a.ref);
+                        nullptr, a.adj_factor, full_column, 1, cur, blk[(done + 1) & 1], a.ref);
         }
         HIPCHK(ctx, hipGetLastError());
         if ((rc = status_check(ctx, cur))) return rc;
-        phi_ref_max_error = max_err_of(ctx);                               // :308
         touched += ctx->h_status->levels_touched;
-        if (a.max_err_hist && it - 1 < a.hist_len) a.max_err_hist[it - 1] = phi_ref_max_error;
-        it += 1;                                                           // :313
-        if (it > a.max_n_iter) {                                           // :315-319
-            if (a.n_iter) *a.n_iter = it - 1;
-            ctx->err = status_text(PGW_ERR_NOT_CONVERGED);
-            ctx->err_col = -1;
-            return PGW_ERR_NOT_CONVERGED;
-        }
+        verdict = lc.record(max_err_of(ctx));                              // :308-319
     }
+    if ((rc = loop_end(ctx, lc, verdict, a.n_iter))) return rc;
     ctx->last_levels_touched = touched;
-    if (a.n_iter) *a.n_iter = it - 1;
     if (a.ps_pgw || a.hus_pgw)
         launch_finalize(ctx, dtype, a.ref, ntime, ncol, a.PS, ls.delta_ps, a.evap, a.ps_pgw, a.hus_pgw, a.qv_done_levels);
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
+}
+
+static int run_ps_loop(pgw_ctx *ctx, const PsLoopArgs &a) {
+    if (ctx->opt[PGW_OPT_TEST_FAIL] == 1) return fail(ctx, PGW_ERR_HIP, "PGW_OPT_TEST_FAIL = 1: forced workspace failure (ws_get)");
+    LoopState ls;
+    int rc;
+    if ((rc = loop_state(ctx, (long long)a.ntime * a.ncol, &ls))) return rc;
+    const bool multipass = ctx->opt[PGW_OPT_MULTIPASS] && !ctx->opt[PGW_OPT_FULL_COLUMN];
+    NEED(ctx, !ctx->reduce_fn || multipass, "a reduce hook (latitude-band sharding) needs the multi-pass loop: "
+                                            "PGW_OPT_MULTIPASS = 1, PGW_OPT_FULL_COLUMN = 0");
+    return multipass ? ps_loop_multi(ctx, a, ls) : ps_loop_single(ctx, a, ls);
 }
 
 extern "C" int pgw_adjust_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long ncol, const void *PS,
@@ -1945,9 +1941,9 @@ extern "C" int pgw_adjust_ps_loop(pgw_ctx *ctx, int dtype, int ntime, long long 
     la.PS = PS; la.FIS = FIS; la.T = T; la.QV = QV;
     la.ta_pgw = ta_pgw; la.evap = evap;
     la.dzg_b = dzg_pref;                                  // the delta at the instant: no bracket
-    la.p_ref = p_ref; la.adj_factor = adj_factor; la.thresh = thresh; la.max_n_iter = max_n_iter;
+    la.p_ref = p_ref; la.adj_factor = adj_factor;
     la.ps_pgw = ps_pgw; la.hus_pgw = hus_pgw;
-    la.n_iter = n_iter; la.max_err_hist = max_err_hist; la.hist_len = max_n_iter;
+    la.n_iter = n_iter; la.ctl = LoopControl{thresh, max_n_iter, 1, max_err_hist, max_n_iter};
     return run_ps_loop(ctx, la);
 }
 
@@ -2026,13 +2022,12 @@ static int run_reinterp_file(pgw_ctx *ctx, pgw_file_args *a, int check_top) {
         else launch(float(), float(), double(), std::true_type());
     };
 
-    double err = INFINITY;                                                  // :186
-    int it = 1;                                                             // :188
-    a->n_iter = 0;
-    for (int i = 0; i < 32; ++i) a->max_err_hist[i] = NAN;
-    while (err > a->thresh) {                                               // :189
+    LoopControl lc = file_loop_control(a);
+    // :186, 189: the reference enters the loop on inf > thresh (no pass at all for a threshold of inf or NaN)
+    LoopControl::Verdict verdict = INFINITY > lc.thresh ? LoopControl::CONTINUE : LoopControl::CONVERGED;
+    while (verdict == LoopControl::CONTINUE) {
         if ((rc = status_reset(ctx))) return rc;
-        if (local) launch_local_p_ref(ctx, dtype, ref, ptf, n2, ncol, a->PS, a->zg3_b, a->zg3_a, zx_hi, zx_new, it == 1 ? 1 : 0, ls);
+        if (local) launch_local_p_ref(ctx, dtype, ref, ptf, n2, ncol, a->PS, a->zg3_b, a->zg3_a, zx_hi, zx_new, lc.n_iter() == 0 ? 1 : 0, ls);
         // ps_pgw of this pass; fixed p_ref: after delta_ps += adj_ps   :192-193
         with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
             using T = decltype(t_);
@@ -2048,18 +2043,10 @@ static int run_reinterp_file(pgw_ctx *ctx, pgw_file_args *a, int check_top) {
         HIPCHK(ctx, hipGetLastError());
         if ((rc = status_check(ctx))) return rc;
         if ((rc = top_pressure_check(ctx, !check_top))) return rc;
-        err = max_err_of(ctx);                                              // :308
-        if (it - 1 < 32) a->max_err_hist[it - 1] = err;
-        it += 1;                                                            // :313
-        if (it > a->max_n_iter) {                                           // :315-319
-            a->n_iter = it - 1;
-            ctx->err = status_text(PGW_ERR_NOT_CONVERGED);
-            ctx->err_col = -1;
-            return PGW_ERR_NOT_CONVERGED;
-        }
+        verdict = lc.record(max_err_of(ctx));                               // :308-319
     }
-    a->n_iter = it - 1;
-    a->passes_launched = it - 1;
+    if ((rc = loop_end(ctx, lc, verdict, &a->n_iter))) return rc;
+    a->passes_launched = lc.n_iter();
     a->levels_touched = 0;
     if ((rc = status_reset(ctx))) return rc;
     reinterp(false);                                                        // ua, va on the final levels   :330-343
@@ -2353,18 +2340,16 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     }
 
     // ---- fixed-point loop + final PS, QV
-    a->n_iter = 0;
-    for (int i = 0; i < 32; ++i) a->max_err_hist[i] = NAN;
-    if (a->local_p_ref) NEED(ctx, a->zg3_b != nullptr, "local_p_ref needs the full zg records (zg3_b / zg3_a)");
     PsLoopArgs la;
+    la.n_iter = &a->n_iter; la.ctl = file_loop_control(a);
+    if (a->local_p_ref) NEED(ctx, a->zg3_b != nullptr, "local_p_ref needs the full zg records (zg3_b / zg3_a)");
     la.dtype = dtype; la.ntime = ntime; la.ncol = ncol;
     la.PS = a->PS; la.FIS = a->FIS; la.T = a->T; la.QV = a->QV;
     la.ta_pgw = a->T_out; la.evap = evap;
     la.dzg_b = a->local_p_ref ? a->zg3_b : a->zg_b; la.dzg_a = a->local_p_ref ? a->zg3_a : a->zg_a;
     la.x_hi = zx_hi; la.x_new = zx_new;
-    la.p_ref = a->p_ref; la.adj_factor = a->adj_factor; la.thresh = a->thresh; la.max_n_iter = a->max_n_iter;
+    la.p_ref = a->p_ref; la.adj_factor = a->adj_factor;
     la.ps_pgw = a->PS_out; la.hus_pgw = a->QV_out;
-    la.n_iter = &a->n_iter; la.max_err_hist = a->max_err_hist; la.hist_len = 32;
     if (a->local_p_ref) { la.local_nplev = zax.n; la.plev_file = zax.plev; }
     la.status_armed = !check_top && !a->local_p_ref;
     la.qv_done_levels = qv_done; la.ref = ref; la.fused_first = fused_first;

@@ -1462,7 +1462,14 @@ def test_kernel_variants_are_bit_identical(opts, dtype):
             # a first launch of 1, 2, 5 or 8 passes (the file needs 6): continuation launches / speculated passes;
             # afterwards the guess is the file's own pass count
             assert ctx.get_option('loop_guess') == b['n_iter']
-            assert b['passes_launched'] >= b['n_iter'] and (opts['loop_guess'] != 8 or b['passes_launched'] == 8)
+            # the launch plan: the guess, clamped to [1, min(8, max_n_iter)], then 2 passes per launch; never more than
+            # max_n_iter still allows, never fewer than 1
+            import pgw4era5_amd.settings as S
+            plan = []
+            while sum(plan) < b['n_iter']:
+                want = 2 if plan else max(min(opts['loop_guess'], 8, S.max_n_iter), 1)
+                plan.append(max(min(want, S.max_n_iter - sum(plan)), 1))
+            assert b['passes_launched'] == sum(plan) and (opts['loop_guess'] != 8 or b['passes_launched'] == 8)
     finally:
         for k, v in old.items():
             if k != 'loop_guess':
