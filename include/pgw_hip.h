@@ -105,7 +105,16 @@ enum pgw_option {
                                  pure-pressure levels already does.  Takes effect with PGW_OPT_MULTIPASS = 1,
                                  PGW_OPT_FULL_COLUMN = 0, a fixed p_ref, i_reinterp = 0, in pgw_step03_file with PGW_OPT_QUAD = 1, and
                                  for float64 level arrays (float64 files, float32 files in reference-dtype mode)  [PGW_QV_FROM_PASS] */
-    PGW_OPT_COUNT = 11
+    PGW_OPT_FINISH_IN_PASS = 11, /* 1 (default): the end of a file on the production path.  The storing pass of PGW_OPT_QV_FROM_PASS
+                                 goes on from where its scan stopped to the first hybrid level and writes ps_pgw, so a file whose
+                                 predicted pass converges launches no finalize kernel (pgw_last_qv_from_pass: 1, every hybrid
+                                 level-column skipped); any other stop runs the finalize kernel over all levels as before (float64
+                                 files only: float32 files in reference-dtype mode keep the finalize kernel with its marks).  And
+                                 pgw_step03_file (PGW_OPT_QUAD = 1, fixed p_ref, i_reinterp = 0, multi-pass loop) enqueues the
+                                 surface riders behind the first loop launch's status read-back, where the stream would wait for
+                                 the host, instead of first.  0: riders first, finalize kernel with marks.  Same bits either way
+                                 under PGW_OPT_QV_FROM_PASS's conditions                                  [PGW_FINISH_IN_PASS] */
+    PGW_OPT_COUNT = 12
 };
 
 /* ---------------------------------------------------------------- context ------------ */
@@ -341,7 +350,8 @@ unsigned long long pgw_last_levels_touched(pgw_ctx *ctx);
 /* PGW_OPT_QV_FROM_PASS: 1 when the finalize kernel of the last pgw_adjust_ps_loop / pgw_step03_file took the QV below p_ref from
  * the converged pass (that pass was the last one of its launch), else 0.  *skipped (may be NULL): the level-columns of hus_pgw
  * the finalize kernel then left alone, summed over columns - it read e and wrote QV on the other
- * (nlev - qv_done_levels) * ntime * ncol - *skipped. */
+ * (nlev - qv_done_levels) * ntime * ncol - *skipped.  With PGW_OPT_FINISH_IN_PASS that pass has written them all and ps_pgw: no
+ * finalize kernel ran, and *skipped is (nlev - qv_done_levels) * ntime * ncol. */
 int pgw_last_qv_from_pass(pgw_ctx *ctx, unsigned long long *skipped);
 
 /* ---------------------------------------------------------------- whole file ---------- */

@@ -28,7 +28,8 @@ KERNEL_IDS = dict(pressure=0, q_to_rh=1, rh_to_q=2, integ_geopot=3, interp_logp=
                   cell_locate=26, regrid_sparse=27)
 
 # enum pgw_option (include/pgw_hip.h)
-OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7, mixed_vec=8, sparse_direct=9, qv_from_pass=10)
+OPTIONS = dict(quad=0, full_column=1, force_vec1=2, multipass=3, loop_guess=4, force_off64=5, test_fail=6, fused_first=7, mixed_vec=8, sparse_direct=9, qv_from_pass=10,
+               finish_in_pass=11)
 
 # PGW_MAX_PLEV / PGW_MAX_PLEV_ZG (include/pgw_hip.h): levels of the plev axis of a delta, and of zg's own axis when the
 # reference level is chosen per column (p_ref_inp = None)

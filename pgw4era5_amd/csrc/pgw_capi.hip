@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -62,6 +63,7 @@ struct pgw_ctx {
     long long prof_count[PGW_K_COUNT];
     double prof_ms[PGW_K_COUNT];
     hipEvent_t t0 = nullptr, t1 = nullptr;
+    hipEvent_t status_read = nullptr;  // behind the status read-back of a multi-pass loop launch (no timing)
     unsigned long long last_levels_touched = 0;
     // PGW_OPT_QV_FROM_PASS: did the last file's finalize kernel use the marks of the converged pass, and how many
     // level-columns of QV did that leave it to skip
@@ -295,13 +297,15 @@ extern "C" int pgw_ctx_create(int device, pgw_ctx **out) {
     c->opt[PGW_OPT_TEST_FAIL] = 0;
     c->opt[PGW_OPT_FUSED_FIRST] = env_flag("PGW_FUSED_FIRST", 1);
     c->opt[PGW_OPT_QV_FROM_PASS] = env_flag("PGW_QV_FROM_PASS", 1);
+    c->opt[PGW_OPT_FINISH_IN_PASS] = env_flag("PGW_FINISH_IN_PASS", 1);
     c->opt[PGW_OPT_MIXED_VEC] = 4;
     c->opt[PGW_OPT_SPARSE_DIRECT] = 0;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc(&c->d_status, (2 + MULTI_MAX_PASS + FUSED_BLOCKS) * sizeof(DevStatus)) != hipSuccess ||
         hipHostMalloc(&c->h_status, (2 + 2 * MULTI_MAX_PASS + FUSED_BLOCKS) * sizeof(DevStatus)) != hipSuccess ||
         hipMalloc(&c->d_small, SMALL_BYTES) != hipSuccess ||
-        hipEventCreate(&c->t0) != hipSuccess || hipEventCreate(&c->t1) != hipSuccess) {
+        hipEventCreate(&c->t0) != hipSuccess || hipEventCreate(&c->t1) != hipSuccess ||
+        hipEventCreateWithFlags(&c->status_read, hipEventDisableTiming) != hipSuccess) {
         pgw_ctx_destroy(c);            // releases whatever was created before the failure
         return PGW_ERR_HIP;
     }
@@ -322,6 +326,7 @@ extern "C" int pgw_ctx_destroy(pgw_ctx *ctx) {
     if (ctx->h_status) hipHostFree(ctx->h_status);
     if (ctx->t0) hipEventDestroy(ctx->t0);
     if (ctx->t1) hipEventDestroy(ctx->t1);
+    if (ctx->status_read) hipEventDestroy(ctx->status_read);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
     return PGW_OK;
@@ -1712,6 +1717,10 @@ struct PsLoopArgs {
     // PGW_OPT_QV_FROM_PASS may apply.  pgw_step03_file with PGW_OPT_QUAD = 0 says no: the pair kernels are kept as an independent
     // cross-check of the production path, and so is the QV their files get - all of it from the finalize kernel's division
     bool qv_from_pass = true;
+    // PGW_OPT_FINISH_IN_PASS, pgw_step03_file: the launch of the surface riders, which depend on nothing else in the file.
+    // The multi-pass loop enqueues it behind its first launch's status read-back, where the stream would otherwise stand
+    // idle until the host has decided; empty: the caller has launched them
+    std::function<int()> riders;
 };
 
 // The loop has stopped: the pass count goes to the caller; out of passes is the reference's error (:315-319).
@@ -1753,8 +1762,9 @@ static int ps_loop_multi(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls)
         if ((rc = ws_get(ctx, 4, (size_t)n2 * sizeof(unsigned short), &m))) return rc;
         marks = (unsigned short *)m;
     }
-    int stored_k = -1;             // pass index, within the launch just read back, of the pass that stored QV (-1: none)
-    bool marks_valid = false;
+    // PGW_OPT_FINISH_IN_PASS: the storing pass also walks its columns' remaining hybrid levels and writes ps_pgw
+    const bool finish = marks && ctx->opt[PGW_OPT_FINISH_IN_PASS] && a.ps_pgw && a.ps_pgw != a.PS;
+    StoredPass sp;                 // the pass that stored QV in the launch just read back, and what the stopping rule made of it
     ctx->last_qv_from_pass = false; ctx->last_qv_skipped = 0;
     if (!a.status_armed && (rc = status_reset(ctx))) return rc;
     LoopControl lc = a.ctl;
@@ -1775,7 +1785,8 @@ static int ps_loop_multi(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls)
             // one column per lane (two columns: 168 VGPRs + scratch; measured 1.36 vs 1.39 ms before the log table)
             constexpr int MULTI_MAXV = 1;
             int vec = pick_vec(ctx, dtype, ncol, {a.ta_pgw, a.evap, a.T, a.QV, a.PS, a.FIS, ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps, dps_hist,
-                                                   marks ? a.hus_pgw : nullptr /* the storing pass writes V-wide rows */}, MULTI_MAXV);
+                                                   marks ? a.hus_pgw : nullptr /* the storing pass writes V-wide rows */,
+                                                   finish ? a.ps_pgw : nullptr}, MULTI_MAXV);
             Levels lv = levels_of(ctx);
             Prof pr(ctx, PGW_K_PS_LOOP_MULTI);
             const LocalPRef loc{ptf, ctx->h_akN, ctx->h_bkN, ls.pref_f, ls.pref_idx};
@@ -1784,7 +1795,8 @@ static int ps_loop_multi(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls)
                 constexpr int V = decltype(v_)::value;
                 // `n` passes from the state as it stands (init: from the ERA state) into `blocks` and the rows of `hist`
                 constexpr bool qv_pass = QV_FROM_PASS<TL, decltype(ref_)::value>;
-                stored_k = -1;
+                const bool finish_pass = finish && FINISH_IN_PASS<TL, decltype(ref_)::value>;
+                int stored_k = -1;
                 auto launch = [&](auto local_, auto flagged_, double p_ref, int init, int n, DevStatus *blocks, double *hist,
                                   unsigned char *flags, DevStatus *st_era) {
                     const bool store = qv_pass && marks && !decltype(local_)::value && !decltype(flagged_)::value;
@@ -1794,7 +1806,8 @@ static int ps_loop_multi(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls)
                                        (const T *)a.QV, (const TL *)a.ta_pgw, (const TL *)a.evap, (const T *)a.PS, (const T *)a.FIS,
                                        delta_src<T>(a.dzg_b, a.dzg_a, a.x_hi, a.x_new), ls.phi_era, ls.dphi, ls.delta_ps, ls.adj_ps,
                                        hist, p_ref, a.adj_factor, init, n, ctx->d_status, blocks, loc, flags, st_era,
-                                       store ? (TL *)a.hus_pgw : nullptr, a.qv_done_levels, marks);
+                                       store ? (TL *)a.hus_pgw : nullptr, a.qv_done_levels, marks,
+                                       store && finish_pass ? (T *)a.ps_pgw : nullptr);
                 };
                 constexpr std::true_type yes{};
                 constexpr std::false_type no{};
@@ -1805,13 +1818,21 @@ static int ps_loop_multi(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls)
                     launch(no, no, a.p_ref, first ? 1 : 0, np, mst, dps_hist, nullptr, nullptr);
                 else if constexpr (V == 1)                                 // MULTI_MAXV = 1: always this branch
                     launch(yes, no, 0.0, first ? 1 : 0, np, mst, dps_hist, nullptr, nullptr);
+                sp.launched(stored_k, finish_pass);
             });
         }
         HIPCHK(ctx, hipGetLastError());
         launched += np;
         HIPCHK(ctx, hipMemcpyAsync(hback, ctx->d_status, sizeof(DevStatus), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(hback + 1, mst, sizeof(DevStatus) * np, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (first && a.riders) {
+            // the host waits for the copies only; the riders run while it reads the figures, and whatever it enqueues next -
+            // a continuation launch, the finalize kernel, the next file - queues behind them
+            HIPCHK(ctx, hipEventRecord(ctx->status_read, ctx->stream));
+            if ((rc = a.riders())) return rc;
+            HIPCHK(ctx, hipEventSynchronize(ctx->status_read));
+        } else
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         // figures of this launch; with a reduce hook: their maxima over the bands of the file
         BandVector red;
         red.set_pre(first ? hback[0].code : 0);
@@ -1838,8 +1859,9 @@ static int ps_loop_multi(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls)
             verdict = lc.record(red.err(k));
             if (verdict == LoopControl::CONVERGED) {
                 conv = dps_hist + (size_t)k * n2;
-                marks_valid = k == stored_k;                           // hus_pgw holds this pass's QV from the marks on
-                if (marks_valid) ctx->last_qv_skipped = h.qv_stored;
+                sp.decided(verdict, k, red.err(k));
+                // hus_pgw holds this pass's QV from the marks on
+                if (sp.final_step() != StoredPass::ALL_LEVELS) ctx->last_qv_skipped = h.qv_stored;
             }
         }
         first = false;
@@ -1850,10 +1872,11 @@ static int ps_loop_multi(pgw_ctx *ctx, const PsLoopArgs &a, const LoopState &ls)
     if ((rc = loop_end(ctx, lc, verdict, a.n_iter))) return rc;
     ctx->opt[PGW_OPT_LOOP_GUESS] = std::min(std::max(lc.n_iter(), 1), MULTI_MAX_PASS);
     ctx->last_levels_touched = touched;
-    ctx->last_qv_from_pass = marks_valid;
-    if (a.ps_pgw || a.hus_pgw)
+    const StoredPass::Final fin = sp.final_step();
+    ctx->last_qv_from_pass = fin != StoredPass::ALL_LEVELS;
+    if ((a.ps_pgw || a.hus_pgw) && fin != StoredPass::NOTHING)
         launch_finalize(ctx, dtype, a.ref, ntime, ncol, a.PS, conv, a.evap, a.ps_pgw, a.hus_pgw, a.qv_done_levels,
-                        marks_valid ? marks : nullptr);
+                        fin == StoredPass::ABOVE_MARKS ? marks : nullptr);
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
 }
@@ -2213,25 +2236,37 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     // each delta file has its own time axis in the reference (load_delta per variable): own bracket, own abscissae
     const double zx_hi = a->per_var_time ? a->zg_x_hi : a->x_hi, zx_new = a->per_var_time ? a->zg_x_new : a->x_new;
 
-    // ---- surface riders (step_03:103-146)
+    // ---- surface riders (step_03:103-146): independent of everything else in the file.  On the production path
+    // (PGW_OPT_FINISH_IN_PASS) the multi-pass loop enqueues them behind its first launch's status read-back; otherwise here
+    std::function<int()> riders;
     if (a->FR_SEA_ICE && a->siconc_b && a->FR_SEA_ICE_out) {
         NEED(ctx, a->ts_b && a->tos_b && a->FR_LAND && a->T_SKIN && a->T_SKIN_out, "surface rider pointer is NULL");
         SoilTable st;
         if ((rc = soil_table(ctx, __func__, a->nsoil, a->soil_depth, &st))) return rc;
         NEED(ctx, a->nsoil == 0 || (a->T_SO && a->T_SO_out && a->ts_clim && a->soil_depth), "soil pointers missing");
-        long long n = (long long)ntime * ncol;
-        Prof pr(ctx, PGW_K_SURFACE);
-        with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
-            using T = decltype(t_);
-            const bool own = a->per_var_time != 0;
-            const DeltaSrc<T> dsic = delta_src<T>(a->siconc_b, a->siconc_a, own ? a->siconc_x_hi : a->x_hi, own ? a->siconc_x_new : a->x_new);
-            const DeltaSrc<T> dts = delta_src<T>(a->ts_b, a->ts_a, own ? a->ts_x_hi : a->x_hi, own ? a->ts_x_new : a->x_new);
-            const DeltaSrc<T> dtos = delta_src<T>(a->tos_b, a->tos_a, own ? a->tos_x_hi : a->x_hi, own ? a->tos_x_new : a->x_new);
-            const RiderSrc<T> r{(const T *)a->FR_SEA_ICE, dsic, dtos, dts, (const T *)a->FR_LAND};
-            hipLaunchKernelGGL((k_surface_update_lerp<T, decltype(ref_)::value>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream,
-                               ntime, ncol, st, r, (const T *)a->ts_clim, (const T *)a->T_SKIN, (const T *)a->T_SO,
-                               (T *)a->FR_SEA_ICE_out, (T *)nullptr /* comb_out */, (T *)a->T_SKIN_out, (T *)a->T_SO_out);
-        });
+        riders = [ctx, a, st, dtype, ref, ntime, ncol]() {
+            long long n = (long long)ntime * ncol;
+            Prof pr(ctx, PGW_K_SURFACE);
+            with_flow(dtype, ref, [&](auto t_, auto, auto ref_) {
+                using T = decltype(t_);
+                const bool own = a->per_var_time != 0;
+                const DeltaSrc<T> dsic = delta_src<T>(a->siconc_b, a->siconc_a, own ? a->siconc_x_hi : a->x_hi, own ? a->siconc_x_new : a->x_new);
+                const DeltaSrc<T> dts = delta_src<T>(a->ts_b, a->ts_a, own ? a->ts_x_hi : a->x_hi, own ? a->ts_x_new : a->x_new);
+                const DeltaSrc<T> dtos = delta_src<T>(a->tos_b, a->tos_a, own ? a->tos_x_hi : a->x_hi, own ? a->tos_x_new : a->x_new);
+                const RiderSrc<T> r{(const T *)a->FR_SEA_ICE, dsic, dtos, dts, (const T *)a->FR_LAND};
+                hipLaunchKernelGGL((k_surface_update_lerp<T, decltype(ref_)::value>), dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream,
+                                   ntime, ncol, st, r, (const T *)a->ts_clim, (const T *)a->T_SKIN, (const T *)a->T_SO,
+                                   (T *)a->FR_SEA_ICE_out, (T *)nullptr /* comb_out */, (T *)a->T_SKIN_out, (T *)a->T_SO_out);
+            });
+            HIPCHK(ctx, hipGetLastError());
+            return (int)PGW_OK;
+        };
+        const bool behind_loop = ctx->opt[PGW_OPT_FINISH_IN_PASS] && ctx->opt[PGW_OPT_QUAD] && ctx->opt[PGW_OPT_MULTIPASS] &&
+                                 !ctx->opt[PGW_OPT_FULL_COLUMN] && !a->local_p_ref && !a->i_reinterp;
+        if (!behind_loop) {
+            if ((rc = riders())) return rc;
+            riders = nullptr;
+        }
     }
 
     if (a->i_reinterp) {                                  // settings.i_reinterp = 1: the loop re-interpolates in every pass
@@ -2354,6 +2389,7 @@ static int step03_file(pgw_ctx *ctx, pgw_file_args *a) {
     la.status_armed = !check_top && !a->local_p_ref;
     la.qv_done_levels = qv_done; la.ref = ref; la.fused_first = fused_first;
     la.qv_from_pass = ctx->opt[PGW_OPT_QUAD] != 0;
+    la.riders = riders;
     rc = run_ps_loop(ctx, la);
     a->levels_touched = ctx->last_levels_touched;
     a->passes_launched = ctx->last_passes_launched;

@@ -3088,6 +3088,10 @@ constexpr int MULTI_MAX_PASS = 8;
 // float32 fast mode is excluded: its loop kernel lost more (1.18 -> 1.30 ms) than its finalize kernel, which moves half the
 // bytes, gained (0.13 -> 0.06 ms).
 template <typename TL, bool REF> constexpr bool QV_FROM_PASS = sizeof(TL) == 8;
+// ... and whose storing pass goes on to the first hybrid level and writes ps_pgw (PGW_OPT_FINISH_IN_PASS).  float32 files in
+// reference-dtype mode are excluded: their loop launch grew by 0.09 ms (1.33 -> 1.42 ms) for a finalize kernel of 0.12 ms, and
+// the per-file figures of the two builds overlapped; they compile the parent's kernel.
+template <typename TL, bool REF> constexpr bool FINISH_IN_PASS = QV_FROM_PASS<TL, REF> && !REF;
 #ifndef MULTI_MINW
 #define MULTI_MINW 4      // 128 VGPRs (12 bytes of scratch per lane): 1.28 -> 1.21 ms against 3 waves / 136 VGPRs; 5 waves spill 132 bytes and lose
 #endif
@@ -3103,7 +3107,7 @@ template <typename TL, bool REF> constexpr bool QV_FROM_PASS = sizeof(TL) == 8;
 struct LocalPRef { PlevTable pt; double akN, bkN; double *p_ref_col; int *p_idx_col; };
 static_assert(kernarg_bytes<LocalPRef, Levels, int, long long, void *, void *, void *, void *, void *, void *, DeltaSrc<double>, void *,
                             void *, void *, void *, void *, double, double, int, int, void *, void *, void *, void *, void *, int,
-                            void *>() <= KERNARG_LIMIT, "k_ps_loop_multi: kernel arguments");
+                            void *, void *>() <= KERNARG_LIMIT, "k_ps_loop_multi: kernel arguments");
 
 template <typename T, typename TL, int V, int U, bool REF, bool LOCAL, bool FLAGGED = false>
 __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, int ntime, long long ncol,
@@ -3120,7 +3124,8 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
                                                          const unsigned char *__restrict__ flags = nullptr,
                                                          const DevStatus *st_era = nullptr,
                                                          TL *__restrict__ hus_out = nullptr, int l_start = 0,
-                                                         unsigned short *__restrict__ marks = nullptr) {
+                                                         unsigned short *__restrict__ marks = nullptr,
+                                                         T *__restrict__ ps_out = nullptr) {
     static_assert(!LOCAL || V == 1, "local p_ref: one column per lane");
     static_assert(!FLAGGED || !LOCAL, "the fused first pass needs a fixed p_ref");
     constexpr bool QVP = QV_FROM_PASS<TL, REF> && !LOCAL && !FLAGGED;
@@ -3264,6 +3269,60 @@ __global__ __launch_bounds__(BLOCK, MULTI_MINW) void k_ps_loop_multi(Levels lv, 
         }
         if constexpr (QVP) {
             if (hus_out) {
+                // PGW_OPT_FINISH_IN_PASS (ps_out given): the wave goes on from where its scan stopped to l_start, with the
+                // quotient of the storing pass and no geopotential, and writes ps_pgw of this pass - what k_finalize_ps_hus
+                // would do for these columns from this pass's delta_ps.  A loop of its own, here where the scan's and the
+                // pass's registers are dead, with the next XU rows of e in flight; e is read for the last time if this pass
+                // is the converged one.  Nothing to do for a wave that walked to the top (ps < ps_mono_min, NaN ps).
+                if constexpr (FINISH_IN_PASS<TL, REF>) if (ps_out) {
+                    constexpr int XU = 4;
+                    double ps[V], en[XU][V];
+#pragma unroll
+                    for (int v = 0; v < V; ++v) ps[v] = ps_of<REF>(ps0[v], dps[v]);
+                    const TL *pe = evap + lbase;
+                    const long long qdiff = (const char *)hus_out - (const char *)evap;
+                    const int top = __builtin_amdgcn_readfirstlane(low) - 1;         // (the stop is wave-uniform)
+#pragma unroll
+                    for (int u = 0; u < XU; ++u) {
+                        const int lu = (top - u) > l_start ? (top - u) : l_start;
+                        if (top >= l_start) loadv_nt<TL, V>(pe + (long long)lu * ncol, en[u]);
+                    }
+                    for (int l = top; l >= l_start; l -= XU) {
+                        double e[XU][V];
+#pragma unroll
+                        for (int u = 0; u < XU; ++u)
+#pragma unroll
+                            for (int v = 0; v < V; ++v) e[u][v] = en[u][v];
+                        if (l - XU >= l_start) {
+#pragma unroll
+                            for (int u = 0; u < XU; ++u) {
+                                const int lu = (l - XU - u) > l_start ? (l - XU - u) : l_start;
+                                loadv_nt<TL, V>(pe + (long long)lu * ncol, en[u]);
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < XU; ++u) {
+                            const int lc = l - u;
+                            if (lc >= l_start) {
+                                const double am = lt.akm[lc], bm = lt.bkm[lc];
+                                double qs[V];
+#pragma unroll
+                                for (int v = 0; v < V; ++v) {
+                                    const double pm = am + ps[v] * bm;
+                                    qs[v] = SharedDivisor(pm - (1 - CON_MW_MD) * e[u][v]).divide(CON_MW_MD * e[u][v]);
+                                }
+                                // the row of hus_pgw as the lane's `pe` plus one uniform byte offset, as in scan_columns
+                                const long long ob = (long long)lc * ncol * (long long)sizeof(TL) + qdiff;
+                                const unsigned int olo = __builtin_amdgcn_readfirstlane((unsigned int)ob);
+                                const unsigned int ohi = __builtin_amdgcn_readfirstlane((unsigned int)((unsigned long long)ob >> 32));
+                                const long long ou = (long long)(((unsigned long long)ohi << 32) | olo);
+                                if (live) storev_nt<TL, V>((TL *)((char *)const_cast<TL *>(pe) + ou), qs);
+                            }
+                        }
+                    }
+                    if (live) storev<T, V>(ps_out + c2, ps);
+                    if (low > l_start) low = l_start;
+                }
                 // the levels low .. N-1 (from l_start on) of these columns now hold the q of pass npass-1; the stop is
                 // wave-uniform, so one lane speaks for the wave's live columns
                 if (live) {

@@ -40,6 +40,34 @@ inline int launch_passes(bool first, int guess, int max_n_iter, int allowed) {
     return np < 1 ? 1 : np;
 }
 
+// Who writes the final PS and QV once the loop has stopped.  The last pass of a launch of the multi-pass kernel may store the
+// QV it forms below p_ref (PGW_OPT_QV_FROM_PASS), and with PGW_OPT_FINISH_IN_PASS it goes on to the first hybrid level and
+// writes PS as well.  That is the file's result only when the very pass is the one whose max |err| met the threshold:
+//   NOTHING      the storing pass finished its columns and is the converged one - no launch after the loop;
+//   ABOVE_MARKS  it is the converged one but stopped where its scan stopped - the finalize kernel does the levels above;
+//   ALL_LEVELS   every other stop - convergence in an earlier pass of the launch or in a pass that did not store, a finished
+//                pass chosen on a NaN maximum (no valid column) - the finalize kernel runs over all levels and overwrites
+//                what was speculated.
+// Out of passes (NOT_CONVERGED) is the reference's error: nothing is finalized then, the caller returns it.
+struct StoredPass {
+    enum Final { NOTHING, ABOVE_MARKS, ALL_LEVELS };
+    int k = -1;                        // index, within the launch being read back, of the pass that stored (-1: none did)
+    bool finished = false;             // ... and walked on to the first hybrid level, PS written
+    bool converged = false;            // the stopping rule chose that pass
+    bool nan_stop = false;             // ... on a NaN maximum
+    void launched(int k_, bool finished_) { k = k_; finished = k_ >= 0 && finished_; converged = nan_stop = false; }
+    // pass `pass_k` of the launch got `verdict` from LoopControl::record(err)
+    void decided(LoopControl::Verdict verdict, int pass_k, double err) {
+        converged = verdict == LoopControl::CONVERGED && pass_k == k;
+        nan_stop = err != err;
+    }
+    Final final_step() const {
+        if (!converged) return ALL_LEVELS;
+        if (!finished) return ABOVE_MARKS;
+        return nan_stop ? ALL_LEVELS : NOTHING;
+    }
+};
+
 // What the bands of a file exchange per launch (pgw_set_reduce_hook: element-wise MAX over the ranks):
 // [status of the kernels before the loop | per pass: status, any-valid flag, max |err| (-inf: no valid column)].
 struct BandVector {

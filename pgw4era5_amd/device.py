@@ -422,7 +422,8 @@ class Context:
         self._check(self.lib.pgw_sync(self.handle))
 
     def set_option(self, name, value):
-        """Per-context option of include/pgw_hip.h `enum pgw_option` ('quad', 'full_column', 'force_vec1', 'multipass', 'loop_guess', 'force_off64', 'test_fail', 'fused_first', 'mixed_vec', 'sparse_direct', 'qv_from_pass');
+        """Per-context option of include/pgw_hip.h `enum pgw_option` ('quad', 'full_column', 'force_vec1', 'multipass', 'loop_guess', 'force_off64', 'test_fail', 'fused_first', 'mixed_vec', 'sparse_direct', 'qv_from_pass',
+        'finish_in_pass');
         returns the previous value."""
         old = self.get_option(name)
         self._check(self.lib.pgw_set_option(self.handle, _lib.OPTIONS[name], int(value)))
@@ -435,7 +436,8 @@ class Context:
 
     def last_qv_from_pass(self):
         """(used, skipped) of the last file or `adjust_ps` loop on this context (`pgw_last_qv_from_pass`): whether its finalize
-        kernel took the QV below p_ref from the converged pass, and the level-columns it skipped because of that."""
+        kernel took the QV below p_ref from the converged pass, and the level-columns it skipped because of that.  With the
+        option 'finish_in_pass' that pass wrote every hybrid level and PS: no finalize kernel ran, all of them are skipped."""
         n = C.c_ulonglong(0)
         used = self.lib.pgw_last_qv_from_pass(self.handle, C.byref(n))
         return bool(used), int(n.value)

@@ -84,6 +84,10 @@ delta_grid = 'era5'
 # axis, keep_hur, an instant with a sub-second part).  `PGW_FILE_PLAN=0` / `=1` overrides.  No influence on any result.
 file_plan = True
 
+# The end of a file in the library (include/pgw_hip.h PGW_OPT_FINISH_IN_PASS, context option 'finish_in_pass', default on): the
+# loop's storing pass writes the final QV of all hybrid levels and PS, and the surface riders run behind the loop launch.
+# `PGW_FINISH_IN_PASS=0` gives the riders first and the finalize kernel.  No influence on any result.
+
 # Placement of the level arrays (T, QV, U, V in and out, the vapour-pressure workspace) in the card's memory.  'spread': the
 # context draws them so that half lie in one stretch of physical memory and half in another (device.SpreadPool; the quad
 # kernel runs 12 % faster than with all of them in one stretch, which is what consecutive hipMallocs give; DESIGN.md section
