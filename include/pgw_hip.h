@@ -950,6 +950,36 @@ int pgw_geopot_on_plev(pgw_ctx *ctx, int dtype_2d, int dtype_a, int dtype_b, int
 int pgw_level_stats(pgw_ctx *ctx, int nrow, long long ncol, const double *x, long long *count, double *sum, double *sumsq,
                     double *maxabs);
 
+/* c3 delta check: T, RH, U, V of an ERA5-like state on a list of pressure levels, and for two states their change and its
+ * distance from the climate deltas.  No reference counterpart as a function.  Vertical grid of pgw_set_levels; per
+ * column and state pa[k] = akm[k] + PS * bkm[k], RH[k] = specific_to_relative_humidity(QV[k], pa[k], T[k])
+ * (functions.py:107-116) and X(p) = interp_extrap_1d(ln pa, X, ln p, 'nan') (functions.py:511-580) for X in (T, RH, U, V):
+ * the first k with ln pa[k] equal to or above ln p; equal gives X[k] bit for bit, k = 0 with "above" and no such k give
+ * NaN.  A column with pa[nlev-1] < pa[0] or a NaN PS gives NaN on every level; no status is raised.  float64 arithmetic
+ * on the stored values whatever the storage types (the float32 roundings of the reference's dtype flow are not
+ * reproduced): the bits of pgw_specific_to_relative_humidity_hybrid + pgw_interp_hybrid_to_plev (F64 -> F64,
+ * PGW_EXTRAP_NAN) on widened arrays.
+ *  plev (1 <= nplev <= 128 = PGW_MAX_PLEV, HOST, any order, repeats allowed): finite and > 1e-4.
+ *  PS_a, PS_b (ntime, ncol) of dtype_2d; T, QV, U, V (ntime, nlev, ncol) of dtype_a / dtype_b.
+ *  All five b pointers NULL: out = X_a.  Otherwise out = change = X_b - X_a, and with out_error != NULL
+ *    out_error = change - delta where plev < ps_hist, else NaN (at and below ps_hist step_03 applies the surface delta,
+ *    so the level's delta is no yardstick there; a NaN ps_hist gives NaN).  delta_X: the records rec_before[i] /
+ *    rec_after[i] (ntime, nplev, ncol) of dtype_delta in the order of plev, i = 0..3 for (ta, hur, ua, va); ps_hist: the
+ *    records ps_hist_before / ps_hist_after (ntime, ncol) of dtype_delta; each interpolated like load_delta
+ *    (functions.py:288-292) with its own x_hi[i], x_new[i] (HOST, i = 4: ps_hist); x_hi[i] == 0: the `before` record itself.
+ *  out, out_error (4, ntime, nplev, ncol) float64, variables in the order (ta, hur, ua, va), rows in the order of plev.
+ *  PGW_ERR_ARG before anything is uploaded or launched, outputs untouched: nplev outside [1, 128], a level not finite or
+ *  not > 1e-4, a bad dtype tag, a null required pointer, some but not all b pointers, out_error without two states or
+ *  without all ten record pointers, a pointer not aligned to its element.
+ *  One launch, timed under PGW_K_HYBRID_TO_PLEV; byte offsets are 32-bit while every array is below 4 GiB
+ *  (PGW_OPT_FORCE_OFF64: 64-bit), the same bits. */
+int pgw_state_on_plev(pgw_ctx *ctx, int dtype_2d, int dtype_a, int dtype_b, int ntime, int nplev, long long ncol,
+                      const double *plev, const void *PS_a, const void *T_a, const void *QV_a, const void *U_a,
+                      const void *V_a, const void *PS_b, const void *T_b, const void *QV_b, const void *U_b,
+                      const void *V_b, int dtype_delta, const void *const *rec_before, const void *const *rec_after,
+                      const void *ps_hist_before, const void *ps_hist_after, const double *x_hi, const double *x_new,
+                      double *out, double *out_error);
+
 #ifdef __cplusplus
 }
 #endif

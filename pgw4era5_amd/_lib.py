@@ -225,6 +225,8 @@ SIGNATURES['pgw_regrid_plan_destroy'] = (_i, [_vp, _vp])
 SIGNATURES['pgw_geopot_on_plev'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _dp] + [_vp] * 7 + [_i, _vp, _vp, _d, _d, _d, _i, _vp,
                                          C.POINTER(_ll)])
 SIGNATURES['pgw_level_stats'] = (_i, [_vp, _i, _ll, _vp, C.POINTER(_ll), _dp, _dp, _dp])
+# delta check (check_deltas.py): T, RH, U, V of one or two states on a level list, change and error against the deltas
+SIGNATURES['pgw_state_on_plev'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _dp] + [_vp] * 10 + [_i, _vpp, _vpp, _vp, _vp, _dp, _dp, _vp, _vp])
 # postproc_cosmo/extpar_adapt.py: T_CL + time mean of the ts delta
 SIGNATURES['pgw_time_mean_add'] = (_i, [_vp, _i, _i, _i, _ll, _vp, _i, _dp, _vp, _vp, _vp, C.POINTER(_ll), C.POINTER(_ll)])
 

@@ -1014,6 +1014,95 @@ extern "C" int pgw_level_stats(pgw_ctx *ctx, int nrow, long long ncol, const dou
     return PGW_OK;
 }
 
+// ------------------------------------------------------------------ delta check: T, RH, U, V on pressure levels
+extern "C" int pgw_state_on_plev(pgw_ctx *ctx, int dtype_2d, int dtype_a, int dtype_b, int ntime, int nplev, long long ncol,
+                                 const double *plev, const void *PS_a, const void *T_a, const void *QV_a, const void *U_a,
+                                 const void *V_a, const void *PS_b, const void *T_b, const void *QV_b, const void *U_b,
+                                 const void *V_b, int dtype_delta, const void *const *rec_before, const void *const *rec_after,
+                                 const void *ps_hist_before, const void *ps_hist_after, const double *x_hi, const double *x_new,
+                                 double *out, double *out_error) {
+    // every check comes before the first upload or launch
+    NEED(ctx, TAG_OK(dtype_2d) && TAG_OK(dtype_a), "dtype_2d and dtype_a must be PGW_F32 or PGW_F64");
+    NEED(ctx, ntime >= 1 && ncol >= 1, "ntime and ncol must be positive");
+    NEED(ctx, ctx->nlev > 0, "pgw_set_levels has not been called");
+    NEED(ctx, nplev >= 1 && nplev <= MAX_PLEV_WIDE, "nplev must be in [1, 128]");
+    static_assert(MAX_PLEV_WIDE == 128, "the message above names the limit");
+    NEED(ctx, plev && PS_a && T_a && QV_a && U_a && V_a && out, "null pointer");
+    for (int i = 0; i < nplev; ++i)
+        if (!(plev[i] > 0.0001 && plev[i] <= 1.7976931348623157e308))
+            return fail(ctx, PGW_ERR_ARG, "pgw_state_on_plev: plev[%d] = %g must be finite and greater than 1e-4", i, plev[i]);
+    const int nb_given = (PS_b != nullptr) + (T_b != nullptr) + (QV_b != nullptr) + (U_b != nullptr) + (V_b != nullptr);
+    NEED(ctx, nb_given == 0 || nb_given == 5, "PS_b, T_b, QV_b, U_b and V_b must be given together");
+    const bool two = nb_given == 5;
+    NEED(ctx, !two || TAG_OK(dtype_b), "dtype_b must be PGW_F32 or PGW_F64");
+    auto aligned = [](const void *p, size_t s) { return ((uintptr_t)p % s) == 0; };
+    const size_t s2 = elem_size(dtype_2d), sa = elem_size(dtype_a), sb = two ? elem_size(dtype_b) : 1;
+    NEED(ctx, aligned(PS_a, s2) && aligned(T_a, sa) && aligned(QV_a, sa) && aligned(U_a, sa) && aligned(V_a, sa) && aligned(PS_b, s2) &&
+                  aligned(T_b, sb) && aligned(QV_b, sb) && aligned(U_b, sb) && aligned(V_b, sb) && aligned(out, 8) && aligned(out_error, 8),
+         "a pointer is not aligned to its element");
+    PlevRecords rec;
+    memset(&rec, 0, sizeof(rec));
+    if (out_error) {
+        NEED(ctx, two, "out_error needs two states");
+        NEED(ctx, TAG_OK(dtype_delta), "dtype_delta must be PGW_F32 or PGW_F64");
+        NEED(ctx, rec_before && rec_after && x_hi && x_new && ps_hist_before && ps_hist_after, "out_error needs the record pointers");
+        const size_t sd = elem_size(dtype_delta);
+        for (int v = 0; v < 4; ++v) {
+            NEED(ctx, rec_before[v] && rec_after[v], "out_error needs all ten record pointers");
+            NEED(ctx, aligned(rec_before[v], sd) && aligned(rec_after[v], sd), "a pointer is not aligned to its element");
+            NEED(ctx, rec_before[v] != (const void *)out && rec_after[v] != (const void *)out, "out must not be one of the inputs");
+            rec.b[v] = rec_before[v]; rec.a[v] = x_hi[v] == 0.0 ? nullptr : rec_after[v];
+        }
+        NEED(ctx, aligned(ps_hist_before, sd) && aligned(ps_hist_after, sd), "a pointer is not aligned to its element");
+        NEED(ctx, out_error != out, "out_error must not be out");
+        rec.ps_b = ps_hist_before; rec.ps_a = x_hi[4] == 0.0 ? nullptr : ps_hist_after;
+        for (int v = 0; v < 5; ++v) { rec.x_hi[v] = x_hi[v]; rec.x_new[v] = x_new[v]; }
+        rec.f32 = dtype_delta == PGW_F32 ? 1 : 0;
+    }
+    for (const void *p : {PS_a, T_a, QV_a, U_a, V_a, PS_b, T_b, QV_b, U_b, V_b})
+        NEED(ctx, p != (const void *)out && (!out_error || p != (const void *)out_error), "an output must not be one of the inputs");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the list in ascending pressure with the permutation back to the caller's rows (stable: repeats keep their order)
+    int row[MAX_PLEV_WIDE];
+    double sorted[MAX_PLEV_WIDE];
+    for (int i = 0; i < nplev; ++i) row[i] = i;
+    std::stable_sort(row, row + nplev, [&](int a, int b) { return plev[a] < plev[b]; });
+    for (int i = 0; i < nplev; ++i) sorted[i] = plev[row[i]];
+    static_assert(MAX_PLEV_WIDE * (sizeof(double) + sizeof(int)) <= SMALL_BYTES, "d_small holds the level list and its rows");
+    double *d_plev = ctx->d_small;
+    int *d_row = (int *)(ctx->d_small + MAX_PLEV_WIDE);
+    HIPCHK(ctx, hipMemcpyAsync(d_plev, sorted, sizeof(double) * nplev, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_row, row, sizeof(int) * nplev, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // `sorted` and `row` go out of scope
+    const unsigned long long cells = (unsigned long long)ntime * (unsigned long long)ncol;
+    const unsigned long long big_in = cells * ctx->nlev * 8ull, big_out = 4ull * cells * nplev * sizeof(double);
+    const bool o32 = big_in < (1ull << 32) && big_out < (1ull << 32) && !ctx->opt[PGW_OPT_FORCE_OFF64];
+    const Levels lv = levels_of(ctx);
+    const unsigned int nb = nblocks((long long)cells, BLOCK);
+    {
+        Prof pr(ctx, PGW_K_HYBRID_TO_PLEV);
+        with_type(dtype_2d, [&](auto t2_) { with_type(dtype_a, [&](auto ta_) { with_offsets(o32, [&](auto o_) {
+            using T2 = decltype(t2_); using TLA = decltype(ta_); using O = decltype(o_);
+            if (!two) {
+                hipLaunchKernelGGL((k_state_plev<T2, TLA, TLA, 1, O>), dim3(nb), dim3(BLOCK), 0, ctx->stream, lv, ntime, nplev, ncol,
+                                   d_plev, d_row, (const T2 *)PS_a, (const TLA *)T_a, (const TLA *)QV_a, (const TLA *)U_a,
+                                   (const TLA *)V_a, (const T2 *)nullptr, (const TLA *)nullptr, (const TLA *)nullptr,
+                                   (const TLA *)nullptr, (const TLA *)nullptr, rec, out, (double *)nullptr);
+                return;
+            }
+            with_type(dtype_b, [&](auto tb_) {
+                using TLB = decltype(tb_);
+                hipLaunchKernelGGL((k_state_plev<T2, TLA, TLB, 2, O>), dim3(nb), dim3(BLOCK), 0, ctx->stream, lv, ntime, nplev, ncol,
+                                   d_plev, d_row, (const T2 *)PS_a, (const TLA *)T_a, (const TLA *)QV_a, (const TLA *)U_a,
+                                   (const TLA *)V_a, (const T2 *)PS_b, (const TLB *)T_b, (const TLB *)QV_b, (const TLB *)U_b,
+                                   (const TLB *)V_b, rec, out, out_error);
+            });
+        }); }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
 // ------------------------------------------------------------------ step_01: level list, lon-lat box, model-top merge
 extern "C" int pgw_select_box(pgw_ctx *ctx, int elem_bytes, int nrec, int nlev_src, int nlat_src, int nlon_src, const void *src,
                               int nlev_sel, const int *lev_index, int lat0, int nlat_sel, int lon0, int nlon_sel, int nlev_dst,

@@ -4203,6 +4203,159 @@ __global__ __launch_bounds__(BLOCK) void k_level_stats(long long ncol, const dou
     }
 }
 
+// =====================================================================================
+// c3  delta check: T, RH, U, V of an ERA5-like state on a list of pressure levels       functions.py:107-116, 511-580, 288-292
+// Per column and state: pa[k] = akm[k] + PS * bkm[k] (product, then sum), RH[k] = q_to_rh(QV[k], pa[k], T[k]), and for X in
+// (T, RH, U, V) X(p) = interp_extrap_1d(ln pa, X, ln p, 'nan'): the first k with ln pa[k] == ln p or > ln p; equal gives
+// X[k], k = 0 with "greater" and no such k give NaN, else X[k-1] + (ln p - ln pa[k-1]) * (X[k] - X[k-1]) / (ln pa[k] -
+// ln pa[k-1]) in this order.  float64 arithmetic on the stored values, every logarithm from pgw_log_tab (equal pressures
+// have equal logarithms): what pgw_specific_to_relative_humidity_hybrid + four pgw_interp_hybrid_to_plev launches
+// (F64 -> F64, PGW_EXTRAP_NAN) give on widened arrays, bit for bit.  A column with pa[N-1] < pa[0] gives NaN everywhere.
+//
+// One thread per column walks the model levels once per state; the targets are held ascending, so the column's position
+// in the list only moves forward, and the level k that ends a bracket emits every target in it for all four variables
+// from ONE pair of logarithms (the divisions share their denominator: the compiler keeps one reciprocal refinement).
+// RH is formed only for the two levels of a bracket that holds a target: at most 2 S e_sat evaluations per state, not N.
+// The leading levels with bkm = 0 take their logarithm from a per-block table like k_hybrid_to_plev.  The next level's
+// four loads are in flight while the current level is worked on.
+// Two states (NS = 2): state a's walk stores X_a in the output rows, state b's walk reads them back (same thread, same
+// address: program order) and stores change = X_b - X_a, and with the record pairs error = change - delta where
+// p < ps_hist, else NaN; delta and ps_hist are interpolated in time like load_delta (DeltaSrc::get), each on its own axis.
+// out / out_error (4, ntime, S, ncol) float64 in the order (ta, hur, ua, va), rows in the caller's level order.
+// =====================================================================================
+struct PlevRecords {         // bracketing records of the four deltas (ntime, S, ncol) and of ps_hist (ntime, ncol); b[0] == nullptr: none
+    const void *b[4], *a[4]; // a[v] == nullptr: the instant is record b[v]
+    const void *ps_b, *ps_a;
+    double x_hi[5], x_new[5];
+    int f32;                 // storage type of all ten
+    __device__ __forceinline__ double get(int v, long long off) const {
+        if (f32) return DeltaSrc<float>{(const float *)b[v], (const float *)a[v], x_hi[v], x_new[v]}.get(off);
+        return DeltaSrc<double>{(const double *)b[v], (const double *)a[v], x_hi[v], x_new[v]}.get(off);
+    }
+    __device__ __forceinline__ double ps_hist(long long off) const {
+        if (f32) return DeltaSrc<float>{(const float *)ps_b, (const float *)ps_a, x_hi[4], x_new[4]}.get(off);
+        return DeltaSrc<double>{(const double *)ps_b, (const double *)ps_a, x_hi[4], x_new[4]}.get(off);
+    }
+};
+
+// The walk of one state.  COMBINE = false: X is stored (streaming when nothing reads it back: NT).  COMBINE = true: the
+// rows hold state a's values; change and, with records, error are stored.
+template <bool COMBINE, bool NT, typename TL, typename O>
+__device__ __forceinline__ void state_walk(const LevTab &lt, int N, int S, int n_pure, const double *s_lx, const double *s_p,
+                                           const int *s_row, const double *s_lap, const TL *__restrict__ Tl,
+                                           const TL *__restrict__ Ql, const TL *__restrict__ Ul, const TL *__restrict__ Vl,
+                                           double ps, O lbase, O rowb_in, O obase, O rowb_out, O varb_out, long long rbase,
+                                           long long ncol, double psh, const PlevRecords &rec, double *out, double *out_error) {
+    const double nan = __builtin_nan("");
+    int jt = 0;
+    double lx = s_lx[0];                                                           // s_lx[S] = NaN ends the list
+    auto emit = [&](const double (&val)[4]) {
+        const int row = s_row[jt];
+        const O o = obase + (O)row * rowb_out;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const O ov = o + (O)v * varb_out;
+            if constexpr (!COMBINE) {
+                if (NT) st_off_nt<double, O>(out, ov, val[v]);
+                else st_off<double, O>(out, ov, val[v]);
+            } else {
+                const double change = val[v] - ld_off<double, O>(out, ov);         // X_b - X_a
+                st_off_nt<double, O>(out, ov, change);
+                if (out_error) {
+                    const double e = (s_p[jt] < psh) ? change - rec.get(v, rbase + (long long)row * ncol) : nan;
+                    st_off_nt<double, O>(out_error, ov, e);
+                }
+            }
+        }
+        ++jt;
+        lx = s_lx[jt];
+    };
+    const bool ps_finite = (ps - ps == 0.0);                                       // 0 * ps = 0: not for NaN / inf
+    const double pa_top = lt.akm[0] + ps * lt.bkm[0], pa_bot = lt.akm[N - 1] + ps * lt.bkm[N - 1];
+    const int nwalk = (pa_bot < pa_top) ? 0 : N;                                   // such a column: NaN on every level
+    auto ld = [&](const TL *p, int k) { return ld_off_nt<TL, O>(p, lbase + (O)k * rowb_in); };
+    TL nt_ = ld(Tl, 0), nq_ = ld(Ql, 0), nu_ = ld(Ul, 0), nv_ = ld(Vl, 0);
+    double xm = 0, pam = 0, tm = 0, qm = 0, um = 0, vm = 0;
+    for (int k = 0; k < nwalk; ++k) {
+        const double t = (double)nt_, q = (double)nq_, u = (double)nu_, w = (double)nv_;
+        const int kn = k + 1 < N ? k + 1 : N - 1;
+        nt_ = ld(Tl, kn); nq_ = ld(Ql, kn); nu_ = ld(Ul, kn); nv_ = ld(Vl, kn);
+        const double pa = lt.akm[k] + ps * lt.bkm[k];
+        const double x = (k < n_pure && ps_finite) ? s_lap[k] : pgw_log_tab(no_speculate(pa), lt.logtab);
+        if (x == lx || x > lx) {                                                   // level k is the first at or past target jt
+            if (k == 0) { pam = pa; tm = t; qm = q; }
+            const double rh = q_to_rh(q, pa, t), rhm = q_to_rh(qm, pam, tm);
+            const double dx = x - xm;
+            do {
+                double val[4];
+                if (x == lx) { val[0] = t; val[1] = rh; val[2] = u; val[3] = w; }  // :540-543
+                else if (k == 0) { val[0] = val[1] = val[2] = val[3] = nan; }      // above the top full level, 'nan'
+                else {                                                             // :575-578
+                    const double f = lx - xm;
+                    val[0] = tm + f * (t - tm) / dx;
+                    val[1] = rhm + f * (rh - rhm) / dx;
+                    val[2] = um + f * (u - um) / dx;
+                    val[3] = vm + f * (w - vm) / dx;
+                }
+                emit(val);
+            } while (x == lx || x > lx);
+            if (jt >= S) break;
+        }
+        xm = x; pam = pa; tm = t; qm = q; um = u; vm = w;
+    }
+    const double none[4] = {nan, nan, nan, nan};
+    while (jt < S) emit(none);                                                     // below the lowest full level
+}
+
+// T2: storage type of PS of both states; TLA / TLB: of the level arrays of state a / b; O: byte-offset type of every array
+template <typename T2, typename TLA, typename TLB, int NS, typename O>
+__global__ __launch_bounds__(BLOCK) void k_state_plev(Levels lv, int ntime, int S, long long ncol, const double *__restrict__ plev_sorted,
+                                                      const int *__restrict__ rows, const T2 *__restrict__ PS_a,
+                                                      const TLA *__restrict__ T_a, const TLA *__restrict__ QV_a,
+                                                      const TLA *__restrict__ U_a, const TLA *__restrict__ V_a,
+                                                      const T2 *__restrict__ PS_b, const TLB *__restrict__ T_b,
+                                                      const TLB *__restrict__ QV_b, const TLB *__restrict__ U_b,
+                                                      const TLB *__restrict__ V_b, PlevRecords rec, double *out, double *out_error) {
+    __shared__ double s_lev[LEVTAB_DOUBLES];
+    __shared__ double s_p[MAX_PLEV_WIDE + 1], s_lx[MAX_PLEV_WIDE + 1];            // ascending pressure, and its logarithm
+    __shared__ int s_row[MAX_PLEV_WIDE + 1];
+    __shared__ double s_lap[MAX_NLEV];                                            // ln akm[k] of the leading levels with bkm = 0
+    __shared__ int s_npure;
+    const int N = lv.nlev;
+    if (threadIdx.x == 0) s_npure = N;
+    LevTab lt = stage_levels<false, true>(lv, s_lev, BLOCK);                      // synchronises
+    for (int i = threadIdx.x; i <= MAX_PLEV_WIDE; i += BLOCK) {
+        const bool in = i < S;
+        const double p = in ? plev_sorted[i] : __builtin_nan("");
+        s_p[i] = p; s_lx[i] = in ? pgw_log_tab(p, lt.logtab) : p; s_row[i] = in ? rows[i] : 0;
+    }
+    for (int i = threadIdx.x; i < N; i += BLOCK) {
+        s_lap[i] = pgw_log_tab(lt.akm[i], lt.logtab);
+        if (!(lt.bkm[i] == 0.0)) atomicMin(&s_npure, i);
+    }
+    __syncthreads();
+    const int n_pure = s_npure;
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= (long long)ntime * ncol) return;
+    const long long t = g / ncol, c = g - t * ncol;
+    const O rowb_out = (O)((unsigned long long)ncol * sizeof(double));
+    const O varb_out = (O)((unsigned long long)ntime * S * ncol * sizeof(double));
+    const O obase = (O)((unsigned long long)(t * S * ncol + c) * sizeof(double));
+    const long long rbase = t * S * ncol + c;
+    const double ps_a = (double)PS_a[g];
+    {
+        const O rowb = (O)((unsigned long long)ncol * sizeof(TLA)), lbase = (O)((unsigned long long)(t * N * ncol + c) * sizeof(TLA));
+        state_walk<false, NS == 1, TLA, O>(lt, N, S, n_pure, s_lx, s_p, s_row, s_lap, T_a, QV_a, U_a, V_a, ps_a, lbase, rowb, obase,
+                                           rowb_out, varb_out, rbase, ncol, 0.0, rec, out, nullptr);
+    }
+    if constexpr (NS == 2) {
+        const O rowb = (O)((unsigned long long)ncol * sizeof(TLB)), lbase = (O)((unsigned long long)(t * N * ncol + c) * sizeof(TLB));
+        const double psh = out_error ? rec.ps_hist(g) : 0.0;                       // NaN: p < psh is false everywhere
+        state_walk<true, true, TLB, O>(lt, N, S, n_pure, s_lx, s_p, s_row, s_lap, T_b, QV_b, U_b, V_b, (double)PS_b[g], lbase, rowb,
+                                       obase, rowb_out, varb_out, rbase, ncol, psh, rec, out, out_error);
+    }
+}
+
 
 // =====================================================================================
 // a10b  bilinear regridding from curvilinear / rotated source grids       functions.py:797-810

@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from ._lib import _dp, _ip, check_nplev
+from ._lib import _dp, _ip, _vpp, check_nplev
 from .constants import CON_G, CON_RD, CON_MW_MD   # noqa: F401  (re-exported like the reference)
 from .device import DeviceArray, default_context, dtype_tag, ptr
 from .operands import (F64, aligned, check_extrapolate, common_dtype, dev, dev_own, fit, float_dtype, is_labelled, out_like,
@@ -444,12 +444,13 @@ def adjust_ps_loop(ak, bk, PS, FIS, T, QV, ta_pgw, hur_pgw, dzg_pref, akm=None, 
 GEOPOT_PLEV_FORM = 1
 
 
-def check_plev(plev):
+def check_plev(plev, most=64):
     """The level list of the hydrostatic check as a float64 vector: 1 to 64 finite pressures above 1e-4 Pa, the guard value
-    of reference functions.py:135 (ValueError otherwise, before anything reaches the device)."""
+    of reference functions.py:135 (ValueError otherwise, before anything reaches the device).  `most`: the capacity of
+    the entry that takes the list (the delta check follows the delta axes: 128)."""
     p = np.ascontiguousarray(raw(plev), dtype=np.float64)
-    if p.ndim != 1 or not 1 <= p.size <= 64:
-        raise ValueError('plev must be a vector of 1 to 64 levels, got shape %s' % (p.shape,))
+    if p.ndim != 1 or not 1 <= p.size <= most:
+        raise ValueError('plev must be a vector of 1 to %d levels, got shape %s' % (most, p.shape))
     if not np.all(np.isfinite(p)):
         raise ValueError('plev must be finite')
     if not np.all(p > 0.0001):
@@ -545,6 +546,101 @@ def level_stats(x):
     cnt, s, q, m = (C.c_longlong * n)(), (C.c_double * n)(), (C.c_double * n)(), (C.c_double * n)()
     ctx._check(ctx.lib.pgw_level_stats(ctx.handle, n, r.shape[1], d.ptr, cnt, s, q, m))
     return dict(count=np.array(cnt[:], dtype=np.int64), sum=np.array(s[:]), sumsq=np.array(q[:]), maxabs=np.array(m[:]))
+
+
+# ------------------------------------------------------------------------------- delta check
+STATE_PLEV_VARS = ('ta', 'hur', 'ua', 'va')              # variable order of `pgw_state_on_plev`, everywhere
+
+
+def _state_plev(states, ak, bk, plev, deltas):
+    p = check_plev(plev, most=128)
+    ak_, bk_ = np.asarray(raw(ak), dtype=np.float64), np.asarray(raw(bk), dtype=np.float64)
+    if ak_.ndim != 1 or ak_.shape != bk_.shape or ak_.size < 2:
+        raise ValueError('ak and bk must be vectors of one length (nlev + 1)')
+    nlev = ak_.size - 1
+    s3 = tuple(raw(states[0][0]).shape)
+    if len(s3) != 3:
+        raise ValueError('ps must be (time, lat, lon), got shape %s' % (s3,))
+    for i, (ps, ta, hus, ua, va) in enumerate(states):
+        st = shape4(ta)
+        lab = 'state %s' % 'ab'[i]
+        for name, x in (('hus', hus), ('ua', ua), ('va', va)):
+            if shape4(x) != st:
+                raise ValueError('%s: ta %s and %s %s differ in shape' % (lab, st, name, shape4(x)))
+        if (st[0], st[2], st[3]) != s3 or tuple(raw(ps).shape) != s3:
+            raise ValueError('%s: ps %s / ta %s do not lie on the grid %s' % (lab, tuple(raw(ps).shape), st, s3))
+        if st[1] != nlev:
+            raise ValueError('%s: %d levels, but ak and bk describe %d' % (lab, st[1], nlev))
+    recs = None
+    if deltas is not None:
+        if len(states) != 2:
+            raise ValueError('deltas need two states')
+        s4, recs = (s3[0], p.size, s3[1], s3[2]), []
+        for name in STATE_PLEV_VARS + ('ps_hist',):
+            if name not in deltas:
+                raise ValueError('deltas: %s is missing (needed: ta, hur, ua, va, ps_hist)' % name)
+            b, a, x_hi, x_new = deltas[name]
+            want = s3 if name == 'ps_hist' else s4
+            for r in (b, a):
+                if r is None or int(np.prod(raw(r).shape, dtype=np.int64)) != int(np.prod(want, dtype=np.int64)) or \
+                        tuple(raw(r).shape)[-2:] != want[-2:]:
+                    raise ValueError('deltas: the records of %s must be %s, got %s' % (name, want, None if r is None else tuple(raw(r).shape)))
+            recs.append((b, a, float(x_hi), float(x_new), want))
+    # nothing has touched the device up to here
+    ctx = default_context()
+    ctx.set_levels(ak_, bk_)
+    dt2 = common_dtype(*[s[0] for s in states])
+    d_states, tags, held = [], [], []
+    for st in states:
+        dtl = common_dtype(*st[1:])
+        d = [dev(ctx, st[0], dt2, s3)] + [dev(ctx, x, dtl) for x in st[1:]]
+        d_states.append(d)
+        tags.append(dtype_tag(dtl))
+    if len(states) == 1:
+        d_states.append([None] * 5)
+        tags.append(0)
+    shape = (4, s3[0], p.size, s3[1], s3[2])
+    out = ctx.empty(shape, F64)
+    err = None
+    tdel, rb, ra, x_hi, x_new = 0, (C.c_void_p * 4)(), (C.c_void_p * 4)(), (C.c_double * 5)(), (C.c_double * 5)()
+    psb = psa = None
+    if recs is not None:
+        dtd = common_dtype(*[r for rec in recs for r in rec[:2]])
+        tdel = dtype_tag(dtd)
+        for i, (b, a, xh, xn, want) in enumerate(recs):
+            d_b, d_a = dev(ctx, b, dtd, want), dev(ctx, a, dtd, want)
+            held += [d_b, d_a]
+            x_hi[i], x_new[i] = xh, xn
+            if i < 4:
+                rb[i], ra[i] = d_b.ptr, d_a.ptr
+            else:
+                psb, psa = d_b, d_a
+        err = ctx.empty(shape, F64)
+    a_, b_ = d_states
+    ctx._check(ctx.lib.pgw_state_on_plev(
+        ctx.handle, dtype_tag(dt2), tags[0], tags[1], s3[0], p.size, s3[1] * s3[2], p.ctypes.data_as(_dp),
+        *[x.ptr for x in a_], *[ptr(x) for x in b_], tdel, C.cast(rb, _vpp), C.cast(ra, _vpp), ptr(psb), ptr(psa), x_hi, x_new,
+        out.ptr, ptr(err)))
+    return out, err
+
+
+def state_on_plev(ps, ta, hus, ua, va, ak, bk, plev):
+    """T, RH, U, V of an ERA5-like state on every pressure of `plev` (`pgw_state_on_plev`): pa = akm + ps * bkm,
+    RH = specific_to_relative_humidity(hus, pa, ta) (reference functions.py:107-116), each variable through
+    interp_extrap_1d(ln pa, X, ln p, 'nan') (:511-580).  ps (time, H0, H1); ta, hus, ua, va (time, N, H0, H1), numpy arrays
+    or DeviceArrays; returns a DeviceArray (4, time, plev, H0, H1) float64 in the order (ta, hur, ua, va), rows in the
+    order of `plev` (1 to 128 levels).  NaN above the top and below the lowest full level.  float64 arithmetic on the
+    stored values.  ValueError for inconsistent shapes or level counts and for a bad `plev`, before the device is touched."""
+    return _state_plev([(ps, ta, hus, ua, va)], ak, bk, plev, None)[0]
+
+
+def state_change_on_plev(ps_a, ta_a, hus_a, ua_a, va_a, ps_b, ta_b, hus_b, ua_b, va_b, ak, bk, plev, deltas=None):
+    """`state_on_plev` of state b minus that of state a, in one launch: (change, None).  With `deltas` - a mapping of
+    'ta', 'hur', 'ua', 'va' and 'ps_hist' to `(record_before, record_after, x_hi, x_new)` as `DeltaSet.pair` hands them
+    out, the level records (time, plev, H0, H1) in the order of `plev` - also error = change - delta where plev < ps_hist,
+    NaN elsewhere, delta and ps_hist interpolated in time like load_delta (functions.py:288-292), each on its own axis:
+    (change, error).  Both are DeviceArrays (4, time, plev, H0, H1) float64."""
+    return _state_plev([(ps_a, ta_a, hus_a, ua_a, va_a), (ps_b, ta_b, hus_b, ua_b, va_b)], ak, bk, plev, deltas)
 
 
 # ------------------------------------------------------------------------------- postproc_cosmo
