@@ -546,6 +546,37 @@ int pgw_regrid_points(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int
                       const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
                       const int *oob, int south_row, int north_row, void *out);
 
+/* Winds on a rotated-pole target grid (not in the reference, whose targets are lat-lon meshes).  A file on a
+ * `rotated_latitude_longitude` mapping stores GRID-RELATIVE components - U along increasing rlon, V along increasing rlat -
+ * while the GCM's ua / va are eastward / northward.  At a target at geographic (lat, lon), the north pole of the rotated grid at
+ * geographic (pole_lat, pole_lon) (CF grid_north_pole_latitude / grid_north_pole_longitude), all in degrees:
+ *    D = pole_lon - lon;   a1 = cos(pole_lat) sin(D);   a2 = sin(pole_lat) cos(lat) - cos(pole_lat) sin(lat) cos(D)
+ *    rho = sqrt(a1^2 + a2^2);   c = a2 / rho,  s = a1 / rho
+ *    u_rot = u c - v s,  v_rot = u s + v c            inverse:  u = u_rot c + v_rot s,  v = -u_rot s + v_rot c
+ * (COSMO's uv2uvrot).  All three run on the context's stream and are timed under PGW_K_REGRID; PGW_ERR_ARG before anything is
+ * launched, the outputs untouched, for a null pointer, n < 1, nfield < 1 or an unknown dtype.
+ *
+ *  pgw_wind_rotation: cos_out[g] = c, sin_out[g] = s of the n targets (lat, lon); all arrays float64, DEVICE.  Sines and
+ *    cosines are exact at multiples of 90 degrees, so a pole at (90, +-180) gives c = 1, s = 0.  rho == 0 (a pole of the
+ *    rotated grid, where the direction is undefined) gives (1, 0); a NaN coordinate gives NaN in both.
+ *  pgw_rotate_pair: u, v (nfield, n) of `dtype` -> u_out, v_out, the rotation by cos / sin (n, float64, DEVICE) in float64,
+ *    each result rounded once to `dtype`; inverse != 0 rotates back.  In place when u_out == u and v_out == v.  16-byte
+ *    accesses where n and the addresses allow, single elements otherwise: the same bits.
+ *  pgw_regrid_points_wind: pgw_regrid_points on src_u and src_v (same arguments, checks and pole values, one set of tables)
+ *    and the rotation by the targets' cos / sin (ntarg, float64, DEVICE) in one launch: u_out, v_out (nfield, ntarg) hold the
+ *    bits of pgw_regrid_points on each component followed by pgw_rotate_pair - each regridded value is rounded to `dtype`
+ *    before it is rotated.  An oob target gives NaN in both. */
+int pgw_wind_rotation(pgw_ctx *ctx, long long n, const double *lat, const double *lon, double pole_lat, double pole_lon,
+                      double *cos_out, double *sin_out);
+int pgw_rotate_pair(pgw_ctx *ctx, int dtype, long long nfield, long long n, const void *u, const void *v, const double *cos,
+                    const double *sin, int inverse, void *u_out, void *v_out);
+int pgw_regrid_points_wind(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, long long ntarg,
+                           const void *src_u, const void *src_v,
+                           const int *lat_lo, const int *lat_hi, const double *lat_dx, const double *lat_Dx,
+                           const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
+                           const int *oob, int south_row, int north_row, const double *cos, const double *sin,
+                           void *u_out, void *v_out);
+
 /* regrid_lat_lon, xESMF branch (functions.py:797-810, settings.py:117-129): what `xe.Regridder(ds_in, ds_era5, "bilinear",
  * periodic=periodic_lon)` (:799-800) asks ESMF for and `regridder(ds_in[var_name])` (:802) applies, for source grids with
  * 2-D coordinates (rotated-pole, curvilinear).  Bilinear on the unit sphere in 3-D Cartesian space, cell edges being chords;

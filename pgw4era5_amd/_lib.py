@@ -217,6 +217,11 @@ SIGNATURES['pgw_bilinear_locate'] = (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _i, _v
 SIGNATURES['pgw_regrid_sparse'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _vp, _vp, _i, _vp])
 # regrid_lat_lon's default branch onto point-wise targets (2-D lat / lon): host tables of length ntarg
 SIGNATURES['pgw_regrid_points'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _ip, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _i, _i, _vp])
+# winds on a rotated-pole target grid: cos / sin of the local rotation, the rotation of a pair, regridding and rotation in one
+SIGNATURES['pgw_wind_rotation'] = (_i, [_vp, _ll, _vp, _vp, _d, _d, _vp, _vp])
+SIGNATURES['pgw_rotate_pair'] = (_i, [_vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _i, _vp, _vp])
+SIGNATURES['pgw_regrid_points_wind'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _vp, _ip, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _i, _i,
+                                             _vp, _vp, _vp, _vp])
 # pgw_regrid_bilinear from tables that stay on the device: records of the source-grid deltas of step_03 (delta_grid = 'source')
 SIGNATURES['pgw_regrid_plan_create'] = (_i, [_vp, _i, _i, _i, _i, _ip, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _ip, _i, _i, _ll, _vpp])
 SIGNATURES['pgw_regrid_plan_apply'] = (_i, [_vp, _vp, _i, _i, _ll, _vp, _vp])

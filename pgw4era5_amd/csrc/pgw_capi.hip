@@ -2941,23 +2941,38 @@ extern "C" int pgw_regrid_plan_destroy(pgw_ctx *ctx, pgw_regrid_plan *plan) {
     return PGW_OK;
 }
 
+// What the point-wise entries check and upload before they launch, under the name of the entry: dtype, shapes, the `narrays`
+// device arrays (non-null, element-aligned), the nine host tables and their brackets; then the tables into slot 3 with room
+// for the pole values of `pole_planes` planes behind them.
+static int point_tables(pgw_ctx *ctx, const char *caller, int dtype, long long nfield, int nlat_s, int nlon_s, long long ntarg,
+                        const void *const *arrays, int narrays, const int *lat_lo, const int *lat_hi, const double *lat_dx,
+                        const double *lat_Dx, const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
+                        const int *oob, int south_row, int north_row, long long pole_planes, PointTables *tb, double **dpole) {
+    NEED_AS(ctx, caller, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
+    NEED_AS(ctx, caller, nfield >= 1 && ntarg >= 1 && ntarg < (1ll << 29), "nfield >= 1 and ntarg in [1, 2^29)");
+    NEED_AS(ctx, caller, nlat_s >= 2 && nlon_s >= 2 && (long long)nlat_s * nlon_s < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
+    NEED_AS(ctx, caller, lat_lo && lat_hi && lat_dx && lat_Dx && lon_lo && lon_hi && lon_dx && lon_Dx && oob, "null pointer");
+    for (int k = 0; k < narrays; ++k) {
+        NEED_AS(ctx, caller, arrays[k], "null pointer");
+        NEED_AS(ctx, caller, ((uintptr_t)arrays[k] % elem_size(dtype)) == 0, "pointers must be element-aligned");
+    }
+    if (int rc = check_brackets(ctx, caller, ntarg, oob, lat_lo, lat_hi, lon_lo, lon_hi, nlat_s, nlon_s, south_row, north_row)) return rc;
+    const size_t n = (size_t)ntarg;
+    return tables_to_slot3(ctx, {{lat_dx, n, &tb->lat_dx}, {lat_Dx, n, &tb->lat_Dx}, {lon_dx, n, &tb->lon_dx}, {lon_Dx, n, &tb->lon_Dx}},
+                           {{lat_lo, n, &tb->lat_lo}, {lat_hi, n, &tb->lat_hi}, {lon_lo, n, &tb->lon_lo}, {lon_hi, n, &tb->lon_hi}, {oob, n, &tb->oob}},
+                           pole_planes, dpole);
+}
+
 // regrid_lat_lon, xarray branch with point-wise targets (functions.py:812-893 with 2-D targ_lat / targ_lon)
 extern "C" int pgw_regrid_points(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, long long ntarg, const void *src,
                                  const int *lat_lo, const int *lat_hi, const double *lat_dx, const double *lat_Dx, const int *lon_lo,
                                  const int *lon_hi, const double *lon_dx, const double *lon_Dx, const int *oob, int south_row,
                                  int north_row, void *out) {
-    NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
-    NEED(ctx, nfield >= 1 && ntarg >= 1 && ntarg < (1ll << 29), "nfield >= 1 and ntarg in [1, 2^29)");
-    NEED(ctx, nlat_s >= 2 && nlon_s >= 2 && (long long)nlat_s * nlon_s < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
-    NEED(ctx, src && out && lat_lo && lat_hi && lat_dx && lat_Dx && lon_lo && lon_hi && lon_dx && lon_Dx && oob, "null pointer");
-    NEED(ctx, ((uintptr_t)src % elem_size(dtype)) == 0 && ((uintptr_t)out % elem_size(dtype)) == 0, "pointers must be element-aligned");
-    if (int rc = check_brackets(ctx, __func__, ntarg, oob, lat_lo, lat_hi, lon_lo, lon_hi, nlat_s, nlon_s, south_row, north_row)) return rc;
-    const size_t n = (size_t)ntarg;
+    const void *arrays[] = {src, out};
     PointTables tb;
     double *dpole;
-    if (int rc = tables_to_slot3(ctx, {{lat_dx, n, &tb.lat_dx}, {lat_Dx, n, &tb.lat_Dx}, {lon_dx, n, &tb.lon_dx}, {lon_Dx, n, &tb.lon_Dx}},
-                              {{lat_lo, n, &tb.lat_lo}, {lat_hi, n, &tb.lat_hi}, {lon_lo, n, &tb.lon_lo}, {lon_hi, n, &tb.lon_hi}, {oob, n, &tb.oob}},
-                              nfield, &dpole))
+    if (int rc = point_tables(ctx, __func__, dtype, nfield, nlat_s, nlon_s, ntarg, arrays, 2, lat_lo, lat_hi, lat_dx, lat_Dx, lon_lo, lon_hi,
+                              lon_dx, lon_Dx, oob, south_row, north_row, nfield, &tb, &dpole))
         return rc;
     const unsigned int bx = nblocks(ntarg, BLOCK);            // one target per thread (k_regrid_points)
     const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
@@ -2968,6 +2983,83 @@ extern "C" int pgw_regrid_points(pgw_ctx *ctx, int dtype, long long nfield, int 
             using T = decltype(t_);
             hipLaunchKernelGGL((k_regrid_points<T>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s, ntarg, gz,
                                (const T *)src, tb, dpole, (T *)out);
+        });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// ------------------------------------------------------------------ winds on a rotated-pole target grid
+extern "C" int pgw_wind_rotation(pgw_ctx *ctx, long long n, const double *lat, const double *lon, double pole_lat, double pole_lon,
+                                 double *cos_out, double *sin_out) {
+    NEED(ctx, n >= 1 && n < (1ll << 31) && lat && lon && cos_out && sin_out, "n must be in [1, 2^31), the pointers not null");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    {
+        Prof pr(ctx, PGW_K_REGRID);
+        hipLaunchKernelGGL(k_wind_rotation, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, lat, lon, pole_lat, pole_lon, cos_out,
+                           sin_out);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// planes per z-slice of k_rotate_pair, where there are that many: the 16 bytes of c and s a lane loads per target are then at
+// most a third of what its planes move (float32: 8 bytes in and 8 out per target and plane, float64 twice that)
+static const long long ROTATE_MIN_PLANES = 3;
+
+extern "C" int pgw_rotate_pair(pgw_ctx *ctx, int dtype, long long nfield, long long n, const void *u, const void *v, const double *cos,
+                               const double *sin, int inverse, void *u_out, void *v_out) {
+    NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
+    NEED(ctx, nfield >= 1 && nfield < (1ll << 40) && n >= 1 && n < (1ll << 31), "nfield >= 1 and n in [1, 2^31)");
+    NEED(ctx, u && v && cos && sin && u_out && v_out, "null pointer");
+    const size_t es = elem_size(dtype);
+    NEED(ctx, (uintptr_t)u % es == 0 && (uintptr_t)v % es == 0 && (uintptr_t)u_out % es == 0 && (uintptr_t)v_out % es == 0 &&
+                  (uintptr_t)cos % 8 == 0 && (uintptr_t)sin % 8 == 0, "pointers must be element-aligned");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // 16 bytes of T per lane and access (planes start n elements apart: n must be a multiple of it), or one element
+    const int full = dtype == PGW_F64 ? 2 : 4;
+    const int vec = pick_vec(ctx, dtype, n, {u, v, cos, sin, u_out, v_out}) == full ? full : 1;
+    const unsigned int bx = nblocks(n / vec, BLOCK);
+    const long long most = (nfield + ROTATE_MIN_PLANES - 1) / ROTATE_MIN_PLANES;
+    const unsigned int gz = (unsigned int)std::min({(long long)z_slices(bx, nfield), most, 65535ll});      // blockIdx.y
+    {
+        Prof pr(ctx, PGW_K_REGRID);
+        with_type(dtype, [&](auto t_) { with_int<2>(vec > 1, [&](auto wide_) {
+            using T = decltype(t_);
+            constexpr int V = decltype(wide_)::value ? 16 / (int)sizeof(T) : 1;
+            hipLaunchKernelGGL((k_rotate_pair<T, V>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, n, gz, (const T *)u,
+                               (const T *)v, cos, sin, inverse, (T *)u_out, (T *)v_out);
+        }); });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// pgw_regrid_points on ua and va together, rotated onto the targets' grid-relative directions in the same launch
+extern "C" int pgw_regrid_points_wind(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s, int nlon_s, long long ntarg,
+                                      const void *src_u, const void *src_v, const int *lat_lo, const int *lat_hi, const double *lat_dx,
+                                      const double *lat_Dx, const int *lon_lo, const int *lon_hi, const double *lon_dx,
+                                      const double *lon_Dx, const int *oob, int south_row, int north_row, const double *cos,
+                                      const double *sin, void *u_out, void *v_out) {
+    NEED(ctx, cos && sin && (uintptr_t)cos % 8 == 0 && (uintptr_t)sin % 8 == 0, "cos / sin: null or misaligned pointer");
+    NEED(ctx, nfield < (1ll << 40), "nfield must be below 2^40");
+    const void *arrays[] = {src_u, src_v, u_out, v_out};
+    PointTables tb;
+    double *dpole;
+    if (int rc = point_tables(ctx, __func__, dtype, nfield, nlat_s, nlon_s, ntarg, arrays, 4, lat_lo, lat_hi, lat_dx, lat_Dx, lon_lo, lon_hi,
+                              lon_dx, lon_Dx, oob, south_row, north_row, 2 * nfield, &tb, &dpole))
+        return rc;
+    const unsigned int bx = nblocks(ntarg, BLOCK);            // one target per thread
+    const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
+    double *dpole_v = dpole + 2 * nfield;                     // [nfield][2] each
+    {
+        Prof pr(ctx, PGW_K_REGRID);
+        launch_pole_means(ctx, dtype, nfield, nlat_s, nlon_s, src_u, south_row, north_row, dpole);
+        launch_pole_means(ctx, dtype, nfield, nlat_s, nlon_s, src_v, south_row, north_row, dpole_v);
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_regrid_points_wind<T>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s, ntarg, gz,
+                               (const T *)src_u, (const T *)src_v, tb, dpole, dpole_v, cos, sin, (T *)u_out, (T *)v_out);
         });
     }
     HIPCHK(ctx, hipGetLastError());

@@ -2872,7 +2872,160 @@ __global__ __launch_bounds__(BLOCK) void k_regrid_points(long long nfield, int n
 }
 
 // =====================================================================================
-// a9  surface riders               step_03_apply_to_era.py:103-146, functions.py:1145-1186
+// a10w  wind components on a rotated-pole target grid (not in the reference: its targets are lat-lon meshes)
+// A file on a `rotated_latitude_longitude` mapping stores U along increasing rlon and V along increasing rlat; the GCM's
+// ua / va are eastward / northward.  At a target at geographic (lat, lon) [deg], north pole of the rotated grid at
+// (pole_lat, pole_lon) [deg] (COSMO's uv2uvrot):
+//   D  = pole_lon - lon
+//   a1 = cos(pole_lat) sin(D)
+//   a2 = sin(pole_lat) cos(lat) - cos(pole_lat) sin(lat) cos(D)
+//   rho = sqrt(a1^2 + a2^2)           (the cosine of the target's rotated latitude)
+//   c = a2 / rho,  s = a1 / rho;      u_rot = u c - v s,  v_rot = u s + v c;      inverse: u = u_rot c + v_rot s, v = -u_rot s + v_rot c
+// rho == 0 (a pole of the rotated grid: no direction) gives (c, s) = (1, 0); a NaN coordinate gives NaN.
+// =====================================================================================
+// sin and cos of an angle in degrees, exact at the multiples of 90 (a pole at 90 N has cos = 0 and the rotation is the
+// identity, where cos(pi / 2) is 6e-17): the angle less its nearest multiple of 90 - an exact difference - goes through
+// sincos in radians (x * (pi / 180), numpy's deg2rad) and the quadrant turns the pair.  NaN and infinities give NaN.
+__device__ __forceinline__ void sincos_deg(double x, double &s, double &c) {
+    const double k = rint(x / 90.0);
+    double sr, cr;
+    sincos((x - 90.0 * k) * (M_PI / 180.0), &sr, &cr);
+    const double m = fmod(k, 4.0);
+    const int q = (m == m) ? ((int)m + 4) & 3 : 0;
+    s = q == 0 ? sr : q == 1 ? cr : q == 2 ? -sr : -cr;
+    c = q == 0 ? cr : q == 1 ? -sr : q == 2 ? -cr : sr;
+}
+
+// one target per lane
+__global__ __launch_bounds__(BLOCK) void k_wind_rotation(long long n, const double *__restrict__ lat, const double *__restrict__ lon,
+                                                         double pole_lat, double pole_lon, double *__restrict__ cos_out,
+                                                         double *__restrict__ sin_out) {
+    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= n) return;
+    double sp, cp, sl, cl, sd, cd;
+    sincos_deg(pole_lat, sp, cp);
+    sincos_deg(lat[g], sl, cl);
+    sincos_deg(pole_lon - lon[g], sd, cd);
+    const double a1 = cp * sd;
+    const double a2 = sp * cl - cp * sl * cd;
+    const double rho = sqrt(a1 * a1 + a2 * a2);
+    cos_out[g] = rho == 0.0 ? 1.0 : a2 / rho;
+    sin_out[g] = rho == 0.0 ? 0.0 : a1 / rho;
+}
+
+// The rotation of one value pair by a target's (c, s) in float64, each result rounded once to T; `s` comes negated for
+// the inverse (u c - v (-s) is u c + v s, u (-s) + v c is -u s + v c: numpy's bits).
+template <typename T>
+__device__ __forceinline__ void rotate_uv(double u, double v, double c, double s, T &u_rot, T &v_rot) {
+    u_rot = (T)(u * c - v * s);
+    v_rot = (T)(u * s + v * c);
+}
+
+// u, v (nfield, n) -> u_out, v_out (nfield, n), in place when u_out == u and v_out == v (no __restrict__ on the four: a
+// lane stores a plane's elements after it has read them, and reads and stores nobody else's).  A lane owns V consecutive
+// targets - 16 bytes of T per access where n and the addresses allow, V = 1 otherwise: the same arithmetic per element, the
+// same bits - keeps their c and s in registers and walks the planes of its z-slice (blockIdx.y) like k_regrid_points: the
+// next plane's two loads are issued before this plane's two streaming stores.
+template <typename T, int V>
+__global__ __launch_bounds__(BLOCK) void k_rotate_pair(long long nfield, long long n, unsigned int gz, const T *u, const T *v,
+                                                       const double *__restrict__ cs, const double *__restrict__ sn, int inverse,
+                                                       T *u_out, T *v_out) {
+    const long long g = ((long long)blockIdx.x * BLOCK + threadIdx.x) * V;
+    if (g >= n) return;
+    double c[V], s[V];
+    loadv16<double, V>(cs + g, c);
+    loadv16<double, V>(sn + g, s);
+    if (inverse) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) s[i] = -s[i];
+    }
+    const long long per = (nfield + gz - 1) / gz;
+    const long long f0 = (long long)blockIdx.y * per, f1 = f0 + per < nfield ? f0 + per : nfield;
+    double cu[V], cv[V], nu[V], nv[V];
+    if (f0 < f1) { loadv_nt<T, V>(u + f0 * n + g, cu); loadv_nt<T, V>(v + f0 * n + g, cv); }
+    for (long long f = f0; f < f1; ++f) {
+        if (f + 1 < f1) { loadv_nt<T, V>(u + (f + 1) * n + g, nu); loadv_nt<T, V>(v + (f + 1) * n + g, nv); }
+        double ru[V], rv[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            T a, b;
+            rotate_uv<T>(cu[i], cv[i], c[i], s[i], a, b);
+            ru[i] = (double)a; rv[i] = (double)b;
+        }
+        storev_nt<T, V>(u_out + f * n + g, ru);
+        storev_nt<T, V>(v_out + f * n + g, rv);
+        if (f + 1 < f1) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) { cu[i] = nu[i]; cv[i] = nv[i]; }
+        }
+    }
+}
+
+// k_regrid_points on both wind components of a rotated-pole target at once, the rotation behind it: per target the
+// corner codes, the two dx and the two reciprocals are formed once and serve both components; a plane costs eight gathers
+// (the next plane's are issued before this plane's two streaming stores).  Each component's value is k_regrid_points' - the
+// same expressions in the same order, its pole values from k_zonal_mean_rows run on that component - ROUNDED TO T, and the
+// pair of T values goes through rotate_uv: the bits of pgw_regrid_points on each component followed by pgw_rotate_pair.
+// An oob target gives NaN in both outputs.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_regrid_points_wind(long long nfield, int nlat_s, int nlon_s, long long ntarg, unsigned int gz,
+                                                              const T *__restrict__ src_u, const T *__restrict__ src_v, PointTables tb,
+                                                              const double *__restrict__ pole_u, const double *__restrict__ pole_v,
+                                                              const double *__restrict__ cs, const double *__restrict__ sn,
+                                                              T *__restrict__ u_out, T *__restrict__ v_out) {
+    const long long g0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    const bool active = g0 < ntarg;
+    const long long g = active ? g0 : ntarg - 1;
+    const bool oob = tb.oob[g] != 0;
+    const bool live = active && !oob;
+    const int jl = tb.lat_lo[g], jh = tb.lat_hi[g], il = tb.lon_lo[g], ih = tb.lon_hi[g];
+    const double ldx = tb.lat_dx[g], odx = tb.lon_dx[g];
+    const SharedDivisor by_lDx(tb.lat_Dx[g]), by_oDx(tb.lon_Dx[g]);
+    const double rc = cs[g], rs = sn[g];
+    int c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int row = k < 2 ? jl : jh;
+        int code = row * nlon_s + ((k & 1) ? ih : il);
+        if (row < 0) code = -1;
+        if (row >= nlat_s) code = -2;
+        c[k] = live ? code : 0;
+    }
+    const long long plane_s = (long long)nlat_s * nlon_s;
+    const long long per = (nfield + gz - 1) / gz;
+    const long long f0 = (long long)blockIdx.y * per, f1 = f0 + per < nfield ? f0 + per : nfield;
+    auto gather = [&](const T *src, long long f, T (&v)[4]) {
+        const T *sp = src + f * plane_s;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = sp[c[k] >= 0 ? c[k] : 0];
+    };
+    auto value = [&](const T (&cur)[4], const double *pole, long long f) {
+        double v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = c[k] >= 0 ? (double)cur[k] : pole[f * 2 + (-1 - c[k])];
+        const double ya = by_lDx.divide(v[2] - v[0]) * ldx + v[0];                // lat pass at the lower lon  :859
+        const double yb = by_lDx.divide(v[3] - v[1]) * ldx + v[1];                // lat pass at the upper lon
+        return (T)(oob ? __builtin_nan("") : by_oDx.divide(yb - ya) * odx + ya);   // lon pass  :892; what pgw_regrid_points stores
+    };
+    T cu[4], cv[4], nu[4], nv[4];
+    if (f0 < f1) { gather(src_u, f0, cu); gather(src_v, f0, cv); }
+    for (long long f = f0; f < f1; ++f) {
+        if (f + 1 < f1) { gather(src_u, f + 1, nu); gather(src_v, f + 1, nv); }
+        T ur, vr;
+        rotate_uv<T>((double)value(cu, pole_u, f), (double)value(cv, pole_v, f), rc, rs, ur, vr);
+        if (active) {
+            __builtin_nontemporal_store(ur, u_out + f * ntarg + g0);              // streaming, as k_regrid_points
+            __builtin_nontemporal_store(vr, v_out + f * ntarg + g0);
+        }
+        if (f + 1 < f1) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { cu[k] = nu[k]; cv[k] = nv[k]; }
+        }
+    }
+}
+
+// =====================================================================================
+// a9  surface riders              step_03_apply_to_era.py:103-146, functions.py:1145-1186
 // =====================================================================================
 constexpr int MAX_SOIL = 16;
 struct SoilTable { double w[MAX_SOIL]; int n; };     // w = exp(-depth/2.8), computed on the host

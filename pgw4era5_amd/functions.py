@@ -876,6 +876,89 @@ def regrid_points(field, src_lat, src_lon, targ_lat, targ_lon):
     return _regrid('regrid_points', field, src_lat, src_lon, targ_lat, targ_lon, points=True)
 
 
+# ------------------------------------------------------------------------------- winds on a rotated-pole target grid
+# Not in the reference (its targets are lat-lon meshes, whose winds are geographic): a file on a `rotated_latitude_longitude`
+# mapping stores GRID-RELATIVE components, U along increasing rlon and V along increasing rlat (include/pgw_hip.h).
+def _same_shape(what, **xs):
+    shapes = {k: tuple(raw(x).shape) for k, x in xs.items()}
+    first = next(iter(shapes.values()))
+    if len(first) < 1 or any(s != first for s in shapes.values()):
+        raise ValueError('%s need one common shape (rank >= 1); got %s' % (what, ', '.join('%s %s' % kv for kv in shapes.items())))
+    return first
+
+
+def wind_rotation(lat, lon, pole_lat, pole_lon):
+    """(cos, sin) of the angle between geographic east and grid east at the points (lat, lon) of a rotated grid whose north pole
+    lies at geographic (pole_lat, pole_lon) - CF `grid_north_pole_latitude` / `grid_north_pole_longitude`; degrees
+    (pgw_wind_rotation).  float64, of the coordinates' common shape (rank >= 1): DeviceArrays when both coordinates are,
+    ndarrays otherwise.  (1, 0) at a pole of the rotated grid, NaN for a NaN coordinate."""
+    shape = _same_shape('lat and lon', lat=lat, lon=lon)
+    ctx = default_context()
+    d_lat, d_lon = dev(ctx, lat, F64), dev(ctx, lon, F64)
+    c, s = ctx.empty(shape, F64), ctx.empty(shape, F64)
+    ctx._check(ctx.lib.pgw_wind_rotation(ctx.handle, c.size, d_lat.ptr, d_lon.ptr, float(pole_lat), float(pole_lon), c.ptr, s.ptr))
+    if isinstance(lat, DeviceArray) and isinstance(lon, DeviceArray):
+        return c, s
+    return c.numpy(), s.numpy()
+
+
+def _wind_pair(ua, va, cos, sin, trailing=None):
+    """Shapes and the dtype of a (ua, va, cos, sin) call, checked before the device is touched: ua and va of one shape with
+    `trailing` horizontal dimensions (default: those of cos / sin) -> (shape, number of planes, dtype - float32 only when both
+    are -, shape of cos / sin)."""
+    shape = _same_shape('ua and va', ua=ua, va=va)
+    cs = _same_shape('cos and sin', cos=cos, sin=sin)
+    trailing = len(cs) if trailing is None else trailing
+    if len(shape) < trailing:
+        raise ValueError('ua and va of shape %s have fewer than %d horizontal dimensions' % (shape, trailing))
+    if 0 in shape or 0 in cs:
+        raise ValueError('ua and va of shape %s, cos and sin of shape %s: an empty array' % (shape, cs))
+    return shape, int(np.prod(shape[:len(shape) - trailing], dtype=np.int64)), common_dtype(ua, va), cs
+
+
+def rotate_wind(ua, va, cos, sin, inverse=False):
+    """Geographic (ua, va) -> grid-relative (u, v) = (ua cos - va sin, ua sin + va cos), or back with inverse=True
+    (pgw_rotate_pair).  cos / sin as `wind_rotation` returns them; the trailing dimensions of ua and va are their shape.
+    Computed in float64 and rounded once to the common dtype of ua and va - float32 only when both are; array kinds as
+    everywhere (u like ua, v like va).  settings.function_dtype_flow has no say: there is no reference function to follow."""
+    shape, nfield, dtype, cs = _wind_pair(ua, va, cos, sin)
+    if shape[len(shape) - len(cs):] != cs:
+        raise ValueError('ua and va of shape %s do not end in the shape %s of cos and sin' % (shape, cs))
+    ctx = default_context()
+    n = int(np.prod(cs, dtype=np.int64))
+    d_u, d_v, d_c, d_s = dev(ctx, ua, dtype), dev(ctx, va, dtype), dev(ctx, cos, F64), dev(ctx, sin, F64)
+    u, v = ctx.empty(shape, dtype), ctx.empty(shape, dtype)
+    ctx._check(ctx.lib.pgw_rotate_pair(ctx.handle, dtype_tag(dtype), nfield, n, d_u.ptr, d_v.ptr, d_c.ptr, d_s.ptr, int(bool(inverse)),
+                                       u.ptr, v.ptr))
+    return out_like(u, ua), out_like(v, va)
+
+
+def regrid_points_wind(ua, va, src_lat, src_lon, targ_lat, targ_lon, cos, sin):
+    """`regrid_points` on ua and va (..., nlat_s, nlon_s) together and `rotate_wind` by the targets' cos / sin (their shape is
+    the targets') in one launch (pgw_regrid_points_wind): (u, v) hold the bits of the three calls - each regridded value is
+    rounded to the dtype before it is rotated.  The extent errors of `regrid_tables` are raised before any launch."""
+    targ_lat, targ_lon = np.asarray(targ_lat, dtype=np.float64), np.asarray(targ_lon, dtype=np.float64)
+    if targ_lat.ndim < 1 or targ_lat.shape != targ_lon.shape:
+        raise ValueError('point-wise targets need lat and lon of one common shape (rank >= 1); got %s and %s'
+                         % (targ_lat.shape, targ_lon.shape))
+    shape, nfield, dtype, cs = _wind_pair(ua, va, cos, sin, 2)
+    if cs != targ_lat.shape:
+        raise ValueError('cos and sin of shape %s do not lie over the targets of shape %s' % (cs, targ_lat.shape))
+    if shape[-2:] != (len(src_lat), len(src_lon)):
+        raise ValueError('field shape does not match the source coordinates')
+    ctx = default_context()
+    tb = regrid_tables(src_lat, src_lon, targ_lat.ravel(), targ_lon.ravel())      # the extent errors, before any launch
+    c = {k: np.ascontiguousarray(v) for k, v in tb.items() if isinstance(v, np.ndarray)}
+    c['oob'] = np.ascontiguousarray(c['lat_oob'] | c['lon_oob'], dtype=np.int32)
+    tabs = [c[k].ctypes.data_as(_ip if c[k].dtype == np.int32 else _dp)
+            for k in 'lat_lo lat_hi lat_dx lat_Dx lon_lo lon_hi lon_dx lon_Dx oob'.split()]
+    d_u, d_v, d_c, d_s = dev(ctx, ua, dtype), dev(ctx, va, dtype), dev(ctx, cos, F64), dev(ctx, sin, F64)
+    u, v = (ctx.empty(shape[:-2] + targ_lat.shape, dtype) for _ in range(2))
+    ctx._check(ctx.lib.pgw_regrid_points_wind(ctx.handle, dtype_tag(dtype), nfield, shape[-2], shape[-1], targ_lat.size, d_u.ptr,
+                                              d_v.ptr, *tabs, tb['south_row'], tb['north_row'], d_c.ptr, d_s.ptr, u.ptr, v.ptr))
+    return out_like(u, ua), out_like(v, va)
+
+
 # ------------------------------------------------------------------------------- regridding, 2-D source coordinates
 def unit_vectors(lat_deg, lon_deg):
     """(..., 3) unit vectors (cos lat cos lon, cos lat sin lon, sin lat) of points in degrees, float64: the only
@@ -1190,14 +1273,25 @@ class _Target:
         ds[name] = ncio.Field(values, tuple(lead) + self.dims, coords, attrs)
 
 
-def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
+def _horizontal_values(f):
+    """A (..., lat, lon) variable of a GCM file as regrid_lat_lon hands it to the kernels: (leading dimensions, values with
+    lat and lon last, float32 / float64 as they are and anything else as float64)."""
+    lead = [d for d in f.dims if d not in (LAT_GCM, LON_GCM)]
+    g = f.transpose(*(lead + [LAT_GCM, LON_GCM]))
+    return lead, g.values if g.values.dtype in (np.float32, np.float64) else g.values.astype(np.float64)
+
+
+def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0, given=None):
     """Bilinear regridding onto the ERA5 grid of `ds_era5` (reference functions.py:748-898).  i_use_xesmf = 0: the xarray
     branch, every lat/lon variable of `ds_gcm` (1-D source coordinates) through the separable kernel when the target's lat
     and lon are 1-D axes of their own (a mesh), through `regrid_points` when they lie over the same dimensions (2-D
     coordinates of a rotated-pole file, one `cell` dimension): the result then lies on the target's dimensions and lat / lon
     are written as variables over them, like the xESMF branch does; any other combination is a ValueError.  i_use_xesmf = 1: the xESMF
     branch (:797-810) for source grids with 2-D coordinates (rotated-pole, curvilinear; 1-D ones are meshed), `var_name`
-    through the cell-locate and sparse-apply kernels.  Returns a new Dataset on the target grid."""
+    through the cell-locate and sparse-apply kernels.  Returns a new Dataset on the target grid.
+    given (not in the reference; xarray branch): {name: (values, attributes)} - variables whose values on the target grid the
+    caller has already (regrid_lat_lon_wind), laid out as this function would lay them out; they get the attributes on top of
+    their own and nothing else about the result differs."""
     from . import ncio
     if i_use_xesmf:
         return _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name)
@@ -1212,15 +1306,87 @@ def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0):
         if name in (LAT_GCM, LON_GCM):
             continue
         if LAT_GCM in f.dims and LON_GCM in f.dims:
-            lead = [d for d in f.dims if d not in (LAT_GCM, LON_GCM)]
-            g = f.transpose(*(lead + [LAT_GCM, LON_GCM]))
-            vals = g.values if g.values.dtype in (np.float32, np.float64) else g.values.astype(np.float64)
-            tg.put_field(out, name, regrid(vals, src_lat, src_lon, tg.lat, tg.lon), lead,
-                         {d: f.coords[d] for d in lead if d in f.coords}, f.attrs)
+            lead, vals = _horizontal_values(f)
+            if given and name in given:
+                res, attrs = given[name][0], dict(f.attrs, **given[name][1])
+            else:
+                res, attrs = regrid(vals, src_lat, src_lon, tg.lat, tg.lon), f.attrs
+            tg.put_field(out, name, res, lead, {d: f.coords[d] for d in lead if d in f.coords}, attrs)
         elif LAT_GCM not in f.dims and LON_GCM not in f.dims:
             out[name] = f
     tg.put_coords(out, ds_gcm[LAT_GCM].attrs, ds_gcm[LON_GCM].attrs)      # point-wise: laid out like the xESMF branch's 2-D target
     return out
+
+
+WIND_MARKER = dict(wind_components='grid_relative')      # on a ua / va variable whose components follow the target's rotated grid
+
+
+def rotated_pole_of(ds, var_name):
+    """(grid_north_pole_latitude, grid_north_pole_longitude) of the rotated grid of a file: from the variable the
+    `grid_mapping` attribute of `var_name` names; where the file has no such variable or attribute, from its only variable
+    with grid_mapping_name = 'rotated_latitude_longitude'.  ValueError when there is none, more than one, or no pole on it."""
+    rotated = [n for n, f in ds.variables.items() if f.attrs.get('grid_mapping_name') == 'rotated_latitude_longitude']
+    named = ds[var_name].attrs.get('grid_mapping') if var_name is not None and var_name in ds else None
+    if named is not None:
+        if named not in rotated:
+            raise ValueError("--rotate_winds auto: the grid_mapping '%s' of %s is not a variable with grid_mapping_name = "
+                             "'rotated_latitude_longitude': no rotated mapping found; give the pole as POLE_LAT,POLE_LON"
+                             % (named, var_name))
+        rotated = [named]
+    if not rotated:
+        raise ValueError("--rotate_winds auto: no rotated mapping found - the target file has no variable with "
+                         "grid_mapping_name = 'rotated_latitude_longitude'; give the pole as POLE_LAT,POLE_LON")
+    if len(rotated) > 1:
+        raise ValueError('--rotate_winds auto: more than one rotated mapping in the target file (%s) and no grid_mapping '
+                         'attribute on %s to choose one; give the pole as POLE_LAT,POLE_LON' % (', '.join(rotated), var_name))
+    attrs = ds[rotated[0]].attrs
+    try:
+        return tuple(float(np.ravel(attrs[k])[0]) for k in ('grid_north_pole_latitude', 'grid_north_pole_longitude'))
+    except KeyError as e:
+        raise ValueError('--rotate_winds auto: the rotated mapping %s of the target file has no %s' % (rotated[0], e)) from None
+
+
+def check_wind_pair(ds_ua, ds_va, names=('ua', 'va')):
+    """What regrid_lat_lon_wind needs of the two files of one period, checked before anything is computed or written:
+    neither variable carries WIND_MARKER already (a second rotation), both lie on the same source grid, the same other
+    dimensions (plev, number of records) and have the same dtype.  ValueError naming the cause."""
+    for ds, name in zip((ds_ua, ds_va), names):
+        if ds[name].attrs.get('wind_components') == WIND_MARKER['wind_components']:
+            raise ValueError("%s already carries wind_components = 'grid_relative': these files have been rotated onto a "
+                             'rotated grid, rotating them again (double rotation) would be wrong' % name)
+    fu, fv = ds_ua[names[0]], ds_va[names[1]]
+    for c in (LAT_GCM, LON_GCM):
+        if c not in ds_ua or c not in ds_va or not np.array_equal(np.asarray(ds_ua[c].values), np.asarray(ds_va[c].values)):
+            raise ValueError('--rotate_winds: %s and %s differ in their source grid (%s)' % (names[0], names[1], c))
+    if tuple(fu.dims) != tuple(fv.dims):
+        raise ValueError('--rotate_winds: %s has dimensions %s, %s has %s' % (names[0], fu.dims, names[1], fv.dims))
+    for d, nu, nv in zip(fu.dims, fu.shape, fv.shape):
+        if d == PLEV_GCM and (nu != nv or not np.array_equal(np.asarray(ds_ua[d].values), np.asarray(ds_va[d].values))):
+            raise ValueError('--rotate_winds: %s and %s differ in plev' % names)
+        if nu != nv:
+            raise ValueError('--rotate_winds: %s and %s differ in the number of records: %d and %d along %s'
+                             % (names[0], names[1], nu, nv, d))
+    if _horizontal_values(fu)[1].dtype != _horizontal_values(fv)[1].dtype:
+        raise ValueError('--rotate_winds: %s and %s differ in dtype (%s, %s)' % (names[0], names[1], fu.dtype, fv.dtype))
+
+
+def regrid_lat_lon_wind(ds_ua, ds_va, ds_era5, pole, names=('ua', 'va')):
+    """`regrid_lat_lon` of a ua file and a va file onto a target with point-wise lat / lon on a rotated grid whose north
+    pole lies at `pole` = (lat, lon), the two wind variables through `regrid_points_wind`: they come out GRID-RELATIVE, carry
+    WIND_MARKER and the pole as attributes, and hold the bits of `rotate_wind` applied to what regrid_lat_lon writes.
+    Everything else in the two datasets is regrid_lat_lon's.  Returns (ds_ua_out, ds_va_out)."""
+    check_wind_pair(ds_ua, ds_va, names)
+    tg = _Target.of(ds_era5[LAT_ERA], ds_era5[LON_ERA])
+    if not tg.points:
+        raise ValueError('the target has 1-D lat / lon axes: the winds of a lat-lon mesh are geographic already, there is '
+                         'nothing to rotate')
+    src_lat, src_lon = (np.asarray(ds_ua[c].values, dtype=np.float64) for c in (LAT_GCM, LON_GCM))
+    cos, sin = wind_rotation(tg.lat, tg.lon, *pole)
+    u, v = regrid_points_wind(_horizontal_values(ds_ua[names[0]])[1], _horizontal_values(ds_va[names[1]])[1], src_lat, src_lon,
+                              tg.lat, tg.lon, cos, sin)
+    attrs = dict(WIND_MARKER, grid_north_pole_latitude=np.float64(pole[0]), grid_north_pole_longitude=np.float64(pole[1]))
+    return (regrid_lat_lon(ds_ua, ds_era5, names[0], given={names[0]: (u, attrs)}),
+            regrid_lat_lon(ds_va, ds_era5, names[1], given={names[1]: (v, attrs)}))
 
 
 # ------------------------------------------------------------------------------- step_02 smoothing

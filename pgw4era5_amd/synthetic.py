@@ -190,6 +190,22 @@ def rotated_pole_grid(nrlat=24, nrlon=48, pole_lat=39.25, pole_lon=-162.0, rlat_
     return rlat, rlon, lat, lon
 
 
+def solid_body_wind(lat, lon, pole_lat, pole_lon):
+    """Geographic (u eastward, v northward) of the solid-body rotation about the axis through (pole_lat, pole_lon) with unit
+    angular velocity on the unit sphere: the velocity p x r of the point r = (lat, lon), p the pole's unit vector.  Degrees;
+    lat and lon broadcast.  On a rotated grid with that north pole the flow runs along increasing rlon: grid-relative, it is
+    (cos(rlat), 0) - a wind field whose rotation `step_02 regridding --rotate_winds` can be checked by eye."""
+    la, lo = np.deg2rad(np.asarray(lat, dtype=np.float64)), np.deg2rad(np.asarray(lon, dtype=np.float64))
+    pa, po = np.deg2rad(float(pole_lat)), np.deg2rad(float(pole_lon))
+    p = np.array([np.cos(pa) * np.cos(po), np.cos(pa) * np.sin(po), np.sin(pa)])
+    r = np.stack(np.broadcast_arrays(np.cos(la) * np.cos(lo), np.cos(la) * np.sin(lo), np.sin(la)), axis=-1)
+    w = np.cross(p, r)
+    one = np.ones(w.shape[:-1])
+    east = np.stack([-np.sin(lo) * one, np.cos(lo) * one, 0.0 * one], axis=-1)
+    north = np.stack([-np.sin(la) * np.cos(lo), -np.sin(la) * np.sin(lo), np.cos(la) * one], axis=-1)
+    return (w * east).sum(axis=-1), (w * north).sum(axis=-1)
+
+
 def make_rotated_delta(nrlat=24, nrlon=48, nplev=3, ntime=2, seed=0, dtype=np.float64, var_name='ta', **grid):
     """An atmospheric climate delta of a rotated-pole regional model, as step_02 `regridding` meets it with
     settings.i_use_xesmf_regridding = 1: `var_name` (time, plev, rlat, rlon) with 2-D `lat` / `lon` over (rlat, rlon),
