@@ -577,6 +577,40 @@ int pgw_regrid_points_wind(pgw_ctx *ctx, int dtype, long long nfield, int nlat_s
                            const int *oob, int south_row, int north_row, const double *cos, const double *sin,
                            void *u_out, void *v_out);
 
+/* The point-wise regridding from a plan: the nine tables of one (source grid, target list) pair, the targets' cos / sin where
+ * the plan rotates, and the pole scratch for up to 2 * max_nfield planes (u and v), uploaded once into device memory the plan
+ * owns - for a caller that regrids many records onto one list of targets in the middle of other work on the context's stream
+ * (step_03 with settings.delta_grid = 'source_points': a delta record is regridded straight into its slot of the DeltaSet's
+ * window, ua / va rotated onto a rotated-pole file's directions in the same launch).
+ *  pgw_points_plan_create: the nine tables HOST, length ntarg, as for pgw_regrid_points and checked like them (shapes, null
+ *    pointers, table entries, pole rows; max_nfield >= 1).  cos / sin (ntarg, float64, DEVICE, as pgw_wind_rotation writes
+ *    them): both given - they are copied into the plan's memory on the stream - or both NULL: the plan cannot rotate.
+ *    PGW_ERR_ARG with *plan = NULL and nothing allocated.  Synchronises the stream once; the host tables and cos / sin may be
+ *    freed after the call.
+ *  pgw_points_plan_apply: src (nfield, nlat_s, nlon_s) of dtype_src, out (nfield, ntarg) of dtype_out, both DEVICE.  Every
+ *    value is computed as pgw_regrid_points computes it for dtype_src (the same kernel, the same bits) and rounded to dtype_src;
+ *    where dtype_out differs, that value is then converted to dtype_out - what a file written by step_02 in the source's type
+ *    holds after the host's astype(dtype_out).
+ *  pgw_points_plan_apply_wind: src_u, src_v -> u_out, v_out likewise, as pgw_regrid_points_wind: each regridded component is
+ *    rounded to dtype_src and rotated in float64, each result rounded once to dtype_src - what a `--rotate_winds` file of
+ *    step_02 holds - and then converted to dtype_out.  The pole means are taken per component.
+ *  Both launch on the context's stream and return: no allocation, no workspace slot, no synchronisation.  PGW_ERR_ARG before
+ *    any launch, the outputs untouched, for: a null plan or pointer, a dtype tag other than PGW_F32 / PGW_F64, nfield outside
+ *    [1, max_nfield], a pointer not aligned to its element size, apply_wind on a plan made without cos / sin.  Timed under
+ *    PGW_K_REGRID.
+ *  pgw_points_plan_destroy: waits for the stream, frees the plan (NULL: nothing to do). */
+typedef struct pgw_points_plan pgw_points_plan;
+int pgw_points_plan_create(pgw_ctx *ctx, int nlat_s, int nlon_s, long long ntarg,
+                           const int *lat_lo, const int *lat_hi, const double *lat_dx, const double *lat_Dx,
+                           const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
+                           const int *oob, int south_row, int north_row, long long max_nfield,
+                           const double *cos, const double *sin, pgw_points_plan **plan);
+int pgw_points_plan_apply(pgw_ctx *ctx, const pgw_points_plan *plan, int dtype_src, int dtype_out, long long nfield,
+                          const void *src, void *out);
+int pgw_points_plan_apply_wind(pgw_ctx *ctx, const pgw_points_plan *plan, int dtype_src, int dtype_out, long long nfield,
+                               const void *src_u, const void *src_v, void *u_out, void *v_out);
+int pgw_points_plan_destroy(pgw_ctx *ctx, pgw_points_plan *plan);
+
 /* regrid_lat_lon, xESMF branch (functions.py:797-810, settings.py:117-129): what `xe.Regridder(ds_in, ds_era5, "bilinear",
  * periodic=periodic_lon)` (:799-800) asks ESMF for and `regridder(ds_in[var_name])` (:802) applies, for source grids with
  * 2-D coordinates (rotated-pole, curvilinear).  Bilinear on the unit sphere in 3-D Cartesian space, cell edges being chords;

@@ -226,6 +226,11 @@ SIGNATURES['pgw_regrid_points_wind'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _vp
 SIGNATURES['pgw_regrid_plan_create'] = (_i, [_vp, _i, _i, _i, _i, _ip, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _ip, _i, _i, _ll, _vpp])
 SIGNATURES['pgw_regrid_plan_apply'] = (_i, [_vp, _vp, _i, _i, _ll, _vp, _vp])
 SIGNATURES['pgw_regrid_plan_destroy'] = (_i, [_vp, _vp])
+# pgw_regrid_points / pgw_regrid_points_wind likewise (delta_grid = 'source_points'): nine host tables, cos / sin on the device
+SIGNATURES['pgw_points_plan_create'] = (_i, [_vp, _i, _i, _ll, _ip, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _i, _i, _ll, _vp, _vp, _vpp])
+SIGNATURES['pgw_points_plan_apply'] = (_i, [_vp, _vp, _i, _i, _ll, _vp, _vp])
+SIGNATURES['pgw_points_plan_apply_wind'] = (_i, [_vp, _vp, _i, _i, _ll, _vp, _vp, _vp, _vp])
+SIGNATURES['pgw_points_plan_destroy'] = (_i, [_vp, _vp])
 # hydrostatic check (check_geopot.py): integ_geopot on a level list, per-level statistics
 SIGNATURES['pgw_geopot_on_plev'] = (_i, [_vp, _i, _i, _i, _i, _i, _ll, _dp] + [_vp] * 7 + [_i, _vp, _vp, _d, _d, _d, _i, _vp,
                                          C.POINTER(_ll)])

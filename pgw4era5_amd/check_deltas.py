@@ -134,8 +134,11 @@ def parse_args(argv=None):
     p.add_argument('-f', '--first_era_step', type=str, default='2006080200', help='first time step, YYYYMMDDHH')
     p.add_argument('-l', '--last_era_step', type=str, default='2006080300', help='last time step (inclusive), YYYYMMDDHH')
     p.add_argument('-H', '--hour_inc_step', type=int, default=3, help='hours between time steps')
-    p.add_argument('--delta_grid', type=str, default=None, choices=('era5', 'source'),
-                   help="grid of the delta files: 'era5' (step_02 wrote them) or 'source' (the GCM's grid); default settings.delta_grid")
+    p.add_argument('--delta_grid', type=str, default=None, choices=('era5', 'source', 'source_points'),
+                   help="grid of the delta files: 'era5' (step_02 wrote them), 'source' (the GCM's grid, mesh files) or "
+                        "'source_points' (the GCM's grid, files of any layout); default settings.delta_grid")
+    p.add_argument('--rotate_winds', type=str, nargs='?', const='auto', default=None, metavar='auto|POLE_LAT,POLE_LON',
+                   help="as step_03's flag: the run rotated the ua / va deltas onto the file's rotated grid (--delta_grid source_points)")
     args = p.parse_args(argv)
     for flag, val in (('-i', args.input_dir), ('-g', args.pgw_dir), ('-d', args.delta_input_dir), ('-o', args.output_dir)):
         if val is None:
@@ -157,9 +160,10 @@ def _cli(argv=None):
     args = parse_args(argv)
     os.makedirs(args.output_dir, exist_ok=True)
     results = []
-    before = os.environ.get('PGW_DELTA_GRID')
-    if args.delta_grid is not None:
-        os.environ['PGW_DELTA_GRID'] = args.delta_grid          # what step_03's command line sets (delta_grid_mode reads it)
+    # what step_03's command line sets (delta_grid_mode reads them)
+    handed = {k: v for k, v in (('PGW_DELTA_GRID', args.delta_grid), ('PGW_ROTATE_WINDS', args.rotate_winds)) if v is not None}
+    before = {k: os.environ.get(k) for k in handed}
+    os.environ.update(handed)
     try:
         for job in file_jobs(args):
             tables = check_file(**job)
@@ -169,11 +173,10 @@ def _cli(argv=None):
                 print(format_table(tables[var], UNITS[var]))
             results.append(tables)
     finally:
-        if args.delta_grid is not None:
-            if before is None:
-                del os.environ['PGW_DELTA_GRID']
-            else:
-                os.environ['PGW_DELTA_GRID'] = before
+        for k, v in before.items():
+            os.environ.pop(k)
+            if v is not None:
+                os.environ[k] = v
     return results
 
 

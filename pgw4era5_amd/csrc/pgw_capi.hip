@@ -2941,6 +2941,16 @@ extern "C" int pgw_regrid_plan_destroy(pgw_ctx *ctx, pgw_regrid_plan *plan) {
     return PGW_OK;
 }
 
+// The shapes and the nine host tables of a point-wise call or plan (nfield: the planes of the call, max_nfield of a plan)
+static int check_point_shapes(pgw_ctx *ctx, const char *caller, long long nfield, int nlat_s, int nlon_s, long long ntarg,
+                              const int *lat_lo, const int *lat_hi, const double *lat_dx, const double *lat_Dx, const int *lon_lo,
+                              const int *lon_hi, const double *lon_dx, const double *lon_Dx, const int *oob) {
+    NEED_AS(ctx, caller, nfield >= 1 && ntarg >= 1 && ntarg < (1ll << 29), "nfield >= 1 and ntarg in [1, 2^29)");
+    NEED_AS(ctx, caller, nlat_s >= 2 && nlon_s >= 2 && (long long)nlat_s * nlon_s < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
+    NEED_AS(ctx, caller, lat_lo && lat_hi && lat_dx && lat_Dx && lon_lo && lon_hi && lon_dx && lon_Dx && oob, "null pointer");
+    return PGW_OK;
+}
+
 // What the point-wise entries check and upload before they launch, under the name of the entry: dtype, shapes, the `narrays`
 // device arrays (non-null, element-aligned), the nine host tables and their brackets; then the tables into slot 3 with room
 // for the pole values of `pole_planes` planes behind them.
@@ -2949,9 +2959,7 @@ static int point_tables(pgw_ctx *ctx, const char *caller, int dtype, long long n
                         const double *lat_Dx, const int *lon_lo, const int *lon_hi, const double *lon_dx, const double *lon_Dx,
                         const int *oob, int south_row, int north_row, long long pole_planes, PointTables *tb, double **dpole) {
     NEED_AS(ctx, caller, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
-    NEED_AS(ctx, caller, nfield >= 1 && ntarg >= 1 && ntarg < (1ll << 29), "nfield >= 1 and ntarg in [1, 2^29)");
-    NEED_AS(ctx, caller, nlat_s >= 2 && nlon_s >= 2 && (long long)nlat_s * nlon_s < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
-    NEED_AS(ctx, caller, lat_lo && lat_hi && lat_dx && lat_Dx && lon_lo && lon_hi && lon_dx && lon_Dx && oob, "null pointer");
+    if (int rc = check_point_shapes(ctx, caller, nfield, nlat_s, nlon_s, ntarg, lat_lo, lat_hi, lat_dx, lat_Dx, lon_lo, lon_hi, lon_dx, lon_Dx, oob)) return rc;
     for (int k = 0; k < narrays; ++k) {
         NEED_AS(ctx, caller, arrays[k], "null pointer");
         NEED_AS(ctx, caller, ((uintptr_t)arrays[k] % elem_size(dtype)) == 0, "pointers must be element-aligned");
@@ -2961,6 +2969,39 @@ static int point_tables(pgw_ctx *ctx, const char *caller, int dtype, long long n
     return tables_to_slot3(ctx, {{lat_dx, n, &tb->lat_dx}, {lat_Dx, n, &tb->lat_Dx}, {lon_dx, n, &tb->lon_dx}, {lon_Dx, n, &tb->lon_Dx}},
                            {{lat_lo, n, &tb->lat_lo}, {lat_hi, n, &tb->lat_hi}, {lon_lo, n, &tb->lon_lo}, {lon_hi, n, &tb->lon_hi}, {oob, n, &tb->oob}},
                            pole_planes, dpole);
+}
+
+// The pole means and k_regrid_points for nfield planes onto ntarg targets, timed under PGW_K_REGRID: one target per thread
+static void launch_points(pgw_ctx *ctx, int dtype_src, int dtype_out, long long nfield, int nlat_s, int nlon_s, long long ntarg,
+                          const void *src, const PointTables &tb, int south_row, int north_row, double *dpole, void *out) {
+    const unsigned int bx = nblocks(ntarg, BLOCK);
+    const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
+    Prof pr(ctx, PGW_K_REGRID);
+    launch_pole_means(ctx, dtype_src, nfield, nlat_s, nlon_s, src, south_row, north_row, dpole);
+    with_type(dtype_src, [&](auto t_) { with_type(dtype_out, [&](auto o_) {
+        using T = decltype(t_);
+        using TOUT = decltype(o_);
+        hipLaunchKernelGGL((k_regrid_points<T, TOUT>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s, ntarg, gz,
+                           (const T *)src, tb, dpole, (TOUT *)out);
+    }); });
+}
+
+// The same for both wind components and the rotation behind them (k_regrid_points_wind); dpole takes [2][nfield][2]
+static void launch_points_wind(pgw_ctx *ctx, int dtype_src, int dtype_out, long long nfield, int nlat_s, int nlon_s, long long ntarg,
+                               const void *src_u, const void *src_v, const PointTables &tb, int south_row, int north_row,
+                               double *dpole, const double *cos, const double *sin, void *u_out, void *v_out) {
+    const unsigned int bx = nblocks(ntarg, BLOCK);
+    const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
+    double *dpole_v = dpole + 2 * nfield;                     // [nfield][2] each
+    Prof pr(ctx, PGW_K_REGRID);
+    launch_pole_means(ctx, dtype_src, nfield, nlat_s, nlon_s, src_u, south_row, north_row, dpole);
+    launch_pole_means(ctx, dtype_src, nfield, nlat_s, nlon_s, src_v, south_row, north_row, dpole_v);
+    with_type(dtype_src, [&](auto t_) { with_type(dtype_out, [&](auto o_) {
+        using T = decltype(t_);
+        using TOUT = decltype(o_);
+        hipLaunchKernelGGL((k_regrid_points_wind<T, TOUT>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s, ntarg,
+                           gz, (const T *)src_u, (const T *)src_v, tb, dpole, dpole_v, cos, sin, (TOUT *)u_out, (TOUT *)v_out);
+    }); });
 }
 
 // regrid_lat_lon, xarray branch with point-wise targets (functions.py:812-893 with 2-D targ_lat / targ_lon)
@@ -2974,17 +3015,7 @@ extern "C" int pgw_regrid_points(pgw_ctx *ctx, int dtype, long long nfield, int 
     if (int rc = point_tables(ctx, __func__, dtype, nfield, nlat_s, nlon_s, ntarg, arrays, 2, lat_lo, lat_hi, lat_dx, lat_Dx, lon_lo, lon_hi,
                               lon_dx, lon_Dx, oob, south_row, north_row, nfield, &tb, &dpole))
         return rc;
-    const unsigned int bx = nblocks(ntarg, BLOCK);            // one target per thread (k_regrid_points)
-    const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
-    {
-        Prof pr(ctx, PGW_K_REGRID);
-        launch_pole_means(ctx, dtype, nfield, nlat_s, nlon_s, src, south_row, north_row, dpole);
-        with_type(dtype, [&](auto t_) {
-            using T = decltype(t_);
-            hipLaunchKernelGGL((k_regrid_points<T>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s, ntarg, gz,
-                               (const T *)src, tb, dpole, (T *)out);
-        });
-    }
+    launch_points(ctx, dtype, dtype, nfield, nlat_s, nlon_s, ntarg, src, tb, south_row, north_row, dpole, out);
     HIPCHK(ctx, hipGetLastError());
     return PGW_OK;
 }
@@ -3049,20 +3080,116 @@ extern "C" int pgw_regrid_points_wind(pgw_ctx *ctx, int dtype, long long nfield,
     if (int rc = point_tables(ctx, __func__, dtype, nfield, nlat_s, nlon_s, ntarg, arrays, 4, lat_lo, lat_hi, lat_dx, lat_Dx, lon_lo, lon_hi,
                               lon_dx, lon_Dx, oob, south_row, north_row, 2 * nfield, &tb, &dpole))
         return rc;
-    const unsigned int bx = nblocks(ntarg, BLOCK);            // one target per thread
-    const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
-    double *dpole_v = dpole + 2 * nfield;                     // [nfield][2] each
-    {
-        Prof pr(ctx, PGW_K_REGRID);
-        launch_pole_means(ctx, dtype, nfield, nlat_s, nlon_s, src_u, south_row, north_row, dpole);
-        launch_pole_means(ctx, dtype, nfield, nlat_s, nlon_s, src_v, south_row, north_row, dpole_v);
-        with_type(dtype, [&](auto t_) {
-            using T = decltype(t_);
-            hipLaunchKernelGGL((k_regrid_points_wind<T>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield, nlat_s, nlon_s, ntarg, gz,
-                               (const T *)src_u, (const T *)src_v, tb, dpole, dpole_v, cos, sin, (T *)u_out, (T *)v_out);
-        });
-    }
+    launch_points_wind(ctx, dtype, dtype, nfield, nlat_s, nlon_s, ntarg, src_u, src_v, tb, south_row, north_row, dpole, cos, sin, u_out,
+                       v_out);
     HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+// A points plan: the nine tables of one (source grid, target list) pair resident on the device, the targets' cos / sin behind
+// them where the plan rotates, and the pole scratch of up to 2 * max_nfield planes (u and v) - what the point-wise entries lay
+// into workspace slot 3 on every call, held once.
+struct pgw_points_plan {
+    int nlat_s, nlon_s, south_row, north_row;
+    long long ntarg, max_nfield;
+    PointTables tb;
+    const double *cs, *sn;                                     // null: the plan cannot rotate
+    double *dpole;
+    char *mem;                                                 // one allocation: [double tables][cos][sin][pole][int tables]
+};
+
+extern "C" int pgw_points_plan_create(pgw_ctx *ctx, int nlat_s, int nlon_s, long long ntarg, const int *lat_lo, const int *lat_hi,
+                                      const double *lat_dx, const double *lat_Dx, const int *lon_lo, const int *lon_hi,
+                                      const double *lon_dx, const double *lon_Dx, const int *oob, int south_row, int north_row,
+                                      long long max_nfield, const double *cos, const double *sin, pgw_points_plan **plan) {
+    NEED(ctx, plan, "null pointer");
+    *plan = nullptr;
+    NEED(ctx, max_nfield < (1ll << 40), "max_nfield must be below 2^40");
+    if (int rc = check_point_shapes(ctx, __func__, max_nfield, nlat_s, nlon_s, ntarg, lat_lo, lat_hi, lat_dx, lat_Dx, lon_lo, lon_hi, lon_dx, lon_Dx, oob)) return rc;
+    NEED(ctx, (cos == nullptr) == (sin == nullptr), "cos and sin: both or neither");
+    NEED(ctx, (uintptr_t)cos % 8 == 0 && (uintptr_t)sin % 8 == 0, "cos / sin: misaligned pointer");
+    if (int rc = check_brackets(ctx, __func__, ntarg, oob, lat_lo, lat_hi, lon_lo, lon_hi, nlat_s, nlon_s, south_row, north_row)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)ntarg;
+    const size_t td = sizeof(double) * 4 * n, tr = cos ? sizeof(double) * 2 * n : 0, tp = sizeof(double) * 4 * (size_t)max_nfield,
+                 ti = sizeof(int) * 5 * n;
+    std::vector<char> h(td + ti);
+    pgw_points_plan *p = new pgw_points_plan{nlat_s, nlon_s, south_row, north_row, ntarg, max_nfield, {}, nullptr, nullptr, nullptr, nullptr};
+    const hipError_t e = hipMalloc((void **)&p->mem, td + tr + tp + ti);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();                               // as pgw_malloc: an allocation that does not fit is an answer
+        delete p;
+        return fail(ctx, PGW_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", td + tr + tp + ti, hipGetErrorString(e));
+    }
+    size_t at = 0;
+    auto put = [&](const auto *host, auto **dev, size_t gap) {
+        memcpy(h.data() + at, host, sizeof(*host) * n);
+        *dev = (std::remove_reference_t<decltype(*dev)>)(p->mem + gap + at);
+        at += sizeof(*host) * n;
+    };
+    put(lat_dx, &p->tb.lat_dx, 0); put(lat_Dx, &p->tb.lat_Dx, 0); put(lon_dx, &p->tb.lon_dx, 0); put(lon_Dx, &p->tb.lon_Dx, 0);
+    p->dpole = (double *)(p->mem + td + tr);
+    put(lat_lo, &p->tb.lat_lo, tr + tp); put(lat_hi, &p->tb.lat_hi, tr + tp); put(lon_lo, &p->tb.lon_lo, tr + tp);
+    put(lon_hi, &p->tb.lon_hi, tr + tp); put(oob, &p->tb.oob, tr + tp);
+    hipError_t c = hipMemcpyAsync(p->mem, h.data(), td, hipMemcpyHostToDevice, ctx->stream);
+    if (c == hipSuccess) c = hipMemcpyAsync(p->mem + td + tr + tp, h.data() + td, ti, hipMemcpyHostToDevice, ctx->stream);
+    if (cos) {
+        p->cs = (const double *)(p->mem + td);
+        p->sn = p->cs + n;
+        if (c == hipSuccess) c = hipMemcpyAsync((void *)p->cs, cos, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream);
+        if (c == hipSuccess) c = hipMemcpyAsync((void *)p->sn, sin, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream);
+    }
+    if (c == hipSuccess) c = hipStreamSynchronize(ctx->stream);        // once per plan: the host tables may be freed after the call
+    if (c != hipSuccess) {
+        (void)hipFree(p->mem);
+        delete p;
+        return fail(ctx, PGW_ERR_HIP, "upload of the point tables failed: %s", hipGetErrorString(c));
+    }
+    *plan = p;
+    return PGW_OK;
+}
+
+// What both apply entries check before they launch: the plan, the dtype tags, nfield and the `narrays` device arrays - the
+// first half of them sources (dtype_src), the second half outputs (dtype_out)
+static int check_points_apply(pgw_ctx *ctx, const char *caller, const pgw_points_plan *plan, int dtype_src, int dtype_out, long long nfield,
+                              const void *const *arrays, int narrays) {
+    NEED_AS(ctx, caller, plan, "null plan");
+    NEED_AS(ctx, caller, (dtype_src == PGW_F32 || dtype_src == PGW_F64) && (dtype_out == PGW_F32 || dtype_out == PGW_F64),
+            "dtypes must be PGW_F32 or PGW_F64");
+    NEED_AS(ctx, caller, nfield >= 1 && nfield <= plan->max_nfield, "nfield must be in [1, max_nfield of the plan]");
+    for (int k = 0; k < narrays; ++k) {
+        NEED_AS(ctx, caller, arrays[k], "null pointer");
+        NEED_AS(ctx, caller, ((uintptr_t)arrays[k] % elem_size(k < narrays / 2 ? dtype_src : dtype_out)) == 0, "pointers must be element-aligned");
+    }
+    return PGW_OK;
+}
+
+extern "C" int pgw_points_plan_apply(pgw_ctx *ctx, const pgw_points_plan *plan, int dtype_src, int dtype_out, long long nfield,
+                                     const void *src, void *out) {
+    const void *arrays[] = {src, out};
+    if (int rc = check_points_apply(ctx, __func__, plan, dtype_src, dtype_out, nfield, arrays, 2)) return rc;
+    launch_points(ctx, dtype_src, dtype_out, nfield, plan->nlat_s, plan->nlon_s, plan->ntarg, src, plan->tb, plan->south_row,
+                  plan->north_row, plan->dpole, out);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_points_plan_apply_wind(pgw_ctx *ctx, const pgw_points_plan *plan, int dtype_src, int dtype_out, long long nfield,
+                                          const void *src_u, const void *src_v, void *u_out, void *v_out) {
+    const void *arrays[] = {src_u, src_v, u_out, v_out};
+    if (int rc = check_points_apply(ctx, __func__, plan, dtype_src, dtype_out, nfield, arrays, 4)) return rc;
+    NEED(ctx, plan->cs, "the plan was made without cos / sin and cannot rotate");
+    launch_points_wind(ctx, dtype_src, dtype_out, nfield, plan->nlat_s, plan->nlon_s, plan->ntarg, src_u, src_v, plan->tb,
+                       plan->south_row, plan->north_row, plan->dpole, plan->cs, plan->sn, u_out, v_out);
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
+extern "C" int pgw_points_plan_destroy(pgw_ctx *ctx, pgw_points_plan *plan) {
+    if (!plan) return PGW_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // no launch may still read the tables
+    HIPCHK(ctx, hipFree(plan->mem));
+    delete plan;
     return PGW_OK;
 }
 

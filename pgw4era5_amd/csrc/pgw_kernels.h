@@ -2823,10 +2823,12 @@ struct PointTables {
     const double *lat_dx, *lat_Dx, *lon_dx, *lon_Dx;
 };
 
-template <typename T>
+// TOUT as in k_regrid: the value is rounded to T - what pgw_regrid_points stores - and that T value converted to TOUT
+// (`regrid_points(x).astype(out)`); TOUT = T is the kernel as it was.
+template <typename T, typename TOUT = T>
 __global__ __launch_bounds__(BLOCK) void k_regrid_points(long long nfield, int nlat_s, int nlon_s, long long ntarg, unsigned int gz,
                                                          const T *__restrict__ src, PointTables tb, const double *__restrict__ pole,
-                                                         T *__restrict__ out) {
+                                                         TOUT *__restrict__ out) {
     const long long g0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const bool active = g0 < ntarg;
     const long long g = active ? g0 : ntarg - 1;
@@ -2863,7 +2865,7 @@ __global__ __launch_bounds__(BLOCK) void k_regrid_points(long long nfield, int n
         const double ya = by_lDx.divide(v[2] - v[0]) * ldx + v[0];                // lat pass at the lower lon  :859
         const double yb = by_lDx.divide(v[3] - v[1]) * ldx + v[1];                // lat pass at the upper lon
         const double r = oob ? __builtin_nan("") : by_oDx.divide(yb - ya) * odx + ya;   // lon pass  :892
-        if (active) __builtin_nontemporal_store((T)r, out + f * ntarg + g0);      // streaming: the output must not push the source planes out of L2
+        if (active) __builtin_nontemporal_store((TOUT)(T)r, out + f * ntarg + g0);   // streaming: the output must not push the source planes out of L2
         if (f + 1 < f1) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
@@ -2966,13 +2968,14 @@ __global__ __launch_bounds__(BLOCK) void k_rotate_pair(long long nfield, long lo
 // (the next plane's are issued before this plane's two streaming stores).  Each component's value is k_regrid_points' - the
 // same expressions in the same order, its pole values from k_zonal_mean_rows run on that component - ROUNDED TO T, and the
 // pair of T values goes through rotate_uv: the bits of pgw_regrid_points on each component followed by pgw_rotate_pair.
-// An oob target gives NaN in both outputs.
-template <typename T>
+// An oob target gives NaN in both outputs.  TOUT: each rotated component, rounded once to T - what a `--rotate_winds` file of
+// step_02 holds - is converted to TOUT; TOUT = T is the kernel as it was.
+template <typename T, typename TOUT = T>
 __global__ __launch_bounds__(BLOCK) void k_regrid_points_wind(long long nfield, int nlat_s, int nlon_s, long long ntarg, unsigned int gz,
                                                               const T *__restrict__ src_u, const T *__restrict__ src_v, PointTables tb,
                                                               const double *__restrict__ pole_u, const double *__restrict__ pole_v,
                                                               const double *__restrict__ cs, const double *__restrict__ sn,
-                                                              T *__restrict__ u_out, T *__restrict__ v_out) {
+                                                              TOUT *__restrict__ u_out, TOUT *__restrict__ v_out) {
     const long long g0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const bool active = g0 < ntarg;
     const long long g = active ? g0 : ntarg - 1;
@@ -3014,8 +3017,8 @@ __global__ __launch_bounds__(BLOCK) void k_regrid_points_wind(long long nfield, 
         T ur, vr;
         rotate_uv<T>((double)value(cu, pole_u, f), (double)value(cv, pole_v, f), rc, rs, ur, vr);
         if (active) {
-            __builtin_nontemporal_store(ur, u_out + f * ntarg + g0);              // streaming, as k_regrid_points
-            __builtin_nontemporal_store(vr, v_out + f * ntarg + g0);
+            __builtin_nontemporal_store((TOUT)ur, u_out + f * ntarg + g0);        // streaming, as k_regrid_points
+            __builtin_nontemporal_store((TOUT)vr, v_out + f * ntarg + g0);
         }
         if (f + 1 < f1) {
 #pragma unroll

@@ -959,6 +959,87 @@ def regrid_points_wind(ua, va, src_lat, src_lon, targ_lat, targ_lon, cos, sin):
     return out_like(u, ua), out_like(v, va)
 
 
+class PointsPlan:
+    """`regrid_points` / `regrid_points_wind` for many calls on one (source grid, target list) pair, beside RegridPlan: targets
+    of one common shape of rank >= 1, target g at (targ_lat[g], targ_lon[g]).  The tables of `regrid_tables` - the reference's
+    extent errors are raised here, before anything is launched - and, with `pole` = (lat, lon) of the rotated grid's north
+    pole, the cos / sin of `wind_rotation` are uploaded once into device memory the plan owns (pgw_points_plan_create); `apply`
+    and `apply_wind` launch on the context's stream without allocating or synchronising.  Sources and outputs are DeviceArrays
+    and may differ in dtype: the outputs hold `regrid_points(src).astype(out.dtype)` / `regrid_points_wind(...)` cast
+    likewise, bit for bit - what a file regridded (and rotated) by step_02 holds after the host's astype."""
+
+    def __init__(self, src_lat, src_lon, targ_lat, targ_lon, max_nfield, pole=None, ctx=None):
+        self.ctx = ctx or default_context()
+        targ_lat, targ_lon = np.asarray(targ_lat, dtype=np.float64), np.asarray(targ_lon, dtype=np.float64)
+        if targ_lat.ndim < 1 or targ_lat.shape != targ_lon.shape:
+            raise ValueError('point-wise targets need lat and lon of one common shape (rank >= 1); got %s and %s'
+                             % (targ_lat.shape, targ_lon.shape))
+        tb = regrid_tables(src_lat, src_lon, targ_lat.ravel(), targ_lon.ravel())
+        self.src_shape, self.targ_shape = (len(src_lat), len(src_lon)), tuple(targ_lat.shape)
+        self.max_nfield = int(max_nfield)
+        self.pole = None if pole is None else (float(pole[0]), float(pole[1]))
+        c = {k: np.ascontiguousarray(v) for k, v in tb.items() if isinstance(v, np.ndarray)}
+        c['oob'] = np.ascontiguousarray(c['lat_oob'] | c['lon_oob'], dtype=np.int32)
+        tabs = [c[k].ctypes.data_as(_ip if c[k].dtype == np.int32 else _dp)
+                for k in 'lat_lo lat_hi lat_dx lat_Dx lon_lo lon_hi lon_dx lon_Dx oob'.split()]
+        cs = (None, None)
+        if self.pole is not None:
+            d_lat, d_lon = (self.ctx.to_device(np.ascontiguousarray(x)) for x in (targ_lat, targ_lon))
+            cs = (self.ctx.empty(self.targ_shape, F64), self.ctx.empty(self.targ_shape, F64))
+            self.ctx._check(self.ctx.lib.pgw_wind_rotation(self.ctx.handle, targ_lat.size, d_lat.ptr, d_lon.ptr, *self.pole,
+                                                           cs[0].ptr, cs[1].ptr))
+        handle = C.c_void_p()
+        self.ctx._check(self.ctx.lib.pgw_points_plan_create(self.ctx.handle, *self.src_shape, targ_lat.size, *tabs, tb['south_row'],
+                                                            tb['north_row'], self.max_nfield, ptr(cs[0]), ptr(cs[1]),
+                                                            C.byref(handle)))
+        self.handle = handle.value
+        if self.pole is not None:                               # the plan holds its own copy (create has synchronised)
+            for x in (d_lat, d_lon) + cs:
+                x.free()
+
+    def _nfield(self, srcs, outs):
+        if self.handle is None:
+            raise ValueError('the points plan has been freed')
+        nt = len(self.targ_shape)
+        lead = tuple(srcs[0].shape[:-2])
+        if (any(len(s.shape) < 2 or tuple(s.shape[-2:]) != self.src_shape or tuple(s.shape[:-2]) != lead for s in srcs)
+                or any(len(o.shape) < nt or tuple(o.shape[len(o.shape) - nt:]) != self.targ_shape
+                       or tuple(o.shape[:len(o.shape) - nt]) != lead for o in outs)):
+            raise ValueError('points plan %s -> %s: sources %s and outputs %s do not fit'
+                             % (self.src_shape, self.targ_shape, [tuple(s.shape) for s in srcs], [tuple(o.shape) for o in outs]))
+        if len({s.dtype for s in srcs}) != 1 or len({o.dtype for o in outs}) != 1:
+            raise ValueError('points plan: the sources must share one dtype and the outputs one')
+        return int(np.prod(lead, dtype=np.int64))
+
+    def apply(self, src, out):
+        """src (..., nlat_s, nlon_s) -> out (...,) + the targets' shape, DeviceArrays with the same leading shape."""
+        nfield = self._nfield((src,), (out,))
+        self.ctx._check(self.ctx.lib.pgw_points_plan_apply(self.ctx.handle, self.handle, dtype_tag(src.dtype), dtype_tag(out.dtype),
+                                                           nfield, src.ptr, out.ptr))
+        return out
+
+    def apply_wind(self, src_u, src_v, out_u, out_v):
+        """ua, va (..., nlat_s, nlon_s) -> grid-relative u, v (...,) + the targets' shape; the plan needs a `pole`."""
+        nfield = self._nfield((src_u, src_v), (out_u, out_v))
+        if self.pole is None:
+            raise ValueError('the points plan was made without a pole and cannot rotate')
+        self.ctx._check(self.ctx.lib.pgw_points_plan_apply_wind(self.ctx.handle, self.handle, dtype_tag(src_u.dtype),
+                                                                dtype_tag(out_u.dtype), nfield, src_u.ptr, src_v.ptr, out_u.ptr,
+                                                                out_v.ptr))
+        return out_u, out_v
+
+    def free(self):
+        if self.handle is not None and self.ctx.handle:
+            self.ctx.lib.pgw_points_plan_destroy(self.ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:                                       # noqa: BLE001 - interpreter shutdown
+            pass
+
+
 # ------------------------------------------------------------------------------- regridding, 2-D source coordinates
 def unit_vectors(lat_deg, lon_deg):
     """(..., 3) unit vectors (cos lat cos lon, cos lat sin lon, sin lat) of points in degrees, float64: the only

@@ -74,8 +74,18 @@ f32_out_dtype = 'float64'
 #     step_02 makes; a record of ta, hur, ua, va, zg when the instant moves past one (pgw_regrid_plan_apply into the record
 #     window of the DeltaSet).  No intermediate files; every output byte is that of the two-step run.  Not with --bands, not
 #     with i_use_xesmf_regridding = 1, ERA5 files with 1-D lat / lon axes only.
+# 'source_points': the same files, for ERA5 files of any layout - 2-D lat / lon over (rlat, rlon) of a rotated-pole file, a cell
+#     list, a mesh: every column of the file is a target of its own at its own (lat, lon) (pgw_points_plan_apply into the record
+#     window).  On a mesh file the output bytes are those of 'source'.  Not with --bands, not with i_use_xesmf_regridding = 1.
 # `--delta_grid` on the step_03 command line (or PGW_DELTA_GRID) overrides; any other value: ValueError.
 delta_grid = 'era5'
+
+# With delta_grid = 'source_points' on a rotated-pole file: None - the ua / va deltas stay eastward / northward -, 'auto' or
+# 'POLE_LAT,POLE_LON' - they are turned onto the file's grid-relative directions as they are regridded (one
+# pgw_points_plan_apply_wind launch per record of the pair), the bits `step_02 regridding --rotate_winds` writes; same syntax,
+# same rule for the pole.  `--rotate_winds` on the step_03 command line (or PGW_ROTATE_WINDS) overrides.  With any other
+# delta_grid, or on a mesh file: ValueError.
+rotate_winds = None
 
 # The host side of a file call.  True: process_file_device keeps, per context, a plan of everything that stays the same from file
 # to file (pointers, shapes, tables, loop controls) and the library brackets the delta records for the instant itself

@@ -45,6 +45,20 @@ def parser():
     return p
 
 
+def wind_pole(rotate_winds, ds_era5):
+    """The value of `--rotate_winds` -> (pole_lat, pole_lon): `auto` from the rotated mapping of the target file (rotated_pole_of),
+    else POLE_LAT,POLE_LON parsed and checked.  ValueError naming the cause.  Also the rule of step_03's --rotate_winds."""
+    if rotate_winds == 'auto':
+        return rotated_pole_of(ds_era5, settings.var_name_map['ua'])
+    try:
+        lat, lon = (float(x) for x in rotate_winds.split(','))
+    except ValueError:
+        raise ValueError("--rotate_winds takes 'auto' or POLE_LAT,POLE_LON in degrees, got %r" % rotate_winds) from None
+    if not (-90.0 <= lat <= 90.0 and -360.0 <= lon <= 360.0):
+        raise ValueError('--rotate_winds: a pole at latitude %r, longitude %r is not a position in degrees' % (lat, lon))
+    return (lat, lon)
+
+
 def _wind_plan(args, var_names, ds_era5):
     """Everything `--rotate_winds` can object to, before a file is written -> (pole, {period: (ds_ua, ds_va)}), the input
     files opened.  ValueError naming the cause."""
@@ -61,16 +75,7 @@ def _wind_plan(args, var_names, ds_era5):
     if have[0] != have[1]:
         raise ValueError('--rotate_winds needs ua and va together: -v lists %s without %s'
                          % ((WINDS[0], WINDS[1]) if have[0] else (WINDS[1], WINDS[0])))
-    if args.rotate_winds == 'auto':
-        pole = rotated_pole_of(ds_era5, settings.var_name_map['ua'])
-    else:
-        try:
-            lat, lon = (float(x) for x in args.rotate_winds.split(','))
-        except ValueError:
-            raise ValueError("--rotate_winds takes 'auto' or POLE_LAT,POLE_LON in degrees, got %r" % args.rotate_winds) from None
-        if not (-90.0 <= lat <= 90.0 and -360.0 <= lon <= 360.0):
-            raise ValueError('--rotate_winds: a pole at latitude %r, longitude %r is not a position in degrees' % (lat, lon))
-        pole = (lat, lon)
+    pole = wind_pole(args.rotate_winds, ds_era5)
     pairs = {}
     if have[0]:
         for period in PERIODS:

@@ -87,8 +87,10 @@ class DeltaSet:
     arrays: dict var -> [nrec, (nplev,) nlat, nlon] for ta,hur,ua,va,zg (4-D) and tas,hurs,ts,tos,siconc,ps_hist (3-D): a
     host array, a DeviceArray, or a record provider (`ncio.RecordReader`: .nrec, .rec_shape, .read_record(r)).  A provider
     with `.device_record(r, out)` (`SourceRecords`: records of a delta on the GCM's grid, regridded on the device) fills a
-    record's DeviceArray itself, in stream order; such a variable always keeps the window.  `plev` in file order (descending
-    for CMIP).
+    record's DeviceArray itself, in stream order; such a variable always keeps the window.  A provider with `.variables` and
+    `.device_pair(r, out_a, out_b)` (`SourceWindRecords`: ua and va regridded and rotated in one launch) stands under both of
+    its variables and fills record r of both at once: their windows hold the same records, in the same order.  `plev` in
+    file order (descending for CMIP).
 
     Time axes: the reference loads every delta file on its own (load_delta, functions.py:195-303), so each variable has
     its own time axis - `times_by_var[var]`, default `delta_times` - and is bracketed on it (monthly tos / siconc beside
@@ -148,7 +150,7 @@ class DeltaSet:
             a = arrays[k]
             if isinstance(a, DeviceArray):
                 self.dev[k] = a
-            elif hasattr(a, 'device_record'):
+            elif hasattr(a, 'device_record') or hasattr(a, 'device_pair'):
                 self._src[k] = a
                 self._cache[k] = {}
             elif self.resident:
@@ -201,10 +203,23 @@ class DeltaSet:
             return self.dev[var].slab(r)
         with self._lock:
             cache = self._cache[var]
+            src = self._src[var]
+            if hasattr(src, 'device_pair'):
+                # both windows in lockstep: a hit is a hit in both, a miss takes the least recently used slot of both and one
+                # launch fills them (in stream order, as below) - the other variable's request for r is then a hit
+                caches = [self._cache[v] for v in src.variables]
+                if r not in cache:
+                    slots = [c.pop(next(iter(c))) if len(c) >= self.WINDOW else self.ctx.empty(src.rec_shape, self.dtype) for c in caches]
+                    src.device_pair(r, *slots)
+                    for c, arr in zip(caches, slots):
+                        c[r] = arr
+                else:
+                    for c in caches:
+                        c[r] = c.pop(r)                             # most recently used last
+                return cache[r]
             if r in cache:
                 cache[r] = cache.pop(r)                             # most recently used last
                 return cache[r]
-            src = self._src[var]
             if hasattr(src, 'device_record'):
                 # the provider writes the record on the context's stream: every kernel that reads the slot of the least
                 # recently used record was launched on it before, so the slot is reused without a host synchronisation
@@ -276,8 +291,8 @@ class DeltaSet:
             if v is not None:
                 v.free()
         for src in self._src.values():
-            if hasattr(src, 'device_record'):
-                src.free()
+            if hasattr(src, 'device_record') or hasattr(src, 'device_pair'):
+                src.free()                                          # a paired provider is met twice: free() may be repeated
         self.dev, self._cache, self._src, self.ts_clim = {}, {}, {}, None
 
 
@@ -766,51 +781,108 @@ class _BandOfRecords:
 
 def delta_grid_mode(bands=False):
     """settings.delta_grid (PGW_DELTA_GRID, which the command line sets for the ranks it starts, overrides): 'era5' or
-    'source', with what 'source' excludes - all ValueErrors, raised before anything is read, copied or launched."""
+    'source', or 'source_points' (the deltas on the GCM's grid as for 'source', every column of the file a target of its own at
+    its own lat / lon, whatever the file's layout), with what the two source values and settings.rotate_winds
+    (PGW_ROTATE_WINDS likewise) exclude - all ValueErrors, raised before anything is read, copied or launched."""
     mode = os.environ.get('PGW_DELTA_GRID') or S.delta_grid
-    if mode not in ('era5', 'source'):
-        raise ValueError("settings.delta_grid must be 'era5' or 'source', got %r" % (mode,))
-    if mode == 'source':
+    if mode not in ('era5', 'source', 'source_points'):
+        raise ValueError("settings.delta_grid must be 'era5' or 'source' (or 'source_points'), got %r" % (mode,))
+    if mode != 'era5':
         if bands:
-            raise ValueError("delta_grid = 'source' regrids whole records and does not run with --bands")
+            raise ValueError("delta_grid = '%s' regrids whole records and does not run with --bands" % mode)
         if S.i_use_xesmf_regridding:
-            raise ValueError("delta_grid = 'source' takes deltas on a regular lat / lon grid (the separable bilinear regridding); "
-                             'with settings.i_use_xesmf_regridding = 1 run step_02 regridding and use the files it writes')
+            raise ValueError("delta_grid = '%s' takes deltas on a regular lat / lon grid (the separable bilinear regridding); "
+                             'with settings.i_use_xesmf_regridding = 1 run step_02 regridding and use the files it writes' % mode)
+    rotate = rotate_winds_request()
+    if rotate is not None:
+        if mode == 'era5':
+            raise ValueError("--rotate_winds with delta_grid = 'era5': the files under -d lie on the ERA5 grid already - rotate "
+                             'in step_02 (`step_02 regridding --rotate_winds`), which writes them')
+        if mode == 'source':
+            raise ValueError("--rotate_winds with delta_grid = 'source': its targets are the mesh of 1-D lat / lon axes, whose "
+                             "winds are geographic; a rotated-pole file takes delta_grid = 'source_points'")
+        if rotate != 'auto':
+            from .step_02_preproc_deltas import wind_pole
+            wind_pole(rotate, None)                             # step_02's parsing errors
     return mode
+
+
+def rotate_winds_request():
+    """settings.rotate_winds (PGW_ROTATE_WINDS, which the command line sets for the ranks it starts, overrides): None - off -,
+    'auto' or 'POLE_LAT,POLE_LON', as `step_02 regridding --rotate_winds` takes it."""
+    return os.environ.get('PGW_ROTATE_WINDS') or S.rotate_winds
+
+
+def _rotation_pole(era5, H):
+    """The pole the winds are rotated about, or None: settings.rotate_winds read on the ERA5 Dataset by step_02's rule
+    (`auto`: rotated_pole_of on the file's mapping).  ValueError on a mesh file, where there is nothing to rotate."""
+    rotate = rotate_winds_request()
+    if rotate is None:
+        return None
+    if is_mesh(H):
+        raise ValueError('--rotate_winds: the file has 1-D %s / %s axes of their own - the winds of a lat-lon mesh are geographic '
+                         'already, there is nothing to rotate' % (S.LAT_ERA, S.LON_ERA))
+    from .step_02_preproc_deltas import wind_pole
+    return wind_pole(rotate, era5)
 
 
 class SourceRecords:
     """Record provider of a DeltaSet over one level variable of a delta file on the GCM's grid: record r is read and decoded
     like step_02 reads it (ncio.RecordReader: `_FillValue` / packing), uploaded into a staging buffer of one source record and
-    regridded straight into the DeviceArray the DeltaSet hands over (functions.RegridPlan.apply: the bits of the regridded
-    file cast to the DeltaSet's dtype) - all on the context's stream, nothing waits.  `rec_shape` is the regridded record's."""
+    regridded straight into the DeviceArray the DeltaSet hands over (functions.RegridPlan.apply onto a mesh,
+    functions.PointsPlan.apply onto point-wise targets laid out as a grid: the bits of the regridded file cast to the
+    DeltaSet's dtype) - all on the context's stream, nothing waits.  `rec_shape` is the regridded record's."""
 
     KEPT = 8                       # host records held after their upload was queued (each file call synchronises the stream)
 
-    def __init__(self, ctx, reader, plan):
+    def __init__(self, ctx, reader, plan, *more_readers):
         self.ctx, self.reader, self.plan = ctx, reader, plan
+        self.readers = (reader,) + more_readers
         self.nrec = int(reader.nrec)
         self.rec_shape = tuple(reader.rec_shape[:-2]) + tuple(plan.targ_shape)
         self.src_dtype = reader.dtype if reader.dtype in (np.dtype('float32'), np.dtype('float64')) else np.dtype('float64')
-        self._stage = None
-        self._held = __import__('collections').deque(maxlen=self.KEPT)
+        self._stages = [None] * len(self.readers)
+        self._held = __import__('collections').deque(maxlen=self.KEPT * len(self.readers))
+
+    def _staged(self, k, r):
+        """Record r of reader k, its upload into that reader's staging buffer queued on the stream."""
+        host = np.ascontiguousarray(self.readers[k].read_record(int(r)), dtype=self.src_dtype)
+        if self._stages[k] is None:
+            self._stages[k] = self.ctx.empty(host.shape, self.src_dtype)
+        self._held.append(host)
+        self.ctx._check(self.ctx.lib.pgw_memcpy_h2d(self.ctx.handle, self._stages[k].ptr, host.ctypes.data, host.nbytes))
+        return self._stages[k]
 
     def device_record(self, r, out):
-        host = np.ascontiguousarray(self.reader.read_record(int(r)), dtype=self.src_dtype)
-        if self._stage is None:
-            self._stage = self.ctx.empty(host.shape, self.src_dtype)
-        self._held.append(host)
-        self.ctx._check(self.ctx.lib.pgw_memcpy_h2d(self.ctx.handle, self._stage.ptr, host.ctypes.data, host.nbytes))
-        self.plan.apply(self._stage, out)
+        self.plan.apply(self._staged(0, r), out)
         return out
 
     def free(self):
-        if self._stage is not None:
-            self._stage.free()                                  # waits for the stream
-            self._stage = None
+        for k, st in enumerate(self._stages):
+            if st is not None:
+                st.free()                                       # waits for the stream
+                self._stages[k] = None
         self._held.clear()
         self.plan.free()
-        self.reader.close()
+        for reader in self.readers:
+            reader.close()
+
+
+class SourceWindRecords(SourceRecords):
+    """The paired provider of ua and va on a rotated-pole file: record r of both files is uploaded and one
+    functions.PointsPlan.apply_wind launch regrids and rotates them into the two DeviceArrays the DeltaSet hands over - the
+    records of the files `step_02 regridding --rotate_winds` writes, cast to the DeltaSet's dtype.  The DeltaSet keeps the two
+    windows in lockstep (DeltaSet.rec), so a record is read, uploaded and launched once for both variables."""
+
+    variables = ('ua', 'va')
+    device_record = None                                        # a record of one of the two alone is not to be had
+
+    def __init__(self, ctx, reader_u, reader_v, plan):
+        super().__init__(ctx, reader_u, plan, reader_v)
+
+    def device_pair(self, r, out_u, out_v):
+        self.plan.apply_wind(self._staged(0, r), self._staged(1, r), out_u, out_v)
+        return out_u, out_v
 
 
 def _open_era5_target(path):
@@ -829,16 +901,59 @@ def _mesh_axes(era5):
     return np.asarray(t_lat.values, dtype=np.float64), np.asarray(t_lon.values, dtype=np.float64)
 
 
-def _load_source_delta_set(ctx, delta_input_dir, dtype, era5):
-    """load_delta_set with delta_grid = 'source': `delta_input_dir` holds what `step_02 regridding` takes as `-i`; the target is
-    the mesh of the lat / lon axes of `era5` (the path of the ERA5 file being processed, or (opened Dataset, path): the
-    Dataset is asked for the axes, the file is opened like step_02's `-e` only when the deltas are not loaded yet)."""
+def _point_targets(era5):
+    """(lat, lon, H) of an ERA5 Dataset for delta_grid = 'source_points': every column a target at its own position - float64
+    arrays in the shape the file's fields go to the device in (era_layout: 2-D coordinates as they are, a cell list as a grid of
+    one row, a mesh as the two axes meshed)."""
+    from .functions import _Target
+    H = era_layout(era5)
+    tg = _Target.of(era5[S.LAT_ERA], era5[S.LON_ERA])
+    if not tg.points:
+        lat, lon = np.meshgrid(tg.lat, tg.lon, indexing='ij')
+    else:
+        lat, lon = _as_grid(tg.lat, H), _as_grid(tg.lon, H)
+    return np.ascontiguousarray(lat), np.ascontiguousarray(lon), H
+
+
+def _header_dataset(reader):
+    """What functions.check_wind_pair asks of a delta file, from the header a RecordReader holds: the coordinates and the
+    variable - dimensions, attributes, dtype - without its values."""
+    from . import ncio
+    ds = ncio.Dataset()
+    for d, c in reader.coords.items():
+        ds[d] = ncio.Field(np.asarray(c), (d,))
+    ds[reader.var] = ncio.Field(ncio.placeholder((reader.nrec,) + tuple(reader.rec_shape), reader.dtype), tuple(reader.dims), {},
+                                dict(reader.attrs))
+    return ds
+
+
+def check_source_wind_files(reader_u, reader_v):
+    """The ua / va files of a rotating run, from their headers: functions.check_wind_pair (no marker of an earlier rotation,
+    one source grid, plev, record count, dtype) and equal time axes - the two are served record by record together."""
+    from .functions import check_wind_pair
+    check_wind_pair(_header_dataset(reader_u), _header_dataset(reader_v), names=SourceWindRecords.variables)
+    tu, tv = (np.asarray(r.coords.get(S.TIME_GCM, ())) for r in (reader_u, reader_v))
+    if tu.shape != tv.shape or not bool(np.all(tu == tv)):
+        raise ValueError('--rotate_winds: ua and va lie on different time axes; record r of both is regridded and rotated together')
+
+
+def _load_source_delta_set(ctx, delta_input_dir, dtype, era5, mode='source'):
+    """load_delta_set with delta_grid = 'source' / 'source_points': `delta_input_dir` holds what `step_02 regridding` takes as
+    `-i`; the target is the mesh of the lat / lon axes of `era5` ('source'), or every column of it at its own lat / lon, by the
+    file's own layout ('source_points': _point_targets; with settings.rotate_winds, ua / va come rotated onto the file's
+    rotated grid through one paired provider).  `era5`: the path of the ERA5 file being processed, or (opened Dataset, path):
+    the Dataset is asked for the coordinates, the file is opened like step_02's `-e` only when the deltas are not loaded yet."""
     from . import functions as F, ncio
     if era5 is None:
-        raise ValueError("delta_grid = 'source' needs the ERA5 file whose lat / lon axes are the target")
+        raise ValueError("delta_grid = '%s' needs the ERA5 file whose lat / lon are the target" % mode)
     era5, era5_path = era5 if isinstance(era5, tuple) else (_open_era5_target(era5), None)
-    targ_lat, targ_lon = _mesh_axes(era5)
-    key =(os.path.abspath(delta_input_dir), np.dtype(dtype).str, ctx.device, None, 'source', targ_lat.tobytes(), targ_lon.tobytes())
+    pole = None
+    if mode == 'source':
+        (targ_lat, targ_lon), H = _mesh_axes(era5), (S.LAT_ERA, S.LON_ERA)
+    else:
+        targ_lat, targ_lon, H = _point_targets(era5)
+        pole = _rotation_pole(era5, H)
+    key = (os.path.abspath(delta_input_dir), np.dtype(dtype).str, ctx.device, None, mode, targ_lat.tobytes(), targ_lon.tobytes(), pole)
     if key in _DELTASETS:
         return _DELTASETS[key]
     if era5_path is not None:
@@ -859,6 +974,8 @@ def _load_source_delta_set(ctx, delta_input_dir, dtype, era5):
         for var in ('hur', 'ua', 'va'):
             if len(plevs[var]) != len(plev) or np.any(plevs[var] != plev):
                 raise ValueError('plev axis of %s differs from that of ta (the four model-level deltas are interpolated together)' % var)
+        if pole is not None:
+            check_source_wind_files(readers['ua'], readers['va'])
         # one plan per source grid: regrid_tables runs here, the reference's extent errors come before any file is processed
         grids = {}
         for var, r in readers.items():
@@ -867,9 +984,17 @@ def _load_source_delta_set(ctx, delta_input_dir, dtype, era5):
             g['nfield'] = max(g['nfield'], int(np.prod(r.rec_shape[:-2], dtype=np.int64)))
             g['vars'].append(var)
         for gkey, g in grids.items():
-            plans[gkey] = F.RegridPlan(g['lat'], g['lon'], targ_lat, targ_lon, g['nfield'], ctx=ctx)
+            if mode == 'source':
+                plans[gkey] = F.RegridPlan(g['lat'], g['lon'], targ_lat, targ_lon, g['nfield'], ctx=ctx)
+            else:
+                winds = pole is not None and 'ua' in g['vars']
+                plans[gkey] = F.PointsPlan(g['lat'], g['lon'], targ_lat, targ_lon, g['nfield'], pole=pole if winds else None, ctx=ctx)
             for var in g['vars']:
-                arrays[var] = SourceRecords(ctx, readers[var], plans[gkey])
+                if pole is not None and var in SourceWindRecords.variables:
+                    if var == 'ua':
+                        arrays['ua'] = arrays['va'] = SourceWindRecords(ctx, readers['ua'], readers['va'], plans[gkey])
+                else:
+                    arrays[var] = SourceRecords(ctx, readers[var], plans[gkey])
         # the surface deltas whole, by the calls of step_02 (step_02_preproc_deltas.main)
         surface = [(v, base['SCEN-HIST'].format(v), v) for v in ('tas', 'hurs', 'ts', 'tos', 'siconc')]
         for var, fname, name in surface + [('ps_hist', base['HIST'].format('ps'), 'ps')]:
@@ -884,12 +1009,12 @@ def _load_source_delta_set(ctx, delta_input_dir, dtype, era5):
             if f.shape[0] > 365 + 1:
                 raise ValueError('%s: %d records of %s; a surface delta stays on the device whole, a year of days at most'
                                  % (path, f.shape[0], name))
-            arrays[var], times[var] = np.asarray(f.values), np.asarray(f.coords[S.TIME_GCM])
+            arrays[var], times[var] = _as_grid(np.asarray(f.values), H), np.asarray(f.coords[S.TIME_GCM])
         dset = DeltaSet(ctx, arrays, times['ta'], plev, dtype, times_by_var=times, resident=True)
     except BaseException:
         for a in arrays.values():
             if hasattr(a, 'device_record'):
-                a.free()
+                a.free()                                        # the paired provider is met twice: free() may be repeated
         for pl in plans.values():
             pl.free()
         for r in readers.values():
@@ -906,11 +1031,12 @@ def load_delta_set(ctx, delta_input_dir, dtype, band=None, era5=None):
     model-level variables must share one plev axis (the quad kernel interpolates them together), zg may have its own.
     When all records fit the HBM budget (DeltaSet) the files are read whole; otherwise they are opened record-wise and
     the DeltaSet keeps a window of records per variable on the device.
-    settings.delta_grid = 'source': the directory holds the deltas on the GCM's grid and `era5` (path or opened Dataset of the
-    ERA5 file being processed) gives the target axes (_load_source_delta_set)."""
+    settings.delta_grid = 'source' / 'source_points': the directory holds the deltas on the GCM's grid and `era5` (path or
+    opened Dataset of the ERA5 file being processed) gives the targets (_load_source_delta_set)."""
     from . import ncio
-    if delta_grid_mode(bands=band is not None) == 'source':
-        return _load_source_delta_set(ctx, delta_input_dir, dtype, era5)
+    mode = delta_grid_mode(bands=band is not None)
+    if mode != 'era5':
+        return _load_source_delta_set(ctx, delta_input_dir, dtype, era5, mode)
     key = (os.path.abspath(delta_input_dir), np.dtype(dtype).str, ctx.device, band)
     if key in _DELTASETS:
         return _DELTASETS[key]
@@ -1463,10 +1589,18 @@ def _cli(argv=None):
                         'interpolate_full: the deltas the run adds, on the model levels, {VAR}_delta_{file} for PS, T, RELHUM, '
                         'U, V, T_SO, T_SKIN (:350-361).  NetCDF-3 files beside the output path; one file at a time per rank; '
                         'not with --bands')
-    p.add_argument('--delta_grid', type=str, default=None, choices=['era5', 'source'],
+    p.add_argument('--delta_grid', type=str, default=None, choices=['era5', 'source', 'source_points'],
+                   metavar='{era5,source}|source_points',
                    help="the grid of the deltas under -d (default: settings.delta_grid).  era5: the files step_02 regridding wrote.  "
                         'source: the files step_02 regridding takes as -i, on the GCM\'s regular lat / lon grid - regridded on the GPU '
-                        'as they are needed, no intermediate files, the same output bytes.  Not with --bands.')
+                        'as they are needed, no intermediate files, the same output bytes; the ERA5 files have 1-D lat / lon axes.  '
+                        'source_points: the same for ERA5 files of any layout (2-D lat / lon of a rotated-pole file, a cell list, a '
+                        'mesh): every column is a target at its own lat / lon.  Neither with --bands.')
+    p.add_argument('--rotate_winds', type=str, nargs='?', const='auto', default=None, metavar='auto|POLE_LAT,POLE_LON',
+                   help='with --delta_grid source_points on a rotated-pole file: the ua / va deltas are turned onto the grid-relative '
+                        'components (along rlon / rlat) the file stores, as `step_02 regridding --rotate_winds` writes them.  auto (the '
+                        "value when none is given): the pole is taken from the file's rotated_latitude_longitude mapping; or the "
+                        "geographic position of the grid's north pole in degrees.  Default: settings.rotate_winds (off)")
     p.add_argument('--bands', action='store_true',
                    help='latency mode: EVERY file is split over all ranks in latitude bands (each rank reads, computes and '
                         'writes its rows; one MAX all-reduce per loop launch) instead of file i -> rank i mod W.  Needs the '
@@ -1481,22 +1615,58 @@ def _cli(argv=None):
         raise ValueError('Delta input directory (-d) is required.')
     if args.debug_mode is not None and args.debug_mode not in ['interpolate_time', 'interpolate_full']:
         raise ValueError('Invalid input for argument --debug_mode! Valid arguments are: "interpolate_time" or "interpolate_full"')
-    if args.delta_grid is None:
-        return _run_cli(args)
-    found = os.environ.get('PGW_DELTA_GRID')
-    os.environ['PGW_DELTA_GRID'] = args.delta_grid              # the ranks of -p N are new processes: they inherit it
+    handed = {k: v for k, v in (('PGW_DELTA_GRID', args.delta_grid), ('PGW_ROTATE_WINDS', args.rotate_winds)) if v is not None}
+    found = {k: os.environ.get(k) for k in handed}
+    os.environ.update(handed)                                   # the ranks of -p N are new processes: they inherit them
     try:
         return _run_cli(args)
     finally:                                                    # a caller of _cli in a longer-lived process finds what it had
-        os.environ.pop('PGW_DELTA_GRID')
-        if found is not None:
-            os.environ['PGW_DELTA_GRID'] = found
+        for k, v in found.items():
+            os.environ.pop(k)
+            if v is not None:
+                os.environ[k] = v
+
+
+def _source_points_preflight(delta_input_dir, era_paths):
+    """What a `--delta_grid source_points` run can object to, from headers and coordinates alone, before a directory is made or a
+    rank started: --rotate_winds on a mesh file (every file that exists is asked for its layout), and on the first file that
+    exists the pole, the ua / va pair of a rotating run (check_source_wind_files) and the reference's extent errors of every
+    source grid (functions.regrid_tables).  ValueError; no field is read, nothing is launched."""
+    from . import functions as F, ncio
+    paths = [p for p in era_paths if os.path.exists(p)]
+    if rotate_winds_request() is not None:
+        for p in paths:
+            if is_mesh(file_layout(p)):
+                _rotation_pole(None, file_layout(p))
+    if not paths:
+        return
+    era5 = _open_era5_target(paths[0])
+    targ_lat, targ_lon, H = _point_targets(era5)
+    pole = _rotation_pole(era5, H)
+    readers = {}
+    try:
+        for var in DeltaSet.VARS_3D:
+            path = os.path.join(delta_input_dir, S.file_name_bases['SCEN-HIST'].format(var))
+            if os.path.exists(path):
+                readers[var] = ncio.RecordReader(path, var)
+        if pole is not None and 'ua' in readers and 'va' in readers:
+            check_source_wind_files(readers['ua'], readers['va'])
+        seen = set()
+        for r in readers.values():
+            if S.LAT_GCM in r.coords and S.LON_GCM in r.coords:
+                lat, lon = (np.asarray(r.coords[c], dtype=np.float64) for c in (S.LAT_GCM, S.LON_GCM))
+                if (lat.tobytes(), lon.tobytes()) not in seen:
+                    seen.add((lat.tobytes(), lon.tobytes()))
+                    F.regrid_tables(lat, lon, targ_lat.ravel(), targ_lon.ravel())
+    finally:
+        for r in readers.values():
+            r.close()
 
 
 def _run_cli(args):
     from pathlib import Path
     from .parallel import IterMP
-    delta_grid_mode(bands=args.bands)                           # before a directory is made or a rank started
+    mode = delta_grid_mode(bands=args.bands)                    # before a directory is made or a rank started
     first = _dt.datetime.strptime(args.first_era_step, '%Y%m%d%H')
     last = _dt.datetime.strptime(args.last_era_step, '%Y%m%d%H')
     inc = _dt.timedelta(hours=args.hour_inc_step)
@@ -1514,6 +1684,8 @@ def _run_cli(args):
         for s in step_args:
             if os.path.exists(s['inp_era_file_path']):
                 _no_bands_on_points(s['inp_era_file_path'])
+    if mode == 'source_points':
+        _source_points_preflight(args.delta_input_dir, [s['inp_era_file_path'] for s in step_args])
     Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     if args.bands:
         return _run_banded(fargs, step_args)

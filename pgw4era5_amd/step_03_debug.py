@@ -94,14 +94,24 @@ def debug_interpolate_time(inp_era_file_path, out_era_file_path, delta_input_dir
     time_field = ncio.Field(np.asarray(era_time.coords[S.TIME_ERA]).reshape(-1)[:1], (S.TIME_GCM,), {}, era_time.attrs)
     era_time.close()
     from . import step_03_apply_to_era as s3
-    era5 = None
-    if s3.delta_grid_mode() == 'source':                    # the deltas lie on the GCM's grid: regridded here, by step_02's call
-        from .functions import interp_wrapper
+    era5, pole, winds = None, None, {}
+    mode = s3.delta_grid_mode()
+    if mode != 'era5':                                      # the deltas lie on the GCM's grid: regridded here, by step_02's calls
+        from .functions import interp_wrapper, regrid_lat_lon_wind
         era5 = s3._open_era5_target(inp_era_file_path)
-        s3._mesh_axes(era5)
+        if mode == 'source':
+            s3._mesh_axes(era5)
+        else:
+            pole = s3._rotation_pole(era5, s3.era_layout(era5))
     for var in TIME_VARS:
         ds = ncio.open_dataset(os.path.join(delta_input_dir, S.file_name_bases['SCEN-HIST'].format(var)))      # functions.py:203
-        if era5 is not None:
+        if pole is not None and var in ('ua', 'va'):        # rotated together, as step_02 regridding --rotate_winds writes them
+            if not winds:
+                other = 'va' if var == 'ua' else 'ua'
+                pair = {var: ds, other: ncio.open_dataset(os.path.join(delta_input_dir, S.file_name_bases['SCEN-HIST'].format(other)))}
+                winds = dict(zip(('ua', 'va'), regrid_lat_lon_wind(pair['ua'], pair['va'], era5, pole)))
+            ds = winds[var]
+        elif era5 is not None:
             ds = interp_wrapper(ds, era5, var, i_use_xesmf=0, nan_interp_kernel_radius=S.nan_interp_kernel_radius,
                                 nan_interp_sharpness=S.nan_interp_sharpness)
         fld = ds[var]
