@@ -640,6 +640,25 @@ int pgw_bilinear_locate(pgw_ctx *ctx, long long ntarg, const double *P, int ny, 
 int pgw_regrid_sparse(pgw_ctx *ctx, int dtype, long long nfield, int ny, int nx, long long ntarg, const void *src,
                       const int *idx, const double *w, int unmapped_nan, void *out);
 
+/* Apply on the winds of a rotated-pole SOURCE grid (not in the reference): src_u, src_v (nfield, ny, nx) of `dtype` are
+ * GRID-RELATIVE (U along rlon, V along rlat of the source grid) where src_cos / src_sin (ny*nx, float64, DEVICE, as
+ * pgw_wind_rotation writes them for the source nodes and the source grid's pole) are given, and u_out, v_out (nfield, ntarg)
+ * follow the targets' rotated grid where targ_cos / targ_sin (ntarg, DEVICE) are given.  The definition is the composed form
+ *    ug, vg = pgw_rotate_pair(src_u, src_v, src_cos, src_sin, inverse = 1)       left out when src_cos = src_sin = NULL
+ *    ur, vr = pgw_regrid_sparse(ug), pgw_regrid_sparse(vg)
+ *    u,  v  = pgw_rotate_pair(ur, vr, targ_cos, targ_sin, inverse = 0)           left out when targ_cos = targ_sin = NULL
+ * and the outputs hold its bits: each geographic source value is rounded to `dtype` before it is weighted, each regridded
+ * value is rounded to `dtype` before it is rotated; a pole node's value is the plain index-order mean of the geographic,
+ * rounded edge row, NaN propagating; an unmapped target's 0.0 (NaN with unmapped_nan != 0) goes through the target rotation
+ * like any other value; absent entries stay unread.  Both pairs NULL: pgw_regrid_sparse on each component.
+ * pgw_regrid_sparse's checks, and PGW_ERR_ARG before anything is launched, both outputs untouched, for: one pointer of a
+ * cos / sin pair NULL and the other not, a pointer not aligned to its element, an output that overlaps an input or the other
+ * output.  Runs on the context's stream, timed under PGW_K_REGRID_SPARSE. */
+int pgw_regrid_sparse_wind(pgw_ctx *ctx, int dtype, long long nfield, int ny, int nx, long long ntarg,
+                           const void *src_u, const void *src_v, const double *src_cos, const double *src_sin,
+                           const int *idx, const double *w, int unmapped_nan,
+                           const double *targ_cos, const double *targ_sin, void *u_out, void *v_out);
+
 /* ---------------------------------------------------------------- surface riders ----- */
 /* a9 step_03_apply_to_era.py:103-146 + integrate_tos functions.py:1145-1186, 2-D fields (n = ntime*ncol)
  *  sic_out = clip(sic + dsic/100, 0, 1)

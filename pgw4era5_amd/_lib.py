@@ -215,6 +215,8 @@ SIGNATURES['pgw_surface_deltas'] = (_i, [_vp, _i, _i, _i, _ll, _i, _dp, _vp, _vp
 # regrid_lat_lon's xESMF branch: locate once per grid pair, apply per variable
 SIGNATURES['pgw_bilinear_locate'] = (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_ll)])
 SIGNATURES['pgw_regrid_sparse'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _vp, _vp, _i, _vp])
+# ... on ua / va of a rotated-pole source together: to geographic in front of the weights, onto a rotated target behind them
+SIGNATURES['pgw_regrid_sparse_wind'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp])
 # regrid_lat_lon's default branch onto point-wise targets (2-D lat / lon): host tables of length ntarg
 SIGNATURES['pgw_regrid_points'] = (_i, [_vp, _i, _ll, _i, _i, _ll, _vp, _ip, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _i, _i, _vp])
 # winds on a rotated-pole target grid: cos / sin of the local rotation, the rotation of a pair, regridding and rotation in one

@@ -3255,6 +3255,61 @@ extern "C" int pgw_regrid_sparse(pgw_ctx *ctx, int dtype, long long nfield, int 
     return PGW_OK;
 }
 
+// ... on ua and va of a rotated-pole source together: turned to geographic in front of the weights, onto a rotated target's
+// directions behind them (k_row_mean_plain_wind, k_regrid_sparse_wind)
+extern "C" int pgw_regrid_sparse_wind(pgw_ctx *ctx, int dtype, long long nfield, int ny, int nx, long long ntarg, const void *src_u,
+                                      const void *src_v, const double *src_cos, const double *src_sin, const int *idx, const double *w,
+                                      int unmapped_nan, const double *targ_cos, const double *targ_sin, void *u_out, void *v_out) {
+    NEED(ctx, dtype == PGW_F32 || dtype == PGW_F64, "dtype must be PGW_F32 or PGW_F64");
+    NEED(ctx, nfield >= 1 && nfield < (1ll << 30) && ntarg >= 1 && ntarg < (1ll << 29), "nfield in [1, 2^30) and ntarg in [1, 2^29)");
+    NEED(ctx, ny >= 2 && nx >= 2 && (long long)ny * nx < (1ll << 30), "source grid must be at least 2 x 2 (and below 2^30 nodes)");
+    NEED(ctx, src_u && src_v && idx && w && u_out && v_out, "null pointer");
+    NEED(ctx, (src_cos == nullptr) == (src_sin == nullptr), "src_cos and src_sin: both or neither");
+    NEED(ctx, (targ_cos == nullptr) == (targ_sin == nullptr), "targ_cos and targ_sin: both or neither");
+    const size_t es = elem_size(dtype);
+    NEED(ctx, (uintptr_t)src_u % es == 0 && (uintptr_t)src_v % es == 0 && (uintptr_t)u_out % es == 0 && (uintptr_t)v_out % es == 0 &&
+                  (uintptr_t)src_cos % 8 == 0 && (uintptr_t)src_sin % 8 == 0 && (uintptr_t)targ_cos % 8 == 0 &&
+                  (uintptr_t)targ_sin % 8 == 0 && (uintptr_t)idx % 4 == 0 && (uintptr_t)w % 8 == 0, "pointers must be element-aligned");
+    // the outputs are written with streaming stores while other blocks still read: they may overlap nothing the kernels read
+    const size_t nsrc = (size_t)ny * nx, nt = (size_t)ntarg, out_bytes = (size_t)nfield * nt * es;
+    const struct { const void *p; size_t bytes; } reads[] = {
+        {src_u, (size_t)nfield * nsrc * es}, {src_v, (size_t)nfield * nsrc * es}, {src_cos, nsrc * 8}, {src_sin, nsrc * 8},
+        {idx, nt * 4 * sizeof(int)}, {w, nt * 4 * 8}, {targ_cos, nt * 8}, {targ_sin, nt * 8}};
+    auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
+        return a && b && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+    };
+    for (const auto &r : reads)
+        NEED(ctx, !overlap(u_out, out_bytes, r.p, r.bytes) && !overlap(v_out, out_bytes, r.p, r.bytes), "an output aliases an input");
+    NEED(ctx, !overlap(u_out, out_bytes, v_out, out_bytes), "u_out and v_out alias each other");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    void *ws = nullptr;
+    if (int rc = ws_get(ctx, 3, 64 + sizeof(double) * 4 * (size_t)nfield, &ws)) return rc;
+    double *dpole_u = (double *)((char *)ws + 64), *dpole_v = dpole_u + 2 * nfield;      // [nfield][2] each
+    // two targets per thread when the plane length and the outputs' alignment allow: 16-byte stores of float64, 8-byte ones of
+    // float32, whose four-wide form would need 310 registers (one wave per SIMD) for the entries' idx, w, cos and sin
+    const int wide = 2;
+    const int W = (ntarg % wide == 0 && aligned16(u_out) && aligned16(v_out) && !ctx->opt[PGW_OPT_FORCE_VEC1]) ? wide : 1;
+    const unsigned int bx = nblocks(ntarg, BLOCK * W);
+    const unsigned int gz = std::min(z_slices(bx, nfield), 65535u);          // blockIdx.y
+    {
+        Prof pr(ctx, PGW_K_REGRID_SPARSE);
+        with_type(dtype, [&](auto t_) {
+            using T = decltype(t_);
+            hipLaunchKernelGGL((k_row_mean_plain_wind<T>), dim3(nblocks(nfield * 2 * 64, BLOCK)), dim3(BLOCK), 0, ctx->stream, nfield, ny,
+                               nx, (const T *)src_u, (const T *)src_v, src_cos, src_sin, dpole_u, dpole_v);
+            auto form = [&](auto w_) {
+                hipLaunchKernelGGL((k_regrid_sparse_wind<T, decltype(w_)::value>), dim3(bx, gz), dim3(BLOCK), 0, ctx->stream, nfield,
+                                   (long long)ny * nx, ntarg, gz, (const T *)src_u, (const T *)src_v, src_cos, src_sin, idx, w, dpole_u,
+                                   dpole_v, unmapped_nan ? 1 : 0, ctx->opt[PGW_OPT_SPARSE_DIRECT] ? 1 : 0, targ_cos, targ_sin,
+                                   (T *)u_out, (T *)v_out);
+            };
+            if (W == 1) form(int_c<1>()); else form(int_c<2>());
+        });
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PGW_OK;
+}
+
 // ------------------------------------------------------------------ surface riders
 extern "C" int pgw_integrate_tos(pgw_ctx *ctx, int dtype, long long n, const void *tos, const void *ts,
                                  const void *land, const void *ice, void *out) {

@@ -4675,6 +4675,22 @@ __global__ __launch_bounds__(BLOCK) void k_row_mean_plain(long long nfield, int 
 // forms read the same T values and do the same arithmetic: same bits.  `force_direct` is the test knob for the second form.
 constexpr int SPARSE_WIN = 2048;
 
+// The weighting rule of one target, the one copy k_regrid_sparse and k_regrid_sparse_wind share: w0*v0, then + wk*vk over
+// the present entries in order; `value(k)` is only called for a present entry; no present entry: `miss`.
+template <typename F>
+__device__ __forceinline__ double sparse_weigh(const int (&id)[4], const double (&wt)[4], double miss, F &&value) {
+    double acc = miss;
+    bool have = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (id[k] >= 0) {
+            const double term = wt[k] * value(k);
+            acc = have ? acc + term : term;
+            have = true;
+        }
+    return acc;
+}
+
 template <typename T, int W>
 __global__ __launch_bounds__(BLOCK) void k_regrid_sparse(long long nfield, long long nsrc, long long ntarg, unsigned int gz,
                                                          const T *__restrict__ src, const int *__restrict__ idx,
@@ -4708,19 +4724,10 @@ __global__ __launch_bounds__(BLOCK) void k_regrid_sparse(long long nfield, long 
     auto combine = [&](long long f, auto &&value) {
         double r[W];
 #pragma unroll
-        for (int u = 0; u < W; ++u) {
-            double acc = miss;
-            bool have = false;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (id[u][k] >= 0) {
-                    const double v = id[u][k] >= nsrc ? pole[f * 2 + (id[u][k] - nsrc)] : value(id[u][k]);
-                    const double term = wt[u][k] * v;
-                    acc = have ? acc + term : term;
-                    have = true;
-                }
-            r[u] = acc;
-        }
+        for (int u = 0; u < W; ++u)
+            r[u] = sparse_weigh(id[u], wt[u], miss, [&](int k) {
+                return id[u][k] >= nsrc ? pole[f * 2 + (id[u][k] - nsrc)] : value(id[u][k]);
+            });
         if (active) storev_nt<T, W>(out + f * ntarg + g0, r);
     };
     if (staged) {
@@ -4735,6 +4742,149 @@ __global__ __launch_bounds__(BLOCK) void k_regrid_sparse(long long nfield, long 
         for (long long f = f0; f < f1; ++f) {
             const T *sp = src + f * nsrc;
             combine(f, [&](int i) { return (double)sp[i]; });
+        }
+    }
+}
+
+// ---- winds of a rotated-pole SOURCE grid (not in the reference): ua / va stored GRID-RELATIVE are turned to geographic with
+// the source nodes' (cs, sn) - the inverse of rotate_uv's rotation: `sn` negated, k_rotate_pair's rule -, each component
+// ROUNDED TO T, before they are weighted; each weighted value is ROUNDED TO T and, where the targets lie on a rotated grid
+// too, the pair goes through rotate_uv with the target's (ct, st): the bits of pgw_rotate_pair(inverse), pgw_regrid_sparse on
+// each component and pgw_rotate_pair.  A null cos / sin pair switches its rotation off (a uniform branch).
+
+// k_row_mean_plain for the pair: the two edge-row means of the geographic, T-rounded components, summed in index order.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_row_mean_plain_wind(long long nfield, int ny, int nx, const T *__restrict__ src_u,
+                                                               const T *__restrict__ src_v, const double *__restrict__ cs,
+                                                               const double *__restrict__ sn, double *__restrict__ pole_u,
+                                                               double *__restrict__ pole_v /* [nfield][2] each */) {
+    const long long wv = ((long long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (wv >= nfield * 2) return;
+    const long long f = wv >> 1;
+    const int which = (int)(wv & 1);
+    const long long row = (long long)(which ? ny - 1 : 0) * nx, at = f * ny * (long long)nx + row;
+    double sum_u = 0.0, sum_v = 0.0;
+    for (int i0 = 0; i0 < nx; i0 += 64) {
+        T a = (T)0, b = (T)0;
+        if (i0 + lane < nx) {
+            a = src_u[at + i0 + lane];
+            b = src_v[at + i0 + lane];
+            if (cs) rotate_uv<T>((double)a, (double)b, cs[row + i0 + lane], -sn[row + i0 + lane], a, b);
+        }
+        const double u = (double)a, v = (double)b;
+        const int n = nx - i0 < 64 ? nx - i0 : 64;
+        for (int k = 0; k < n; ++k) { sum_u = sum_u + __shfl(u, k, 64); sum_v = sum_v + __shfl(v, k, 64); }
+    }
+    if (lane == 0) { pole_u[f * 2 + which] = sum_u / (double)nx; pole_v[f * 2 + which] = sum_v / (double)nx; }
+}
+
+// k_regrid_sparse on both components at once: a target's idx / w and its (ct, st) serve both.  The same two forms by the
+// same rule, with a window of SPARSE_WIND_WIN elements: the staged form turns each source element of the window to
+// geographic ONCE while it stages it (a thread stages the same SPARSE_WIND_WIN / BLOCK window elements of every plane and
+// keeps their cs / sn in registers) and holds the T-rounded geographic pair in LDS, two buffers per component - at 1024
+// elements that is 32 KiB of float64, what k_regrid_sparse holds, so as many blocks per CU; the direct form gathers a
+// target's four pairs and their cs / sn (registers, once per z-slice) and turns them per target.  The host launches W = 2
+// (or 1): four float32 targets per thread would need 310 registers for the entries' idx, w, cs and sn.
+constexpr int SPARSE_WIND_WIN = 1024;
+
+template <typename T, int W>
+__global__ __launch_bounds__(BLOCK) void k_regrid_sparse_wind(long long nfield, long long nsrc, long long ntarg, unsigned int gz,
+                                                              const T *__restrict__ src_u, const T *__restrict__ src_v,
+                                                              const double *__restrict__ src_cos, const double *__restrict__ src_sin,
+                                                              const int *__restrict__ idx, const double *__restrict__ w,
+                                                              const double *__restrict__ pole_u, const double *__restrict__ pole_v,
+                                                              int unmapped_nan, int force_direct,
+                                                              const double *__restrict__ targ_cos, const double *__restrict__ targ_sin,
+                                                              T *__restrict__ u_out, T *__restrict__ v_out) {
+    constexpr int PER = SPARSE_WIND_WIN / BLOCK;              // window elements a thread stages per plane
+    __shared__ T s_u[2][SPARSE_WIND_WIN], s_v[2][SPARSE_WIND_WIN];
+    __shared__ int s_lo, s_hi;
+    const long long g0 = ((long long)blockIdx.x * BLOCK + threadIdx.x) * W;
+    const bool active = g0 < ntarg;                           // W | ntarg when W > 1, as k_regrid_sparse
+    int id[W][4];
+    double wt[W][4], ct[W], st[W];
+    if (threadIdx.x == 0) { s_lo = 0x7fffffff; s_hi = -1; }
+    __syncthreads();
+    int lo = 0x7fffffff, hi = -1;
+#pragma unroll
+    for (int u = 0; u < W; ++u) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            id[u][k] = active ? idx[4 * (g0 + u) + k] : -1;
+            if (id[u][k] >= nsrc + 2) id[u][k] = -1;           // nothing beyond the two pole nodes is ever read
+            wt[u][k] = active ? w[4 * (g0 + u) + k] : 0.0;
+            if (id[u][k] >= 0 && id[u][k] < nsrc) { lo = id[u][k] < lo ? id[u][k] : lo; hi = id[u][k] > hi ? id[u][k] : hi; }
+        }
+        ct[u] = (targ_cos && active) ? targ_cos[g0 + u] : 1.0;
+        st[u] = (targ_cos && active) ? targ_sin[g0 + u] : 0.0;
+    }
+    if (hi >= 0) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
+    __syncthreads();
+    const int w0 = s_lo, span = s_hi - s_lo + 1;              // span <= 0: the block reads no source element
+    const bool staged = !force_direct && span > 0 && span <= SPARSE_WIND_WIN;
+    const long long per = (nfield + gz - 1) / gz;
+    const long long f0 = (long long)blockIdx.y * per, f1 = f0 + per < nfield ? f0 + per : nfield;
+    const double miss = unmapped_nan ? __builtin_nan("") : 0.0;
+    // `pair(u, k, gu, gv)`: the geographic, T-rounded pair of a present entry that is a source element
+    auto combine = [&](long long f, auto &&pair) {
+        double ru[W], rv[W];
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            double gu[4], gv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (id[u][k] >= nsrc) { gu[k] = pole_u[f * 2 + (id[u][k] - nsrc)]; gv[k] = pole_v[f * 2 + (id[u][k] - nsrc)]; }
+                else if (id[u][k] >= 0) pair(u, k, gu[k], gv[k]);
+            T a = (T)sparse_weigh(id[u], wt[u], miss, [&](int k) { return gu[k]; });
+            T b = (T)sparse_weigh(id[u], wt[u], miss, [&](int k) { return gv[k]; });
+            if (targ_cos) rotate_uv<T>((double)a, (double)b, ct[u], st[u], a, b);
+            ru[u] = (double)a; rv[u] = (double)b;
+        }
+        if (active) { storev_nt<T, W>(u_out + f * ntarg + g0, ru); storev_nt<T, W>(v_out + f * ntarg + g0, rv); }
+    };
+    if (staged) {
+        double wc[PER], ws[PER];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int c = threadIdx.x + j * BLOCK;
+            wc[j] = (src_cos && c < span) ? src_cos[w0 + c] : 1.0;
+            ws[j] = (src_cos && c < span) ? -src_sin[w0 + c] : 0.0;
+        }
+        int buf = 0;
+        for (long long f = f0; f < f1; ++f, buf ^= 1) {
+            const T *pu = src_u + f * nsrc + w0, *pv = src_v + f * nsrc + w0;
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                const int c = threadIdx.x + j * BLOCK;
+                if (c < span) {
+                    T a = pu[c], b = pv[c];
+                    if (src_cos) rotate_uv<T>((double)a, (double)b, wc[j], ws[j], a, b);
+                    s_u[buf][c] = a; s_v[buf][c] = b;
+                }
+            }
+            __syncthreads();                                  // the other buffers are last read one plane back, before this barrier
+            combine(f, [&](int u, int k, double &gu, double &gv) {
+                gu = (double)s_u[buf][id[u][k] - w0]; gv = (double)s_v[buf][id[u][k] - w0];
+            });
+        }
+    } else {
+        double ec[W][4], es[W][4];
+#pragma unroll
+        for (int u = 0; u < W; ++u)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool elem = src_cos && id[u][k] >= 0 && id[u][k] < nsrc;
+                ec[u][k] = elem ? src_cos[id[u][k]] : 1.0;
+                es[u][k] = elem ? -src_sin[id[u][k]] : 0.0;
+            }
+        for (long long f = f0; f < f1; ++f) {
+            const T *pu = src_u + f * nsrc, *pv = src_v + f * nsrc;
+            combine(f, [&](int u, int k, double &gu, double &gv) {
+                T a = pu[id[u][k]], b = pv[id[u][k]];
+                if (src_cos) rotate_uv<T>((double)a, (double)b, ec[u][k], es[u][k], a, b);
+                gu = (double)a; gv = (double)b;
+            });
         }
     }
 }

@@ -1213,6 +1213,42 @@ def regrid_curvilinear(field, weights):
     return out_like(out, field)
 
 
+def regrid_curvilinear_wind(ua, va, weights, src_cos=None, src_sin=None, targ_cos=None, targ_sin=None):
+    """Apply phase for the winds of a rotated-pole source grid, in one launch (pgw_regrid_sparse_wind): ua, va (..., ny, nx)
+    GRID-RELATIVE on the source grid where src_cos / src_sin - `wind_rotation` of the source's 2-D coordinates and the source
+    grid's pole, of shape weights.src_shape - are given, are turned to geographic, regridded with `weights`, and - where
+    targ_cos / targ_sin of shape weights.targ_shape are given - rotated onto the targets' grid.  (u, v) hold the bits of
+        ug, vg = rotate_wind(ua, va, src_cos, src_sin, inverse=True)
+        ur, vr = regrid_curvilinear(ug, weights), regrid_curvilinear(vg, weights)
+        u,  v  = rotate_wind(ur, vr, targ_cos, targ_sin)
+    with the first / last line left out for a pair that is None.  dtype: float32 only when ua and va both are; array kinds as
+    everywhere (u like ua, v like va).  Unmapped targets as `regrid_curvilinear`."""
+    from . import settings as S
+    shape = _same_shape('ua and va', ua=ua, va=va)
+    if len(shape) < 2 or tuple(shape[-2:]) != weights.src_shape:
+        raise ValueError('ua and va of shape %s do not match the source coordinates %s' % (shape, weights.src_shape))
+    if 0 in shape:
+        raise ValueError('ua and va of shape %s: an empty array' % (shape,))
+    for what, c, s, over in (('src', src_cos, src_sin, weights.src_shape), ('targ', targ_cos, targ_sin, weights.targ_shape)):
+        if (c is None) != (s is None):
+            raise ValueError('%s_cos and %s_sin: both or neither' % (what, what))
+        if c is not None and _same_shape('%s_cos and %s_sin' % (what, what), cos=c, sin=s) != over:
+            raise ValueError('%s_cos and %s_sin of shape %s do not lie over the %s grid of shape %s'
+                             % (what, what, tuple(raw(c).shape), 'source' if what == 'src' else 'target', over))
+    dtype = common_dtype(ua, va)
+    ctx = default_context()
+    nfield = int(np.prod(shape[:-2], dtype=np.int64))
+    ntarg = int(np.prod(weights.targ_shape, dtype=np.int64))
+    d_u, d_v = dev(ctx, ua, dtype), dev(ctx, va, dtype)
+    d_cs = [None if x is None else dev(ctx, x, F64) for x in (src_cos, src_sin, targ_cos, targ_sin)]
+    p = [None if x is None else x.ptr for x in d_cs]
+    u, v = (ctx.empty(tuple(shape[:-2]) + weights.targ_shape, dtype) for _ in range(2))
+    ctx._check(ctx.lib.pgw_regrid_sparse_wind(ctx.handle, dtype_tag(dtype), nfield, shape[-2], shape[-1], ntarg, d_u.ptr, d_v.ptr,
+                                              p[0], p[1], weights.idx.ptr, weights.w.ptr, 1 if S.xesmf_unmapped_to_nan else 0,
+                                              p[2], p[3], u.ptr, v.ptr))
+    return out_like(u, ua), out_like(v, va)
+
+
 # ------------------------------------------------------------------------------- delta files
 _DATASET_CACHE = {}
 
@@ -1271,9 +1307,9 @@ def load_delta_interp(delta_input_dir, var_name, target_P, era5_date_time, targe
 
 
 # ------------------------------------------------------------------------------- step_02
-def _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name):
-    """The xESMF branch of regrid_lat_lon (reference functions.py:797-810) on the GPU."""
-    from . import ncio
+def _curvilinear_source(ds_gcm, ds_era5, var_name):
+    """What the xESMF branch takes from its files before it regrids `var_name`: -> (weights, values (..., ny, nx) as the
+    kernels take them).  ValueError when the variable does not end in the source grid's horizontal dimensions."""
     from . import settings as S
     src_lat, src_lon = np.asarray(ds_gcm[LAT_GCM].values), np.asarray(ds_gcm[LON_GCM].values)
     periodic_lon = periodic_lon_rule(src_lon)                   # :778-789
@@ -1285,13 +1321,27 @@ def _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name):
     if tuple(f.dims[-2:]) != hdims:
         raise ValueError('%s has dimensions %s; its last two must be the horizontal dimensions %s of the source grid'
                          % (var_name, tuple(f.dims), hdims))
-    t_lat, t_lon = ds_era5[LAT_ERA], ds_era5[LON_ERA]
-    targ_lat, targ_lon = np.asarray(t_lat.values, dtype=np.float64), np.asarray(t_lon.values, dtype=np.float64)
+    targ_lat, targ_lon = (np.asarray(ds_era5[c].values, dtype=np.float64) for c in (LAT_ERA, LON_ERA))
     weights = curvilinear_weights(src_lat, src_lon, targ_lat, targ_lon, periodic_lon)          # xe.Regridder  :799-800
     vals = f.values                                            # float32 / float64 of either byte order keep their width
     vals = vals.astype(vals.dtype.newbyteorder('=') if vals.dtype.kind == 'f' and vals.dtype.itemsize in (4, 8) else np.float64,
                        copy=False)
-    res = regrid_curvilinear(np.ascontiguousarray(vals), weights)                              # regridder(...)  :802
+    return weights, np.ascontiguousarray(vals)
+
+
+def _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name, given=None):
+    """The xESMF branch of regrid_lat_lon (reference functions.py:797-810) on the GPU.  given (not in the reference):
+    (values, attributes) - the values of `var_name` on the target grid the caller has already (regrid_lat_lon_source_wind);
+    the variable gets them and the attributes in place of its own, nothing else about the result differs."""
+    from . import ncio
+    f = ds_gcm[var_name]
+    t_lat, t_lon = ds_era5[LAT_ERA], ds_era5[LON_ERA]
+    targ_lat, targ_lon = np.asarray(t_lat.values, dtype=np.float64), np.asarray(t_lon.values, dtype=np.float64)
+    if given is None:
+        weights, vals = _curvilinear_source(ds_gcm, ds_era5, var_name)
+        res = regrid_curvilinear(vals, weights)                                                # regridder(...)  :802
+    else:
+        res = given[0]
     lead = tuple(f.dims[:-2])
     out = ncio.Dataset(attrs=ds_gcm.attrs)                                                     # :810
     for d in lead:
@@ -1305,7 +1355,8 @@ def _regrid_lat_lon_curvilinear(ds_gcm, ds_era5, var_name):
         out['height'] = ds_gcm['height']
     for name in [var_name, TIME_GCM, PLEV_GCM, LAT_GCM, LON_GCM, 'height']:                   # :805-808
         if name in ds_gcm and name in out:
-            out[name] = ncio.Field(out[name].values, out[name].dims, out[name].coords, ds_gcm[name].attrs, name)
+            attrs = given[1] if given is not None and name == var_name else ds_gcm[name].attrs
+            out[name] = ncio.Field(out[name].values, out[name].dims, out[name].coords, attrs, name)
     return out
 
 
@@ -1402,53 +1453,63 @@ def regrid_lat_lon(ds_gcm, ds_era5, var_name, method='bilinear', i_use_xesmf=0, 
 WIND_MARKER = dict(wind_components='grid_relative')      # on a ua / va variable whose components follow the target's rotated grid
 
 
-def rotated_pole_of(ds, var_name):
+def rotated_pole_of(ds, var_name, flag='--rotate_winds', file='target file'):
     """(grid_north_pole_latitude, grid_north_pole_longitude) of the rotated grid of a file: from the variable the
     `grid_mapping` attribute of `var_name` names; where the file has no such variable or attribute, from its only variable
-    with grid_mapping_name = 'rotated_latitude_longitude'.  ValueError when there is none, more than one, or no pole on it."""
+    with grid_mapping_name = 'rotated_latitude_longitude'.  ValueError when there is none, more than one, or no pole on it;
+    `flag` and `file` are the words its messages name the command-line flag and the file with."""
     rotated = [n for n, f in ds.variables.items() if f.attrs.get('grid_mapping_name') == 'rotated_latitude_longitude']
     named = ds[var_name].attrs.get('grid_mapping') if var_name is not None and var_name in ds else None
     if named is not None:
         if named not in rotated:
-            raise ValueError("--rotate_winds auto: the grid_mapping '%s' of %s is not a variable with grid_mapping_name = "
+            raise ValueError("%s auto: the grid_mapping '%s' of %s is not a variable with grid_mapping_name = "
                              "'rotated_latitude_longitude': no rotated mapping found; give the pole as POLE_LAT,POLE_LON"
-                             % (named, var_name))
+                             % (flag, named, var_name))
         rotated = [named]
     if not rotated:
-        raise ValueError("--rotate_winds auto: no rotated mapping found - the target file has no variable with "
-                         "grid_mapping_name = 'rotated_latitude_longitude'; give the pole as POLE_LAT,POLE_LON")
+        raise ValueError("%s auto: no rotated mapping found - the %s has no variable with "
+                         "grid_mapping_name = 'rotated_latitude_longitude'; give the pole as POLE_LAT,POLE_LON" % (flag, file))
     if len(rotated) > 1:
-        raise ValueError('--rotate_winds auto: more than one rotated mapping in the target file (%s) and no grid_mapping '
-                         'attribute on %s to choose one; give the pole as POLE_LAT,POLE_LON' % (', '.join(rotated), var_name))
+        raise ValueError('%s auto: more than one rotated mapping in the %s (%s) and no grid_mapping '
+                         'attribute on %s to choose one; give the pole as POLE_LAT,POLE_LON' % (flag, file, ', '.join(rotated), var_name))
     attrs = ds[rotated[0]].attrs
     try:
         return tuple(float(np.ravel(attrs[k])[0]) for k in ('grid_north_pole_latitude', 'grid_north_pole_longitude'))
     except KeyError as e:
-        raise ValueError('--rotate_winds auto: the rotated mapping %s of the target file has no %s' % (rotated[0], e)) from None
+        raise ValueError('%s auto: the rotated mapping %s of the %s has no %s' % (flag, rotated[0], file, e)) from None
 
 
-def check_wind_pair(ds_ua, ds_va, names=('ua', 'va')):
+def _curvilinear_dtype(f):
+    """The dtype the xESMF branch regrids a variable in: float32 / float64 of either byte order, anything else as float64."""
+    dt = np.asarray(f.values).dtype
+    return dt.newbyteorder('=') if dt.kind == 'f' and dt.itemsize in (4, 8) else np.dtype(np.float64)
+
+
+def check_wind_pair(ds_ua, ds_va, names=('ua', 'va'), flag='--rotate_winds', source_winds=False):
     """What regrid_lat_lon_wind needs of the two files of one period, checked before anything is computed or written:
     neither variable carries WIND_MARKER already (a second rotation), both lie on the same source grid, the same other
-    dimensions (plev, number of records) and have the same dtype.  ValueError naming the cause."""
+    dimensions (plev, number of records) and have the same dtype.  ValueError naming the cause, under the name `flag`.
+    source_winds: the rule of regrid_lat_lon_source_wind - the caller states what the source's components follow, so a
+    variable that carries the marker is accepted, and the dtype is the one the xESMF branch regrids in."""
     for ds, name in zip((ds_ua, ds_va), names):
-        if ds[name].attrs.get('wind_components') == WIND_MARKER['wind_components']:
+        if not source_winds and ds[name].attrs.get('wind_components') == WIND_MARKER['wind_components']:
             raise ValueError("%s already carries wind_components = 'grid_relative': these files have been rotated onto a "
                              'rotated grid, rotating them again (double rotation) would be wrong' % name)
     fu, fv = ds_ua[names[0]], ds_va[names[1]]
     for c in (LAT_GCM, LON_GCM):
         if c not in ds_ua or c not in ds_va or not np.array_equal(np.asarray(ds_ua[c].values), np.asarray(ds_va[c].values)):
-            raise ValueError('--rotate_winds: %s and %s differ in their source grid (%s)' % (names[0], names[1], c))
+            raise ValueError(flag + ': %s and %s differ in their source grid (%s)' % (names[0], names[1], c))
     if tuple(fu.dims) != tuple(fv.dims):
-        raise ValueError('--rotate_winds: %s has dimensions %s, %s has %s' % (names[0], fu.dims, names[1], fv.dims))
+        raise ValueError(flag + ': %s has dimensions %s, %s has %s' % (names[0], fu.dims, names[1], fv.dims))
     for d, nu, nv in zip(fu.dims, fu.shape, fv.shape):
         if d == PLEV_GCM and (nu != nv or not np.array_equal(np.asarray(ds_ua[d].values), np.asarray(ds_va[d].values))):
-            raise ValueError('--rotate_winds: %s and %s differ in plev' % names)
+            raise ValueError(flag + ': %s and %s differ in plev' % names)
         if nu != nv:
-            raise ValueError('--rotate_winds: %s and %s differ in the number of records: %d and %d along %s'
+            raise ValueError(flag + ': %s and %s differ in the number of records: %d and %d along %s'
                              % (names[0], names[1], nu, nv, d))
-    if _horizontal_values(fu)[1].dtype != _horizontal_values(fv)[1].dtype:
-        raise ValueError('--rotate_winds: %s and %s differ in dtype (%s, %s)' % (names[0], names[1], fu.dtype, fv.dtype))
+    kind = _curvilinear_dtype if source_winds else (lambda f: _horizontal_values(f)[1].dtype)
+    if kind(fu) != kind(fv):
+        raise ValueError(flag + ': %s and %s differ in dtype (%s, %s)' % (names[0], names[1], fu.dtype, fv.dtype))
 
 
 def regrid_lat_lon_wind(ds_ua, ds_va, ds_era5, pole, names=('ua', 'va')):
@@ -1468,6 +1529,43 @@ def regrid_lat_lon_wind(ds_ua, ds_va, ds_era5, pole, names=('ua', 'va')):
     attrs = dict(WIND_MARKER, grid_north_pole_latitude=np.float64(pole[0]), grid_north_pole_longitude=np.float64(pole[1]))
     return (regrid_lat_lon(ds_ua, ds_era5, names[0], given={names[0]: (u, attrs)}),
             regrid_lat_lon(ds_va, ds_era5, names[1], given={names[1]: (v, attrs)}))
+
+
+WIND_POLE_ATTRS = ('grid_north_pole_latitude', 'grid_north_pole_longitude')
+
+
+def regrid_lat_lon_source_wind(ds_ua, ds_va, ds_era5, source_pole, target_pole, names=('ua', 'va')):
+    """The xESMF branch of `regrid_lat_lon` (i_use_xesmf = 1) of a ua file and a va file whose source grid is a rotated-pole
+    grid with north pole at `source_pole` = (lat, lon) and whose winds are GRID-RELATIVE on it (None: they are geographic),
+    onto the target of `ds_era5`; target_pole = (lat, lon): the target is a rotated grid (point-wise lat / lon) and the winds
+    come out GRID-RELATIVE on it, with WIND_MARKER and the pole as `regrid_lat_lon_wind` writes them; None: they come out
+    geographic and carry no marker, whatever the source variables carry.  The two wind variables go through
+    `regrid_curvilinear_wind` (the bits of rotate_wind(inverse), regrid_curvilinear, rotate_wind); everything else in the two
+    datasets is what regrid_lat_lon(i_use_xesmf=1) writes.  Returns (ds_ua_out, ds_va_out)."""
+    check_wind_pair(ds_ua, ds_va, names, flag='--source_winds', source_winds=True)
+    src_lat, src_lon = (np.asarray(ds_ua[c].values, dtype=np.float64) for c in (LAT_GCM, LON_GCM))
+    if source_pole is not None and not (src_lat.ndim == 2 and src_lat.shape == src_lon.shape):
+        raise ValueError('a source pole needs 2-D source coordinates: the winds of a source with 1-D lat / lon axes are '
+                         'geographic already')
+    if target_pole is not None and not _Target.of(ds_era5[LAT_ERA], ds_era5[LON_ERA]).points:
+        raise ValueError('the target has 1-D lat / lon axes: the winds of a lat-lon mesh are geographic already, there is '
+                         'nothing to rotate')
+    weights, ua = _curvilinear_source(ds_ua, ds_era5, names[0])
+    _, va = _curvilinear_source(ds_va, ds_era5, names[1])
+    src_cs = wind_rotation(src_lat, src_lon, *source_pole) if source_pole is not None else (None, None)
+    targ_cs = (None, None)
+    if target_pole is not None:
+        targ_cs = wind_rotation(*(np.asarray(ds_era5[c].values, dtype=np.float64) for c in (LAT_ERA, LON_ERA)), *target_pole)
+    u, v = regrid_curvilinear_wind(ua, va, weights, *src_cs, *targ_cs)
+    out = []
+    for ds, name, values in ((ds_ua, names[0], u), (ds_va, names[1], v)):
+        attrs = {k: a for k, a in ds[name].attrs.items() if k not in WIND_MARKER and k not in WIND_POLE_ATTRS}
+        if target_pole is not None:
+            attrs.update(WIND_MARKER, **dict(zip(WIND_POLE_ATTRS, (np.float64(target_pole[0]), np.float64(target_pole[1])))))
+        elif not any(k in ds[name].attrs for k in WIND_MARKER):
+            attrs = ds[name].attrs
+        out.append(_regrid_lat_lon_curvilinear(ds, ds_era5, name, given=(values, attrs)))
+    return tuple(out)
 
 
 # ------------------------------------------------------------------------------- step_02 smoothing

@@ -15,15 +15,24 @@ Not in the reference: `--rotate_winds [auto | POLE_LAT,POLE_LON]` for a target f
 GRID-RELATIVE (U along increasing rlon, V along increasing rlat) while the GCM's ua / va are eastward / northward: ua and
 va of each period are regridded together and rotated onto the grid's directions (functions.regrid_lat_lon_wind), so that
 step_03 adds like to like.  Off by default; with it off nothing about a run differs.
+
+Not in the reference either: `--source_winds [auto | POLE_LAT,POLE_LON | geographic]` for settings.i_use_xesmf_regridding = 1
+and deltas from a regional model on a rotated-pole grid, whose stored ua / va are GRID-RELATIVE on the SOURCE grid: ua and va of
+each period are turned to geographic, regridded together and - with `--rotate_winds` - rotated onto a rotated target's
+directions, in one launch (functions.regrid_lat_lon_source_wind).  `geographic` declares the source winds eastward /
+northward, for `--rotate_winds` with the setting on.  Off by default; with it off nothing about a run differs.
 """
 import argparse
 import os
 from pathlib import Path
 
+import numpy as np
+
 from . import ncio
-from .functions import filter_data, interp_wrapper, regrid_lat_lon_wind, check_wind_pair, rotated_pole_of, _Target
+from .functions import (filter_data, interp_wrapper, regrid_lat_lon_wind, regrid_lat_lon_source_wind, check_wind_pair, rotated_pole_of,
+                        _Target)
 from . import settings
-from .settings import file_name_bases, nan_interp_kernel_radius, nan_interp_sharpness, LAT_ERA, LON_ERA
+from .settings import file_name_bases, nan_interp_kernel_radius, nan_interp_sharpness, LAT_ERA, LON_ERA, LAT_GCM, LON_GCM
 
 DEFAULT_VARS = 'ta,hur,ua,va,zg,hurs,tas,ps,tos,ts,siconc'
 WINDS = ('ua', 'va')
@@ -42,40 +51,62 @@ def parser():
                         'rlat) instead of eastward / northward.  auto (the value when none is given): the pole is taken from '
                         "the target file's rotated_latitude_longitude mapping; or the geographic position of the grid's north "
                         'pole in degrees.  Default: off')
+    p.add_argument('--source_winds', type=str, nargs='?', const='auto', default=None, metavar='auto|POLE_LAT,POLE_LON|geographic',
+                   help='regridding with settings.i_use_xesmf_regridding = 1 from a rotated-pole source grid: the ua / va of the '
+                        'input files are grid-relative components (along rlon / rlat of the source grid) and are turned to '
+                        "eastward / northward before they are regridded.  auto (the value when none is given): the pole is taken "
+                        "from the ua input file's rotated_latitude_longitude mapping; or the geographic position of the source "
+                        "grid's north pole in degrees; geographic: the input winds are eastward / northward (for --rotate_winds "
+                        'with the setting on).  Default: off')
     return p
 
 
-def wind_pole(rotate_winds, ds_era5):
+def wind_pole(rotate_winds, ds_era5, flag='--rotate_winds', var_name=None, file='target file'):
     """The value of `--rotate_winds` -> (pole_lat, pole_lon): `auto` from the rotated mapping of the target file (rotated_pole_of),
-    else POLE_LAT,POLE_LON parsed and checked.  ValueError naming the cause.  Also the rule of step_03's --rotate_winds."""
+    else POLE_LAT,POLE_LON parsed and checked.  ValueError naming the cause.  Also the rule of step_03's --rotate_winds, and -
+    under the name `flag`, on the variable `var_name` of the `file` - of --source_winds."""
     if rotate_winds == 'auto':
-        return rotated_pole_of(ds_era5, settings.var_name_map['ua'])
+        return rotated_pole_of(ds_era5, settings.var_name_map['ua'] if var_name is None else var_name, flag, file)
     try:
         lat, lon = (float(x) for x in rotate_winds.split(','))
     except ValueError:
-        raise ValueError("--rotate_winds takes 'auto' or POLE_LAT,POLE_LON in degrees, got %r" % rotate_winds) from None
+        raise ValueError("%s takes 'auto' or POLE_LAT,POLE_LON in degrees, got %r" % (flag, rotate_winds)) from None
     if not (-90.0 <= lat <= 90.0 and -360.0 <= lon <= 360.0):
-        raise ValueError('--rotate_winds: a pole at latitude %r, longitude %r is not a position in degrees' % (lat, lon))
+        raise ValueError('%s: a pole at latitude %r, longitude %r is not a position in degrees' % (flag, lat, lon))
     return (lat, lon)
 
 
 def _wind_plan(args, var_names, ds_era5):
-    """Everything `--rotate_winds` can object to, before a file is written -> (pole, {period: (ds_ua, ds_va)}), the input
-    files opened.  ValueError naming the cause."""
+    """Everything `--rotate_winds` and `--source_winds` can object to, before a file is written -> (source pole, target pole,
+    {period: (ds_ua, ds_va)}), the input files opened; a pole is None where that side's winds are geographic.  ValueError
+    naming the cause."""
+    source = args.source_winds is not None
+    flag = '--rotate_winds' if args.rotate_winds is not None else '--source_winds'
     if args.processing_step == 'smoothing':
-        raise ValueError('--rotate_winds belongs to the regridding step: smoothing runs on the GCM grid, where the winds are '
-                         'geographic')
-    if settings.i_use_xesmf_regridding:
+        raise ValueError('%s belongs to the regridding step: smoothing runs on the GCM grid, where the winds are %s'
+                         % (flag, 'geographic' if flag == '--rotate_winds' else 'left as they are'))
+    if settings.i_use_xesmf_regridding and not source:
         raise ValueError('--rotate_winds with settings.i_use_xesmf_regridding = 1 is not built: a curvilinear or rotated source '
-                         'grid may carry grid-relative winds of its own, which would have to be turned to geographic first')
-    if not _Target.of(ds_era5[LAT_ERA], ds_era5[LON_ERA]).points:
-        raise ValueError('--rotate_winds: the target file has 1-D lat / lon axes - the winds of a lat-lon mesh are geographic '
-                         'already, there is nothing to rotate')
+                         'grid may carry grid-relative winds of its own, which would have to be turned to geographic first - '
+                         'say what the source winds follow with --source_winds [auto | POLE_LAT,POLE_LON | geographic]')
+    if source and not settings.i_use_xesmf_regridding:
+        raise ValueError('--source_winds needs settings.i_use_xesmf_regridding = 1: in the default branch the source is a '
+                         'lat-lon mesh, whose winds are geographic already')
+    if source and args.source_winds == 'geographic' and args.rotate_winds is None:
+        raise ValueError('--source_winds geographic without --rotate_winds: geographic winds onto geographic directions, there '
+                         'is nothing to rotate')
+    if args.rotate_winds is not None:
+        tg = _Target.of(ds_era5[LAT_ERA], ds_era5[LON_ERA])
+        if not tg.points:
+            raise ValueError('--rotate_winds: the target file has 1-D lat / lon axes - the winds of a lat-lon mesh are geographic '
+                             'already, there is nothing to rotate')
+        if source and tg.lat.ndim != 2:
+            raise ValueError('--rotate_winds with --source_winds: the target file needs 2-D lat / lon, got %d-D' % tg.lat.ndim)
     have = [w in var_names for w in WINDS]
-    if have[0] != have[1]:
-        raise ValueError('--rotate_winds needs ua and va together: -v lists %s without %s'
-                         % ((WINDS[0], WINDS[1]) if have[0] else (WINDS[1], WINDS[0])))
-    pole = wind_pole(args.rotate_winds, ds_era5)
+    if have[0] != have[1] or (source and not have[0]):
+        raise ValueError('%s needs ua and va together: -v lists %s' % (flag, 'neither' if not (have[0] or have[1]) else
+                         '%s without %s' % ((WINDS[0], WINDS[1]) if have[0] else (WINDS[1], WINDS[0]))))
+    pole = wind_pole(args.rotate_winds, ds_era5) if args.rotate_winds is not None else None
     pairs = {}
     if have[0]:
         for period in PERIODS:
@@ -84,8 +115,15 @@ def _wind_plan(args, var_names, ds_era5):
                 if not os.path.exists(path):
                     raise ValueError('Files for variable ' + w + ' are missing')
             pairs[period] = tuple(ncio.open_dataset(path) for path in paths)
-            check_wind_pair(*pairs[period], names=WINDS)
-    return pole, pairs
+            check_wind_pair(*pairs[period], names=WINDS, flag=flag, source_winds=source)
+    source_pole = None
+    if source and args.source_winds != 'geographic':
+        ds_ua = pairs[PERIODS[0]][0]
+        source_pole = wind_pole(args.source_winds, ds_ua, '--source_winds', WINDS[0], 'source ua file')
+        if any(np.ndim(ds[c].values) != 2 for ds in pairs[PERIODS[0]] for c in (LAT_GCM, LON_GCM)):
+            raise ValueError('--source_winds %s: the source files have 1-D lat / lon axes - the winds of a lat-lon mesh are '
+                             'geographic already; a pole needs 2-D source coordinates' % args.source_winds)
+    return source_pole, pole, pairs
 
 
 def main(argv=None):
@@ -102,7 +140,8 @@ def main(argv=None):
     print('Run {} for variable names {}.'.format(args.processing_step, var_names))
     smoothing = args.processing_step == 'smoothing'
     ds_era5 = None if smoothing else ncio.open_dataset(args.era5_file_path, decode_times=False)
-    pole, wind_pairs = _wind_plan(args, var_names, ds_era5) if args.rotate_winds is not None else (None, {})
+    flagged = args.rotate_winds is not None or args.source_winds is not None
+    source_pole, pole, wind_pairs = _wind_plan(args, var_names, ds_era5) if flagged else (None, None, {})
     rotated = {}                                             # period -> {'ua': dataset, 'va': dataset}, made when the first is due
     done = []
     for var_name in var_names:
@@ -121,7 +160,11 @@ def main(argv=None):
                 raise ValueError('Files for variable ' + var_name + ' are missing')
             if var_name in WINDS and clim_period in wind_pairs:
                 if clim_period not in rotated:
-                    rotated[clim_period] = dict(zip(WINDS, regrid_lat_lon_wind(*wind_pairs[clim_period], ds_era5, pole, names=WINDS)))
+                    if args.source_winds is not None:
+                        pair = regrid_lat_lon_source_wind(*wind_pairs[clim_period], ds_era5, source_pole, pole, names=WINDS)
+                    else:
+                        pair = regrid_lat_lon_wind(*wind_pairs[clim_period], ds_era5, pole, names=WINDS)
+                    rotated[clim_period] = dict(zip(WINDS, pair))
                 ds_out = rotated[clim_period][var_name]
             else:
                 ds_gcm = ncio.open_dataset(inp)
